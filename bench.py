@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """cVAE training-steps/sec on MI355X (BASELINE.json metric), one process per GPU.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,13 +13,19 @@ batch); value = job-steps per second over all GPUs.  Ranks share nothing on the 
 scaling); RCCL carries the barriers, the max-over-ranks of the elapsed time and, at the end, the
 sweep's one collective: the all_gather of the per-model metric table (sweep.gather_metrics).
 
-Timing: W warm-up steps, then further untimed launches until at least --min-warm-s seconds of work
-have run (clocks and caches settled), then the K-step region is timed `--repeats` times, each
-bracketed by barrier + synchronize; `value` / `ms_per_step` come from the MEDIAN region, min / max
-are reported beside it.
+Timing: untimed launches until at least --min-warm-s seconds of work have run (clocks settled; their
+training is rolled back, so what the timed steps compute does not depend on how many ran), then W
+warm-up steps, then the K-step region is timed `--repeats` times (default 1), each bracketed by
+barrier + synchronize; `value` / `ms_per_step` come from the MEDIAN region, min / max are reported
+beside it.
 
-Inputs are synthetic, resident in HBM before the timed region.  The CPU leg
-times the oracle (a PyTorch-CPU port of the same step, oracle/) on the host cores, rank 0 only.
+A plain run does only that and prints the result line.  --full adds what the headline does not
+need: the region timed 9 times by default, the roofline of nm_step_kernel from HIP events, the
+device record, the small-sweep legs, the metric-table all_gather and the CPU leg, which times the
+oracle (a PyTorch-CPU port of the same step, oracle/) on the host cores, rank 0 only.
+
+Inputs are synthetic, seeded, resident in HBM before the timed region.
+--dump-outputs DIR writes what the last timed step left for the caller (dump_outputs).
 """
 import argparse
 import hashlib
@@ -169,22 +175,28 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=128)
     ap.add_argument("--warmup", type=int, default=16)
-    ap.add_argument("--repeats", type=int, default=9, help="times the K-step region is timed (median reported)")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: the K-step region timed --repeats (default 9) times, "
+                         "the roofline, the device record, the small-sweep legs, the metric-table all_gather and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (rank 0's models) as DIR/<name>.npy, float32: see dump_outputs")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="times the K-step region is timed (median reported); default 1, 9 with --full")
     ap.add_argument("--min-warm-s", type=float, default=0.5, help="untimed work before the first timed region")
     ap.add_argument("--jobs", type=int, default=256, help="independent models per GPU (one workgroup each)")
     ap.add_argument("--procedure", default="SE-gPoE", help="SM-<modality> | SE-<combine> | UCA-<combine>")
     ap.add_argument("--steps-per-launch", type=int, default=128,
                     help="train steps inside one persistent launch (the timed K steps run as ceil(K / this) launches)")
-    ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU baseline (0 = skip)")
+    ap.add_argument("--cpu-budget", type=float, default=12.0, help="--full: seconds of CPU baseline (0 = skip)")
     ap.add_argument("--placement", choices=["none", "rank"], default="none",
                     help="job -> fold map: none = fold j mod 5; rank = the models of a fold sit on the same XCD(s) and share "
                          "its L2 copy of the fold's ROI tables (speed / traffic only)")
     ap.add_argument("--lean", action="store_true",
-                    help="only the warm-up and the timed regions: no small-sweep legs, no traced launch for the device record "
-                         "(profiler passes: every nm_step_kernel dispatch of the run is then one of the K-step launches)")
+                    help="--full without the small-sweep legs and the traced launch for the device record (profiler passes: "
+                         "every nm_step_kernel dispatch of the run is then a warm-up or a K-step launch)")
     ap.add_argument("--small-sweep", type=int, default=1,
-                    help="1: also time the metric's literal shape -- 5 folds -- and the reference's 20-cell sweep and one model "
-                         "alone (own short legs after the timed region, rank 0 at N = 1; 0 = skip)")
+                    help="--full, 1: also time the metric's literal shape -- 5 folds -- and the reference's 20-cell sweep and "
+                         "one model alone (own short legs after the timed region, rank 0 at N = 1; 0 = skip)")
     ap.add_argument("--subjects", type=int, default=1280)
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline (0 = min(affinity, 16))")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse the\n                    multi-rank path on a one-GPU box together with --share-device)")
@@ -197,9 +209,11 @@ def main():
     ap.add_argument("--cells", type=int, default=20, help="--scaling strong: models of the grid (folds x procedures x replicas)")
     ap.add_argument("--window-s", type=float, default=2.0, help="--scaling strong: wall-clock window every rank trains for")
     ap.add_argument("--cpu-all-shapes", action="store_true",
-                    help="cpu_baseline also for the other BASELINE shapes (config 2, early fusion, UCA, config 5 trunk): "
+                    help="--full: cpu_baseline also for the other BASELINE shapes (config 2, early fusion, UCA, config 5 trunk): "
                          "a few seconds each, off by default so that the driver's form stays short")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 9 if args.full else 1
 
     T0 = time.perf_counter()
     import torch
@@ -270,19 +284,31 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    # ---- warm-up: W steps, then whole K-step regions until min_warm_s of work has run ----
-    run_steps(args.warmup)
-    barrier()
+    # ---- warm-up: launches of the timed size until min_warm_s of work has run, rolled back; then the W steps ----
+    snap = [(j.params.clone(), j.adam_m.clone(), j.adam_v.clone(), j.step, j.t) for j in jobs] if args.min_warm_s > 0 else None
     warm_extra, tw = 0, time.perf_counter()
     while time.perf_counter() - tw < args.min_warm_s:
-        run_steps(args.steps)
+        run_steps(spl)
         torch.cuda.synchronize(dev)
-        warm_extra += args.steps
+        warm_extra += spl
+    if warm_extra:
+        # (the extra count depends on the clock: without the roll-back the timed steps would start from a different
+        #  state every run, and two builds could not be compared output for output.  The W steps come after it, so the
+        #  timed region starts on caches filled by training, not by the copies)
+        for j, (p, m, v, step, t) in zip(jobs, snap):
+            j.params.copy_(p)
+            j.adam_m.copy_(m)
+            j.adam_v.copy_(v)
+            j.step, j.t = step, t
+            j.params_changed()
+        js._upload()                       # the bf16 shadow images of the restored weights: rebuilt here, not in a launch
+    del snap
+    run_steps(args.warmup)
     barrier()
-    log(f"warmup done ({args.warmup} + {warm_extra} steps)")
+    log(f"warmup done ({warm_extra} steps rolled back + {args.warmup})")
 
     # ---- timed: the K-step region, `repeats` times, each bracketed by barrier + synchronize ----
-    events, regions = [], []
+    events, regions = ([] if args.full else None), []
     for _ in range(max(1, args.repeats)):
         barrier()
         t0 = time.perf_counter()
@@ -300,7 +326,57 @@ def main():
         f"({len(regions)} x {args.steps} steps)")
     # sanity: training really happened and stayed finite
     js.assert_finite()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), torch, jobs, log)
 
+    total_job_steps = args.jobs * args.steps * world
+    value = total_job_steps / elapsed
+    out = {
+        "metric": "cVAE training-steps/sec (batch 256, 379-ROI x 3-modality)",
+        "value": round(value, 2), "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "bf16", "data": "synthetic", "full": args.full,
+        "repeats": len(regions), "ms_per_step_min": round(min(regions) / args.steps * 1e3, 4),
+        "ms_per_step_max": round(max(regions) / args.steps * 1e3, 4), "warmup_extra_steps": warm_extra,
+        "config": {"workload": f"{args.procedure} cVAE_multimodal sweep: {len(spec.input_dims)} x 379 ROI, batch 256, "
+                               f"c=29, H=[110,110], Z=10, 5 folds x replicas, {args.jobs} independent models per GPU, "
+                               f"in-kernel reparameterisation draw",
+                   "jobs_per_gpu": args.jobs, "steps_per_launch": spl, "params_per_model": work["n_params"],
+                   "train_rows_per_model": jobs[0].tables[0].N, "parallelism": f"sweep-sharded x{world}"},
+        "roofline": None,
+    }
+    if args.full:
+        full_legs(args, torch, nm, sweep, workload, cohort, dev, dist, rank, world, log, js, jobs, spec, work, spl, events,
+                  value, out)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, torch, jobs, log):
+    """What the timed path hands its caller after the last timed step, as float32 .npy files: every model's loss row of
+    that step (loss_last_step [jobs, NM_LOSS_STRIDE]: total, kl, ll, ...), model 0's trained parameters whole
+    (params_model0, the kernel's flat layout) and the same seeded sample of positions of every model's (params_sample
+    [jobs, <= 16384]) -- a few tens of MB at most."""
+    import numpy as np
+    out_dir.mkdir(parents=True, exist_ok=True)
+    n = min(int(j.params.numel()) for j in jobs)
+    per_model = min(n, 16384, (32 << 20) // 4 // len(jobs))
+    idx = np.sort(np.random.default_rng(20250418).choice(n, size=per_model, replace=False))
+    idx = torch.from_numpy(idx).to(jobs[0].device)
+    arrays = {"loss_last_step": torch.stack([j.loss_log[(j.step - 1) % j.loss_cap] for j in jobs]),
+              "params_model0": jobs[0].params,
+              "params_sample": torch.stack([j.params.index_select(0, idx) for j in jobs])}
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a.detach().float().cpu().numpy())
+    log(f"outputs of the last timed step -> {out_dir}: " + ", ".join(f"{k} {tuple(a.shape)}" for k, a in arrays.items()))
+
+
+def full_legs(args, torch, nm, sweep, workload, cohort, dev, dist, rank, world, log, js, jobs, spec, work, spl, events,
+              value, out):
+    """--full: everything the headline figure does not need, into `out`.  Runs after the timed regions (and the output
+    dump): the traced launch of the device record trains the jobs on."""
     # ---- roofline of the dominant kernel (nm_step_kernel), from HIP events on its own stream ----
     kern_ms = sum(e0.elapsed_time(e1) for e0, e1, _ in events)
     launches = len(events)
@@ -321,30 +397,13 @@ def main():
             traffic = rec["hbm_bytes_per_job_step_corrected"] * args.jobs * steps_per_launch
             traffic_src = (f"profiles/pmc_hbm_traffic.json ({rec.get('tag', '?')}: FETCH x2 + WRITE, "
                            f"{rec.get('steps_per_launch')} steps/launch)")
-    roofline = {"bound": "hbm", "achieved": round(hbm_gbs, 2), "peak": 8000.0, "unit": "GB/s",
-                "frac": round(hbm_gbs / 8000.0, 5), "traffic": traffic, "traffic_source": traffic_src,
-                "kernel": "nm_step_kernel", "avg_launch_ms": round(avg_launch_s * 1e3, 4), "launches_timed": launches,
-                "algorithmic_bytes_per_job_step": work["bytes"],
-                "mfma_bf16_tflops": round(flop_per_launch / avg_launch_s / 1e12, 3),
-                "mfma_frac_of_2500": round(flop_per_launch / avg_launch_s / 2.5e15, 5),
-                "kernel_src_sha16": kernel_src_sha16()}
-
-    total_job_steps = args.jobs * args.steps * world
-    value = total_job_steps / elapsed
-    out = {
-        "metric": "cVAE training-steps/sec (batch 256, 379-ROI x 3-modality)",
-        "value": round(value, 2), "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-        "repeats": len(regions), "ms_per_step_min": round(min(regions) / args.steps * 1e3, 4),
-        "ms_per_step_max": round(max(regions) / args.steps * 1e3, 4), "warmup_extra_steps": warm_extra,
-        "config": {"workload": f"{args.procedure} cVAE_multimodal sweep: {len(spec.input_dims)} x 379 ROI, batch 256, "
-                               f"c=29, H=[110,110], Z=10, 5 folds x replicas, {args.jobs} independent models per GPU, "
-                               f"in-kernel reparameterisation draw",
-                   "jobs_per_gpu": args.jobs, "steps_per_launch": spl, "params_per_model": work["n_params"],
-                   "train_rows_per_model": jobs[0].tables[0].N, "parallelism": f"sweep-sharded x{world}"},
-        "roofline": roofline,
-    }
+    out["roofline"] = {"bound": "hbm", "achieved": round(hbm_gbs, 2), "peak": 8000.0, "unit": "GB/s",
+                       "frac": round(hbm_gbs / 8000.0, 5), "traffic": traffic, "traffic_source": traffic_src,
+                       "kernel": "nm_step_kernel", "avg_launch_ms": round(avg_launch_s * 1e3, 4), "launches_timed": launches,
+                       "algorithmic_bytes_per_job_step": work["bytes"],
+                       "mfma_bf16_tflops": round(flop_per_launch / avg_launch_s / 1e12, 3),
+                       "mfma_frac_of_2500": round(flop_per_launch / avg_launch_s / 2.5e15, 5),
+                       "kernel_src_sha16": kernel_src_sha16()}
 
     # ---- what the record needs to explain box-to-box differences: the clocks this run saw ----
     if rank == 0:
@@ -432,10 +491,6 @@ def main():
                 sps2, n2 = time_cpu_steps(st2, bt, budget_s=min(4.0, args.cpu_budget))
                 others[name] = {"value": round(sps2, 2), "unit": "steps/s", "steps": n2}
             out["cpu_baseline"]["other_shapes"] = others
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if dist is not None:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -1255,7 +1255,7 @@ def test_bench_two_ranks_share_device():
     timing and the final all_gather of the metric table with both ranks' rows."""
     import json
     r = _run_two_ranks(["bench.py", "--gpus", "2", "--backend", "gloo", "--share-device", "--jobs", "8", "--steps", "4", "--warmup", "1",
-                        "--repeats", "2", "--min-warm-s", "0", "--cpu-budget", "0"])
+                        "--repeats", "2", "--min-warm-s", "0", "--cpu-budget", "0", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     out = json.loads(line)

@@ -3,7 +3,7 @@
 TAG=$1
 O=gpurun_out/$TAG
 mkdir -p $O
-python bench.py > $O/bench_default.json 2> $O/bench_default.err; cut -c1-330 $O/bench_default.json
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; cut -c1-330 $O/bench_default.json
 for i in 1 2; do python bench.py --cpu-budget 0 --steps 20 --warmup 5 2>/dev/null >> $O/bench_steps20.json; done; cut -c60-200 $O/bench_steps20.json
 for j in 5 20; do python bench.py --cpu-budget 0 --jobs $j 2>/dev/null > $O/bench_jobs$j.json; cut -c60-200 $O/bench_jobs$j.json; done
 bash tools/run_rocprof_stats.sh $TAG > $O/rocprof_stats.log 2>&1; cp gpurun_out/prof_$TAG/kernel_stats.csv $O/kernel_stats_bench_default.csv; cp gpurun_out/prof_$TAG/bench.json $O/bench_under_rocprof.json; head -3 $O/kernel_stats_bench_default.csv | cut -c1-200

@@ -4,7 +4,7 @@
 ALT=$1
 for i in 1 2 3; do
   for lib in libnmhip.so $ALT; do
-    v=$(NMHIP_LIB_NAME=$lib python bench.py --lean --cpu-budget 0 --repeats 5 2>/dev/null | python -c "import json,sys; o=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(o['value'], o['roofline']['frac'])")
+    v=$(NMHIP_LIB_NAME=$lib python bench.py --full --lean --cpu-budget 0 --repeats 5 2>/dev/null | python -c "import json,sys; o=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(o['value'], o['roofline']['frac'])")
     echo "$lib $v"
   done
 done

@@ -5,7 +5,7 @@ TAG=$1
 O=gpurun_out/$TAG
 mkdir -p $O
 step() { name=$1; shift; "$@" 2> $O/$name.err || echo "!! step $name failed (see $O/$name.err)"; }
-step bench_default bash -c "python bench.py > $O/bench_default.json"; cut -c1-330 $O/bench_default.json
+step bench_default bash -c "python bench.py --full > $O/bench_default.json"; cut -c1-330 $O/bench_default.json
 for i in 1 2; do step bench_steps20_$i bash -c "python bench.py --cpu-budget 0 --small-sweep 0 --steps 20 --warmup 5 >> $O/bench_steps20.json"; done; cut -c60-200 $O/bench_steps20.json
 step rocprof_stats bash -c "bash tools/run_rocprof_stats.sh $TAG > $O/rocprof_stats.log"; cp gpurun_out/prof_$TAG/kernel_stats.csv $O/kernel_stats_bench_default.csv; cp gpurun_out/prof_$TAG/bench.json $O/bench_under_rocprof.json; head -3 $O/kernel_stats_bench_default.csv | cut -c1-200
 step pmc bash -c "bash tools/run_pmc.sh $TAG --steps 32 --warmup 4 --steps-per-launch 32 > $O/pmc.log"; cp gpurun_out/pmc_$TAG/pmc_hbm_traffic.json $O/; tail -1 $O/pmc.log | cut -c1-400
