@@ -11,6 +11,11 @@ from pathlib import Path
 
 NM_MAX_MOD = 8
 NM_MAX_EXP = 4
+# the row-split launch's Adam sweep (csrc/nm_rowsplit.hip: SwTab, SW_NV): weight passes and vector segments per modality,
+# and the vector elements (biases, logvar_out, alpha) nm_rowsplit_ok admits -- 3 per thread of k = 2 workgroups of 512
+NM_RS_MAX_PASSES = 128
+NM_RS_MAX_VSEGS = 144
+NM_RS_MAX_VEC = 3 * 2 * 512
 NM_MAX_HID = 8
 NM_MAX_CLS = 5
 NM_MAX_CLS_WIDTH = 512
@@ -38,6 +43,9 @@ NM_LOSS_CONTRAST = 14
 NM_F_BNSTATS = 256
 NM_F_SPLIT = 512
 NM_F_FAULT_INJECT = 1024
+# values of a job's hand-off error word (nm_split_errors): a hand-off timed out / the row-split kernel refused the shape
+NM_SYNC_ERR_TIMEOUT = 1
+NM_SYNC_ERR_SHAPE = 2
 NM_METRICS_MAX_N = 8192
 NM_METRICS_STRIDE = 8
 

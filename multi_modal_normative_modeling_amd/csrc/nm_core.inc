@@ -159,6 +159,8 @@ struct WsLayout {
 };
 constexpr int WS_SYNC_BYTES = 256;       // hand-off counters of the split mode: A at +0, B at +64, error flag at +128
 constexpr int WS_SYNC_ERR_WORD = 32;
+// values of the error word: a hand-off timed out / the row-split kernel refused the job's shape (nm_rowsplit.hip: rs_fits)
+constexpr unsigned WS_SYNC_ERR_TIMEOUT = 1u, WS_SYNC_ERR_SHAPE = 2u;
 // row-split launch (words of tile 0 unless noted): A[q] at word q, B[q] at 16 + q (q < 4: arrivals of the M modality parts of
 // slice q), C at 33 (all M k workgroups of the job: partials complete), D[m] at 40 + m (the k slices of modality m: sweep
 // complete); words 48.. of EVERY tile: that slice's loss shares (kl, then ll_m)
@@ -513,7 +515,7 @@ __device__ __forceinline__ bool split_handoff(const Ctx& c, GAS unsigned* cnt, G
     while (__hip_atomic_load((unsigned*)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
       // (another part that has already given up also ends this wait: no part is left spinning for its full bound)
       if (++spins > (1 << 22) || __hip_atomic_load((unsigned*)err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-        __hip_atomic_store((unsigned*)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store((unsigned*)err, WS_SYNC_ERR_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         ok = false;
         break;
       }

@@ -92,6 +92,28 @@ __device__ __forceinline__ SwVec sw_vseg(const nm_job_t* J, int m, int s) {
   return SwVec{(int)G.T.b_off, G.N, 0, 0, G.T.sh_b};
 }
 
+// Do the sweep's tables and its SW_NV * KH * WG vector elements hold every modality of the job?  The counts rs_build_tables
+// forms, from the descriptor alone: every workgroup of a job -- slices and helpers -- reaches the same answer, so a refused
+// job leaves the launch before its first hand-off and nobody waits.  (nm_rowsplit_ok is the host's stricter statement:
+// it counts alpha always and the vector capacity of k = 2 without helpers.)  A few scalar operations per launch.
+__device__ __forceinline__ bool rs_fits(const nm_job_t* J, int M, int KH) {
+  const int L = J->L, Me = experts(J);
+  int sh = 0;
+  for (int i = 0; i < L; ++i) sh += J->H[i];
+  for (int m = 0; m < M; ++m) {
+    const nm_modality_t& md = J->mod[m];
+    const int nck = (md.D + OCH - 1) / OCH, nch = (md.Kx + XCH - 1) / XCH;
+    const bool enc = m < Me;
+    const int has_alpha = (enc && md.alpha >= 0 && J->combine == NM_COMBINE_GPOE && !(Me == 1 && J->single_bypass)) ? 1 : 0;
+    const int npass = nck + L + (enc ? 2 + (L - 1) + nch : 0);
+    const int nseg = 2 * nck + L + (enc ? 2 + L : 0) + has_alpha;
+    // out_b and logvar_out (D each), the decoder's biases, the heads' and the encoder's biases, alpha
+    const int vtot = 2 * md.D + sh + (enc ? 2 * J->Z + sh : 0) + has_alpha;
+    if (npass > NM_RS_MAX_PASSES || nseg > NM_RS_MAX_VSEGS || vtot > SW_NV * KH * WG) return false;
+  }
+  return true;
+}
+
 // Once per launch: the tables of modality m into S, from there into the workspace slot `gtab`.
 __device__ __forceinline__ void rs_build_tables(const Ctx& cc, int m, GAS char* gtab) {
   Ctx c = cc;
@@ -103,6 +125,7 @@ __device__ __forceinline__ void rs_build_tables(const Ctx& cc, int m, GAS char* 
   const int nck = (md.D + OCH - 1) / OCH, nch = (md.Kx + XCH - 1) / XCH;
   const bool enc = m < Me;
   const bool has_alpha = enc && md.alpha >= 0 && J->combine == NM_COMBINE_GPOE && !(Me == 1 && J->single_bypass);
+  // (min(): a bound on the table writes only -- a job whose counts exceed them never gets here, rs_fits)
   const int npass = min(nck + L + (enc ? 2 + (L - 1) + nch : 0), NM_RS_MAX_PASSES);
   const int nseg = min(2 * nck + L + (enc ? 2 + L : 0) + (has_alpha ? 1 : 0), NM_RS_MAX_VSEGS);
   for (int g = c.tid; g < npass; g += WG) {
@@ -277,7 +300,7 @@ __device__ __forceinline__ bool wait_counter(const Ctx& c, GAS unsigned* cnt, GA
     bool ok = true;
     while (__hip_atomic_load((unsigned*)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
       if (++spins > (1 << 22) || __hip_atomic_load((unsigned*)err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-        __hip_atomic_store((unsigned*)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store((unsigned*)err, WS_SYNC_ERR_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         ok = false;
         break;
       }
@@ -331,6 +354,12 @@ __global__ __launch_bounds__(WG) void nm_rs_kernel(const nm_job_t* __restrict__ 
   for (int i = c.tid; i < SMEM_BYTES / 4; i += WG) reinterpret_cast<uint32_t*>(smem)[i] = 0u;
   __syncthreads();
   const WsLayout wl = ws_layout(J->M, J->L, J->Z);
+  if (!rs_fits(J, M, KH)) {        // (uniform over the job's workgroups: all leave, none is left waiting at a hand-off)
+    if (part == 0 && q == 0 && c.tid == 0)
+      __hip_atomic_store((unsigned*)((GAS unsigned*)(c.ws0 + wl.sync) + WS_SYNC_ERR_WORD), WS_SYNC_ERR_SHAPE, __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+    return;
+  }
   GAS char* const gtab = c.ws + wl.rs_tab + (int64_t)part * WS_RS_TAB_BYTES;    // (helpers: slice 0's tables, complete at D below)
   if (!helper) rs_build_tables(c, part, gtab);
 #ifdef NM_RS_DEBUG_TABLES

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .layout import ModelSpec, ParamLayout
+from .layout import ModelSpec, ParamLayout, rowsplit_limit
 
 BATCH = _lib.NM_BATCH
 
@@ -190,6 +190,8 @@ class Job:
         self._wsh = None                 # bf16 shadow images of the weights (nm_job_t.wsh)
         self._gpart = None               # row-split launch: k slices of fp32 gradient partials (nm_job_t.gpart)
         self._gpart_k = 0
+        self._rs_ok_version = None       # _version at which nm_rowsplit_ok last accepted this job
+        self._rs_limit = (None, None)    # (Kx of the kernel modalities, layout.rowsplit_limit of them)
         self.shadow_dirty = True         # params were written by the host: nm_sync_shadow before the next launch
         self._ensure_workspace(n_tiles_ws)
         # optional exports
@@ -250,10 +252,18 @@ class Job:
                 and self.out_mu is None and self.out_logvar is None and self.out_z is None)
 
     def rowsplit_ok(self) -> bool:
-        """Can this model run row-split (nm_rowsplit_ok: plain cVAE / cVAE_multimodal-type models on the fused kernel)?"""
+        """Can this model run row-split (nm_rowsplit_ok: plain cVAE / cVAE_multimodal-type models on the fused kernel whose
+        modalities fit the Adam sweep's tables, layout.rowsplit_limit)?"""
         s = self.spec
         return (not s.wide and s.kind in ("single", "multimodal") and len(self.kmods) == s.M and s.M <= _lib.NM_MAX_EXP
-                and self.tc_weight == 0.0)
+                and self.tc_weight == 0.0 and self.rowsplit_limit() is None)
+
+    def rowsplit_limit(self) -> Optional[str]:
+        """The row-split sweep table limit a modality of this model exceeds (layout.rowsplit_limit), or None."""
+        kxs = tuple(self.tables[m].Kx for m, _, _ in self.kmods)
+        if self._rs_limit[0] != kxs:                               # (asked on every train() call of a small set)
+            self._rs_limit = (kxs, rowsplit_limit(self.spec, kxs))
+        return self._rs_limit[1]
 
     def set_fi(self, fi):
         """Regression target per table row (FI, ..._regression.py:86-87); padded with zeros to rows_alloc."""
@@ -464,6 +474,8 @@ class JobSet:
         self._dev = None
         self._sig = None
         self._split_pending = False      # a split launch has run since the hand-off error words were last read
+        self._pending_kinds = set()      # ... of which kinds ("split", "rowsplit"): the error message names their switch
+        self._err_kinds = set()          # the kinds behind the error words in flight
 
     def check_split_errors(self, block: bool = True):
         """Raise NmError if a hand-off of a split launch (one workgroup per modality) timed out: the job's workgroups left
@@ -478,11 +490,22 @@ class JobSet:
                 ev.synchronize()
             if ev.query():
                 self._err_inflight = None
-                bad = host.nonzero().flatten().tolist()
+                kinds = self._err_kinds
+                vals = host.tolist()
+                shape = [i for i, v in enumerate(vals) if v == _lib.NM_SYNC_ERR_SHAPE]
+                bad = [i for i, v in enumerate(vals) if v != 0 and v != _lib.NM_SYNC_ERR_SHAPE]
+                if shape:
+                    raise _lib.NmError(f"row-split launch: job(s) {shape[:8]} exceed the Adam sweep's tables (passes, vector "
+                                       f"segments or vector elements; nm_rowsplit_ok) and were refused by the kernel; their "
+                                       f"parameters were not updated -- run them with rowsplit=1 or NMHIP_ROWSPLIT=0")
                 if bad:
-                    raise _lib.NmError(f"split launch: the hand-off between the workgroups of job(s) {bad[:8]} timed out "
+                    # (the switch that turns the pending launch kind off: row slices / one workgroup per modality)
+                    switch = " / ".join(v for kd, v in (("rowsplit", "NMHIP_ROWSPLIT=0"), ("split", "NMHIP_SPLIT=0"))
+                                        if kd in kinds) or "NMHIP_SPLIT=0"
+                    what = "row-split" if kinds == {"rowsplit"} else "split"
+                    raise _lib.NmError(f"{what} launch: the hand-off between the workgroups of job(s) {bad[:8]} timed out "
                                        f"(the parts of a model must all be resident at once: another stream or process "
-                                       f"occupying CUs breaks that); their parameters are not valid -- re-run with NMHIP_SPLIT=0")
+                                       f"occupying CUs breaks that); their parameters are not valid -- re-run with {switch}")
         if self._split_pending and self._dev is not None and getattr(self, "_err_inflight", None) is None:
             n = len(self.jobs)
             if getattr(self, "_err_dev", None) is None:
@@ -494,6 +517,7 @@ class JobSet:
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(self.device))
             self._err_inflight = (ev, self._err_host)
+            self._err_kinds, self._pending_kinds = self._pending_kinds, set()
             self._split_pending = False
             if block:
                 self.check_split_errors(True)
@@ -563,6 +587,7 @@ class JobSet:
         _lib.check(self.lib.nm_launch_split(ptr, len(self.jobs), len(self.jobs[0].kmods), int(step0), int(n_steps), int(flags),
                                             _stream_ptr(self.device)), "nm_launch_split")
         self._split_pending = True
+        self._pending_kinds.add("split")
 
     def split_parts(self) -> int:
         """Workgroups per model for a training launch: the M modalities of a model as separate workgroups when the
@@ -584,16 +609,17 @@ class JobSet:
         needs the whole batch in one workgroup.  NMHIP_ROWSPLIT = 0 switches it off, 2 / 4 cap k."""
         mode = os.environ.get("NMHIP_ROWSPLIT", "auto")
         M = len(self.jobs[0].kmods)
-        if mode == "0" or self.wide or any(len(j.kmods) != M or not j.rowsplit_ok() for j in self.jobs):
+        if mode == "0" or self.wide:
             return 1
         if not hasattr(self, "_cus"):
             self._cus = torch.cuda.get_device_properties(self.device).multi_processor_count
         groups = (len(self.jobs) * M + 7) // 8 * 8
         kmax = int(mode) if mode in ("2", "4") else 4
-        for k in (4, 2):
-            if k <= kmax and groups * k <= self._cus:
-                return k
-        return 1
+        # (the set size first: a full chip's set -- every train() call of the headline -- skips the per-job checks)
+        ks = [k for k in (4, 2) if k <= kmax and groups * k <= self._cus]
+        if not ks or any(len(j.kmods) != M or not j.rowsplit_ok() for j in self.jobs):
+            return 1
+        return ks[0]
 
     def rowsplit_helpers(self, k: int) -> int:
         """Helper workgroups per (model, modality) of a row-split launch: the CUs the k slices leave idle join the Adam
@@ -608,8 +634,14 @@ class JobSet:
         return min(int(env), room) if env != "auto" else min(room, 12)
 
     def _launch_rowsplit(self, k: int, step0: int, n_steps: int, flags: int, helpers: Optional[int] = None):
-        for j in self.jobs:
+        for i, j in enumerate(self.jobs):
             j._ensure_rowsplit(k)
+            # (the kernel refuses such a job too, but only after the launch: say which limit, before anything runs)
+            if j._rs_ok_version != j._version:
+                if self.lib.nm_rowsplit_ok(C.byref(j.struct())) != 0:
+                    why = j.rowsplit_limit() or "not a plain cVAE / cVAE_multimodal model on the fused kernel"
+                    raise ValueError(f"job {i} of the set cannot run row-split (nm_rowsplit_ok): {why}")
+                j._rs_ok_version = j._version
         ptr = self._upload(k)
         h = self.rowsplit_helpers(k) if helpers is None else int(helpers)
         # start offsets over ~one step's time once the launch fills a good part of the chip (measured: 0.37 ns per
@@ -620,6 +652,7 @@ class JobSet:
         _lib.check(self.lib.nm_launch_rowsplit(ptr, len(self.jobs), len(self.jobs[0].kmods), int(k), h, int(step0), int(n_steps),
                                                int(flags), spread, _stream_ptr(self.device)), "nm_launch_rowsplit")
         self._split_pending = True
+        self._pending_kinds.add("rowsplit")
 
     def train(self, n_steps: int, scalar_tr: bool = False, profile: bool = False, split: Optional[bool] = None,
               rowsplit: Optional[int] = None, helpers: Optional[int] = None):
@@ -644,6 +677,7 @@ class JobSet:
             _lib.check(self.lib.nm_launch_split(ptr, len(self.jobs), parts, int(step0), int(n_steps), int(flags),
                                                 _stream_ptr(self.device)), "nm_launch_split")
             self._split_pending = True
+            self._pending_kinds.add("split")
         else:
             self._launch(step0, n_steps, 1, flags, scalar_tr)
         for j in self.jobs:
@@ -662,6 +696,7 @@ class JobSet:
             _lib.check(self.lib.nm_launch_split(ptr, len(self.jobs), len(self.jobs[0].kmods), int(s), 1, int(flags),
                                                 _stream_ptr(self.device)), "nm_launch_split")
             self._split_pending = True
+            self._pending_kinds.add("split")
         else:
             self._launch(s, 1, 1, flags, scalar_tr)
 

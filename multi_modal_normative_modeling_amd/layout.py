@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -117,6 +117,32 @@ class ModelSpec:
             return ([(m, True, self.dec_prefix(m, "health")) for m in range(self.M)] +
                     [(m, False, self.dec_prefix(m, "disease")) for m in range(self.M)])
         return [(m, True, self.dec_prefix(m)) for m in range(self.M)]
+
+
+def rowsplit_limit(spec: ModelSpec, kxs: Optional[Sequence[int]] = None) -> Optional[str]:
+    """The first of the row-split sweep's table limits (nm_rowsplit_ok, csrc/nmhip.hip) a kernel modality of `spec`
+    exceeds, as a message; None if every modality fits.  kxs: the packed operand width Kx of every kernel modality
+    (Table.Kx; default: the packing rule D + c + 1 rounded up to 32).  Same formulas and constants as the C check:
+    per modality ceil(D / 64) output chunks and ceil(Kx / 64) input chunks give the weight passes and vector segments,
+    and 2 D + 2 Z + 1 + 2 sum(H) is its vector elements (biases, logvar_out, alpha)."""
+    L, Z, sh = len(spec.hidden), spec.latent, sum(spec.hidden)
+    for i, (m, _, _) in enumerate(spec.kernel_modalities()):
+        D = spec.input_dims[m]
+        kx = int(kxs[i]) if kxs is not None else (D + spec.net_c_dim + 1 + 31) // 32 * 32
+        nck, nch = -(-D // 64), -(-kx // 64)
+        if nck + 2 * L + 1 + nch > _lib.NM_RS_MAX_PASSES:
+            return f"modality {i}: {nck + 2 * L + 1 + nch} weight passes > NM_RS_MAX_PASSES = {_lib.NM_RS_MAX_PASSES}"
+        if 2 * nck + 2 * L + 3 > _lib.NM_RS_MAX_VSEGS:
+            return f"modality {i}: {2 * nck + 2 * L + 3} vector segments > NM_RS_MAX_VSEGS = {_lib.NM_RS_MAX_VSEGS}"
+        vtot = 2 * D + 2 * Z + 1 + 2 * sh
+        if vtot > _lib.NM_RS_MAX_VEC:
+            return f"modality {i}: {vtot} vector elements > NM_RS_MAX_VEC = {_lib.NM_RS_MAX_VEC}"
+    return None
+
+
+def rowsplit_fits(spec: ModelSpec, kxs: Optional[Sequence[int]] = None) -> bool:
+    """Do the row-split sweep's tables hold every kernel modality of `spec` (rowsplit_limit)?  Pure: no GPU needed."""
+    return rowsplit_limit(spec, kxs) is None
 
 
 def tensor_table(spec: ModelSpec) -> List[Tuple[str, Tuple[int, ...]]]:

@@ -217,3 +217,75 @@ def test_spec_limits_raise():
         nm.ParamLayout(nm.ModelSpec([10, 10, 10], [200, 100], 100, 2, True, "mvtcae"))
     with pytest.raises(ValueError):
         nm.ParamLayout(nm.ModelSpec([10] * 5, [20], 5, 2))
+
+
+def _rs_probe(dims, L=2, Z=10, C_=29, H=(110, 110), combine="gpoe"):
+    """A descriptor nm_rowsplit_ok accepts but for the sweep's table limits (one D per modality)."""
+    j = _probe(M=len(dims), L=L, Z=Z, C_=C_, H=H, D=dims[0])
+    for m, d in enumerate(dims):
+        j.mod[m].D = d
+        j.mod[m].Kx = (d + C_ + 1 + 31) // 32 * 32
+    j.combine = _lib.NM_COMBINE[combine]
+    j.w_off, j.gpart, j.n_params, j.gpart_stride = -1, 4096, 256, 256
+    return j
+
+
+def test_rowsplit_table_limits_at_their_edges(lib):
+    """nm_rowsplit_ok and layout.rowsplit_fits at the row-split sweep's vector capacity (2 D + 2 Z + 1 + 2 sum(H) <= 3072):
+    one element below it is accepted, one above is refused -- past it the sweep would leave biases unsummed and unupdated."""
+    from multi_modal_normative_modeling_amd.layout import rowsplit_fits, rowsplit_limit
+    assert _lib.NM_RS_MAX_VEC == 3072 and _lib.NM_RS_MAX_PASSES == 128 and _lib.NM_RS_MAX_VSEGS == 144
+    for H, Z, d_ok in (((110, 110), 10, 1305), ((127, 127, 127), 64, 1090)):
+        assert 2 * d_ok + 2 * Z + 1 + 2 * sum(H) == 3071
+        for d, want in ((d_ok, True), (d_ok + 1, False)):
+            assert (lib.nm_rowsplit_ok(C.byref(_rs_probe([d], L=len(H), Z=Z, H=H))) == 0) == want, (H, d)
+            assert rowsplit_fits(nm.ModelSpec([d], list(H), Z, 29)) == want, (H, d)
+    assert "vector elements" in rowsplit_limit(nm.ModelSpec([1306], [110, 110], 10, 29))
+    # three modalities, one of them just over: the model is refused
+    assert lib.nm_rowsplit_ok(C.byref(_rs_probe([379, 1305, 379]))) == 0
+    assert lib.nm_rowsplit_ok(C.byref(_rs_probe([379, 1306, 379]))) == -20
+    assert rowsplit_fits(nm.ModelSpec([379, 1305, 379], [110, 110], 10, 29, True))
+    assert rowsplit_limit(nm.ModelSpec([379, 1306, 379], [110, 110], 10, 29, True)).startswith("modality 1:")
+
+
+def test_rowsplit_fits_agrees_with_c_check_on_a_grid(lib):
+    """layout.rowsplit_fits == (nm_rowsplit_ok == 0) on 240 seeded shapes: 1-4 modalities, 1-5 hidden layers up to 127
+    wide, latent up to 64, D from 16 to 4100, gPoE and PoE.
+
+    Why only the vector limit binds: it keeps 2 D <= 3072, so D <= 1533, i.e. at most 24 output chunks and (with
+    c <= 127) 26 input chunks of 64 columns; with at most NM_MAX_HID = 8 hidden layers that is <= 24 + 17 + 26 = 67
+    weight passes (limit 128) and <= 48 + 19 = 67 vector segments (limit 144).  Asserted below over the grid and for the
+    worst case, so that widening the vector capacity (more elements per thread, a k-aware check) has to revisit the
+    pass and segment tables."""
+    import random
+    from multi_modal_normative_modeling_amd.layout import rowsplit_fits
+    rng = random.Random(2024)
+    n_acc = n_ref = 0
+    worst_pass = worst_seg = 0
+    for _ in range(240):
+        M, L = rng.randint(1, 4), rng.randint(1, 5)
+        H = tuple(rng.randint(1, 127) for _ in range(L))
+        Z = rng.randint(1, 64)
+        C_ = rng.randint(1, min(63, 127 - Z))
+        edge = (3072 - 2 * Z - 1 - 2 * sum(H)) // 2           # the largest D the vector limit admits
+        dims = [rng.choice((rng.randint(16, 4100), edge + rng.randint(-2, 2), rng.randint(16, max(16, edge))))
+                for _ in range(M)]
+        dims = [min(4100, max(16, d)) for d in dims]
+        combine = rng.choice(("gpoe", "poe"))
+        spec = nm.ModelSpec(dims, list(H), Z, C_, True)
+        got = rowsplit_fits(spec)
+        want = lib.nm_rowsplit_ok(C.byref(_rs_probe(dims, L=L, Z=Z, C_=C_, H=H, combine=combine))) == 0
+        assert got == want, (dims, H, Z, C_, combine)
+        n_acc, n_ref = n_acc + want, n_ref + (not want)
+        for d in dims:
+            if 2 * d + 2 * Z + 1 + 2 * sum(H) <= _lib.NM_RS_MAX_VEC:
+                nck, nch = -(-d // 64), -(-((d + C_ + 1 + 31) // 32 * 32) // 64)
+                worst_pass = max(worst_pass, nck + 2 * L + 1 + nch)
+                worst_seg = max(worst_seg, 2 * nck + 2 * L + 3)
+    assert n_acc >= 40 and n_ref >= 40, (n_acc, n_ref)
+    assert worst_pass <= 67 and worst_seg <= 67, (worst_pass, worst_seg)
+    d_max = (_lib.NM_RS_MAX_VEC - 2 - 1 - 2) // 2              # Z = 1, one hidden unit
+    nck, nch = -(-d_max // 64), -(-((d_max + 127 + 1 + 31) // 32 * 32) // 64)
+    L = _lib.NM_MAX_HID
+    assert nck + 2 * L + 1 + nch <= 67 < _lib.NM_RS_MAX_PASSES
+    assert 2 * nck + 2 * L + 3 <= 67 < _lib.NM_RS_MAX_VSEGS

@@ -269,7 +269,7 @@ def test_rowsplit_handoff_timeout_is_reported():
     js = nm.JobSet([job])
     before = job.params.cpu().clone()
     js._launch_rowsplit(2, 0, 1, _lib.NM_F_BACKWARD | _lib.NM_F_ADAM | _lib.NM_F_FAULT_INJECT)
-    with pytest.raises(_lib.NmError):
+    with pytest.raises(_lib.NmError, match="NMHIP_ROWSPLIT=0"):       # (the switch that turns the row-split launch off)
         js.check_split_errors(block=True)
     torch.cuda.synchronize()
     assert torch.equal(job.params.cpu(), before)          # nothing computed from missing partials reached the parameters
