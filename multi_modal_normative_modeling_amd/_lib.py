@@ -6,7 +6,6 @@ caller gets an exception.  ``oracle/`` is never imported from here.
 from __future__ import annotations
 
 import ctypes as C
-import os
 from pathlib import Path
 
 NM_MAX_MOD = 8
@@ -49,8 +48,7 @@ NM_SYNC_ERR_SHAPE = 2
 NM_METRICS_MAX_N = 8192
 NM_METRICS_STRIDE = 8
 
-LIB_NAME = os.environ.get("NMHIP_LIB_NAME", "libnmhip.so")     # diagnostic builds (tools/ablate.py) override the name
-LIB_PATH = Path(__file__).resolve().parent / LIB_NAME
+LIB_PATH = Path(__file__).resolve().parent / "libnmhip.so"
 
 
 class NmModality(C.Structure):

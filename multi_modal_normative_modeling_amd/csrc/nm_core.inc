@@ -36,13 +36,6 @@
 
 namespace {
 
-// export stores of the forward-only step (out_loc / out_sqerr): plain.  1 = non-temporal, as in rounds 2-3, for the A/B: a
-// row's bytes of a chunk leave as 64-byte pieces from two waves; plain stores merge in L2 into full lines, the streaming
-// policy sent partial lines to memory (general kernel 497 -> 479 us per pass; the compact kernel 458 -> 328 us:
-// profiles/r04k_ab_devpass_export_stores.txt)
-#ifndef NM_EXPORT_NT
-#define NM_EXPORT_NT 0
-#endif
 constexpr int NWM = 2;           // wave grid: row groups
 constexpr int NWN = 4;           //            feature-tile groups
 constexpr int NWAVES = NWM * NWN;
@@ -255,14 +248,11 @@ __device__ __forceinline__ float lrelu(float v, bool nl, float slope) { return (
 // v_rcp_f32, 1 ulp each; exp through x log2(e): ~|x| 2^-24 relative on top) in place of the library's correctly rounded
 // sequences (~12 / ~15 / ~10 instructions each).  A fused element costs 5 exponentials, a logarithm and 5 divisions
 // forward and about three times that backward, and the element loops of a 64-row slice are bound by exactly these
-// instructions.  The results feed bf16 operands (z) and sums checked at 1e-4 (KL) -- NM_PRECISE_FUSION = 1 restores
-// the library calls for an A/B.
-#ifndef NM_PRECISE_FUSION
-#define NM_PRECISE_FUSION 0
-#endif
-__device__ __forceinline__ float fx_exp(float x) { return NM_PRECISE_FUSION ? expf(x) : __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
-__device__ __forceinline__ float fx_log(float x) { return NM_PRECISE_FUSION ? logf(x) : __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
-__device__ __forceinline__ float fx_rcp(float x) { return NM_PRECISE_FUSION ? 1.0f / x : __builtin_amdgcn_rcpf(x); }
+// instructions.  The results feed bf16 operands (z) and sums checked at 1e-4 (KL); the A/B against the library calls is
+// profiles/r04p_ab_fusion_math.txt.
+__device__ __forceinline__ float fx_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
+__device__ __forceinline__ float fx_log(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
+__device__ __forceinline__ float fx_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 
 __device__ __forceinline__ unsigned lds_addr(const void* p) {
   return (unsigned)(size_t)(const __attribute__((address_space(3))) void*)p;
@@ -2120,18 +2110,12 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
               }
               const int64_t gi = (int64_t)(c.row0 + r) * xp + dg0;
               if (!FWD_ONLY || dg0 < xp) {
-                if (MODE == 1) {                  // read back by the head phase of this workgroup
-                  if (md.out_loc) *(GAS f32x4*)(asg(md.out_loc) + gi) = lo;
-                  if (md.out_sqerr) *(GAS f32x4*)(asg(md.out_sqerr) + gi) = sq;
-                } else {
-#if NM_EXPORT_NT
-                  if (md.out_loc) __builtin_nontemporal_store(lo, (GAS f32x4*)(asg(md.out_loc) + gi));       // written once,
-                  if (md.out_sqerr) __builtin_nontemporal_store(sq, (GAS f32x4*)(asg(md.out_sqerr) + gi));   // read elsewhere
-#else
-                  if (md.out_loc) *(GAS f32x4*)(asg(md.out_loc) + gi) = lo;
-                  if (md.out_sqerr) *(GAS f32x4*)(asg(md.out_sqerr) + gi) = sq;
-#endif
-                }
+                // (plain stores, also where another kernel reads them: a row's bytes of a chunk leave as 64-byte pieces
+                //  from two waves; plain stores merge in L2 into full lines, non-temporal ones sent partial lines to
+                //  memory -- general kernel 497 -> 479 us per pass, the compact kernel 458 -> 328 us:
+                //  profiles/r04k_ab_devpass_export_stores.txt)
+                if (md.out_loc) *(GAS f32x4*)(asg(md.out_loc) + gi) = lo;
+                if (md.out_sqerr) *(GAS f32x4*)(asg(md.out_sqerr) + gi) = sq;
               }
               if (FWD_ONLY) rdev[FWD_ONLY ? rt : 0] += rs;
               else if (md.out_rowdev) atomicAdd(&c.rowacc[r], rs);
@@ -2749,13 +2733,11 @@ __global__ __launch_bounds__(WG) void nm_step_kernel(const nm_job_t* __restrict_
   // number of s_sleep(127), spread the workgroups over three steps instead of one -- tools/wg_spread.py).  The offset
   // is pure cost at the end of the launch, so short launches get less of it and very short ones none.
   {
-#ifndef NM_FWD_DEPHASE_DIV
-#define NM_FWD_DEPHASE_DIV 4
-#endif
-    // (forward only, many row tiles: the first workgroup of every CU -- tile 0 of each job -- starts late by a fraction
-    //  of a tile's time, the following tiles inherit the stagger)
+    // (forward only, many row tiles: the first workgroup of every CU -- tile 0 of each job -- starts late by a quarter
+    //  of the offset, the following tiles inherit the stagger)
+    constexpr int FWD_DEPHASE_DIV = 4;
     int us = steps_per_tile >= 64 ? J->dephase : (steps_per_tile >= 8 ? (J->dephase >> 2) : 0);
-    if (MODE == 3) us = (NM_FWD_DEPHASE_DIV > 0 && tile_idx == 0 && gridDim.y > 1) ? J->dephase / NM_FWD_DEPHASE_DIV : 0;
+    if (MODE == 3) us = (tile_idx == 0 && gridDim.y > 1) ? J->dephase / FWD_DEPHASE_DIV : 0;
     if (us > 0) {
       const unsigned long long t0 = __builtin_amdgcn_s_memrealtime(), ticks = 100ull * (unsigned long long)min(us, 20000);
       while (__builtin_amdgcn_s_memrealtime() - t0 < ticks) __builtin_amdgcn_s_sleep(16);

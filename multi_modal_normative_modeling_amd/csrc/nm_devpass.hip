@@ -19,18 +19,10 @@
 // those, models with several experts, a first hidden layer wider than 112 or a latent wider than 32 stay on nm_forward.
 #include "nm_core.inc"
 
-// export stores: plain.  NM_DV_NT = 1 makes them non-temporal ("written once, read by another kernel") for the A/B that
-// decided it: 458 us per pass non-temporal against 328 us plain (profiles/r04k_ab_devpass_export_stores.txt) -- a row's
-// 256 bytes of a chunk leave as four 64-byte stores; plain stores merge in L2 into full lines before they go to memory,
-// the streaming policy sent them on as partial lines.
-#ifndef NM_DV_NT
-#define NM_DV_NT 0
-#endif
-#if NM_DV_NT
-#define NM_DV_STORE(v, p) __builtin_nontemporal_store(v, p)
-#else
-#define NM_DV_STORE(v, p) (*(p) = (v))
-#endif
+// export stores: plain, not non-temporal ("written once, read by another kernel"), as the A/B decided: 458 us per pass
+// non-temporal against 328 us plain (profiles/r04k_ab_devpass_export_stores.txt) -- a row's 256 bytes of a chunk leave
+// as four 64-byte stores; plain stores merge in L2 into full lines before they go to memory, the streaming policy sent
+// them on as partial lines.
 constexpr int DV_RT = 4;
 constexpr int DV_ROWS = DV_RT * 32;                                   // 128
 constexpr int DV_P_BYTES = DV_ROWS * LDP * 2;                         // 34,816
@@ -255,8 +247,8 @@ __global__ __launch_bounds__(WG, 4) void nm_devpass_kernel(const nm_job_t* __res
       if (d0 + ft * 16 < xp) {                      // wave-uniform
         if (dg0 < xp) {
           const int64_t gi = (int64_t)(row0 + orow) * xp + dg0;
-          if (md.out_loc) NM_DV_STORE(lo, (GAS f32x4*)(asg(md.out_loc) + gi));
-          if (md.out_sqerr) NM_DV_STORE(sq, (GAS f32x4*)(asg(md.out_sqerr) + gi));
+          if (md.out_loc) *(GAS f32x4*)(asg(md.out_loc) + gi) = lo;
+          if (md.out_sqerr) *(GAS f32x4*)(asg(md.out_sqerr) + gi) = sq;
         }
         stores_prev += (md.out_loc ? 1 : 0) + (md.out_sqerr ? 1 : 0);
       }

@@ -32,10 +32,7 @@
 // hand-waited with a counted vmcnt -- per pass a wave has only a tile or two, so a loop per pass with the compiler's
 // waits costs one exposed memory round trip per pass (the first version: 90 k cycles of a 345 k-cycle step).  The passes'
 // geometries sit in a small table in S (all of P / Q / S is dead during the sweep), built by one thread per pass.
-#ifndef NM_SW_DEPTH
-#define NM_SW_DEPTH 4
-#endif
-constexpr int SW_DEPTH = NM_SW_DEPTH;
+constexpr int SW_DEPTH = 4;
 constexpr int SW_NV = 3;                 // vector elements per thread (biases, logvar_out, alpha: 2 D + ... per modality)
 struct SwRec { int w_off, KT, kt0, nkt; float rnkt; int sh_pitch; GAS char* sh; };     // 32 bytes
 // One vector parameter segment: elements [idx0, idx0 + n) of the master (a bias, a chunk of logvar_out, alpha), with an
@@ -189,11 +186,7 @@ __device__ __forceinline__ void rs_sweep(const Ctx& cc, int m, u32x4 tpre, int K
   for (int i = 0; i < SW_NV; ++i) {
     const int e0 = (i * KH + c.rsq) * WG + c.tid;
     vidx[i] = -1; vcopy[i] = nullptr; vp[i] = 0.f; vm[i] = 0.f; vv[i] = 0.f;
-#ifdef NM_RS_NO_VEC
-    if (false) {
-#else
     if (e0 < tab->vtot) {
-#endif
       int sgi = 0;
       for (int sI = 1; sI < tab->nseg; ++sI) sgi += (e0 >= tab->vec[sI].off) ? 1 : 0;
       const SwVec sg = tab->vec[sgi];
@@ -362,18 +355,6 @@ __global__ __launch_bounds__(WG) void nm_rs_kernel(const nm_job_t* __restrict__ 
   }
   GAS char* const gtab = c.ws + wl.rs_tab + (int64_t)part * WS_RS_TAB_BYTES;    // (helpers: slice 0's tables, complete at D below)
   if (!helper) rs_build_tables(c, part, gtab);
-#ifdef NM_RS_DEBUG_TABLES
-  {   // diagnostic build: dump the table header of workgroup (job 0, part 0, slice 0) into the loss log and leave
-    if (blockIdx.x == 0 && c.tid == 0 && J->loss_log) {
-      const GAS int* t = (const GAS int*)gtab;
-      gf32 row = asg(J->loss_log);
-      for (int i = 0; i < 16; ++i) row[i] = (float)t[i];
-      const GAS int* v = (const GAS int*)(gtab + 544 + NM_RS_MAX_PASSES * 32);
-      for (int i = 0; i < 16; ++i) row[16 + i] = (float)v[i];
-    }
-    return;
-  }
-#endif
   GAS unsigned* const sync0 = (GAS unsigned*)(c.ws0 + wl.sync);
   GAS unsigned* const sync_c = sync0 + WS_SYNC_C_WORD;
   GAS unsigned* const sync_d = sync0 + WS_SYNC_D_WORD + part;

@@ -8,6 +8,7 @@ PyTorch is used for device memory and streams only; all arithmetic is in libnmhi
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 import os
 import zlib
@@ -459,6 +460,10 @@ class Job:
         return math.ceil(self.tables[0].N / BATCH)
 
 
+# the launches that leave hand-off error words behind (nm_split_errors), by the kind their error message names
+_HANDOFF_KINDS = {"nm_launch_split": "split", "nm_launch_rowsplit": "rowsplit"}
+
+
 class JobSet:
     """Device array of job descriptors = the unit one launch runs (one workgroup per job)."""
 
@@ -473,9 +478,16 @@ class JobSet:
         self.lib = _lib.load()
         self._dev = None
         self._sig = None
+        self._dephase_vals = None        # the start offsets this set last assigned (_set_dephase)
         self._split_pending = False      # a split launch has run since the hand-off error words were last read
         self._pending_kinds = set()      # ... of which kinds ("split", "rowsplit"): the error message names their switch
         self._err_kinds = set()          # the kinds behind the error words in flight
+        self._err_inflight = None        # (event, pinned host copy) of the error words being fetched
+        self._err_dev = self._err_host = None
+
+    @functools.cached_property
+    def _cus(self) -> int:
+        return torch.cuda.get_device_properties(self.device).multi_processor_count
 
     def check_split_errors(self, block: bool = True):
         """Raise NmError if a hand-off of a split launch (one workgroup per modality) timed out: the job's workgroups left
@@ -483,9 +495,8 @@ class JobSet:
         copy into pinned memory behind the launch); block=True -- everything that reads results: assert_finite, losses,
         sweep.save_model -- waits for the words of every split launch so far; block=False -- before the next launch of
         this set -- only looks at words that have already arrived, so a loop of launches is never stalled by the check."""
-        infl = getattr(self, "_err_inflight", None)
-        if infl is not None:
-            ev, host = infl
+        if self._err_inflight is not None:
+            ev, host = self._err_inflight
             if block:
                 ev.synchronize()
             if ev.query():
@@ -506,9 +517,9 @@ class JobSet:
                     raise _lib.NmError(f"{what} launch: the hand-off between the workgroups of job(s) {bad[:8]} timed out "
                                        f"(the parts of a model must all be resident at once: another stream or process "
                                        f"occupying CUs breaks that); their parameters are not valid -- re-run with {switch}")
-        if self._split_pending and self._dev is not None and getattr(self, "_err_inflight", None) is None:
+        if self._split_pending and self._dev is not None and self._err_inflight is None:
             n = len(self.jobs)
-            if getattr(self, "_err_dev", None) is None:
+            if self._err_dev is None:
                 self._err_dev = torch.zeros(n, dtype=torch.int32, device=self.device)
                 self._err_host = torch.zeros(n, dtype=torch.int32).pin_memory()
             _lib.check(self.lib.nm_split_errors(self._dev.data_ptr(), n, self._err_dev.data_ptr(), 1,
@@ -525,29 +536,20 @@ class JobSet:
     def _set_dephase(self):
         """Start offsets of the jobs of a long launch (nm_job_t.dephase): workgroup b lands on XCD b mod 8 (observed
         placement, speed only), so the 32 jobs that share an XCD -- its L2 and its link to memory -- are spread
-        evenly over one step, and the XCDs are staggered against each other by a fraction of that spacing.
-        NMHIP_DEPHASE = 0 switches it off, "xcd" is the round-1 scheme (one offset per XCD)."""
-        mode = os.environ.get("NMHIP_DEPHASE", "cu")
-        scale = float(os.environ.get("NMHIP_DEPHASE_SCALE", "1"))
-        n = len(self.jobs)
-        key = (mode, scale, n)
-        vals = getattr(self, "_dephase_vals", None)
+        evenly over one step, and the XCDs are staggered against each other by a fraction of that spacing.  Sets of
+        fewer than 16 jobs start at once."""
+        vals = self._dephase_vals
         # (host time of a launch matters: it precedes the launch -- so the offsets are computed once per set; a job that
         #  another set has re-timed in between is noticed by comparing the values this set assigned)
-        if getattr(self, "_dephase_key", None) == key and vals is not None and all(j.dephase_sleeps == v for j, v in zip(self.jobs, vals)):
+        if vals is not None and all(j.dephase_sleeps == v for j, v in zip(self.jobs, vals)):
             return
-        self._dephase_key = key
+        n = len(self.jobs)
+        per_xcd = max(1, (n + 7) // 8)
         for b, j in enumerate(self.jobs):
             # ~2.05 ns per parameter and step with the chip full (measured: 0.73 ms for 355 k parameters)
             step_us = j.layout.n_params * 2.05e-3
-            if mode == "0" or n < 16:
-                frac = 0.0
-            elif mode == "xcd":
-                frac = (b & 7) / 8
-            else:
-                per_xcd = max(1, (n + 7) // 8)
-                frac = ((b >> 3) + (b & 7) / 8) / per_xcd
-            s = int(round(step_us * frac * scale))
+            frac = 0.0 if n < 16 else ((b >> 3) + (b & 7) / 8) / per_xcd
+            s = int(round(step_us * frac))
             if s != j.dephase_sleeps:
                 j.dephase_sleeps = s
                 j._version += 1
@@ -575,19 +577,23 @@ class JobSet:
                 j.shadow_dirty = False
         return self._dev.data_ptr()
 
-    def _launch(self, step0, steps_per_tile, n_tiles, flags, scalar_tr=False):
+    def _issue(self, entry: str, n_tiles: int, *args):
+        """Every launch of the set: the descriptors up with n_tiles workspace tiles per job, then the C entry point
+        `entry`(jobs, n_jobs, *args, stream).  A split / row-split launch leaves its hand-off error words to be read."""
         ptr = self._upload(n_tiles)
-        fn = self.lib.nm_launch_wide if self.wide else (self.lib.nm_launch_scalar_tr if scalar_tr else self.lib.nm_launch)
-        _lib.check(fn(ptr, len(self.jobs), int(step0), int(steps_per_tile), int(n_tiles), int(flags),
-                      _stream_ptr(self.device)), "nm_launch_wide" if self.wide else "nm_launch")
+        _lib.check(getattr(self.lib, entry)(ptr, len(self.jobs), *map(int, args), _stream_ptr(self.device)), entry)
+        kind = _HANDOFF_KINDS.get(entry)
+        if kind is not None:
+            self._split_pending = True
+            self._pending_kinds.add(kind)
+
+    def _launch(self, step0, steps_per_tile, n_tiles, flags, scalar_tr=False):
+        entry = "nm_launch_wide" if self.wide else ("nm_launch_scalar_tr" if scalar_tr else "nm_launch")
+        self._issue(entry, n_tiles, step0, steps_per_tile, n_tiles, flags)
 
     def _launch_split(self, step0, n_steps, flags):
         """nm_launch_split: every model as one workgroup per modality (small sets; see split_parts)."""
-        ptr = self._upload(1)
-        _lib.check(self.lib.nm_launch_split(ptr, len(self.jobs), len(self.jobs[0].kmods), int(step0), int(n_steps), int(flags),
-                                            _stream_ptr(self.device)), "nm_launch_split")
-        self._split_pending = True
-        self._pending_kinds.add("split")
+        self._issue("nm_launch_split", 1, len(self.jobs[0].kmods), step0, n_steps, flags)
 
     def split_parts(self) -> int:
         """Workgroups per model for a training launch: the M modalities of a model as separate workgroups when the
@@ -597,10 +603,7 @@ class JobSet:
         mode = os.environ.get("NMHIP_SPLIT", "auto")
         if mode == "0" or M < 2 or self.wide or any(len(j.kmods) != M for j in self.jobs):
             return 1
-        if not hasattr(self, "_cus"):
-            self._cus = torch.cuda.get_device_properties(self.device).multi_processor_count
-        cus = self._cus
-        fits = (len(self.jobs) + 7) // 8 * 8 * M <= cus
+        fits = (len(self.jobs) + 7) // 8 * 8 * M <= self._cus
         return M if fits else 1
 
     def rowsplit_k(self) -> int:
@@ -611,8 +614,6 @@ class JobSet:
         M = len(self.jobs[0].kmods)
         if mode == "0" or self.wide:
             return 1
-        if not hasattr(self, "_cus"):
-            self._cus = torch.cuda.get_device_properties(self.device).multi_processor_count
         groups = (len(self.jobs) * M + 7) // 8 * 8
         kmax = int(mode) if mode in ("2", "4") else 4
         # (the set size first: a full chip's set -- every train() call of the headline -- skips the per-job checks)
@@ -627,8 +628,6 @@ class JobSet:
         k = 4): 6 helpers give all of the gain, beyond 12 the extra arrivals at the hand-off cost what the shorter sweep
         saves -- so at most 12.  NMHIP_RS_HELPERS pins it."""
         env = os.environ.get("NMHIP_RS_HELPERS", "auto")
-        if not hasattr(self, "_cus"):
-            self._cus = torch.cuda.get_device_properties(self.device).multi_processor_count
         groups = (len(self.jobs) * len(self.jobs[0].kmods) + 7) // 8 * 8
         room = max(0, min(self._cus // groups, 32) - k)
         return min(int(env), room) if env != "auto" else min(room, 12)
@@ -642,63 +641,70 @@ class JobSet:
                     why = j.rowsplit_limit() or "not a plain cVAE / cVAE_multimodal model on the fused kernel"
                     raise ValueError(f"job {i} of the set cannot run row-split (nm_rowsplit_ok): {why}")
                 j._rs_ok_version = j._version
-        ptr = self._upload(k)
         h = self.rowsplit_helpers(k) if helpers is None else int(helpers)
         # start offsets over ~one step's time once the launch fills a good part of the chip (measured: 0.37 ns per
-        # parameter and step for one model at k = 4); NMHIP_RS_SPREAD scales it, 0 switches it off
-        wgs = len(self.jobs) * len(self.jobs[0].kmods) * k
-        scale = float(os.environ.get("NMHIP_RS_SPREAD", "1"))
-        spread = int(self.jobs[0].layout.n_params * 0.37e-3 * (4 / k) * scale) if wgs >= 96 else 0
-        _lib.check(self.lib.nm_launch_rowsplit(ptr, len(self.jobs), len(self.jobs[0].kmods), int(k), h, int(step0), int(n_steps),
-                                               int(flags), spread, _stream_ptr(self.device)), "nm_launch_rowsplit")
-        self._split_pending = True
-        self._pending_kinds.add("rowsplit")
+        # parameter and step for one model at k = 4)
+        M = len(self.jobs[0].kmods)
+        spread = int(self.jobs[0].layout.n_params * 0.37e-3 * (4 / k)) if len(self.jobs) * M * k >= 96 else 0
+        self._issue("nm_launch_rowsplit", k, M, k, h, step0, n_steps, flags, spread)
+
+    def _training_form(self, split: Optional[bool], rowsplit: Optional[int]):
+        """The form of a training launch: ("rowsplit", k row slices per (model, modality)), ("split", one workgroup per
+        modality) or ("whole", one workgroup per model).  rowsplit=None: rowsplit_k() unless split is given; split=None:
+        split_parts()."""
+        k = (self.rowsplit_k() if split is None else 1) if rowsplit is None else int(rowsplit)
+        if k > 1:
+            return "rowsplit", k
+        parts = self.split_parts() if split is None else (len(self.jobs[0].kmods) if split else 1)
+        return ("split", parts) if parts > 1 else ("whole", 1)
+
+    def _launch_form(self, form, step0: int, n_steps: int, flags: int, helpers: Optional[int], scalar_tr: bool):
+        kind, k = form
+        if kind == "rowsplit":
+            self._launch_rowsplit(k, step0, n_steps, flags, helpers)
+        elif kind == "split":
+            self._launch_split(step0, n_steps, flags)
+        else:
+            self._launch(step0, n_steps, 1, flags, scalar_tr)
+
+    def _check_jobs(self, head: Optional[str] = None, caller: str = "", at_step: bool = True) -> int:
+        """Preconditions of a launch: every job at the same step (at_step; returned) and, for a head model's step
+        (head = "regression" / "endtoend"), jobs of that kind with their targets set and the same batches per epoch."""
+        step0 = self.jobs[0].step
+        for j in self.jobs:
+            if head == "regression" and (j.spec.kind != "regression" or j.fi_target is None):
+                raise ValueError(f"{caller} needs regression jobs with fi_target set")
+            if head == "endtoend" and (j.spec.kind != "endtoend" or not j.spec.classifier_layers or j.labels is None):
+                raise ValueError(f"{caller} needs end-to-end jobs with a classifier and labels set")
+            if at_step and j.step != step0:
+                raise ValueError("jobs of one set must be at the same step")
+        if head is not None and any(j.batches_per_epoch != self.jobs[0].batches_per_epoch for j in self.jobs):
+            raise ValueError("jobs of one set must have the same number of batches")
+        return step0
+
+    def _advance(self, n_steps: int):
+        for j in self.jobs:
+            j.step += n_steps
+            j.t += n_steps
 
     def train(self, n_steps: int, scalar_tr: bool = False, profile: bool = False, split: Optional[bool] = None,
               rowsplit: Optional[int] = None, helpers: Optional[int] = None):
         """n_steps fused train steps per job in ONE launch (forward + ELBO + backward + Adam).  Small sets put several
         workgroups behind a model: k row slices per (model, modality) (rowsplit=None: rowsplit_k(); results agree with the
         one-workgroup launch to fp32 summation order), else one workgroup per modality (split=None: automatically;
-        bit-identical to the one-workgroup launch)."""
-        step0 = self.jobs[0].step
-        if any(j.step != step0 for j in self.jobs):
-            raise ValueError("jobs of one set must be at the same step")
+        bit-identical to the one-workgroup launch).  scalar_tr: the whole-batch launch on the scalar-loader kernel."""
+        step0 = self._check_jobs()
         flags = _lib.NM_F_BACKWARD | _lib.NM_F_ADAM | (_lib.NM_F_PROFILE if profile else 0)
-        k = (self.rowsplit_k() if split is None else 1) if rowsplit is None else int(rowsplit)
-        if k > 1 and not scalar_tr:
-            self._launch_rowsplit(k, step0, n_steps, flags, helpers)
-            for j in self.jobs:
-                j.step += n_steps
-                j.t += n_steps
-            return
-        parts = self.split_parts() if split is None else (len(self.jobs[0].kmods) if split else 1)
-        if parts > 1 and not scalar_tr:
-            ptr = self._upload(1)
-            _lib.check(self.lib.nm_launch_split(ptr, len(self.jobs), parts, int(step0), int(n_steps), int(flags),
-                                                _stream_ptr(self.device)), "nm_launch_split")
-            self._split_pending = True
-            self._pending_kinds.add("split")
-        else:
-            self._launch(step0, n_steps, 1, flags, scalar_tr)
-        for j in self.jobs:
-            j.step += n_steps
-            j.t += n_steps
+        form = ("whole", 1) if scalar_tr else self._training_form(split, rowsplit)
+        self._launch_form(form, step0, n_steps, flags, helpers, scalar_tr)
+        self._advance(n_steps)
 
     def grads(self, step: Optional[int] = None, export: bool = True, scalar_tr: bool = False, split: bool = False,
               rowsplit: int = 1, helpers: Optional[int] = None):
         """forward + loss + backward for one step; gradients land in job.grads (no update)."""
         s = self.jobs[0].step if step is None else step
         flags = _lib.NM_F_BACKWARD | _lib.NM_F_GRADS | (_lib.NM_F_EXPORT if export else 0)
-        if rowsplit > 1:
-            self._launch_rowsplit(rowsplit, s, 1, flags, helpers)
-        elif split:
-            ptr = self._upload(1)
-            _lib.check(self.lib.nm_launch_split(ptr, len(self.jobs), len(self.jobs[0].kmods), int(s), 1, int(flags),
-                                                _stream_ptr(self.device)), "nm_launch_split")
-            self._split_pending = True
-            self._pending_kinds.add("split")
-        else:
-            self._launch(s, 1, 1, flags, scalar_tr)
+        self._launch_form(self._training_form(split, rowsplit), s, 1, flags, helpers, scalar_tr)
 
     def devpass_ok(self) -> bool:
         """Can the set's deviation pass run on the compact kernel (nm_devpass: 128-row tiles, two workgroups per CU)?
@@ -708,15 +714,14 @@ class JobSet:
             return False
         return all(j.devpass_ok() for j in self.jobs)
 
-    def forward(self, tile0: int = 0, n_tiles: Optional[int] = None, loss: bool = True):
+    def forward(self, tile0: int = 0, n_tiles: Optional[int] = None, loss: bool = True, trace: bool = False):
         """forward-only over row tiles (one workgroup per (job, 256-row tile)); fills the exports.  loss=False: only the
         per-ROI / per-subject deviations and the reconstruction are wanted (the deviation pass of
-        ..._regression.py:163-192) -- one-expert sets then run on the compact kernel, two workgroups per CU."""
+        ..._regression.py:163-192) -- one-expert sets then run on the compact kernel, two workgroups per CU.  trace: the
+        compact kernel records its phase cycles (nm_trace_read_dv)."""
         nt = self.jobs[0].tables[0].n_tiles if n_tiles is None else n_tiles
         if not loss and self.devpass_ok():
-            ptr = self._upload(1)
-            _lib.check(self.lib.nm_devpass(ptr, len(self.jobs), int(tile0) * 2, int(nt) * 2, int(getattr(self, "_dv_flags", 0)),
-                                           _stream_ptr(self.device)), "nm_devpass")
+            self._issue("nm_devpass", 1, tile0 * 2, nt * 2, _lib.NM_F_TRACE if trace else 0)
             return
         self._launch(tile0, 1, nt, _lib.NM_F_EXPORT)
 
@@ -726,28 +731,34 @@ class JobSet:
         fills out_fi_pred and loss_log[..][NM_LOSS_REG]; with backward also job.reg_dres (d MSE / d x_hat, bf16 chunk
         images) and the regressor's gradients / Adam update (cVAE.py:2309-2346).  Training runs through
         train_regression (one launch for trunk and head)."""
-        ptr = self._upload(max(n_tiles, 1))
         flags = (_lib.NM_F_BACKWARD if backward else 0) | (_lib.NM_F_GRADS if grads and backward else 0) | \
                 (_lib.NM_F_ADAM if adam and backward else 0)
-        _lib.check(self.lib.nm_head_regression(ptr, len(self.jobs), int(step), int(tile0), int(n_tiles), int(flags),
-                                               _stream_ptr(self.device)), "nm_head_regression")
+        self._issue("nm_head_regression", max(n_tiles, 1), step, tile0, n_tiles, flags)
 
     def head_classifier(self, backward: bool, grads: bool = True, adam: bool = False, bn_stats: bool = False,
                         step: int = 0, tile0: int = 0, n_tiles: int = 1):
         """nm_head_classifier on the latent / deviations a preceding NM_F_EXPORT launch exported: fills out_logits
         and loss_log[..][NM_LOSS_CE / NM_LOSS_CONTRAST]; with backward also dz_extra, the hinge row coefficients
         and the classifier's gradients / Adam update (cVAE.py:2004-2018, 2140-2200)."""
-        ptr = self._upload(max(n_tiles, 1))
         flags = (_lib.NM_F_BACKWARD if backward else 0) | (_lib.NM_F_GRADS if grads and backward else 0) | \
                 (_lib.NM_F_ADAM if adam and backward else 0) | (_lib.NM_F_BNSTATS if bn_stats else 0)
-        _lib.check(self.lib.nm_head_classifier(ptr, len(self.jobs), int(step), int(tile0), int(n_tiles), int(flags),
-                                               _stream_ptr(self.device)), "nm_head_classifier")
+        self._issue("nm_head_classifier", max(n_tiles, 1), step, tile0, n_tiles, flags)
 
     def _train_head(self, step0: int, n_steps: int, flags: int = 0):
         """nm_train_steps_head: all n_steps in one persistent launch, the trunk's forward evaluated once per step."""
-        ptr = self._upload(1)
-        _lib.check(self.lib.nm_train_steps_head(ptr, len(self.jobs), int(step0), int(n_steps), int(flags),
-                                                _stream_ptr(self.device)), "nm_train_steps_head")
+        self._issue("nm_train_steps_head", 1, step0, n_steps, flags)
+
+    def _head_step(self, head: str, s: int, adam: bool):
+        """One head-model step as three launches -- the form a trunk on the general-shape path or a classifier with blocks
+        wider than 128 runs in: the trunk's forward with its exports, the head (forward, backward, its Adam update or
+        gradients, the extra gradient it hands the trunk), the trunk's backward + Adam / gradients with that gradient."""
+        tile0 = s % self.jobs[0].batches_per_epoch
+        self._launch(s, 1, 1, _lib.NM_F_EXPORT)
+        if head == "regression":
+            self.head_regression(backward=True, grads=not adam, adam=adam, step=s, tile0=tile0)
+        else:
+            self.head_classifier(backward=True, grads=not adam, adam=adam, bn_stats=True, step=s, tile0=tile0)
+        self._launch(s, 1, 1, _lib.NM_F_BACKWARD | (_lib.NM_F_ADAM if adam else _lib.NM_F_GRADS))
 
     def train_endtoend(self, n_steps: int, fused: bool = True):
         """n_steps train steps of cVAE_multimodal_endtoend jobs on the device, no host sync (the loop of
@@ -758,66 +769,42 @@ class JobSet:
         fused=False: the three-launches-per-step form it replaced (trunk forward twice), kept as a cross-check -- and the
         form a trunk on the general-shape path or a classifier with blocks wider than 128 (-Layers "256 128 64") runs in:
         the persistent head kernel holds the one-tile classifier only."""
-        step0 = self.jobs[0].step
+        step0 = self._check_jobs("endtoend", "train_endtoend")
         for j in self.jobs:
-            if j.spec.kind != "endtoend" or not j.spec.classifier_layers or j.labels is None:
-                raise ValueError("train_endtoend needs end-to-end jobs with a classifier and labels set")
-            if j.step != step0:
-                raise ValueError("jobs of one set must be at the same step")
             j.cls_train, j.cls_use_mu = True, False
             j.prepare_classifier()
-        nb = self.jobs[0].batches_per_epoch
-        if any(j.batches_per_epoch != nb for j in self.jobs):
-            raise ValueError("jobs of one set must have the same number of batches")
         tiled_head = any(w > 128 for j in self.jobs for w in j.spec.classifier_layers)
         if fused and not self.wide and not tiled_head:
             self._train_head(step0, n_steps, _lib.NM_F_BNSTATS)
         else:
             for s in range(step0, step0 + n_steps):
-                self._launch(s, 1, 1, _lib.NM_F_EXPORT)
-                self.head_classifier(backward=True, grads=False, adam=True, bn_stats=True, step=s, tile0=s % nb)
-                self._launch(s, 1, 1, _lib.NM_F_BACKWARD | _lib.NM_F_ADAM)
-        for j in self.jobs:
-            j.step += n_steps
-            j.t += n_steps
+                self._head_step("endtoend", s, adam=True)
+        self._advance(n_steps)
 
     def train_regression(self, n_steps: int):
         """n_steps train steps of cVAE_multimodal_regression jobs in one persistent launch, no host sync (the loop of
         multimodal_kfold_train_cvae_supervised_regression.py:112-125): per step (i) the trunk's forward, leaving the
         residuals as bf16 chunk images, (ii) the regressor: forward, MSE, backward, its Adam update, d MSE / d x_hat,
-        (iii) the trunk's backward + Adam with that extra gradient (nm_train_steps_head)."""
-        step0 = self.jobs[0].step
+        (iii) the trunk's backward + Adam with that extra gradient (nm_train_steps_head).  A trunk on the general-shape
+        path runs the three-launch form (_head_step)."""
+        step0 = self._check_jobs("regression", "train_regression")
         for j in self.jobs:
-            if j.spec.kind != "regression" or j.fi_target is None:
-                raise ValueError("train_regression needs regression jobs with fi_target set")
-            if j.step != step0:
-                raise ValueError("jobs of one set must be at the same step")
             j.prepare_regression()
-        nb = self.jobs[0].batches_per_epoch
-        if any(j.batches_per_epoch != nb for j in self.jobs):
-            raise ValueError("jobs of one set must have the same number of batches")
         if self.wide:
-            # a trunk on the general-shape path: three launches per step (residual images out, the regressor with its
-            # update and d MSE / d x_hat, the trunk's backward + Adam with that extra gradient)
             for s in range(step0, step0 + n_steps):
-                self._launch(s, 1, 1, _lib.NM_F_EXPORT)
-                self.head_regression(backward=True, grads=False, adam=True, step=s, tile0=s % nb)
-                self._launch(s, 1, 1, _lib.NM_F_BACKWARD | _lib.NM_F_ADAM)
+                self._head_step("regression", s, adam=True)
         else:
             self._train_head(step0, n_steps)
-        for j in self.jobs:
-            j.step += n_steps
-            j.t += n_steps
+        self._advance(n_steps)
 
-    def grads_head(self, step: int = 0, bn_stats: bool = False):
-        """Gradients of one head-model step's total loss into job.grads, no update (the eager facade's backward)."""
-        if self.wide:                      # (regression model on a general-shape trunk: the three-launch form)
-            nb = self.jobs[0].batches_per_epoch
-            self._launch(step, 1, 1, _lib.NM_F_EXPORT)
-            self.head_regression(backward=True, grads=True, adam=False, step=step, tile0=step % nb)
-            self._launch(step, 1, 1, _lib.NM_F_BACKWARD | _lib.NM_F_GRADS)
-            return
-        self._train_head(step, 1, _lib.NM_F_GRADS | (_lib.NM_F_BNSTATS if bn_stats else 0))
+    def grads_head(self, step: int = 0):
+        """Gradients of one regression-model step's total loss into job.grads, no update (the eager facade's backward);
+        a trunk on the general-shape path runs the three-launch form."""
+        self._check_jobs("regression", "grads_head", at_step=False)
+        if self.wide:
+            self._head_step("regression", step, adam=False)
+        else:
+            self._train_head(step, 1, _lib.NM_F_GRADS)
 
     def losses(self) -> torch.Tensor:
         """[n_jobs, loss_cap, 8] on the host."""

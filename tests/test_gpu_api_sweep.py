@@ -1482,6 +1482,36 @@ def test_regression_training_on_a_wide_trunk_matches_oracle_trajectory():
         assert float((sd[k] - Pr[k]).abs().max()) <= 2.0 * lr * 2 + 1e-6, k
 
 
+def test_grads_head_refuses_jobs_without_a_regression_head():
+    """JobSet.grads_head runs the regression head: a set of other models, or of regression models without fi_target, raises
+    ValueError before anything is launched -- on the general-shape path, whose three launches would otherwise run the
+    regressor on whatever they were given, and on the fused path.  With fi_target set the same set's gradients come back."""
+    g = torch.Generator().manual_seed(23)
+    B, cdim = 200, 2
+    c = torch.rand(B, cdim, generator=g)
+    for dims, hidden in (([150, 90], [200, 144]), ([60, 50], [32, 16])):
+        xs = [torch.randn(B, d, generator=g) for d in dims]
+        for kind in ("multimodal", "regression"):
+            spec = nm.ModelSpec(dims, hidden, 8, cdim, True, kind)
+            job = nm.Job(spec, [nm.Table(x, c, DEV) for x in xs], combine="gpoe",
+                         state=nm.ParamLayout(spec).init_reference_rule(3))
+            job.set_eps(torch.randn(1, 256, 8, generator=g))
+            job.grads.fill_(float("nan"))
+            js = nm.JobSet([job])
+            assert js.wide == (hidden[0] > 127)
+            with pytest.raises(ValueError, match="grads_head needs regression jobs with fi_target set"):
+                js.grads_head(0)
+            torch.cuda.synchronize()
+            assert bool(job.grads.isnan().all()), (dims, kind)
+            if kind == "regression":
+                job.set_fi(torch.randn(B, generator=g).numpy())
+                job.grads.zero_()
+                js.grads_head(0)
+                torch.cuda.synchronize()
+                js.assert_finite()
+                assert bool(job.grads.isfinite().all()) and float(job.grads.abs().max()) > 0, dims
+
+
 def test_endtoend_training_on_a_wide_trunk_matches_oracle_trajectory():
     """cVAE_multimodal_endtoend with hidden widths beyond the fused tile (an -H list of commands_list9_endtoend.sh:24): the trunk
     runs on the general-shape path, the classifier head in its own kernel, three launches per step (JobSet.train_endtoend);

@@ -37,9 +37,7 @@ if not a.general:
     from multi_modal_normative_modeling_amd import _lib
     lib = _lib.load(); buf = (C.c_ulonglong * 512)()
     lib.nm_trace_read_dv(buf, 1)
-    djs._dv_flags = _lib.NM_F_TRACE
-    djs.forward(loss=False); torch.cuda.synchronize()
-    djs._dv_flags = 0
+    djs.forward(loss=False, trace=True); torch.cuda.synchronize()
     lib.nm_trace_read_dv(buf, 1)
     tags = {0: "enc first layer", 1: "enc hidden", 2: "heads + draw", 4: "z|c + request", 5: "dec hidden", 6: "out: wait + GEMM", 7: "out: epilogue", 8: "row sums"}
     print("trace of workgroup (0,0), tile 0: cycles per wave 0 / mean; total", sum(buf[t] for t in range(64)))
