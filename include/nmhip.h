@@ -18,7 +18,7 @@
  *   nm_pack_table    the per-batch torch.cat((x, c), dim=1) of cVAE.py:163 done once per table
  *
  * Conventions: plain C, raw DEVICE pointers (tensor.data_ptr()), explicit sizes, a hipStream_t
- * passed as void*, int status return (0 ok, <0 argument error, >0 hipError_t).  Nothing here
+ * passed as void*, int status return (NM_OK, an NM_E_* argument error < 0, or a hipError_t > 0).  Nothing here
  * allocates memory the caller does not own: every buffer, including the workspace, is passed
  * in.  Functions are re-entrant per (device, stream).
  */
@@ -43,6 +43,34 @@ extern "C" {
 /* the general-shape path (nm_job_t.wide, nm_launch_wide): any hidden width / latent up to these */
 #define NM_WIDE_MAX_WIDTH 4096
 #define NM_WIDE_MAX_LATENT 128
+
+/* Status of every entry point that returns int (or int64_t, where a negative result is a status): NM_OK, a negative
+ * argument error below, or a positive hipError_t.  nm_status_string() gives the text. */
+enum {
+  NM_OK            = 0,
+  NM_E_NULL        = -1,   /* a required pointer is NULL                                                         */
+  NM_E_MODALITIES  = -2,   /* modalities out of range (1..NM_MAX_MOD decoders, 1..NM_MAX_EXP experts)             */
+  NM_E_LAYERS      = -3,   /* hidden layers out of range (1..NM_MAX_HID)                                          */
+  NM_E_WIDTH       = -4,   /* hidden width out of range (1..NM_MAX_WIDTH; wide: 1..NM_WIDE_MAX_WIDTH)             */
+  NM_E_LATENT      = -5,   /* latent out of range (1..NM_MAX_LATENT; wide: 1..NM_WIDE_MAX_LATENT)                 */
+  NM_E_LATENT_COV  = -6,   /* latent + c_dim exceeds NM_MAX_WIDTH                                                 */
+  NM_E_PITCH       = -7,   /* table pitch: Kx, x_pitch, Cz or rows_alloc break their multiples / minima           */
+  NM_E_GEOMETRY    = -8,   /* bad launch geometry (counts < 1, negative step / tile, several tiles with a backward pass) */
+  NM_E_COMBINE     = -9,   /* unknown NM_COMBINE_*                                                                */
+  NM_E_OFFSETS     = -10,  /* parameter offsets must be multiples of 4 floats (weight matrices: of 256)           */
+  NM_E_REG_HEAD    = -11,  /* regression head: reg_w / reg_b offsets or the reg_resid / reg_dres buffers          */
+  NM_E_METRICS     = -12,  /* metrics: n_sets >= 1 and 1 <= max_set <= NM_METRICS_MAX_N                           */
+  NM_E_CLS_HEAD    = -13,  /* classifier head: blocks, widths, classes, offsets or the out_mu / out_z export      */
+  NM_E_COUNTS      = -14,  /* n_rows, loss_cap and eps_cap must be >= 1                                           */
+  NM_E_SHADOW      = -15,  /* wsh (shadow images) missing                                                         */
+  NM_E_RESIDENCY   = -16,  /* split / row-split launch: more workgroups than CUs (they wait for each other, so all must be resident) */
+  NM_E_PREP        = -17,  /* input preparation: 1 <= rows <= NM_PREP_MAX_ROWS, at least one source / column / bin */
+  NM_E_OUTPUT      = -18,  /* out_kind not 0 / 1, n_private outside 0..Z, or a private latent without an encoder per decoder */
+  NM_E_WIDE_TC     = -19,  /* general-shape path: total correlation needs experts x latent <= 256                 */
+  NM_E_ROWSPLIT    = -20,  /* the job cannot run row-split (nm_rowsplit_ok)                                       */
+  NM_E_N_PARAMS    = -21,  /* n_params must be set and stay below 2^30 floats                                     */
+  NM_E_DEVPASS     = -22   /* the job cannot run on the deviation-pass kernel (nm_devpass_ok)                     */
+};
 
 /* expert fusion, cVAE.py:1144-1164 */
 enum { NM_COMBINE_POE = 0, NM_COMBINE_GPOE = 1, NM_COMBINE_MOE = 2, NM_COMBINE_MOPOE = 3,
@@ -210,7 +238,7 @@ typedef struct nm_job {
   float*  gpart;
   int64_t gpart_stride;
   int64_t n_params;       /* floats in params / adam_m / adam_v / grads: the kernels address them with 32-bit byte offsets,
-                             so n_params must stay below 2^30 (nm_validate_job: -21)                                   */
+                             so n_params must stay below 2^30 (nm_validate_job: NM_E_N_PARAMS)                                   */
   nm_modality_t mod[NM_MAX_MOD];
 } nm_job_t;
 
@@ -242,7 +270,7 @@ int64_t nm_workspace_bytes(const nm_job_t* job_host);
  * the stacked means as 'qz_xs', cVAE.py:1845); general-shape jobs: [expert][256][Z rounded to 16] (no step parity). */
 int64_t nm_workspace_offset(const nm_job_t* job_host, int what);
 
-/* Validate shapes against the kernel's limits. 0 ok, negative = which limit. */
+/* Validate shapes against the kernel's limits. NM_OK, or the NM_E_* of the limit that is broken. */
 int nm_validate_job(const nm_job_t* job_host);
 
 /* Core launch.  jobs_dev: device array of n_jobs descriptors.  Workgroup (j, t) runs job j
@@ -258,7 +286,7 @@ int nm_launch(const nm_job_t* jobs_dev, int n_jobs, int step0, int steps_per_til
  * and decoder), placed on one XCD.  The parts meet twice per step through agent-scope hand-offs in the job's workspace
  * (after the encoders: the experts' mu / logvar; after the decoders: d z and the per-modality log-likelihoods); every
  * other byte a part touches is its own.  flags must include NM_F_BACKWARD; every job needs M == parts; results are
- * bit-identical to nm_launch.  Status -16: ceil(n_jobs / 8) * 8 * parts exceeds the CU count (the parts wait for each
+ * bit-identical to nm_launch.  Status NM_E_RESIDENCY: ceil(n_jobs / 8) * 8 * parts exceeds the CU count (the parts wait for each
  * other inside the launch, so all of them must be resident). */
 int nm_launch_split(const nm_job_t* jobs_dev, int n_jobs, int parts, int step0, int n_steps, int flags, void* stream);
 /* nm_launch for jobs with nm_job_t.wide = 1 (every job of the launch): the shapes of the reference's sweeps that do not fit
@@ -280,10 +308,15 @@ int nm_launch_wide(const nm_job_t* jobs_dev, int n_jobs, int step0, int steps_pe
  * sweep (the sweep of a slice is bound by what one CU pulls from memory; a small set leaves most CUs idle).  Results do
  * not depend on it (every parameter's update is the same arithmetic whichever workgroup runs it).
  * NM_F_PROFILE: diagnostic, forces write-through stores also inside a group that shares an XCD (A/B of the L2-local path).
- * Status -16: ceil(n_jobs * M / 8) * 8 * (k + helpers) exceeds the CU count; errors of the hand-offs: nm_split_errors. */
+ * Status NM_E_RESIDENCY: ceil(n_jobs * M / 8) * 8 * (k + helpers) exceeds the CU count; errors of the hand-offs: nm_split_errors. */
 int nm_launch_rowsplit(const nm_job_t* jobs_dev, int n_jobs, int M, int k, int helpers, int step0, int n_steps, int flags,
                        int spread_us, void* stream);
-/* 0: the job can run row-split; -20: it uses a switch that needs the whole batch in one workgroup (total correlation,
+/* Limits of the row-split launch's Adam sweep, per modality (nm_rowsplit_ok refuses a job beyond them): weight passes,
+ * vector segments, and vector elements (biases, logvar_out, alpha: 3 per thread of k = 2 workgroups of 512). */
+#define NM_RS_MAX_PASSES 128
+#define NM_RS_MAX_VSEGS  144
+#define NM_RS_MAX_VEC    3072
+/* NM_OK: the job can run row-split; NM_E_ROWSPLIT: it uses a switch that needs the whole batch in one workgroup (total correlation,
  * learnable loss weights, private latents, sigmoid output, decoder-only modalities, head models, general-shape path) */
 int nm_rowsplit_ok(const nm_job_t* job_host);
 /* Zero the hand-off words of every job (first 256 bytes of workspace tile 0); the split launches call it themselves. */
@@ -293,7 +326,7 @@ int nm_sync_reset(const nm_job_t* jobs_dev, int n_jobs, void* stream);
  * (tile0 + n_tiles) * 128), writing mod[0].out_sqerr / out_rowdev / out_loc and nothing else (no loss log, no latent exports).
  * 128-row tiles, 75 KB of LDS: two workgroups per CU; 16-row tiles past the table's end are skipped.  Row by row the same
  * arithmetic and draws as nm_forward (bit-identical exports).  Every job of the launch must pass nm_devpass_ok (host-side
- * check: -22 = needs nm_forward: several experts, first hidden width > 112, latent > 32, non-Gaussian output, ...). */
+ * check: NM_E_DEVPASS = needs nm_forward: several experts, first hidden width > 112, latent > 32, non-Gaussian output, ...). */
 int nm_devpass(const nm_job_t* jobs_dev, int n_jobs, int tile0, int n_tiles, int flags, void* stream);   /* flags: 0 or NM_F_TRACE */
 int nm_trace_read_dv(unsigned long long* out512, int reset);
 int nm_devpass_ok(const nm_job_t* job_host);
@@ -303,6 +336,9 @@ int nm_trace_read_rs(unsigned long long* out512, int reset);
  * cleared -- its workgroups left the launch at that point and its parameters / moments are not to be trusted (the
  * launch itself still returns 0: the kernel cannot fail the stream).  clear != 0 zeroes the words after reading.
  * The reference has no counterpart (single process, single model: cVAE.py:1166-1196). */
+/* values of out_dev[j]: a hand-off timed out / the row-split kernel refused the job's shape */
+#define NM_SYNC_ERR_TIMEOUT 1
+#define NM_SYNC_ERR_SHAPE   2
 int nm_split_errors(const nm_job_t* jobs_dev, int n_jobs, int* out_dev, int clear, void* stream);
 
 /* Convenience wrappers over nm_launch (same status convention). */

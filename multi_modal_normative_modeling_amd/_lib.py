@@ -10,6 +10,7 @@ from pathlib import Path
 
 NM_MAX_MOD = 8
 NM_MAX_EXP = 4
+# every integer NM_* constant below mirrors include/nmhip.h (tests/test_cabi_cpu.py holds them to it)
 # the row-split launch's Adam sweep (csrc/nm_rowsplit.hip: SwTab, SW_NV): weight passes and vector segments per modality,
 # and the vector elements (biases, logvar_out, alpha) nm_rowsplit_ok admits -- 3 per thread of k = 2 workgroups of 512
 NM_RS_MAX_PASSES = 128
@@ -47,6 +48,31 @@ NM_SYNC_ERR_TIMEOUT = 1
 NM_SYNC_ERR_SHAPE = 2
 NM_METRICS_MAX_N = 8192
 NM_METRICS_STRIDE = 8
+
+# status codes (nmhip.h; nm_status_string gives the text)
+NM_OK = 0
+NM_E_NULL = -1
+NM_E_MODALITIES = -2
+NM_E_LAYERS = -3
+NM_E_WIDTH = -4
+NM_E_LATENT = -5
+NM_E_LATENT_COV = -6
+NM_E_PITCH = -7
+NM_E_GEOMETRY = -8
+NM_E_COMBINE = -9
+NM_E_OFFSETS = -10
+NM_E_REG_HEAD = -11
+NM_E_METRICS = -12
+NM_E_CLS_HEAD = -13
+NM_E_COUNTS = -14
+NM_E_SHADOW = -15
+NM_E_RESIDENCY = -16
+NM_E_PREP = -17
+NM_E_OUTPUT = -18
+NM_E_WIDE_TC = -19
+NM_E_ROWSPLIT = -20
+NM_E_N_PARAMS = -21
+NM_E_DEVPASS = -22
 
 LIB_PATH = Path(__file__).resolve().parent / "libnmhip.so"
 

@@ -33,6 +33,7 @@
 #include <stdint.h>
 #include <math.h>
 #include "nmhip.h"
+#include "nm_host.inc"
 
 namespace {
 
@@ -142,8 +143,8 @@ __host__ __device__ inline int wpad(int n) { return rup(n + 1, 32); }   // width
 // One workspace per concurrently running tile of a job.  When the modalities of a model run as separate workgroups
 // (NM_F_SPLIT) they share it: the expert statistics are double-buffered by step parity (a part may already be one
 // step ahead), and every part has its own joint statistics / d z / decoder activations / z|c slot.
-// row-split launch: the Adam sweep's tables (nm_rowsplit.hip: SwTab), one slot per modality part in every tile
-constexpr int NM_RS_MAX_PASSES = 128, NM_RS_MAX_VSEGS = 144;
+// row-split launch: the Adam sweep's tables (nm_rowsplit.hip: SwTab; NM_RS_MAX_PASSES / NM_RS_MAX_VSEGS entries, nmhip.h),
+// one slot per modality part in every tile
 constexpr int WS_RS_TAB_BYTES = 8192;
 struct WsLayout {
   int64_t sync, rs_tab, mu_m, lv_m, mu_j, lv_j, es, dz, enc_act, dec_act, zc, total;
@@ -153,7 +154,7 @@ struct WsLayout {
 constexpr int WS_SYNC_BYTES = 256;       // hand-off counters of the split mode: A at +0, B at +64, error flag at +128
 constexpr int WS_SYNC_ERR_WORD = 32;
 // values of the error word: a hand-off timed out / the row-split kernel refused the job's shape (nm_rowsplit.hip: rs_fits)
-constexpr unsigned WS_SYNC_ERR_TIMEOUT = 1u, WS_SYNC_ERR_SHAPE = 2u;
+constexpr unsigned WS_SYNC_ERR_TIMEOUT = NM_SYNC_ERR_TIMEOUT, WS_SYNC_ERR_SHAPE = NM_SYNC_ERR_SHAPE;   // (nmhip.h)
 // row-split launch (words of tile 0 unless noted): A[q] at word q, B[q] at 16 + q (q < 4: arrivals of the M modality parts of
 // slice q), C at 33 (all M k workgroups of the job: partials complete), D[m] at 40 + m (the k slices of modality m: sweep
 // complete); words 48.. of EVERY tile: that slice's loss shares (kl, then ll_m)
@@ -2697,6 +2698,36 @@ __device__ __forceinline__ void carve_lds(Ctx& c, unsigned char* smem) {
   c.abort = reinterpret_cast<unsigned*>(c.tlast + 8);
 }
 
+// Adam's step constants of optimizer step t (1-based) at learning rate lr: lr over the first bias correction and
+// 1 / sqrt of the second, in double, as torch.optim.Adam computes them on the host.
+__host__ __device__ __forceinline__ void adam_bias_consts(double lr, float beta1, float beta2, int64_t t, float& step_size,
+                                                          float& inv_bc2_sqrt) {
+  const double tt = (double)t;
+  step_size = (float)(lr / (1.0 - pow((double)beta1, tt)));
+  inv_bc2_sqrt = (float)(1.0 / sqrt(1.0 - pow((double)beta2, tt)));
+}
+// ... of a job's optimizer step t_opt, at the learning rate of that step: the schedule table (param_group['lr'] = clr per
+// step) or the constant
+__device__ __forceinline__ void adam_step_consts(const nm_job_t* J, int64_t t_opt, float& step_size, float& inv_bc2_sqrt) {
+  const double lr_t = (J->lr_table && J->lr_cap > 0) ? J->lr_table[(t_opt - 1) % J->lr_cap] : (double)J->lr;
+  adam_bias_consts(lr_t, J->beta1, J->beta2, t_opt, step_size, inv_bc2_sqrt);
+}
+
+// Row window of a whole-batch workgroup: 256-row tile b of the job's tables (a step's batch, or an inference tile)
+__device__ __forceinline__ void tile_rows(Ctx& c, const nm_job_t* J, int b) {
+  c.row0 = b * ROWS;
+  c.nrows = min(ROWS, J->n_rows - c.row0);
+  c.inv_b = 1.0f / (float)c.nrows;
+}
+
+// Wait `us` microseconds (at most 20 ms) on the constant-rate counter all XCDs share, 100 ticks per microsecond (s_sleep
+// counts are not shader cycles: the first version of this, a fixed number of s_sleep(127), spread the workgroups over three
+// steps instead of one -- tools/wg_spread.py).
+__device__ __forceinline__ void wait_us(int us) {
+  const unsigned long long t0 = __builtin_amdgcn_s_memrealtime(), ticks = 100ull * (unsigned long long)min(us, 20000);
+  while (__builtin_amdgcn_s_memrealtime() - t0 < ticks) __builtin_amdgcn_s_sleep(16);
+}
+
 template <bool SCALAR_TR, int MODE = 0>
 __global__ __launch_bounds__(WG) void nm_step_kernel(const nm_job_t* __restrict__ jobs, int step0, int steps_per_tile,
                                                      int flags, int n_jobs, int nparts) {
@@ -2728,36 +2759,23 @@ __global__ __launch_bounds__(WG) void nm_step_kernel(const nm_job_t* __restrict_
   for (int i = c.tid; i < SMEM_BYTES / 4; i += WG) reinterpret_cast<uint32_t*>(smem)[i] = 0u;
   __syncthreads();
   // De-phase the workgroups of a launch: identical models otherwise run their HBM-heavy weight-gradient / Adam phases
-  // in lockstep and share the DRAM 256 ways at once.  nm_job_t.dephase = this job's start offset in microseconds,
-  // waited for on the constant-rate counter (s_sleep counts are not shader cycles: the first version of this, a fixed
-  // number of s_sleep(127), spread the workgroups over three steps instead of one -- tools/wg_spread.py).  The offset
-  // is pure cost at the end of the launch, so short launches get less of it and very short ones none.
+  // in lockstep and share the DRAM 256 ways at once.  nm_job_t.dephase = this job's start offset in microseconds
+  // (wait_us).  The offset is pure cost at the end of the launch, so short launches get less of it and very short
+  // ones none.
   {
     // (forward only, many row tiles: the first workgroup of every CU -- tile 0 of each job -- starts late by a quarter
     //  of the offset, the following tiles inherit the stagger)
     constexpr int FWD_DEPHASE_DIV = 4;
     int us = steps_per_tile >= 64 ? J->dephase : (steps_per_tile >= 8 ? (J->dephase >> 2) : 0);
     if (MODE == 3) us = (tile_idx == 0 && gridDim.y > 1) ? J->dephase / FWD_DEPHASE_DIV : 0;
-    if (us > 0) {
-      const unsigned long long t0 = __builtin_amdgcn_s_memrealtime(), ticks = 100ull * (unsigned long long)min(us, 20000);
-      while (__builtin_amdgcn_s_memrealtime() - t0 < ticks) __builtin_amdgcn_s_sleep(16);
-    }
+    if (us > 0) wait_us(us);
   }
   const int nb = (J->n_rows + ROWS - 1) / ROWS;
   const int s_begin = step0 + tile_idx * steps_per_tile;
   for (int s = s_begin; s < s_begin + steps_per_tile; ++s) {
-    int b = s % nb;
     c.lstep = s - s_begin;
-    c.row0 = b * ROWS;
-    c.nrows = min(ROWS, J->n_rows - c.row0);
-    c.inv_b = 1.0f / (float)c.nrows;
-    // bias corrections in double, as torch.optim.Adam computes them on the host
-    const int64_t t_opt = J->adam_off + (int64_t)s + 1;
-    const double tt = (double)t_opt;
-    // learning rate of this optimizer step: the schedule table (param_group['lr'] = clr per step) or the constant
-    const double lr_t = (J->lr_table && J->lr_cap > 0) ? J->lr_table[(t_opt - 1) % J->lr_cap] : (double)J->lr;
-    c.step_size = (float)(lr_t / (1.0 - pow((double)J->beta1, tt)));
-    c.inv_bc2_sqrt = (float)(1.0 / sqrt(1.0 - pow((double)J->beta2, tt)));
+    tile_rows(c, J, s % nb);
+    adam_step_consts(J, J->adam_off + (int64_t)s + 1, c.step_size, c.inv_bc2_sqrt);
     if (flags & NM_F_PROFILE) c.t_last = clock64();
     if (flags & 64) c.tlast[c.wave_s] = clock64();
     lds_barrier();

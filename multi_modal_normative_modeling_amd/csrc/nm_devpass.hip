@@ -277,12 +277,12 @@ __global__ __launch_bounds__(WG, 4) void nm_devpass_kernel(const nm_job_t* __res
 extern "C" {
 
 /* 0: the job's deviation pass can run on the compact kernel (one expert with the single-expert bypass, no private latent /
- * learnable weights / total correlation, first hidden width <= 112, latent <= 32, Gaussian output); -22 otherwise. */
+ * learnable weights / total correlation, first hidden width <= 112, latent <= 32, Gaussian output); NM_E_DEVPASS otherwise. */
 int nm_devpass_ok(const nm_job_t* j) {
-  if (!j) return -1;
+  if (!j) return NM_E_NULL;
   const int Me = j->M_enc > 0 ? j->M_enc : j->M;
-  if (j->wide || j->M != 1 || Me != 1 || !j->single_bypass || j->n_private != 0 || j->tc_weight != 0.f || j->w_off >= 0) return -22;
-  if (j->H[0] > DV_MAX_H0 || rup(j->Z, 16) > 32 || j->out_kind != 0) return -22;
+  if (j->wide || j->M != 1 || Me != 1 || !j->single_bypass || j->n_private != 0 || j->tc_weight != 0.f || j->w_off >= 0) return NM_E_DEVPASS;
+  if (j->H[0] > DV_MAX_H0 || rup(j->Z, 16) > 32 || j->out_kind != 0) return NM_E_DEVPASS;
   return 0;
 }
 
@@ -290,25 +290,13 @@ int nm_devpass_ok(const nm_job_t* j) {
  * [tile0 * 128, (tile0 + n_tiles) * 128): out_sqerr / out_rowdev / out_loc of modality 0, nothing else (no loss log, no
  * latent exports).  Every job must pass nm_devpass_ok. */
 int nm_devpass(const nm_job_t* jobs_dev, int n_jobs, int tile0, int n_tiles, int flags, void* stream) {
-  if (!jobs_dev) return -1;
-  if (n_jobs < 1 || n_tiles < 1 || tile0 < 0) return -8;
-  hipError_t e = hipFuncSetAttribute((const void*)nm_devpass_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DV_SMEM);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(nm_devpass_kernel, dim3(n_jobs, n_tiles), dim3(WG), DV_SMEM, (hipStream_t)stream, jobs_dev, tile0,
-                     flags & NM_F_TRACE);
-  return (int)hipGetLastError();
+  if (int bad = check_launch_geometry(jobs_dev, n_jobs, n_tiles, 1, tile0, 0)) return bad;
+  return launch_kernel(nm_devpass_kernel, dim3(n_jobs, n_tiles), dim3(WG), DV_SMEM, stream, jobs_dev, tile0, flags & NM_F_TRACE);
 }
 
 /* NM_F_TRACE read-out of nm_devpass ([8 waves][64 tags] interval cycles of workgroup (0, 0), as nm_trace_read) */
 int nm_trace_read_dv(unsigned long long* out512, int reset) {
-  if (!out512) return -1;
-  hipError_t e = hipMemcpyFromSymbol(out512, HIP_SYMBOL(nm_trace_cycles), sizeof(unsigned long long) * 512);
-  if (e != hipSuccess) return (int)e;
-  if (reset) {
-    static unsigned long long z[512];
-    e = hipMemcpyToSymbol(HIP_SYMBOL(nm_trace_cycles), z, sizeof(z));
-  }
-  return (int)e;
+  return read_counters(out512, nm_trace_cycles, reset);
 }
 
 }  // extern "C"

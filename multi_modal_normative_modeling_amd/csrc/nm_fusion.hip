@@ -10,6 +10,7 @@
 #include <stdint.h>
 #include <math.h>
 #include "nmhip.h"
+#include "nm_host.inc"
 
 namespace {
 
@@ -113,25 +114,23 @@ extern "C" {
 int nm_combine_latent(const float* mus, const float* variances, int M, int64_t n, int combine, const float* alpha_raw,
                       int single_bypass, int in_log, int out_log, float var_floor, float* out_mu, float* out_var,
                       void* stream) {
-  if (!mus || !variances || !out_mu || !out_var) return -1;
-  if (M < 1 || M > FUSE_MAX) return -2;
-  if (n < 1) return -8;
-  if (combine < NM_COMBINE_POE || combine > NM_COMBINE_MOPOE) return -9;
-  if (combine == NM_COMBINE_GPOE && !alpha_raw) return -1;
+  if (!mus || !variances || !out_mu || !out_var) return NM_E_NULL;
+  if (M < 1 || M > FUSE_MAX) return NM_E_MODALITIES;
+  if (n < 1) return NM_E_GEOMETRY;
+  if (combine < NM_COMBINE_POE || combine > NM_COMBINE_MOPOE) return NM_E_COMBINE;
+  if (combine == NM_COMBINE_GPOE && !alpha_raw) return NM_E_NULL;
   FuseArgs a{mus, variances, alpha_raw, out_mu, out_var, n, M, combine, in_log, out_log, single_bypass, var_floor};
   const int threads = 256;
   const int64_t blocks = (n + threads - 1) / threads;
-  if (blocks > 0x7fffffff) return -8;
-  hipLaunchKernelGGL(combine_latent_kernel, dim3((unsigned)blocks), dim3(threads), 0, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
+  if (blocks > 0x7fffffff) return NM_E_GEOMETRY;
+  return launch_kernel(combine_latent_kernel, dim3((unsigned)blocks), dim3(threads), 0, stream, a);
 }
 
 int nm_total_correlation(const float* qz_xs, int M, int B, int Z, float* out, void* stream) {
-  if (!qz_xs || !out) return -1;
-  if (M < 1 || M > FUSE_MAX) return -2;
-  if (B < 1 || Z < 1 || Z > 128) return -5;
-  hipLaunchKernelGGL(total_correlation_kernel, dim3(1), dim3(512), 0, (hipStream_t)stream, qz_xs, M, B, Z, out);
-  return (int)hipGetLastError();
+  if (!qz_xs || !out) return NM_E_NULL;
+  if (M < 1 || M > FUSE_MAX) return NM_E_MODALITIES;
+  if (B < 1 || Z < 1 || Z > 128) return NM_E_LATENT;
+  return launch_kernel(total_correlation_kernel, dim3(1), dim3(512), 0, stream, qz_xs, M, B, Z, out);
 }
 
 }  // extern "C"

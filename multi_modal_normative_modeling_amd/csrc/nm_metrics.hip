@@ -17,6 +17,7 @@
 #include <stdint.h>
 #include <math.h>
 #include "nmhip.h"
+#include "nm_host.inc"
 
 namespace {
 
@@ -239,21 +240,16 @@ extern "C" {
 
 int nm_posthoc_metrics(const float* scores, const int32_t* labels, const int32_t* offsets, int n_sets, int max_set,
                        const double* thr_in, double* out, void* stream) {
-  if (!scores || !labels || !offsets || !out) return -1;
-  if (n_sets < 1 || max_set < 1 || max_set > MAXN) return -12;
-  hipError_t e = hipFuncSetAttribute((const void*)posthoc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, METRICS_SMEM);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(posthoc_kernel, dim3(n_sets), dim3(MT), METRICS_SMEM, (hipStream_t)stream, scores, labels, offsets,
-                     thr_in, out);
-  return (int)hipGetLastError();
+  if (!scores || !labels || !offsets || !out) return NM_E_NULL;
+  if (n_sets < 1 || max_set < 1 || max_set > MAXN) return NM_E_METRICS;
+  return launch_kernel(posthoc_kernel, dim3(n_sets), dim3(MT), METRICS_SMEM, stream, scores, labels, offsets, thr_in, out);
 }
 
 int nm_confusion_metrics(const int32_t* pred, const int32_t* labels, const int32_t* offsets, int n_sets, double* out,
                          void* stream) {
-  if (!pred || !labels || !offsets || !out) return -1;
-  if (n_sets < 1) return -12;
-  hipLaunchKernelGGL(confusion_kernel, dim3(n_sets), dim3(MT), 0, (hipStream_t)stream, pred, labels, offsets, out);
-  return (int)hipGetLastError();
+  if (!pred || !labels || !offsets || !out) return NM_E_NULL;
+  if (n_sets < 1) return NM_E_METRICS;
+  return launch_kernel(confusion_kernel, dim3(n_sets), dim3(MT), 0, stream, pred, labels, offsets, out);
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "nmhip.h"
+#include "nm_host.inc"
 
 namespace {
 
@@ -193,45 +194,38 @@ extern "C" {
 
 int nm_prep_scaler_fit(const double* const* srcs_dev, const int32_t* src_D_dev, int n_src, int D, const int32_t* rows_dev,
                        int n_rows, double* center_dev, double* scale_dev, void* stream) {
-  if (!srcs_dev || !src_D_dev || !rows_dev || !center_dev || !scale_dev) return -1;
-  if (n_src < 1 || D < 1 || n_rows < 1 || n_rows > PREP_MAX_N) return -17;
+  if (!srcs_dev || !src_D_dev || !rows_dev || !center_dev || !scale_dev) return NM_E_NULL;
+  if (n_src < 1 || D < 1 || n_rows < 1 || n_rows > PREP_MAX_N) return NM_E_PREP;
   int P = 1;
   while (P < n_rows) P <<= 1;
   const int smem = P * 8;
-  hipError_t e = hipFuncSetAttribute((const void*)scaler_fit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(scaler_fit_kernel, dim3(D), dim3(PREP_WG), smem, (hipStream_t)stream, srcs_dev, src_D_dev, n_src, D, rows_dev,
-                     n_rows, center_dev, scale_dev);
-  return (int)hipGetLastError();
+  return launch_kernel(scaler_fit_kernel, dim3(D), dim3(PREP_WG), smem, stream, srcs_dev, src_D_dev, n_src, D, rows_dev, n_rows,
+                       center_dev, scale_dev);
 }
 
 int nm_prep_onehot(const double* age_dev, const double* gender_dev, const int32_t* rows_dev, int n_rows, const double* age_edges_dev,
                    int age_bins, const double* gender_edges_dev, int gender_bins, float* c_out_dev, void* stream) {
-  if (!age_dev || !gender_dev || !rows_dev || !age_edges_dev || !gender_edges_dev || !c_out_dev) return -1;
-  if (n_rows < 1 || n_rows > PREP_MAX_N || age_bins < 1 || gender_bins < 1) return -17;
+  if (!age_dev || !gender_dev || !rows_dev || !age_edges_dev || !gender_edges_dev || !c_out_dev) return NM_E_NULL;
+  if (n_rows < 1 || n_rows > PREP_MAX_N || age_bins < 1 || gender_bins < 1) return NM_E_PREP;
   int P = 1;
   while (P < n_rows) P <<= 1;
   const int smem = P * 12;
-  hipError_t e = hipFuncSetAttribute((const void*)onehot_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(onehot_kernel, dim3(2), dim3(PREP_WG), smem, (hipStream_t)stream, age_dev, gender_dev, rows_dev, n_rows,
-                     age_edges_dev, age_bins, gender_edges_dev, gender_bins, c_out_dev, age_bins + gender_bins);
-  return (int)hipGetLastError();
+  return launch_kernel(onehot_kernel, dim3(2), dim3(PREP_WG), smem, stream, age_dev, gender_dev, rows_dev, n_rows, age_edges_dev,
+                       age_bins, gender_edges_dev, gender_bins, c_out_dev, age_bins + gender_bins);
 }
 
 int nm_pack_table_raw(const double* const* srcs_dev, const int32_t* src_D_dev, int n_src, const int32_t* rows_dev, int n_rows,
                       const double* center_dev, const double* scale_dev, const float* c_dev, int rows_alloc, int D, int C, int Kx,
                       uint16_t* xb, float* x_f32_out, int x_pitch, uint16_t* cz_out, int Cz, void* stream) {
-  if (!srcs_dev || !src_D_dev || !rows_dev || !center_dev || !scale_dev || !xb || (C > 0 && !c_dev)) return -1;
-  if (Kx % 32 != 0 || Kx < D + C + 1 || rows_alloc < n_rows || rows_alloc % NM_BATCH != 0) return -7;
-  if (x_f32_out && (x_pitch % 4 != 0 || x_pitch < D || x_pitch > Kx)) return -7;
-  if (cz_out && (Cz % 8 != 0 || Cz < C + 1)) return -7;
+  if (!srcs_dev || !src_D_dev || !rows_dev || !center_dev || !scale_dev || !xb || (C > 0 && !c_dev)) return NM_E_NULL;
+  if (Kx % 32 != 0 || Kx < D + C + 1 || rows_alloc < n_rows || rows_alloc % NM_BATCH != 0) return NM_E_PITCH;
+  if (x_f32_out && (x_pitch % 4 != 0 || x_pitch < D || x_pitch > Kx)) return NM_E_PITCH;
+  if (cz_out && (Cz % 8 != 0 || Cz < C + 1)) return NM_E_PITCH;
   const int64_t total = nm_xb_elems(rows_alloc, Kx);
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(pack_raw_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, srcs_dev, src_D_dev, n_src, rows_dev, n_rows,
-                     center_dev, scale_dev, c_dev, rows_alloc, D, C, Kx, xb, x_f32_out, x_pitch, cz_out, Cz);
-  return (int)hipGetLastError();
+  return launch_kernel(pack_raw_kernel, dim3(blocks), dim3(256), 0, stream, srcs_dev, src_D_dev, n_src, rows_dev, n_rows,
+                       center_dev, scale_dev, c_dev, rows_alloc, D, C, Kx, xb, x_f32_out, x_pitch, cz_out, Cz);
 }
 
 }  // extern "C"

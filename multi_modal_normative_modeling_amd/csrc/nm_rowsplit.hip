@@ -34,6 +34,7 @@
 // geometries sit in a small table in S (all of P / Q / S is dead during the sweep), built by one thread per pass.
 constexpr int SW_DEPTH = 4;
 constexpr int SW_NV = 3;                 // vector elements per thread (biases, logvar_out, alpha: 2 D + ... per modality)
+static_assert(NM_RS_MAX_VEC == SW_NV * 2 * WG, "nm_rowsplit_ok admits what k = 2 workgroups hold");
 struct SwRec { int w_off, KT, kt0, nkt; float rnkt; int sh_pitch; GAS char* sh; };     // 32 bytes
 // One vector parameter segment: elements [idx0, idx0 + n) of the master (a bias, a chunk of logvar_out, alpha), with an
 // optional fp32 copy inside a shadow image's vector piece; `off` = its first element in the concatenation of all segments
@@ -466,48 +467,29 @@ __global__ __launch_bounds__(WG) void nm_rs_kernel(const nm_job_t* __restrict__ 
 extern "C" {
 
 /* Row-split launch (include/nmhip.h): n_jobs models of M modalities each, k in {2, 4} row slices per (model, modality).
- * Every job needs k workspace tiles and gpart / gpart_stride; -16: the launch would not be resident at once;
- * -20: a job of the launch cannot run row-split (see nm_rowsplit_ok). */
+ * Every job needs k workspace tiles and gpart / gpart_stride; NM_E_RESIDENCY: the launch would not be resident
+ * at once; NM_E_ROWSPLIT: a job of the launch cannot run row-split (see nm_rowsplit_ok). */
 int nm_launch_rowsplit(const nm_job_t* jobs_dev, int n_jobs, int M, int k, int helpers, int step0, int n_steps, int flags,
                        int spread_us, void* stream) {
-  if (!jobs_dev) return -1;
-  if (n_jobs < 1 || n_steps < 1 || step0 < 0 || M < 1 || M > NM_MAX_EXP || (k != 2 && k != 4)) return -8;
-  if (!(flags & NM_F_BACKWARD) || !(flags & (NM_F_ADAM | NM_F_GRADS))) return -8;
-  if ((flags & NM_F_GRADS) && n_steps != 1) return -8;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return -8;
-  if (helpers < 0 || helpers > 60) return -8;
+  if (int bad = check_launch_geometry(jobs_dev, n_jobs, 1, n_steps, step0, flags)) return bad;
+  if (M < 1 || M > NM_MAX_EXP || (k != 2 && k != 4)) return NM_E_GEOMETRY;
+  if (!(flags & NM_F_BACKWARD) || !(flags & (NM_F_ADAM | NM_F_GRADS))) return NM_E_GEOMETRY;
+  if ((flags & NM_F_GRADS) && n_steps != 1) return NM_E_GEOMETRY;
+  const int cus = cu_count();
+  if (cus < 1 || helpers < 0 || helpers > 60) return NM_E_GEOMETRY;
   const int groups = (n_jobs * M + 7) / 8 * 8;
   const int wgs = groups * (k + helpers);
-  if (wgs > cus) return -16;            // the workgroups of a model wait for each other: all must be resident
-  hipStream_t st = (hipStream_t)stream;
+  if (wgs > cus) return NM_E_RESIDENCY;            // the workgroups of a model wait for each other: all must be resident
   nm_sync_reset(jobs_dev, n_jobs, stream);
   flags &= (NM_F_BACKWARD | NM_F_ADAM | NM_F_GRADS | NM_F_EXPORT | NM_F_TRACE | NM_F_FAULT_INJECT | NM_F_PROFILE);
   if (spread_us < 0 || n_steps < 16) spread_us = 0;          // (an offset is pure cost at the end of a short launch)
-  hipError_t e;
-  if (k == 2) {
-    e = hipFuncSetAttribute((const void*)nm_rs_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(nm_rs_kernel<2>, dim3(wgs), dim3(WG), SMEM_BYTES, st, jobs_dev, step0, n_steps, flags, n_jobs, M, spread_us, helpers);
-  } else {
-    e = hipFuncSetAttribute((const void*)nm_rs_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(nm_rs_kernel<4>, dim3(wgs), dim3(WG), SMEM_BYTES, st, jobs_dev, step0, n_steps, flags, n_jobs, M, spread_us, helpers);
-  }
-  return (int)hipGetLastError();
+  return launch_kernel(k == 2 ? nm_rs_kernel<2> : nm_rs_kernel<4>, dim3(wgs), dim3(WG), SMEM_BYTES, stream, jobs_dev, step0, n_steps,
+                       flags, n_jobs, M, spread_us, helpers);
 }
 
 /* NM_F_TRACE read-out of the row-split kernels (this translation unit has its own copy of the timers). */
 int nm_trace_read_rs(unsigned long long* out512, int reset) {
-  if (!out512) return -1;
-  hipError_t e = hipMemcpyFromSymbol(out512, HIP_SYMBOL(nm_trace_cycles), sizeof(unsigned long long) * 512);
-  if (e != hipSuccess) return (int)e;
-  if (reset) {
-    static unsigned long long z[512];
-    e = hipMemcpyToSymbol(HIP_SYMBOL(nm_trace_cycles), z, sizeof(z));
-  }
-  return (int)e;
+  return read_counters(out512, nm_trace_cycles, reset);
 }
 
 }  // extern "C"

@@ -896,24 +896,14 @@ __global__ __launch_bounds__(WG) void nm_wide_step_kernel(const nm_job_t* __rest
   // DRAM while the forward / dgrad phases leave it idle.
   {
     const int us = steps_per_tile >= 64 ? J->dephase : (steps_per_tile >= 8 ? (J->dephase >> 2) : 0);
-    if (us > 0 && (flags & NM_F_ADAM)) {
-      const unsigned long long t0 = __builtin_amdgcn_s_memrealtime(), ticks = 100ull * (unsigned long long)min(us, 20000);
-      while (__builtin_amdgcn_s_memrealtime() - t0 < ticks) __builtin_amdgcn_s_sleep(16);
-    }
+    if (us > 0 && (flags & NM_F_ADAM)) wait_us(us);
   }
   const int nb = (J->n_rows + ROWS - 1) / ROWS;
   const int s_begin = step0 + tile_idx * steps_per_tile;
   for (int s = s_begin; s < s_begin + steps_per_tile; ++s) {
-    const int b = s % nb;
     c.lstep = s - s_begin;
-    c.row0 = b * ROWS;
-    c.nrows = min(ROWS, J->n_rows - c.row0);
-    c.inv_b = 1.0f / (float)c.nrows;
-    const int64_t t_opt = J->adam_off + (int64_t)s + 1;
-    const double tt = (double)t_opt;
-    const double lr_t = (J->lr_table && J->lr_cap > 0) ? J->lr_table[(t_opt - 1) % J->lr_cap] : (double)J->lr;
-    c.step_size = (float)(lr_t / (1.0 - pow((double)J->beta1, tt)));
-    c.inv_bc2_sqrt = (float)(1.0 / sqrt(1.0 - pow((double)J->beta2, tt)));
+    tile_rows(c, J, s % nb);
+    adam_step_consts(J, J->adam_off + (int64_t)s + 1, c.step_size, c.inv_bc2_sqrt);
     if (flags & 64) c.tlast[c.wave_s] = clock64();
     lds_barrier();
     relaunder(c);

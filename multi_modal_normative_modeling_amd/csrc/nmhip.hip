@@ -51,11 +51,7 @@ __device__ __forceinline__ bool head_setup(Ctx& c, unsigned char* smem, const nm
   c.nrows = min(ROWS, J->n_rows - c.row0);
   if (c.nrows <= 0) return false;
   c.inv_b = 1.0f / (float)c.nrows;
-  const int64_t t_opt = J->adam_off + (int64_t)step + 1;
-  const double tt = (double)t_opt;
-  const double lr_t = (J->lr_table && J->lr_cap > 0) ? J->lr_table[(t_opt - 1) % J->lr_cap] : (double)J->lr;
-  c.step_size = (float)(lr_t / (1.0 - pow((double)J->beta1, tt)));
-  c.inv_bc2_sqrt = (float)(1.0 / sqrt(1.0 - pow((double)J->beta2, tt)));
+  adam_step_consts(J, J->adam_off + (int64_t)step + 1, c.step_size, c.inv_bc2_sqrt);
   return true;
 }
 
@@ -1016,14 +1012,8 @@ __global__ __launch_bounds__(WG) void nm_head_step_kernel(const nm_job_t* __rest
   const int bflags = NM_F_BACKWARD | ((flags & NM_F_GRADS) ? NM_F_GRADS : NM_F_ADAM);
   for (int s = step0; s < step0 + n_steps; ++s) {
     c.lstep = s - step0;
-    c.row0 = (s % nb) * ROWS;
-    c.nrows = min(ROWS, J->n_rows - c.row0);
-    c.inv_b = 1.0f / (float)c.nrows;
-    const int64_t t_opt = J->adam_off + (int64_t)s + 1;
-    const double tt = (double)t_opt;
-    const double lr_t = (J->lr_table && J->lr_cap > 0) ? J->lr_table[(t_opt - 1) % J->lr_cap] : (double)J->lr;
-    c.step_size = (float)(lr_t / (1.0 - pow((double)J->beta1, tt)));
-    c.inv_bc2_sqrt = (float)(1.0 / sqrt(1.0 - pow((double)J->beta2, tt)));
+    tile_rows(c, J, s % nb);
+    adam_step_consts(J, J->adam_off + (int64_t)s + 1, c.step_size, c.inv_bc2_sqrt);
     if (flags & 64) c.tlast[c.wave_s] = clock64();
     lds_barrier();
     relaunder(c);
@@ -1284,35 +1274,21 @@ int nm_version(void) { return 10; }
 
 /* phase profile (NM_F_PROFILE): read / reset the per-phase shader-clock accumulators */
 int nm_prof_read(unsigned long long* out32, int reset) {
-  if (!out32) return -1;
-  hipError_t e = hipMemcpyFromSymbol(out32, HIP_SYMBOL(nm_prof_cycles), sizeof(unsigned long long) * 32);
-  if (e != hipSuccess) return (int)e;
-  if (reset) {
-    unsigned long long z[32] = {0};
-    e = hipMemcpyToSymbol(HIP_SYMBOL(nm_prof_cycles), z, sizeof(z));
-  }
-  return (int)e;
+  return read_counters(out32, nm_prof_cycles, reset);
 }
 
 /* NM_F_TRACE read-out: [8 waves][64 tags] interval cycles of workgroup (0,0); reset != 0 clears. */
 int nm_trace_read(unsigned long long* out512, int reset) {
-  if (!out512) return -1;
-  hipError_t e = hipMemcpyFromSymbol(out512, HIP_SYMBOL(nm_trace_cycles), sizeof(unsigned long long) * 512);
-  if (e != hipSuccess) return (int)e;
-  if (reset) {
-    static unsigned long long z[512];
-    e = hipMemcpyToSymbol(HIP_SYMBOL(nm_trace_cycles), z, sizeof(z));
-  }
-  return (int)e;
+  return read_counters(out512, nm_trace_cycles, reset);
 }
 
 int nm_wgtimes_read(unsigned long long* out1024) {
-  if (!out1024) return -1;
+  if (!out1024) return NM_E_NULL;
   return (int)hipMemcpyFromSymbol(out1024, HIP_SYMBOL(nm_wg_times), sizeof(unsigned long long) * 1024);
 }
 
 int nm_abi_sizes(int64_t* sizeof_job, int64_t* sizeof_modality) {
-  if (!sizeof_job || !sizeof_modality) return -1;
+  if (!sizeof_job || !sizeof_modality) return NM_E_NULL;
   *sizeof_job = (int64_t)sizeof(nm_job_t);
   *sizeof_modality = (int64_t)sizeof(nm_modality_t);
   return 0;
@@ -1320,101 +1296,101 @@ int nm_abi_sizes(int64_t* sizeof_job, int64_t* sizeof_modality) {
 
 const char* nm_status_string(int status) {
   switch (status) {
-    case 0: return "ok";
-    case -1: return "null pointer";
-    case -2: return "modalities out of range (1..NM_MAX_MOD decoders, 1..NM_MAX_EXP experts)";
-    case -3: return "hidden layers out of range (1..NM_MAX_HID)";
-    case -4: return "hidden width out of range (1..NM_MAX_WIDTH)";
-    case -5: return "latent out of range (1..NM_MAX_LATENT)";
-    case -6: return "latent + c_dim exceeds NM_MAX_WIDTH";
-    case -7: return "table pitch: Kx must be a multiple of 32 and >= D + C + 1, x_pitch a multiple of 4 and >= D, Cz a multiple of 8 and >= C + 1";
-    case -14: return "n_rows, loss_cap and eps_cap must be >= 1";
-    case -18: return "out_kind must be 0 or 1, 0 <= n_private <= Z, and a private latent needs an encoder per decoder";
-    case -19: return "general-shape path (wide): mvtCAE's total correlation needs experts x latent <= 256";
-    case -17: return "input preparation: 1 <= rows <= NM_PREP_MAX_ROWS, at least one source / column / bin";
-    case -16: return "split launch: jobs x parts exceeds the number of CUs (the parts of a model wait for each other and must all be resident)";
-    case -20: return "row-split launch: the job uses a switch that needs the whole batch in one workgroup, or lacks gpart / workspace tiles";
-    case -22: return "deviation-pass kernel: one expert with the single-expert bypass, first hidden width <= 112, latent <= 32, Gaussian output only";
-    case -21: return "n_params must be set and stay below 2^30 floats (32-bit byte offsets into params / adam_m / adam_v)";
-    case -15: return "wsh (shadow images) missing: allocate nm_fill_shadow() bytes, zero them and call nm_sync_shadow()";
-    case -8: return "bad launch geometry";
-    case -9: return "unknown combine";
-    case -10: return "parameter tensor offsets must be multiples of 4 floats (weight matrices: of 256)";
-    case -13: return "classifier head: 0..NM_MAX_CLS blocks of width 1..NM_MAX_CLS_WIDTH, 2..NM_MAX_CLASSES classes, offsets multiples of 4, out_mu/out_z export";
-    case -12: return "metrics: n_sets >= 1 and 1 <= max_set <= NM_METRICS_MAX_N";
-    case -11: return "regression head: needs reg_w / reg_b offsets (weights: multiples of 256, biases: of 4) and the reg_resid / reg_dres image buffers (16-byte aligned)";
+    case NM_OK: return "ok";
+    case NM_E_NULL: return "null pointer";
+    case NM_E_MODALITIES: return "modalities out of range (1..NM_MAX_MOD decoders, 1..NM_MAX_EXP experts)";
+    case NM_E_LAYERS: return "hidden layers out of range (1..NM_MAX_HID)";
+    case NM_E_WIDTH: return "hidden width out of range (1..NM_MAX_WIDTH)";
+    case NM_E_LATENT: return "latent out of range (1..NM_MAX_LATENT)";
+    case NM_E_LATENT_COV: return "latent + c_dim exceeds NM_MAX_WIDTH";
+    case NM_E_PITCH: return "table pitch: Kx must be a multiple of 32 and >= D + C + 1, x_pitch a multiple of 4 and >= D, Cz a multiple of 8 and >= C + 1";
+    case NM_E_GEOMETRY: return "bad launch geometry";
+    case NM_E_COMBINE: return "unknown combine";
+    case NM_E_OFFSETS: return "parameter tensor offsets must be multiples of 4 floats (weight matrices: of 256)";
+    case NM_E_REG_HEAD: return "regression head: needs reg_w / reg_b offsets (weights: multiples of 256, biases: of 4) and the reg_resid / reg_dres image buffers (16-byte aligned)";
+    case NM_E_METRICS: return "metrics: n_sets >= 1 and 1 <= max_set <= NM_METRICS_MAX_N";
+    case NM_E_CLS_HEAD: return "classifier head: 0..NM_MAX_CLS blocks of width 1..NM_MAX_CLS_WIDTH, 2..NM_MAX_CLASSES classes, offsets multiples of 4, out_mu/out_z export";
+    case NM_E_COUNTS: return "n_rows, loss_cap and eps_cap must be >= 1";
+    case NM_E_SHADOW: return "wsh (shadow images) missing: allocate nm_fill_shadow() bytes, zero them and call nm_sync_shadow()";
+    case NM_E_RESIDENCY: return "split launch: jobs x parts exceeds the number of CUs (the parts of a model wait for each other and must all be resident)";
+    case NM_E_PREP: return "input preparation: 1 <= rows <= NM_PREP_MAX_ROWS, at least one source / column / bin";
+    case NM_E_OUTPUT: return "out_kind must be 0 or 1, 0 <= n_private <= Z, and a private latent needs an encoder per decoder";
+    case NM_E_WIDE_TC: return "general-shape path (wide): mvtCAE's total correlation needs experts x latent <= 256";
+    case NM_E_ROWSPLIT: return "row-split launch: the job uses a switch that needs the whole batch in one workgroup, or lacks gpart / workspace tiles";
+    case NM_E_N_PARAMS: return "n_params must be set and stay below 2^30 floats (32-bit byte offsets into params / adam_m / adam_v)";
+    case NM_E_DEVPASS: return "deviation-pass kernel: one expert with the single-expert bypass, first hidden width <= 112, latent <= 32, Gaussian output only";
     default: return status > 0 ? hipGetErrorString((hipError_t)status) : "unknown argument error";
   }
 }
 
 int nm_validate_job(const nm_job_t* j) {
-  if (!j) return -1;
-  if (j->M < 1 || j->M > NM_MAX_MOD) return -2;
-  if (j->M_enc < 0 || j->M_enc > j->M || (j->M_enc == 0 ? j->M : j->M_enc) > NM_MAX_EXP) return -2;
-  if (j->L < 1 || j->L > NM_MAX_HID) return -3;
+  if (!j) return NM_E_NULL;
+  if (j->M < 1 || j->M > NM_MAX_MOD) return NM_E_MODALITIES;
+  if (j->M_enc < 0 || j->M_enc > j->M || (j->M_enc == 0 ? j->M : j->M_enc) > NM_MAX_EXP) return NM_E_MODALITIES;
+  if (j->L < 1 || j->L > NM_MAX_HID) return NM_E_LAYERS;
   if (j->wide) {
     // the general-shape path (nm_launch_wide): any width, latent <= 128; the plain cVAE / cVAE_multimodal model only
     for (int i = 0; i < j->L; ++i)
-      if (j->H[i] < 1 || j->H[i] > NM_WIDE_MAX_WIDTH) return -4;
-    if (j->Z < 1 || j->Z > NM_WIDE_MAX_LATENT) return -5;
+      if (j->H[i] < 1 || j->H[i] > NM_WIDE_MAX_WIDTH) return NM_E_WIDTH;
+    if (j->Z < 1 || j->Z > NM_WIDE_MAX_LATENT) return NM_E_LATENT;
     // (the heads of the end-to-end and the regression model run as their own kernels, nm_head_classifier /
     //  nm_head_regression, on any trunk)
     // (mvtCAE's switches -- ProductOfExperts2 on variances, the variance floor, the total-correlation term -- are served; its
     //  log-sum-exps sit in 256 floats of LDS)
     // (so are the DMVAE family's: private latents, sigmoid output, learnable loss weights)
-    if (j->tc_weight != 0.f && (j->M_enc > 0 ? j->M_enc : j->M) * j->Z > 256) return -19;
+    if (j->tc_weight != 0.f && (j->M_enc > 0 ? j->M_enc : j->M) * j->Z > 256) return NM_E_WIDE_TC;
   } else {
   for (int i = 0; i < j->L; ++i)
-    if (j->H[i] < 1 || j->H[i] > NM_MAX_WIDTH) return -4;
-  if (j->Z < 1 || j->Z > NM_MAX_LATENT) return -5;
-  if (j->Z + j->C > NM_MAX_WIDTH) return -6;
+    if (j->H[i] < 1 || j->H[i] > NM_MAX_WIDTH) return NM_E_WIDTH;
+  if (j->Z < 1 || j->Z > NM_MAX_LATENT) return NM_E_LATENT;
+  if (j->Z + j->C > NM_MAX_WIDTH) return NM_E_LATENT_COV;
   }
-  if (j->combine < 0 || j->combine > NM_COMBINE_POE2V) return -9;
-  if (j->out_kind < 0 || j->out_kind > 1 || j->n_private < 0 || j->n_private > j->Z) return -18;
-  if (j->n_private > 0 && j->M_enc != 0 && j->M_enc != j->M) return -18;      // a private latent needs the modality's own encoder
-  if (j->n_rows < 1 || j->loss_cap < 1 || j->eps_cap < 1) return -14;       // modulo divisors / batch count in the kernel
-  if (j->n_params < 1 || j->n_params >= ((int64_t)1 << 30)) return -21;      // (unsigned)(offset << 2) in the Adam units
-  if (!j->wsh && !j->wide) return -15;
+  if (j->combine < 0 || j->combine > NM_COMBINE_POE2V) return NM_E_COMBINE;
+  if (j->out_kind < 0 || j->out_kind > 1 || j->n_private < 0 || j->n_private > j->Z) return NM_E_OUTPUT;
+  if (j->n_private > 0 && j->M_enc != 0 && j->M_enc != j->M) return NM_E_OUTPUT;      // a private latent needs the modality's own encoder
+  if (j->n_rows < 1 || j->loss_cap < 1 || j->eps_cap < 1) return NM_E_COUNTS;       // modulo divisors / batch count in the kernel
+  if (j->n_params < 1 || j->n_params >= ((int64_t)1 << 30)) return NM_E_N_PARAMS;      // (unsigned)(offset << 2) in the Adam units
+  if (!j->wsh && !j->wide) return NM_E_SHADOW;
   for (int m = 0; m < j->M; ++m) {
     const nm_modality_t& md = j->mod[m];
-    if (md.D < 1 || md.Kx % 32 != 0 || md.Kx < md.D + j->C + 1) return -7;
-    if (md.x_pitch % 4 != 0 || md.x_pitch < md.D) return -7;
-    if (md.Cz % 8 != 0 || md.Cz < j->C + 1) return -7;
+    if (md.D < 1 || md.Kx % 32 != 0 || md.Kx < md.D + j->C + 1) return NM_E_PITCH;
+    if (md.x_pitch % 4 != 0 || md.x_pitch < md.D) return NM_E_PITCH;
+    if (md.Cz % 8 != 0 || md.Cz < j->C + 1) return NM_E_PITCH;
     for (int i = 0; i < j->L; ++i) {
-      if ((md.enc_b[i] | md.dec_b[i]) & 3) return -10;
-      if ((md.enc_w[i] | md.dec_w[i]) & 255) return -10;
+      if ((md.enc_b[i] | md.dec_b[i]) & 3) return NM_E_OFFSETS;
+      if ((md.enc_w[i] | md.dec_w[i]) & 255) return NM_E_OFFSETS;
     }
-    if ((md.mu_b | md.lv_b | md.out_b) & 3) return -10;
-    if (j->out_kind == 0 && (md.logvar_out < 0 || (md.logvar_out & 3))) return -10;
-    if ((md.mu_w | md.lv_w | md.out_w) & 255) return -10;
+    if ((md.mu_b | md.lv_b | md.out_b) & 3) return NM_E_OFFSETS;
+    if (j->out_kind == 0 && (md.logvar_out < 0 || (md.logvar_out & 3))) return NM_E_OFFSETS;
+    if ((md.mu_w | md.lv_w | md.out_w) & 255) return NM_E_OFFSETS;
   }
   if (j->cls_classes > 0) {
-    if (j->cls_layers < 0 || j->cls_layers > NM_MAX_CLS || j->cls_classes < 2 || j->cls_classes > NM_MAX_CLASSES) return -13;
+    if (j->cls_layers < 0 || j->cls_layers > NM_MAX_CLS || j->cls_classes < 2 || j->cls_classes > NM_MAX_CLASSES) return NM_E_CLS_HEAD;
     for (int i = 0; i < j->cls_layers; ++i) {
-      if (j->cls_width[i] < 1 || j->cls_width[i] > NM_MAX_CLS_WIDTH) return -13;
-      if ((j->cls_b[i] | j->cls_bn_w[i] | j->cls_bn_b[i] | j->cls_bn_mean[i] | j->cls_bn_var[i]) & 3) return -13;
-      if (j->cls_w[i] & 255) return -13;
+      if (j->cls_width[i] < 1 || j->cls_width[i] > NM_MAX_CLS_WIDTH) return NM_E_CLS_HEAD;
+      if ((j->cls_b[i] | j->cls_bn_w[i] | j->cls_bn_b[i] | j->cls_bn_mean[i] | j->cls_bn_var[i]) & 3) return NM_E_CLS_HEAD;
+      if (j->cls_w[i] & 255) return NM_E_CLS_HEAD;
     }
-    if ((j->cls_b[j->cls_layers] & 3) || (j->cls_w[j->cls_layers] & 255)) return -13;
-    if (!(j->cls_use_mu ? j->out_mu : j->out_z)) return -13;
+    if ((j->cls_b[j->cls_layers] & 3) || (j->cls_w[j->cls_layers] & 255)) return NM_E_CLS_HEAD;
+    if (!(j->cls_use_mu ? j->out_mu : j->out_z)) return NM_E_CLS_HEAD;
   }
   if (j->reg_head) {
     for (int i = 0; i < 3; ++i)
-      if (j->reg_w[i] < 0 || j->reg_b[i] < 0 || (j->reg_w[i] & 255) || (j->reg_b[i] & 3)) return -11;
-    if (!j->reg_resid || !j->reg_dres || ((uintptr_t)j->reg_resid & 15) || ((uintptr_t)j->reg_dres & 15)) return -11;
+      if (j->reg_w[i] < 0 || j->reg_b[i] < 0 || (j->reg_w[i] & 255) || (j->reg_b[i] & 3)) return NM_E_REG_HEAD;
+    if (!j->reg_resid || !j->reg_dres || ((uintptr_t)j->reg_resid & 15) || ((uintptr_t)j->reg_dres & 15)) return NM_E_REG_HEAD;
   }
   return 0;
 }
 
 int64_t nm_fill_shadow(nm_job_t* j) {
-  if (!j) return -1;
-  if (j->M < 1 || j->M > NM_MAX_MOD || j->L < 1 || j->L > NM_MAX_HID) return -2;
+  if (!j) return NM_E_NULL;
+  if (j->M < 1 || j->M > NM_MAX_MOD || j->L < 1 || j->L > NM_MAX_HID) return NM_E_MODALITIES;
   const int Me = j->M_enc > 0 ? j->M_enc : j->M;
   const int Zs = rup(j->Z, 16), L = j->L;
   int64_t o = WSH_ZERO_BYTES;                      // a line of zeros first: the source of every pad segment (dma_img)
   for (int m = 0; m < j->M; ++m) {
     nm_modality_t& md = j->mod[m];
-    if (md.Kx < 32 || md.D < 1) return -7;
+    if (md.Kx < 32 || md.D < 1) return NM_E_PITCH;
     for (int i = 0; i < NM_MAX_HID; ++i) { md.enc_s[i] = 0; md.dec_s[i] = 0; }
     md.heads_s = 0;
     md.out_s = 0;
@@ -1437,18 +1413,17 @@ int64_t nm_fill_shadow(nm_job_t* j) {
 }
 
 int nm_sync_shadow(const nm_job_t* jobs_dev, int n_jobs, void* stream) {
-  if (!jobs_dev) return -1;
-  if (n_jobs < 1) return -8;
+  if (!jobs_dev) return NM_E_NULL;
+  if (n_jobs < 1) return NM_E_GEOMETRY;
   // few jobs (the eager facade: one): many blocks per job, so that the rebuild is not one workgroup's serial loop
   const int slices = n_jobs >= 64 ? 4 : (n_jobs >= 8 ? 16 : 64);
-  hipLaunchKernelGGL(sync_shadow_kernel, dim3(n_jobs, slices), dim3(256), 0, (hipStream_t)stream, jobs_dev);
-  return (int)hipGetLastError();
+  return launch_kernel(sync_shadow_kernel, dim3(n_jobs, slices), dim3(256), 0, stream, jobs_dev);
 }
 
 /* Where a tile's workspace keeps the experts' statistics after a launch of the fused kernels: byte offset of
  * mu_m (what = 0) / logvar_m (what = 1), fp32 [step parity][expert][256][Z rounded to 16]; < 0: none (general-shape jobs). */
 int64_t nm_workspace_offset(const nm_job_t* j, int what) {
-  if (!j || what < 0 || what > 1) return -1;
+  if (!j || what < 0 || what > 1) return NM_E_NULL;
   if (j->wide) {                                   // (general-shape jobs: [expert][256][Z rounded to 16], no step parity)
     const WideWs ww = wide_ws_layout(j);
     return what == 0 ? ww.mu_m : ww.lv_m;
@@ -1458,7 +1433,7 @@ int64_t nm_workspace_offset(const nm_job_t* j, int what) {
 }
 
 int64_t nm_workspace_bytes(const nm_job_t* j) {
-  if (!j) return -1;
+  if (!j) return NM_E_NULL;
   int64_t b = trunk_ws_bytes(j);                      // the head's region sits behind the trunk's
   int64_t hb = 0;
   if (j->reg_head) hb = ACT_BYTES;        // regression head: its first hidden activation, kept for the backward pass
@@ -1467,87 +1442,64 @@ int64_t nm_workspace_bytes(const nm_job_t* j) {
 }
 
 int nm_sync_reset(const nm_job_t* jobs_dev, int n_jobs, void* stream) {
-  if (!jobs_dev) return -1;
-  if (n_jobs < 1) return -8;
-  hipLaunchKernelGGL(sync_reset_kernel, dim3((n_jobs * (WS_SYNC_BYTES / 4) + 255) / 256), dim3(256), 0, (hipStream_t)stream, jobs_dev, n_jobs);
-  return (int)hipGetLastError();
+  if (!jobs_dev) return NM_E_NULL;
+  if (n_jobs < 1) return NM_E_GEOMETRY;
+  return launch_kernel(sync_reset_kernel, dim3((n_jobs * (WS_SYNC_BYTES / 4) + 255) / 256), dim3(256), 0, stream, jobs_dev, n_jobs);
 }
 
 int nm_rowsplit_ok(const nm_job_t* j) {
-  if (!j) return -1;
-  if (j->wide || j->reg_head || j->cls_classes > 0 || j->cls_layers > 0) return -20;
-  if (j->w_off >= 0 || j->tc_weight != 0.f || j->n_private != 0 || j->out_kind != 0) return -20;
-  if (j->M_enc != 0 && j->M_enc != j->M) return -20;
-  if (j->M > NM_MAX_EXP) return -20;
+  if (!j) return NM_E_NULL;
+  if (j->wide || j->reg_head || j->cls_classes > 0 || j->cls_layers > 0) return NM_E_ROWSPLIT;
+  if (j->w_off >= 0 || j->tc_weight != 0.f || j->n_private != 0 || j->out_kind != 0) return NM_E_ROWSPLIT;
+  if (j->M_enc != 0 && j->M_enc != j->M) return NM_E_ROWSPLIT;
+  if (j->M > NM_MAX_EXP) return NM_E_ROWSPLIT;
   for (int m = 0; m < j->M; ++m) {                 // the sweep's tables (nm_rowsplit.hip): passes, vector segments and elements
     const int nck = (j->mod[m].D + OCH - 1) / OCH, nch = (j->mod[m].Kx + XCH - 1) / XCH;
-    if (nck + 2 * j->L + 1 + nch > NM_RS_MAX_PASSES || 2 * nck + 2 * j->L + 3 > NM_RS_MAX_VSEGS) return -20;
+    if (nck + 2 * j->L + 1 + nch > NM_RS_MAX_PASSES || 2 * nck + 2 * j->L + 3 > NM_RS_MAX_VSEGS) return NM_E_ROWSPLIT;
     int64_t vtot = 2 * (int64_t)j->mod[m].D + 2 * j->Z + 1;
     for (int i = 0; i < j->L; ++i) vtot += 2 * j->H[i];
-    if (vtot > 2 * WG * 3) return -20;              // three vector elements per thread at k = 2 (nm_rowsplit.hip: SW_NV)
+    if (vtot > NM_RS_MAX_VEC) return NM_E_ROWSPLIT;              // three vector elements per thread at k = 2 (nm_rowsplit.hip: SW_NV)
   }
   // (the sweep addresses slice q's partials at a 32-bit byte offset q * gpart_stride * 4 from slice 0's, q < 4)
-  if (!j->gpart || j->gpart_stride < j->n_params || (j->gpart_stride & 255) || j->gpart_stride >= ((int64_t)1 << 28)) return -20;
+  if (!j->gpart || j->gpart_stride < j->n_params || (j->gpart_stride & 255) || j->gpart_stride >= ((int64_t)1 << 28)) return NM_E_ROWSPLIT;
   return 0;
 }
 
 static int launch_impl(const nm_job_t* jobs_dev, int n_jobs, int step0, int steps_per_tile, int n_tiles, int flags,
                        void* stream, bool scalar_tr, int parts = 1) {
-  if (!jobs_dev) return -1;
-  if (n_jobs < 1 || steps_per_tile < 1 || n_tiles < 1 || step0 < 0) return -8;
-  // concurrent tiles of one job share its parameters, moments and gradient buffer: forward-only
-  if (n_tiles > 1 && (flags & (NM_F_BACKWARD | NM_F_ADAM | NM_F_GRADS))) return -8;
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid(n_jobs, n_tiles), block(WG);
+  if (int bad = check_launch_geometry(jobs_dev, n_jobs, n_tiles, steps_per_tile, step0, flags)) return bad;
+  dim3 grid(n_jobs, n_tiles);
   flags &= ~NM_F_SPLIT;
   if (parts <= 1) flags &= ~NM_F_FAULT_INJECT;
   if (parts > 1) {
     // several workgroups per model: they wait for each other inside the launch, so every one of them must be
     // resident at once -- one workgroup per CU (LDS), hence at most as many workgroups as the device has CUs
-    if (n_tiles != 1 || parts > NM_MAX_MOD || !(flags & NM_F_BACKWARD)) return -8;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return -8;
+    if (n_tiles != 1 || parts > NM_MAX_MOD || !(flags & NM_F_BACKWARD)) return NM_E_GEOMETRY;
+    const int cus = cu_count();
+    if (cus < 1) return NM_E_GEOMETRY;
     const int wgs = (n_jobs + 7) / 8 * 8 * parts;
-    if (wgs > cus) return -16;
+    if (wgs > cus) return NM_E_RESIDENCY;
     grid = dim3(wgs, 1);
     flags |= NM_F_SPLIT;
     nm_sync_reset(jobs_dev, n_jobs, stream);
   }
-  hipError_t e;
-  if (!scalar_tr && !(flags & NM_F_BACKWARD)) {           // forward only: the instantiation without the backward pass
-    e = hipFuncSetAttribute((const void*)nm_step_kernel<false, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((nm_step_kernel<false, 3>), grid, block, SMEM_BYTES, st, jobs_dev, step0, steps_per_tile, flags, n_jobs, parts);
-  } else if (scalar_tr) {
-    e = hipFuncSetAttribute((const void*)nm_step_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(nm_step_kernel<true>, grid, block, SMEM_BYTES, st, jobs_dev, step0, steps_per_tile, flags, n_jobs, parts);
-  } else {
-    e = hipFuncSetAttribute((const void*)nm_step_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(nm_step_kernel<false>, grid, block, SMEM_BYTES, st, jobs_dev, step0, steps_per_tile, flags, n_jobs, parts);
-  }
-  return (int)hipGetLastError();
+  auto kernel = nm_step_kernel<false, 3>;                 // forward only: the instantiation without the backward pass
+  if (scalar_tr) kernel = nm_step_kernel<true>;
+  else if (flags & NM_F_BACKWARD) kernel = nm_step_kernel<false>;
+  return launch_kernel(kernel, grid, dim3(WG), SMEM_BYTES, stream, jobs_dev, step0, steps_per_tile, flags, n_jobs, parts);
 }
 
 /* The general-shape path (csrc/nm_wide.inc): jobs with nm_job_t.wide = 1 -- hidden widths > 127, latent > 64 or
  * latent + c_dim > 127 -- one workgroup per (job, tile), same launch contract as nm_launch. */
 int nm_launch_wide(const nm_job_t* jobs_dev, int n_jobs, int step0, int steps_per_tile, int n_tiles, int flags, void* stream) {
-  if (!jobs_dev) return -1;
-  if (n_jobs < 1 || steps_per_tile < 1 || n_tiles < 1 || step0 < 0) return -8;
-  if (n_tiles > 1 && (flags & (NM_F_BACKWARD | NM_F_ADAM | NM_F_GRADS))) return -8;
-  hipError_t e = hipFuncSetAttribute((const void*)nm_wide_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-  if (e != hipSuccess) return (int)e;
+  if (int bad = check_launch_geometry(jobs_dev, n_jobs, n_tiles, steps_per_tile, step0, flags)) return bad;
   flags &= (NM_F_BACKWARD | NM_F_ADAM | NM_F_GRADS | NM_F_EXPORT | NM_F_ZGIVEN | NM_F_TRACE);
-  hipLaunchKernelGGL(nm_wide_step_kernel, dim3(n_jobs, n_tiles), dim3(WG), SMEM_BYTES, (hipStream_t)stream, jobs_dev, step0,
-                     steps_per_tile, flags);
-  return (int)hipGetLastError();
+  return launch_kernel(nm_wide_step_kernel, dim3(n_jobs, n_tiles), dim3(WG), SMEM_BYTES, stream, jobs_dev, step0, steps_per_tile, flags);
 }
 
 /* Small sweeps: every model runs as `parts` workgroups, one per modality (decoder), which meet twice per step (after
  * the encoders: expert statistics; after the decoders: d z).  All jobs of the launch must have M == parts decoders.
- * Results equal the one-workgroup launch bit for bit.  -16: more workgroups than CUs (they could not all be resident). */
+ * Results equal the one-workgroup launch bit for bit.  NM_E_RESIDENCY: more workgroups than CUs (they could not all be resident). */
 int nm_launch_split(const nm_job_t* jobs_dev, int n_jobs, int parts, int step0, int n_steps, int flags, void* stream) {
   return launch_impl(jobs_dev, n_jobs, step0, n_steps, 1, flags, stream, false, parts);
 }
@@ -1555,10 +1507,9 @@ int nm_launch_split(const nm_job_t* jobs_dev, int n_jobs, int parts, int step0, 
 /* Error words of the jobs' split launches: out_dev[j] != 0 <=> a hand-off of job j timed out in some nm_launch_split
  * since the words were last cleared (its parts left the launch; the parameters are not to be trusted). */
 int nm_split_errors(const nm_job_t* jobs_dev, int n_jobs, int* out_dev, int clear, void* stream) {
-  if (!jobs_dev || !out_dev) return -1;
-  if (n_jobs < 1) return -8;
-  hipLaunchKernelGGL(split_errors_kernel, dim3((n_jobs + 255) / 256), dim3(256), 0, (hipStream_t)stream, jobs_dev, n_jobs, out_dev, clear);
-  return (int)hipGetLastError();
+  if (!jobs_dev || !out_dev) return NM_E_NULL;
+  if (n_jobs < 1) return NM_E_GEOMETRY;
+  return launch_kernel(split_errors_kernel, dim3((n_jobs + 255) / 256), dim3(256), 0, stream, jobs_dev, n_jobs, out_dev, clear);
 }
 
 int nm_launch(const nm_job_t* jobs_dev, int n_jobs, int step0, int steps_per_tile, int n_tiles, int flags,
@@ -1573,39 +1524,23 @@ int nm_launch_scalar_tr(const nm_job_t* jobs_dev, int n_jobs, int step0, int ste
 }
 
 int nm_head_regression(const nm_job_t* jobs_dev, int n_jobs, int step, int tile0, int n_tiles, int flags, void* stream) {
-  if (!jobs_dev) return -1;
-  if (n_jobs < 1 || n_tiles < 1 || step < 0 || tile0 < 0) return -8;
-  // concurrent tiles of one job share its parameters, moments, gradient buffer and reg_dres: forward-only
-  if (n_tiles > 1 && (flags & (NM_F_BACKWARD | NM_F_ADAM | NM_F_GRADS))) return -8;
-  hipError_t e = hipFuncSetAttribute((const void*)nm_reghead_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(nm_reghead_kernel, dim3(n_jobs, n_tiles), dim3(WG), SMEM_BYTES, (hipStream_t)stream, jobs_dev, step,
-                     tile0, flags);
-  return (int)hipGetLastError();
+  // (several tiles run forward only: they would also share reg_dres)
+  if (int bad = check_launch_geometry(jobs_dev, n_jobs, n_tiles, 1, step < tile0 ? step : tile0, flags)) return bad;
+  return launch_kernel(nm_reghead_kernel, dim3(n_jobs, n_tiles), dim3(WG), SMEM_BYTES, stream, jobs_dev, step, tile0, flags);
 }
 
 int nm_head_classifier(const nm_job_t* jobs_dev, int n_jobs, int step, int tile0, int n_tiles, int flags, void* stream) {
-  if (!jobs_dev) return -1;
-  if (n_jobs < 1 || n_tiles < 1 || step < 0 || tile0 < 0) return -8;
-  if (n_tiles > 1 && (flags & (NM_F_BACKWARD | NM_F_ADAM | NM_F_GRADS))) return -8;
-  hipError_t e = hipFuncSetAttribute((const void*)nm_clshead_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(nm_clshead_kernel, dim3(n_jobs, n_tiles), dim3(WG), SMEM_BYTES, (hipStream_t)stream, jobs_dev, step,
-                     tile0, flags);
-  return (int)hipGetLastError();
+  if (int bad = check_launch_geometry(jobs_dev, n_jobs, n_tiles, 1, step < tile0 ? step : tile0, flags)) return bad;
+  return launch_kernel(nm_clshead_kernel, dim3(n_jobs, n_tiles), dim3(WG), SMEM_BYTES, stream, jobs_dev, step, tile0, flags);
 }
 
 /* n_steps train steps of head models (every job: regression head, or end-to-end with classifier, labels / targets and
  * exchange buffers set) in ONE persistent launch, one workgroup per job: see nm_head_step_kernel. */
 int nm_train_steps_head(const nm_job_t* jobs_dev, int n_jobs, int step0, int n_steps, int flags, void* stream) {
-  if (!jobs_dev) return -1;
-  if (n_jobs < 1 || n_steps < 1 || step0 < 0) return -8;
-  hipError_t e = hipFuncSetAttribute((const void*)nm_head_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-  if (e != hipSuccess) return (int)e;
-  if ((flags & NM_F_GRADS) && n_steps != 1) return -8;
-  hipLaunchKernelGGL(nm_head_step_kernel, dim3(n_jobs), dim3(WG), SMEM_BYTES, (hipStream_t)stream, jobs_dev, step0, n_steps,
-                     flags & (NM_F_PROFILE | NM_F_TRACE | NM_F_GRADS | NM_F_BNSTATS));
-  return (int)hipGetLastError();
+  if (int bad = check_launch_geometry(jobs_dev, n_jobs, 1, n_steps, step0, flags)) return bad;
+  if ((flags & NM_F_GRADS) && n_steps != 1) return NM_E_GEOMETRY;
+  return launch_kernel(nm_head_step_kernel, dim3(n_jobs), dim3(WG), SMEM_BYTES, stream, jobs_dev, step0, n_steps,
+                       flags & (NM_F_PROFILE | NM_F_TRACE | NM_F_GRADS | NM_F_BNSTATS));
 }
 
 int nm_train_steps(const nm_job_t* jobs_dev, int n_jobs, int step0, int n_steps, void* stream) {
@@ -1630,46 +1565,41 @@ int nm_deviation(const nm_job_t* jobs_dev, int n_jobs, int tile0, int n_tiles, v
 
 int nm_adam_step(float* params, const float* grads, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                  float eps, int64_t t, void* stream) {
-  if (!params || !grads || !m || !v) return -1;
-  if (n <= 0 || t < 1) return -8;
-  double bc1 = 1.0 - pow((double)beta1, (double)t), bc2 = 1.0 - pow((double)beta2, (double)t);
-  float step_size = (float)((double)lr / bc1), inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+  if (!params || !grads || !m || !v) return NM_E_NULL;
+  if (n <= 0 || t < 1) return NM_E_GEOMETRY;
+  float step_size, inv_bc2_sqrt;
+  adam_bias_consts((double)lr, beta1, beta2, t, step_size, inv_bc2_sqrt);
   int blocks = (int)((n + 255) / 256);
   if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(adam_flat_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, n, beta1,
-                     beta2, eps, step_size, inv_bc2_sqrt);
-  return (int)hipGetLastError();
+  return launch_kernel(adam_flat_kernel, dim3(blocks), dim3(256), 0, stream, params, grads, m, v, n, beta1, beta2, eps, step_size,
+                       inv_bc2_sqrt);
 }
 
 int64_t nm_xb_elems(int rows_alloc, int Kx) {
-  if (rows_alloc < 1 || rows_alloc % NM_BATCH != 0 || Kx < 32 || Kx % 32 != 0) return -7;
+  if (rows_alloc < 1 || rows_alloc % NM_BATCH != 0 || Kx < 32 || Kx % 32 != 0) return NM_E_PITCH;
   return (int64_t)rows_alloc * ((Kx + XCH - 1) / XCH) * LDX;
 }
 
 int nm_pack_table(const float* x, const float* c, int n_rows, int rows_alloc, int D, int C, int Kx, uint16_t* xb,
                   float* x_f32_out, int x_pitch, uint16_t* cz_out, int Cz, void* stream) {
-  if (!x || !xb || (C > 0 && !c)) return -1;
-  if (Kx % 32 != 0 || Kx < D + C + 1 || rows_alloc < n_rows || rows_alloc % NM_BATCH != 0) return -7;
-  if (x_f32_out && (x_pitch % 4 != 0 || x_pitch < D || x_pitch > Kx)) return -7;
-  if (cz_out && (Cz % 8 != 0 || Cz < C + 1)) return -7;
+  if (!x || !xb || (C > 0 && !c)) return NM_E_NULL;
+  if (Kx % 32 != 0 || Kx < D + C + 1 || rows_alloc < n_rows || rows_alloc % NM_BATCH != 0) return NM_E_PITCH;
+  if (x_f32_out && (x_pitch % 4 != 0 || x_pitch < D || x_pitch > Kx)) return NM_E_PITCH;
+  if (cz_out && (Cz % 8 != 0 || Cz < C + 1)) return NM_E_PITCH;
   int64_t total = nm_xb_elems(rows_alloc, Kx);
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(pack_table_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, c, n_rows, rows_alloc, D, C,
-                     Kx, xb, x_f32_out, x_pitch, cz_out, Cz);
-  return (int)hipGetLastError();
+  return launch_kernel(pack_table_kernel, dim3(blocks), dim3(256), 0, stream, x, c, n_rows, rows_alloc, D, C, Kx, xb, x_f32_out,
+                       x_pitch, cz_out, Cz);
 }
 
 int nm_test_gemm(int mode, const float* A, const float* B, float* Cout, int M, int N, int K, void* stream) {
-  if (!A || !B || !Cout) return -1;
-  if (M != ROWS || mode < 0 || mode > 3) return -8;
-  if (mode == 0 && (K > PW || N > PW)) return -8;
-  if (mode == 1 && (N > PW || K > 96)) return -8;
-  if (mode >= 2 && (N > PW || K > PW)) return -8;
-  hipError_t e = hipFuncSetAttribute((const void*)test_gemm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(test_gemm_kernel, dim3(1), dim3(WG), SMEM_BYTES, (hipStream_t)stream, mode, A, B, Cout, M, N, K);
-  return (int)hipGetLastError();
+  if (!A || !B || !Cout) return NM_E_NULL;
+  if (M != ROWS || mode < 0 || mode > 3) return NM_E_GEOMETRY;
+  if (mode == 0 && (K > PW || N > PW)) return NM_E_GEOMETRY;
+  if (mode == 1 && (N > PW || K > 96)) return NM_E_GEOMETRY;
+  if (mode >= 2 && (N > PW || K > PW)) return NM_E_GEOMETRY;
+  return launch_kernel(test_gemm_kernel, dim3(1), dim3(WG), SMEM_BYTES, stream, mode, A, B, Cout, M, N, K);
 }
 
 }  // extern "C"

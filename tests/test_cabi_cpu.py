@@ -29,6 +29,38 @@ def test_header_symbols_are_exported(lib):
         assert hasattr(lib, sym), sym
 
 
+def _header_constants():
+    """Every integer constant include/nmhip.h defines: `#define NM_X <int>` and `NM_X = <int>` inside an enum."""
+    header = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "nmhip.h").read_text(), flags=re.S)
+    consts = {name: int(val) for name, val in re.findall(r"^#define\s+(NM_\w+)\s+(-?\d+)\s*$", header, flags=re.M)}
+    for body in re.findall(r"\benum\s*\{([^}]*)\}", header):
+        for name, val in re.findall(r"\b(NM_\w+)\s*=\s*(-?\d+)", body):
+            assert name not in consts, name
+            consts[name] = int(val)
+    return consts
+
+
+def test_python_mirror_matches_header(lib):
+    """Every integer NM_* constant of _lib.py has the value include/nmhip.h gives it (no exception list), the combine
+    table too, and every status name of the header is mirrored and has a text of its own."""
+    header = _header_constants()
+    mirror = {k: v for k, v in vars(_lib).items() if k.startswith("NM_") and isinstance(v, int)}
+    assert len(mirror) >= 33 + 23 and len(header) >= len(mirror)
+    for name, val in mirror.items():
+        assert name in header, name
+        assert header[name] == val, (name, val, header[name])
+    for key, val in _lib.NM_COMBINE.items():
+        assert header["NM_COMBINE_" + key.upper()] == val, key
+    status = {k: v for k, v in header.items() if k == "NM_OK" or k.startswith("NM_E_")}
+    assert sorted(status.values()) == list(range(-22, 1))
+    texts = {}
+    for name, val in status.items():
+        assert mirror.get(name) == val, name
+        texts[name] = lib.nm_status_string(val)
+        assert texts[name] and texts[name] != lib.nm_status_string(-1000), name     # (-1000: the text of an unknown code)
+    assert len(set(texts.values())) == len(texts)
+
+
 def test_abi_struct_sizes_match(lib):
     sj, sm = C.c_int64(0), C.c_int64(0)
     assert lib.nm_abi_sizes(C.byref(sj), C.byref(sm)) == 0
@@ -54,27 +86,27 @@ def _probe(M=1, L=2, Z=10, C_=29, H=(110, 110), D=379):
 
 def test_validate_job_limits(lib):
     assert lib.nm_validate_job(C.byref(_probe())) == 0
-    assert lib.nm_validate_job(C.byref(_probe(M=5))) == -2
-    assert lib.nm_validate_job(C.byref(_probe(L=9, H=(8, 8, 8)))) == -3
+    assert lib.nm_validate_job(C.byref(_probe(M=5))) == _lib.NM_E_MODALITIES
+    assert lib.nm_validate_job(C.byref(_probe(L=9, H=(8, 8, 8)))) == _lib.NM_E_LAYERS
     assert lib.nm_validate_job(C.byref(_probe(L=5, H=(90, 90, 90, 90, 90)))) == 0     # "-H 90 90 90 90 90 10", commands_list9_endtoend.sh:24
-    assert lib.nm_validate_job(C.byref(_probe(H=(128, 110)))) == -4
-    assert lib.nm_validate_job(C.byref(_probe(Z=65))) == -5
-    assert lib.nm_validate_job(C.byref(_probe(Z=64, C_=64))) == -6
+    assert lib.nm_validate_job(C.byref(_probe(H=(128, 110)))) == _lib.NM_E_WIDTH
+    assert lib.nm_validate_job(C.byref(_probe(Z=65))) == _lib.NM_E_LATENT
+    assert lib.nm_validate_job(C.byref(_probe(Z=64, C_=64))) == _lib.NM_E_LATENT_COV
     bad = _probe()
     bad.mod[0].Kx = 400
-    assert lib.nm_validate_job(C.byref(bad)) == -7
-    assert b"Kx" in lib.nm_status_string(-7)
+    assert lib.nm_validate_job(C.byref(bad)) == _lib.NM_E_PITCH
+    assert b"Kx" in lib.nm_status_string(_lib.NM_E_PITCH)
     for field in ("n_rows", "loss_cap", "eps_cap"):            # modulo divisors inside the kernel
         bad = _probe()
         setattr(bad, field, 0)
-        assert lib.nm_validate_job(C.byref(bad)) == -14
+        assert lib.nm_validate_job(C.byref(bad)) == _lib.NM_E_COUNTS
     bad = _probe()
     bad.wsh = None
-    assert lib.nm_validate_job(C.byref(bad)) == -15
+    assert lib.nm_validate_job(C.byref(bad)) == _lib.NM_E_SHADOW
     for n in (0, 1 << 30):                                      # 32-bit byte offsets into params / adam_m / adam_v
         bad = _probe()
         bad.n_params = n
-        assert lib.nm_validate_job(C.byref(bad)) == -21
+        assert lib.nm_validate_job(C.byref(bad)) == _lib.NM_E_N_PARAMS
     # deviation-pass kernel: one expert with the bypass, first hidden width <= 112, latent <= 32, Gaussian output
     ok = _probe()
     ok.w_off, ok.single_bypass = -1, 1
@@ -83,10 +115,10 @@ def test_validate_job_limits(lib):
         bad = _probe()
         bad.w_off, bad.single_bypass = -1, 1
         setattr(bad, field, val)
-        assert lib.nm_devpass_ok(C.byref(bad)) == -22, field
+        assert lib.nm_devpass_ok(C.byref(bad)) == _lib.NM_E_DEVPASS, field
     bad = _probe(H=(113, 110))
     bad.w_off, bad.single_bypass = -1, 1
-    assert lib.nm_devpass_ok(C.byref(bad)) == -22
+    assert lib.nm_devpass_ok(C.byref(bad)) == _lib.NM_E_DEVPASS
     # row-split launch: plain multimodal models with a partial-gradient buffer only
     ok = _probe(M=3)
     ok.w_off, ok.gpart, ok.gpart_stride = -1, 4096, 118528
@@ -96,14 +128,14 @@ def test_validate_job_limits(lib):
         bad = _probe(M=3)
         bad.w_off, bad.gpart, bad.gpart_stride = -1, 4096, 118528
         setattr(bad, field, val)
-        assert lib.nm_rowsplit_ok(C.byref(bad)) == -20, field
+        assert lib.nm_rowsplit_ok(C.byref(bad)) == _lib.NM_E_ROWSPLIT, field
     bad = _probe()
     bad.mod[0].enc_w[0] = 8                                     # weight matrices start on a tile boundary
-    assert lib.nm_validate_job(C.byref(bad)) == -10
+    assert lib.nm_validate_job(C.byref(bad)) == _lib.NM_E_OFFSETS
     # the general-shape path (nm_job_t.wide): the widths / latents of the reference's sweeps the fused tile cannot hold
     for kw in (dict(H=(1024, 512, 256), L=3, Z=32), dict(H=(300, 300), Z=30), dict(H=(110, 110), Z=100), dict(H=(2048,), L=1, Z=10)):
         j = _probe(**kw)
-        assert lib.nm_validate_job(C.byref(j)) in (-4, -5, -6)      # not a fused-kernel shape ...
+        assert lib.nm_validate_job(C.byref(j)) in (_lib.NM_E_WIDTH, _lib.NM_E_LATENT, _lib.NM_E_LATENT_COV)    # not a fused-kernel shape ...
         j.wide, j.w_off = 1, -1
         j.wsh = None                                                # ... and the wide path needs no shadow images
         assert lib.nm_validate_job(C.byref(j)) == 0
@@ -120,13 +152,13 @@ def test_validate_job_limits(lib):
     assert lib.nm_validate_job(C.byref(j)) == 0
     j = _probe(H=(300, 300), Z=100, M=3)
     j.wide, j.w_off, j.tc_weight = 1, -1, 3e-4
-    assert lib.nm_validate_job(C.byref(j)) == -19
+    assert lib.nm_validate_job(C.byref(j)) == _lib.NM_E_WIDE_TC
     j = _probe(H=(300, 300), Z=30)
     j.wide, j.reg_head, j.w_off = 1, 1, -1
-    assert lib.nm_validate_job(C.byref(j)) == -11                   # (regression head: its own buffers are checked as ever)
+    assert lib.nm_validate_job(C.byref(j)) == _lib.NM_E_REG_HEAD    # (regression head: its own buffers are checked as ever)
     n = lib.nm_fill_shadow(C.byref(j))                              # ... and its first-layer images are the job's only shadow
     assert 0 < n < 1 << 20 and j.reg_s > 0 and j.mod[0].enc_s[0] == 0 and j.mod[0].out_s == 0
-    assert lib.nm_validate_job(C.byref(_probe(H=(5000, 10)))) == -4
+    assert lib.nm_validate_job(C.byref(_probe(H=(5000, 10)))) == _lib.NM_E_WIDTH
 
 
 def test_shadow_layout(lib):
@@ -243,7 +275,7 @@ def test_rowsplit_table_limits_at_their_edges(lib):
     assert "vector elements" in rowsplit_limit(nm.ModelSpec([1306], [110, 110], 10, 29))
     # three modalities, one of them just over: the model is refused
     assert lib.nm_rowsplit_ok(C.byref(_rs_probe([379, 1305, 379]))) == 0
-    assert lib.nm_rowsplit_ok(C.byref(_rs_probe([379, 1306, 379]))) == -20
+    assert lib.nm_rowsplit_ok(C.byref(_rs_probe([379, 1306, 379]))) == _lib.NM_E_ROWSPLIT
     assert rowsplit_fits(nm.ModelSpec([379, 1305, 379], [110, 110], 10, 29, True))
     assert rowsplit_limit(nm.ModelSpec([379, 1306, 379], [110, 110], 10, 29, True)).startswith("modality 1:")
 

@@ -328,7 +328,7 @@ def test_split_launch_many_small_models_and_refusal():
     big = nm.JobSet([make_job(g, 0) for _ in range(96)])  # 96 x 3 = 288 workgroups > 256 CUs
     ptr = big._upload(1)
     st = torch.cuda.current_stream().cuda_stream
-    assert lib.nm_launch_split(ptr, 96, 3, 0, 1, _lib.NM_F_BACKWARD | _lib.NM_F_GRADS, st) == -16
+    assert lib.nm_launch_split(ptr, 96, 3, 0, 1, _lib.NM_F_BACKWARD | _lib.NM_F_GRADS, st) == _lib.NM_E_RESIDENCY
     assert big.split_parts() == 1
 
 

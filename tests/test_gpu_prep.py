@@ -59,10 +59,10 @@ def test_training_from_device_built_tables_equals_host_built():
 
 def test_prep_argument_errors():
     lib = nm._lib.load()
-    assert lib.nm_prep_scaler_fit(None, None, 1, 1, None, 1, None, None, None) == -1
+    assert lib.nm_prep_scaler_fit(None, None, 1, 1, None, 1, None, None, None) == nm._lib.NM_E_NULL
     dc = DeviceCohort(prep.synthetic_cohort(n=64, d=8), DEV)
     ptrs, widths, n_src, D, keep = dc._sources("fMRI")
     rows = torch.zeros(9000, dtype=torch.int32, device=DEV)
     out = torch.empty(D, dtype=torch.float64, device=DEV)
     assert lib.nm_prep_scaler_fit(ptrs.data_ptr(), widths.data_ptr(), n_src, D, rows.data_ptr(), 9000, out.data_ptr(),
-                                  out.data_ptr(), None) == -17
+                                  out.data_ptr(), None) == nm._lib.NM_E_PREP
