@@ -311,6 +311,28 @@ int nm_launch_wide(const nm_job_t* jobs_dev, int n_jobs, int step0, int steps_pe
  * Status NM_E_RESIDENCY: ceil(n_jobs * M / 8) * 8 * (k + helpers) exceeds the CU count; errors of the hand-offs: nm_split_errors. */
 int nm_launch_rowsplit(const nm_job_t* jobs_dev, int n_jobs, int M, int k, int helpers, int step0, int n_steps, int flags,
                        int spread_us, void* stream);
+/* The row-split launch for a GRID of models that differ in their number of modalities: the reference's unit of work is
+ * 5 folds x {SM-T1w_sMRI, SM-T2w_sMRI, SM-fMRI, UCA-gPoE} (commands_list_deviation.sh:13-23, trained one after another by
+ * multimodal_kfold_train_cvae_supervised.py:68,82) -- 15 one-modality and 5 four-modality models, here ONE launch.
+ * job_M_host[j] (host memory, n_jobs ints, read before the call returns) = modalities of job j, which must equal that
+ * job's nm_job_t.M; group g of the launch is the g-th (job, modality) pair in set order (nm_rowsplit_groups), so a set
+ * whose jobs all have M modalities gets exactly nm_launch_rowsplit's map -- that entry point is this one with every job
+ * listed at M.  The map travels by value in the kernel's arguments: no device buffer, nothing to keep alive.  Arguments,
+ * flags, helpers, spread_us and results per model as nm_launch_rowsplit: a model's result depends on k only, not on the
+ * other models of the launch.  Status NM_E_NULL: jobs_dev or job_M_host missing; NM_E_GEOMETRY: a count outside
+ * 1..NM_MAX_EXP, k not 2 / 4, the flag rules above; NM_E_RESIDENCY: ceil(sum(job_M_host) / 8) * 8 groups exceed
+ * NM_RS_MAX_GROUPS, or groups * (k + helpers) the CU count.  A job listed with a count that is not its own is refused by the
+ * kernel before its first hand-off (nm_split_errors: NM_SYNC_ERR_SHAPE, parameters untouched); the other jobs train. */
+int nm_launch_rowsplit_mixed(const nm_job_t* jobs_dev, int n_jobs, const int* job_M_host, int k, int helpers, int step0,
+                             int n_steps, int flags, int spread_us, void* stream);
+/* The group map of that launch, host only (no device access): table_out[g] = job | part << 16 | job_M_host[job] << 24 for
+ * the jobs in set order and the parts of a job in order, then NM_RS_GROUP_PAD up to the next multiple of 8.  Returns the
+ * number of slots written (a multiple of 8, at most NM_RS_MAX_GROUPS: groups * k <= 256 CUs with k >= 2), or NM_E_NULL
+ * (an array missing), NM_E_GEOMETRY (n_jobs < 1, a count outside 1..NM_MAX_EXP, cap below the slots needed),
+ * NM_E_RESIDENCY (more than NM_RS_MAX_GROUPS slots).  The reference has no counterpart (one model per process). */
+#define NM_RS_MAX_GROUPS 128
+#define NM_RS_GROUP_PAD  65535
+int nm_rowsplit_groups(const int* job_M_host, int n_jobs, int* table_out, int cap);
 /* Limits of the row-split launch's Adam sweep, per modality (nm_rowsplit_ok refuses a job beyond them): weight passes,
  * vector segments, and vector elements (biases, logvar_out, alpha: 3 per thread of k = 2 workgroups of 512). */
 #define NM_RS_MAX_PASSES 128

@@ -16,6 +16,9 @@ NM_MAX_EXP = 4
 NM_RS_MAX_PASSES = 128
 NM_RS_MAX_VSEGS = 144
 NM_RS_MAX_VEC = 3 * 2 * 512
+# the group map of a row-split launch (nm_rowsplit_groups): slots per launch, the entry of a padding slot
+NM_RS_MAX_GROUPS = 128
+NM_RS_GROUP_PAD = 65535
 NM_MAX_HID = 8
 NM_MAX_CLS = 5
 NM_MAX_CLS_WIDTH = 512
@@ -162,6 +165,8 @@ def load():
     lib.nm_launch_wide.argtypes = [vp, i32, i32, i32, i32, i32, vp]
     lib.nm_split_errors.argtypes = [vp, i32, vp, i32, vp]
     lib.nm_launch_rowsplit.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+    lib.nm_launch_rowsplit_mixed.argtypes = [vp, i32, C.POINTER(i32), i32, i32, i32, i32, i32, i32, vp]
+    lib.nm_rowsplit_groups.argtypes = [C.POINTER(i32), i32, C.POINTER(i32), i32]
     lib.nm_rowsplit_ok.argtypes = [C.POINTER(NmJob)]
     lib.nm_sync_reset.argtypes = [vp, i32, vp]
     lib.nm_trace_read_rs.argtypes = [C.POINTER(C.c_ulonglong), i32]
@@ -206,6 +211,7 @@ EXPORTED_SYMBOLS = [
     "nm_fill_shadow", "nm_sync_shadow", "nm_xb_elems", "nm_launch_split", "nm_launch_wide", "nm_split_errors", "nm_combine_latent", "nm_total_correlation",
     "nm_prep_scaler_fit", "nm_prep_onehot", "nm_pack_table_raw",
     "nm_launch_rowsplit", "nm_rowsplit_ok", "nm_sync_reset", "nm_trace_read_rs", "nm_devpass", "nm_devpass_ok", "nm_trace_read_dv", "nm_workspace_offset",
+    "nm_launch_rowsplit_mixed", "nm_rowsplit_groups",
 ]
 
 

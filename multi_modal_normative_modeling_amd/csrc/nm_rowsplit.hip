@@ -312,13 +312,23 @@ __device__ __forceinline__ bool wait_counter(const Ctx& c, GAS unsigned* cnt, GA
 // ---- kernel ----------------------------------------------------------------------------------------------------------
 // Grid: groups of KS workgroups = the row slices of one (job, modality), every group on ONE XCD (workgroups b and b + 8
 // share an XCD -- observed placement, speed only: the partials of a group then meet in that XCD's L2; correctness comes from
-// the hand-off protocol): workgroup b = ((slot * KH + q) << 3) + xcd is member q of group slot * 8 + xcd = job * M + m; members
+// the hand-off protocol): workgroup b = ((slot * KH + q) << 3) + xcd is member q of group slot * 8 + xcd; members
 // q < KS are the row slices, members KS <= q < KH = KS + H are HELPERS: a small set leaves most CUs idle, and the Adam sweep --
 // a quarter of a slice's step, bound by what ONE CU pulls from memory -- needs nothing but the partials in memory, so the
 // idle CUs take a share of its tiles.  A helper waits for hand-off C (it publishes nothing), sweeps, arrives at D.
+//
+// Which (job, modality) a group is comes from the GROUP MAP, a table the host builds (nm_rowsplit_groups: jobs in set order,
+// the parts of a job in order -- for a set whose jobs all have M modalities exactly group / M, group % M) and passes BY VALUE
+// in the kernel arguments: the jobs of one launch may differ in their number of modalities (the reference's grid is 15
+// one-modality and 5 four-modality models, commands_list_deviation.sh:13-23).  One entry per group: the job in bits 0..15
+// (NM_RS_GROUP_PAD: a slot that only rounds the count up to a multiple of 8), the part in bits 16..23, the job's modality count
+// as the host believed it in bits 24..31.  The lookup is one scalar load from the argument segment (the group is uniform
+// over the workgroup); no device buffer, no upload, no lifetime rule.
+constexpr int RS_MAP_SLOTS = NM_RS_MAX_GROUPS;         // groups * k <= CUs (256) with k >= 2
+struct RsMap { unsigned e[RS_MAP_SLOTS]; };
 template <int KS>
 __global__ __launch_bounds__(WG) void nm_rs_kernel(const nm_job_t* __restrict__ jobs, int step0, int n_steps, int flags,
-                                                   int n_jobs, int M, int spread_us, int H) {
+                                                   int n_jobs, int spread_us, int H, const RsMap map) {
   constexpr int RTV = 8 / KS;
   NM_GEOM(RTV);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -326,13 +336,16 @@ __global__ __launch_bounds__(WG) void nm_rs_kernel(const nm_job_t* __restrict__ 
   const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
   const int q = idx % KH, group = (idx / KH) * 8 + xcd;
   const bool helper = q >= KS;
-  const int job_idx = group / M, part = group - job_idx * M;
-  if (job_idx >= n_jobs) return;
-  if ((flags & NM_F_FAULT_INJECT) && part == M - 1 && q == KS - 1) return;   // diagnostic: a workgroup that never arrives
+  if (group >= RS_MAP_SLOTS) return;
+  const unsigned ent = map.e[group];
+  const int job_idx = (int)(ent & 0xffffu), part = (int)((ent >> 16) & 0xffu), M_map = (int)(ent >> 24);
+  if (job_idx >= n_jobs) return;                                              // a padding slot
+  if ((flags & NM_F_FAULT_INJECT) && part == M_map - 1 && q == KS - 1) return;   // diagnostic: a workgroup that never arrives
   if ((flags & 64) && blockIdx.x < 512 && threadIdx.x == 0) nm_wg_times[blockIdx.x][0] = __builtin_amdgcn_s_memrealtime();
   const nm_job_t* J = jobs + job_idx;
   Ctx c;
   c.job = J;
+  const int M = J->M;               // everything below counts with the job's own modalities, never a launch-wide number
   c.part = part;
   c.nparts = M;
   c.slope = J->act_slope;
@@ -348,8 +361,12 @@ __global__ __launch_bounds__(WG) void nm_rs_kernel(const nm_job_t* __restrict__ 
   for (int i = c.tid; i < SMEM_BYTES / 4; i += WG) reinterpret_cast<uint32_t*>(smem)[i] = 0u;
   __syncthreads();
   const WsLayout wl = ws_layout(J->M, J->L, J->Z);
-  if (!rs_fits(J, M, KH)) {        // (uniform over the job's workgroups: all leave, none is left waiting at a hand-off)
-    if (part == 0 && q == 0 && c.tid == 0)
+  // Refused before the first hand-off, so nobody is left waiting: a map entry that disagrees with the job (the host listed it
+  // with another modality count: EVERY group the map gives this job sees that, the groups of other jobs are not touched), or
+  // a job the sweep's tables cannot hold (uniform over the job's workgroups).
+  const bool map_ok = M_map == M && part < M;
+  if (!map_ok || !rs_fits(J, M, KH)) {
+    if ((part == 0 || !map_ok) && q == 0 && c.tid == 0)
       __hip_atomic_store((unsigned*)((GAS unsigned*)(c.ws0 + wl.sync) + WS_SYNC_ERR_WORD), WS_SYNC_ERR_SHAPE, __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_AGENT);
     return;
@@ -466,25 +483,61 @@ __global__ __launch_bounds__(WG) void nm_rs_kernel(const nm_job_t* __restrict__ 
 
 extern "C" {
 
-/* Row-split launch (include/nmhip.h): n_jobs models of M modalities each, k in {2, 4} row slices per (model, modality).
- * Every job needs k workspace tiles and gpart / gpart_stride; NM_E_RESIDENCY: the launch would not be resident
- * at once; NM_E_ROWSPLIT: a job of the launch cannot run row-split (see nm_rowsplit_ok). */
-int nm_launch_rowsplit(const nm_job_t* jobs_dev, int n_jobs, int M, int k, int helpers, int step0, int n_steps, int flags,
-                       int spread_us, void* stream) {
+/* The group map of a row-split launch (include/nmhip.h), host only: entry = job | part << 16 | M << 24. */
+int nm_rowsplit_groups(const int* job_M_host, int n_jobs, int* table_out, int cap) {
+  if (!job_M_host || !table_out) return NM_E_NULL;
+  if (n_jobs < 1 || cap < 8) return NM_E_GEOMETRY;
+  int64_t groups = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    if (job_M_host[j] < 1 || job_M_host[j] > NM_MAX_EXP) return NM_E_GEOMETRY;
+    groups += job_M_host[j];
+  }
+  const int64_t slots = (groups + 7) / 8 * 8;
+  if (slots > NM_RS_MAX_GROUPS) return NM_E_RESIDENCY;      // (also bounds n_jobs to what an entry's job field holds)
+  if (slots > cap) return NM_E_GEOMETRY;
+  int g = 0;
+  for (int j = 0; j < n_jobs; ++j)
+    for (int m = 0; m < job_M_host[j]; ++m) table_out[g++] = (int)((unsigned)j | (unsigned)m << 16 | (unsigned)job_M_host[j] << 24);
+  for (; g < (int)slots; ++g) table_out[g] = (int)NM_RS_GROUP_PAD;
+  return (int)slots;
+}
+
+/* Row-split launch over a set whose jobs may differ in their number of modalities (include/nmhip.h): k in {2, 4} row slices
+ * per (model, modality).  Every job needs k workspace tiles and gpart / gpart_stride; NM_E_RESIDENCY: the launch would
+ * not be resident at once.  A job the Adam sweep cannot hold, or one listed with a modality count that is not its own,
+ * is refused by the kernel (nm_split_errors: NM_SYNC_ERR_SHAPE). */
+int nm_launch_rowsplit_mixed(const nm_job_t* jobs_dev, int n_jobs, const int* job_M_host, int k, int helpers, int step0,
+                             int n_steps, int flags, int spread_us, void* stream) {
   if (int bad = check_launch_geometry(jobs_dev, n_jobs, 1, n_steps, step0, flags)) return bad;
-  if (M < 1 || M > NM_MAX_EXP || (k != 2 && k != 4)) return NM_E_GEOMETRY;
+  if (!job_M_host) return NM_E_NULL;
+  if (k != 2 && k != 4) return NM_E_GEOMETRY;
   if (!(flags & NM_F_BACKWARD) || !(flags & (NM_F_ADAM | NM_F_GRADS))) return NM_E_GEOMETRY;
   if ((flags & NM_F_GRADS) && n_steps != 1) return NM_E_GEOMETRY;
+  RsMap map;
+  const int groups = nm_rowsplit_groups(job_M_host, n_jobs, (int*)map.e, RS_MAP_SLOTS);
+  if (groups < 0) return groups;
+  for (int g = groups; g < RS_MAP_SLOTS; ++g) map.e[g] = NM_RS_GROUP_PAD;
   const int cus = cu_count();
   if (cus < 1 || helpers < 0 || helpers > 60) return NM_E_GEOMETRY;
-  const int groups = (n_jobs * M + 7) / 8 * 8;
   const int wgs = groups * (k + helpers);
   if (wgs > cus) return NM_E_RESIDENCY;            // the workgroups of a model wait for each other: all must be resident
   nm_sync_reset(jobs_dev, n_jobs, stream);
   flags &= (NM_F_BACKWARD | NM_F_ADAM | NM_F_GRADS | NM_F_EXPORT | NM_F_TRACE | NM_F_FAULT_INJECT | NM_F_PROFILE);
   if (spread_us < 0 || n_steps < 16) spread_us = 0;          // (an offset is pure cost at the end of a short launch)
   return launch_kernel(k == 2 ? nm_rs_kernel<2> : nm_rs_kernel<4>, dim3(wgs), dim3(WG), SMEM_BYTES, stream, jobs_dev, step0, n_steps,
-                       flags, n_jobs, M, spread_us, helpers);
+                       flags, n_jobs, spread_us, helpers, map);
+}
+
+/* Row-split launch of n_jobs models of M modalities each (include/nmhip.h): the mixed launch with every job listed at M --
+ * the same kernel, the same map (group / M, group % M).  NM_E_ROWSPLIT is nm_rowsplit_ok's, not this call's. */
+int nm_launch_rowsplit(const nm_job_t* jobs_dev, int n_jobs, int M, int k, int helpers, int step0, int n_steps, int flags,
+                       int spread_us, void* stream) {
+  if (int bad = check_launch_geometry(jobs_dev, n_jobs, 1, n_steps, step0, flags)) return bad;
+  if (M < 1 || M > NM_MAX_EXP) return NM_E_GEOMETRY;
+  if (n_jobs > NM_RS_MAX_GROUPS) return NM_E_RESIDENCY;
+  int job_M[NM_RS_MAX_GROUPS];
+  for (int j = 0; j < n_jobs; ++j) job_M[j] = M;
+  return nm_launch_rowsplit_mixed(jobs_dev, n_jobs, job_M, k, helpers, step0, n_steps, flags, spread_us, stream);
 }
 
 /* NM_F_TRACE read-out of the row-split kernels (this translation unit has its own copy of the timers). */

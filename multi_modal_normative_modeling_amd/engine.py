@@ -461,7 +461,7 @@ class Job:
 
 
 # the launches that leave hand-off error words behind (nm_split_errors), by the kind their error message names
-_HANDOFF_KINDS = {"nm_launch_split": "split", "nm_launch_rowsplit": "rowsplit"}
+_HANDOFF_KINDS = {"nm_launch_split": "split", "nm_launch_rowsplit": "rowsplit", "nm_launch_rowsplit_mixed": "rowsplit"}
 
 
 class JobSet:
@@ -507,7 +507,8 @@ class JobSet:
                 bad = [i for i, v in enumerate(vals) if v != 0 and v != _lib.NM_SYNC_ERR_SHAPE]
                 if shape:
                     raise _lib.NmError(f"row-split launch: job(s) {shape[:8]} exceed the Adam sweep's tables (passes, vector "
-                                       f"segments or vector elements; nm_rowsplit_ok) and were refused by the kernel; their "
+                                       f"segments or vector elements; nm_rowsplit_ok) -- or the launch's group map lists them "
+                                       f"with a modality count that is not theirs -- and were refused by the kernel; their "
                                        f"parameters were not updated -- run them with rowsplit=1 or NMHIP_ROWSPLIT=0")
                 if bad:
                     # (the switch that turns the pending launch kind off: row slices / one workgroup per modality)
@@ -581,7 +582,9 @@ class JobSet:
         """Every launch of the set: the descriptors up with n_tiles workspace tiles per job, then the C entry point
         `entry`(jobs, n_jobs, *args, stream).  A split / row-split launch leaves its hand-off error words to be read."""
         ptr = self._upload(n_tiles)
-        _lib.check(getattr(self.lib, entry)(ptr, len(self.jobs), *map(int, args), _stream_ptr(self.device)), entry)
+        # (a ctypes array -- the per-job modality counts of nm_launch_rowsplit_mixed -- passes as it is)
+        args = [a if isinstance(a, C.Array) else int(a) for a in args]
+        _lib.check(getattr(self.lib, entry)(ptr, len(self.jobs), *args, _stream_ptr(self.device)), entry)
         kind = _HANDOFF_KINDS.get(entry)
         if kind is not None:
             self._split_pending = True
@@ -606,21 +609,28 @@ class JobSet:
         fits = (len(self.jobs) + 7) // 8 * 8 * M <= self._cus
         return M if fits else 1
 
-    def rowsplit_k(self) -> int:
+    def rowsplit_k(self, mixed: bool = False) -> int:
         """Row slices per (model, modality) for a training launch (nm_launch_rowsplit): the largest k in {4, 2} for which
-        all ceil(jobs * M / 8) * 8 * k workgroups are resident at once, 1 if the set is too large for that or a model
-        needs the whole batch in one workgroup.  NMHIP_ROWSPLIT = 0 switches it off, 2 / 4 cap k."""
+        all ceil(groups / 8) * 8 * k workgroups are resident at once (groups = the (model, modality) pairs of the set), 1 if
+        the set is too large for that or a model needs the whole batch in one workgroup.  NMHIP_ROWSPLIT = 0 switches it
+        off, 2 / 4 cap k.  mixed=False (what train() / grads() ask): a set whose models differ in their number of
+        modalities keeps k = 1; mixed=True: such a set counts too (one launch for a grid of one- and several-modality
+        models: nm_launch_rowsplit_mixed, train(n, rowsplit=k))."""
         mode = os.environ.get("NMHIP_ROWSPLIT", "auto")
         M = len(self.jobs[0].kmods)
         if mode == "0" or self.wide:
             return 1
-        groups = (len(self.jobs) * M + 7) // 8 * 8
+        groups = ((self._rs_groups() if mixed else len(self.jobs) * M) + 7) // 8 * 8
         kmax = int(mode) if mode in ("2", "4") else 4
         # (the set size first: a full chip's set -- every train() call of the headline -- skips the per-job checks)
-        ks = [k for k in (4, 2) if k <= kmax and groups * k <= self._cus]
-        if not ks or any(len(j.kmods) != M or not j.rowsplit_ok() for j in self.jobs):
+        ks = [k for k in (4, 2) if k <= kmax and groups * k <= self._cus and groups <= _lib.NM_RS_MAX_GROUPS]
+        if not ks or any((len(j.kmods) != M and not mixed) or not j.rowsplit_ok() for j in self.jobs):
             return 1
         return ks[0]
+
+    def _rs_groups(self) -> int:
+        """(model, modality) pairs of the set = groups of a row-split launch before rounding up to a multiple of 8."""
+        return sum(len(j.kmods) for j in self.jobs)
 
     def rowsplit_helpers(self, k: int) -> int:
         """Helper workgroups per (model, modality) of a row-split launch: the CUs the k slices leave idle join the Adam
@@ -628,7 +638,7 @@ class JobSet:
         k = 4): 6 helpers give all of the gain, beyond 12 the extra arrivals at the hand-off cost what the shorter sweep
         saves -- so at most 12.  NMHIP_RS_HELPERS pins it."""
         env = os.environ.get("NMHIP_RS_HELPERS", "auto")
-        groups = (len(self.jobs) * len(self.jobs[0].kmods) + 7) // 8 * 8
+        groups = (self._rs_groups() + 7) // 8 * 8
         room = max(0, min(self._cus // groups, 32) - k)
         return min(int(env), room) if env != "auto" else min(room, 12)
 
@@ -642,11 +652,14 @@ class JobSet:
                     raise ValueError(f"job {i} of the set cannot run row-split (nm_rowsplit_ok): {why}")
                 j._rs_ok_version = j._version
         h = self.rowsplit_helpers(k) if helpers is None else int(helpers)
-        # start offsets over ~one step's time once the launch fills a good part of the chip (measured: 0.37 ns per
-        # parameter and step for one model at k = 4)
-        M = len(self.jobs[0].kmods)
-        spread = int(self.jobs[0].layout.n_params * 0.37e-3 * (4 / k)) if len(self.jobs) * M * k >= 96 else 0
-        self._issue("nm_launch_rowsplit", k, M, k, h, step0, n_steps, flags, spread)
+        # start offsets over ~one step's time -- of the set's largest model -- once the launch fills a good part of the chip
+        # (measured: 0.37 ns per parameter and step for one model at k = 4)
+        Ms = [len(j.kmods) for j in self.jobs]
+        spread = int(max(j.layout.n_params for j in self.jobs) * 0.37e-3 * (4 / k)) if sum(Ms) * k >= 96 else 0
+        if all(m == Ms[0] for m in Ms):
+            self._issue("nm_launch_rowsplit", k, Ms[0], k, h, step0, n_steps, flags, spread)
+        else:        # models that differ in their number of modalities: the group map is built from the per-job counts
+            self._issue("nm_launch_rowsplit_mixed", k, (C.c_int * len(Ms))(*Ms), k, h, step0, n_steps, flags, spread)
 
     def _training_form(self, split: Optional[bool], rowsplit: Optional[int]):
         """The form of a training launch: ("rowsplit", k row slices per (model, modality)), ("split", one workgroup per

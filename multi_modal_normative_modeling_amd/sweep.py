@@ -87,8 +87,12 @@ def gather_metrics(local: torch.Tensor, max_rows: int, device=None) -> torch.Ten
 def run_cells(cohort: prep.SyntheticCohort, cells: Sequence[Cell], n_folds: int, epochs: int, device, out_dir=None,
               lr: float = 1e-4, steps_per_launch: int = 64, oversample_percentage: Optional[float] = None,
               hidden: Sequence[int] = workload.HIDDEN, latent: int = workload.LATENT,
-              per_procedure_dirs: bool = False, model: str = "cVAE_multimodal", models_dir=None) -> torch.Tensor:
+              per_procedure_dirs: bool = False, model: str = "cVAE_multimodal", models_dir=None,
+              one_launch: Optional[bool] = None) -> torch.Tensor:
     """Train the given cells concurrently, run the ROI-wise deviation pass, return the metric rows.
+    `one_launch`: cells of different shapes (the reference's grid: one-modality SM-* and four-modality UCA-* models,
+    commands_list_deviation.sh:13-23) train in ONE row-split launch instead of shape group after shape group -- None: when
+    that changes no model's result (_one_launch_k), True: insist (ValueError names what stands against it), False: never.
     `oversample_percentage` switches the training rows to the train script's own recipe (utils.generate_kfold_ids:
     KFold over healthy + other, bootstrap resample with replacement, merged back in table order); None = the plain
     KFold split of the regression script."""
@@ -120,15 +124,19 @@ def run_cells(cohort: prep.SyntheticCohort, cells: Sequence[Cell], n_folds: int,
     groups: Dict[tuple, List[int]] = {}
     for i, j in enumerate(jobs):
         groups.setdefault(tuple(j.spec.input_dims), []).append(i)
+    k_one, why_not = (0, "switched off") if one_launch is False else _one_launch_k(jobs, list(groups.values()), epochs)
+    if one_launch and not k_one:
+        raise ValueError(f"one_launch=True: the cells cannot train in one row-split launch: {why_not}")
     t0 = time.perf_counter()
     total_steps = 0
-    for idxs in groups.values():
+    # (one launch: every cell in one set, k row slices per (model, modality) -- the k each shape group gets on its own)
+    for idxs in ([list(range(len(jobs)))] if k_one else groups.values()):
         js = JobSet([jobs[i] for i in idxs])
         n = epochs * jobs[idxs[0]].batches_per_epoch
         done = 0
         while done < n:
             k = min(steps_per_launch, n - done)
-            js.train(k)
+            js.train(k, rowsplit=k_one or None)
             done += k
         total_steps += n * len(idxs)
         js.assert_finite()
@@ -169,6 +177,25 @@ def run_cells(cohort: prep.SyntheticCohort, cells: Sequence[Cell], n_folds: int,
         rows.append([c.job_id, c.fold, c.proc_id, finals[i], sps, float(pm[i, 0]), float(pm[i, 1]), float(pm[i, 2]),
                      float(pm[i, 3]), float(pm[i, 4]), float(sc[~dx].mean()), float(sc[dx].mean())])
     return torch.tensor(rows, dtype=torch.float32)
+
+
+def _one_launch_k(jobs: Sequence[Job], groups: Sequence[Sequence[int]], epochs: int):
+    """(k, None) if the shape groups of run_cells can train as ONE set with k row slices and every model's result stays
+    what the grouped loop gives it, else (0, the condition that fails).  A row-split result depends on k only, not on the
+    other models of the launch, so that holds when (a) every model can run row-split, (b) the set as a whole gets the k
+    every shape group gets on its own, and (c) all groups run the same number of steps."""
+    bad = [i for i, j in enumerate(jobs) if not j.rowsplit_ok()]
+    if bad:
+        return 0, f"cell(s) {bad[:8]} cannot run row-split (Job.rowsplit_ok)"
+    k = JobSet(list(jobs)).rowsplit_k(mixed=True)
+    if k <= 1:
+        return 0, "the set is too large for row slices (JobSet.rowsplit_k(mixed=True) == 1) or NMHIP_ROWSPLIT=0"
+    own = [JobSet([jobs[i] for i in idxs]).rowsplit_k() for idxs in groups]
+    if any(ko != k for ko in own):
+        return 0, f"the shape groups get k = {own} on their own, the whole set k = {k}: results would change"
+    if len({epochs * jobs[idxs[0]].batches_per_epoch for idxs in groups}) > 1:
+        return 0, "the shape groups differ in their number of steps"
+    return k, None
 
 
 def deviation_roiwise_many(views, cohort: prep.SyntheticCohort, device, want_matrix: bool = True,
@@ -493,6 +520,9 @@ def build_parser():
     ap.add_argument("--backend", type=str, default="nccl", help="torch.distributed backend when WORLD_SIZE > 1 (nccl = RCCL)")
     ap.add_argument("--share-device", action="store_true",
                     help="rehearsal of the multi-rank path on a one-GPU box: every rank uses cuda:0 (with --backend gloo)")
+    ap.add_argument("--one-launch", dest="one_launch", choices=("auto", "on", "off"), default="auto",
+                    help="train a rank's cells of different shapes (SM-* and UCA-* models) in one row-split launch: auto = when "
+                         "no model's result changes by it, on = insist, off = shape group after shape group")
     return ap
 
 
@@ -557,6 +587,8 @@ def main(argv=None, _run_cells=None) -> torch.Tensor:
     # run_cells writes a cell's CSVs into <out>/<procedure>/ when procedures share modalities (per_procedure_dirs)
     kw = {} if _run_cells is not None else {"per_procedure_dirs": True, "model": args.model,
                                             "models_dir": out_dir if (args.save_models and out_dir is not None) else None}
+    if args.one_launch != "auto":                 # (auto is run_cells' own default: nothing is passed)
+        kw["one_launch"] = args.one_launch == "on"
     t_rank = time.perf_counter()
     local = runner(cohort, mine, args.n_splits, args.epochs, device, out_dir=None if args.no_csv else out_dir,
                    lr=args.base_learning_rate, oversample_percentage=oversample, hidden=hidden, latent=latent, **kw)
