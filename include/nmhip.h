@@ -398,6 +398,21 @@ int nm_head_classifier(const nm_job_t* jobs_dev, int n_jobs, int step, int tile0
  * go to job.grads instead (the eager facade's backward); NM_F_BNSTATS: the classifier's BatchNorm running statistics move. */
 int nm_train_steps_head(const nm_job_t* jobs_dev, int n_jobs, int step0, int n_steps, int flags, void* stream);
 
+/* The same launch for small sets -- a five-fold run of cVAE_multimodal_regression or cVAE_multimodal_endtoend leaves the
+ * one-workgroup form on 5 CUs: every model runs as `parts` workgroups, one per decoder (regression: 3; end-to-end: 6, two
+ * decoder banks of which the first three parts also own an encoder), the head on part 0.  The parts meet at the two
+ * hand-offs of nm_launch_split, each passed twice per step: the second arrival after the encoders follows part 0's head,
+ * so nothing reads the head's gradients before they are complete.  The reference has no counterpart (one model per
+ * process, one stream of kernels per step).  Every job needs M == parts, 2 <= parts <= NM_MAX_MOD, a fused-kernel trunk
+ * (not wide) and, end-to-end, the one-tile classifier (blocks <= 128 wide); buffers and flags as nm_train_steps_head;
+ * calls nm_sync_reset.  Results equal nm_train_steps_head bit for bit.
+ * Status NM_E_NULL: jobs_dev missing; NM_E_GEOMETRY: a count < 1, a negative step, parts outside 2..NM_MAX_MOD,
+ * NM_F_GRADS with n_steps != 1 (all decided before the device is asked anything); NM_E_RESIDENCY: ceil(n_jobs / 8) * 8 *
+ * parts exceeds the CU count (the parts wait for each other, so all must be resident).  A job whose M differs from
+ * `parts` is refused by the kernel (nm_split_errors: NM_SYNC_ERR_SHAPE, parameters untouched); the other jobs train.
+ * A hand-off that times out: NM_SYNC_ERR_TIMEOUT, the job's parts leave the launch before anything else is updated. */
+int nm_train_steps_head_split(const nm_job_t* jobs_dev, int n_jobs, int parts, int step0, int n_steps, int flags, void* stream);
+
 /* ---- post-hoc metrics of the sweep on the device ------------------------------------
  * Sets are segments [offsets[s], offsets[s+1]) of the concatenated arrays; one workgroup per set, at most
  * NM_METRICS_MAX_N scores per set.  out is [n_sets][NM_METRICS_STRIDE] fp64. */

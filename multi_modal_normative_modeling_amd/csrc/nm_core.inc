@@ -115,7 +115,8 @@ struct Ctx {
   int gwt;           // row-split: 1 = also the bytes that stay inside the (job, modality) group -- gradient partials, shadow
                      // images -- are stored write-through; 0 = the group's workgroups were FOUND on one XCD at kernel start
                      // (one L2: its own coherence point), those bytes are stored plain and stay in that L2
-  int lstep;         // step index inside this launch (hand-off targets)
+  int lstep;         // hand-off round inside this launch (targets of A and B): the step index for the kernels that pass both once
+                     // per step, 2 * step + pass for the head models' two-pass step (nm_head_step_kernel)
   float slope;       // negative slope of the activation (nm_job_t.act_slope)
   float* red;        // [64] reduction scratch
   float* colacc;     // [128] per-column accumulators
@@ -1863,9 +1864,11 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
     const GAS char* oblob = wsh + md.out_s;
     // z | c | 1: built by the first decoder; the others reuse it when all tables carry the same covariates
     const bool reuse_zc = J->shared_cov && M > 1 && !split && S == 0;
-    // (two-pass modes: every decoder keeps its own activations -- and its own z | c | 1 unless that one is shared)
-    GAS char* const ws_dec = ws_dec0 + (MODE != 0 ? (int64_t)m * L * wl.act : 0);
-    GAS char* const ws_zc = ws_zc0 + ((MODE != 0 && !reuse_zc) ? (int64_t)m * wl.act : 0);
+    // (two-pass modes: every decoder keeps its own activations -- and its own z | c | 1 unless that one is shared; split:
+    //  ws_dec0 / ws_zc0 are part m's slots already, the ones the one-workgroup launch uses for decoder m)
+    const bool part_slot = (MODE == 1 || MODE == 2) && split;
+    GAS char* const ws_dec = ws_dec0 + ((MODE != 0 && !part_slot) ? (int64_t)m * L * wl.act : 0);
+    GAS char* const ws_zc = ws_zc0 + ((MODE != 0 && !part_slot && !reuse_zc) ? (int64_t)m * wl.act : 0);
     if (MODE == 2) {
       // second pass: the last hidden activation comes back from the workspace, chunk 0 of the output layer with it
       lds_barrier();                                   // P / S are drained by whatever ran before

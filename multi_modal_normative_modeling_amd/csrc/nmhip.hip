@@ -988,12 +988,43 @@ __global__ __launch_bounds__(WG) void nm_clshead_kernel(const nm_job_t* __restri
 //   pass 2  per decoder: output chunks again from the saved last hidden activation, now with those extra gradients,
 //           NLL backward, dgrad, wgrad + Adam; then the decoders' hidden layers, fusion and encoders backward (MODE 2).
 // The trunk's forward runs once (the three-launch form ran it twice), nothing returns to the host between steps.
-__global__ __launch_bounds__(WG) void nm_head_step_kernel(const nm_job_t* __restrict__ jobs, int step0, int n_steps, int flags) {
+//
+// SPLIT (nm_train_steps_head_split, nparts = M): M workgroups per model, one per decoder, mapped as in nm_step_kernel (the parts
+// of a job are workgroups b, b + 8, ... of one XCD; padding workgroups return at once).  Every part runs its own modality
+// of both passes (run_step's c.part) and meets the others at run_step's two hand-offs, which a head step passes twice --
+// c.lstep counts those rounds, 2 * step + pass:
+//   pass 1, A  every expert's statistics are visible; B  every decoder's exports (residual images, deviations, latent)
+//              and its ll_m are visible: part 0 writes the loss row and runs the head, the other parts go straight on;
+//   pass 2, A  reached by part 0 AFTER the head, so it doubles as "the head's gradients (reg_dres, dz_out, the hinge row
+//              coefficients) are complete"; B  every decoder's d z is visible: the parts with an encoder run its backward.
+// reg_dres / dz_out hold ONE batch: the head of step s + 1 overwrites them after B of that step's pass 1, which every
+// part reaches only after it has finished step s's pass 2 -- the order above is what makes one buffer enough.
+// A part whose hand-off timed out leaves the launch after that pass (c.abort), before the head or another update runs.
+// SPLIT = false: c.part = -1 and c.nparts = 1 are compile-time constants, so run_step's split branches fold away and the
+// one-workgroup launch is the code it was before the split form existed (as one kernel with nparts at run time it was
+// 1.3 - 1.9 % slower: profiles/heads_split_one_kernel_runtime_parts.json).
+template <bool SPLIT>
+__global__ __launch_bounds__(WG) void nm_head_step_kernel(const nm_job_t* __restrict__ jobs, int step0, int n_steps, int flags,
+                                                          int n_jobs, int nparts_arg) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const nm_job_t* J = jobs + blockIdx.x;
+  const int nparts = SPLIT ? nparts_arg : 1;
+  int job_idx = blockIdx.x, part = -1;
+  if (SPLIT) {
+    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
+    job_idx = (idx / nparts) * 8 + xcd;
+    part = idx % nparts;
+    if (job_idx >= n_jobs) return;
+  }
+  const nm_job_t* J = jobs + job_idx;
+  if (SPLIT && J->M != nparts) {           // listed with a modality count that is not the job's: refused, nothing is touched
+    if (threadIdx.x == 0)
+      __hip_atomic_store((unsigned*)((char*)J->workspace + ws_layout(J->M, J->L, J->Z).sync) + WS_SYNC_ERR_WORD, WS_SYNC_ERR_SHAPE,
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return;
+  }
   Ctx c;
   c.job = J;
-  c.part = -1; c.nparts = 1; c.slope = J->act_slope;
+  c.part = part; c.nparts = nparts; c.slope = J->act_slope;
   carve_lds(c, smem);
   relaunder(c);
   c.t_last = 0;
@@ -1011,7 +1042,7 @@ __global__ __launch_bounds__(WG) void nm_head_step_kernel(const nm_job_t* __rest
   // NM_F_GRADS: gradients of the step's total into job.grads, no update (the eager facade's backward)
   const int bflags = NM_F_BACKWARD | ((flags & NM_F_GRADS) ? NM_F_GRADS : NM_F_ADAM);
   for (int s = step0; s < step0 + n_steps; ++s) {
-    c.lstep = s - step0;
+    c.lstep = 2 * (s - step0);
     tile_rows(c, J, s % nb);
     adam_step_consts(J, J->adam_off + (int64_t)s + 1, c.step_size, c.inv_bc2_sqrt);
     if (flags & 64) c.tlast[c.wave_s] = clock64();
@@ -1019,17 +1050,22 @@ __global__ __launch_bounds__(WG) void nm_head_step_kernel(const nm_job_t* __rest
     relaunder(c);
     c.flags = NM_F_EXPORT | tflags;
     run_step<false, 1>(c, s);
+    if (SPLIT && *c.abort != 0u) break;      // a hand-off timed out (wave-uniform: LDS word read by all)
     handoff_barrier();                            // exports and saved activations are complete
     tr(c, 20);
     relaunder(c);
     c.flags = bflags | tflags;
-    if (J->reg_head) reg_head_body(c, J, s, hws, true);
-    else if (J->cls_classes > 0) cls_head_body<false>(c, J, s, hws, true, (flags & NM_F_BNSTATS) != 0);
+    if (!SPLIT || part == 0) {                    // (split: the head belongs to part 0)
+      if (J->reg_head) reg_head_body(c, J, s, hws, true);
+      else if (J->cls_classes > 0) cls_head_body<false>(c, J, s, hws, true, (flags & NM_F_BNSTATS) != 0);
+    }
     handoff_barrier();                            // the head's gradients for the trunk are complete
     tr(c, 29);
     relaunder(c);
     c.flags = bflags | tflags;
+    c.lstep = 2 * (s - step0) + 1;
     run_step<false, 2>(c, s);
+    if (SPLIT && *c.abort != 0u) break;
     handoff_barrier();                            // the next step reads what this one stored
   }
 }
@@ -1539,8 +1575,24 @@ int nm_head_classifier(const nm_job_t* jobs_dev, int n_jobs, int step, int tile0
 int nm_train_steps_head(const nm_job_t* jobs_dev, int n_jobs, int step0, int n_steps, int flags, void* stream) {
   if (int bad = check_launch_geometry(jobs_dev, n_jobs, 1, n_steps, step0, flags)) return bad;
   if ((flags & NM_F_GRADS) && n_steps != 1) return NM_E_GEOMETRY;
-  return launch_kernel(nm_head_step_kernel, dim3(n_jobs), dim3(WG), SMEM_BYTES, stream, jobs_dev, step0, n_steps,
-                       flags & (NM_F_PROFILE | NM_F_TRACE | NM_F_GRADS | NM_F_BNSTATS));
+  return launch_kernel(nm_head_step_kernel<false>, dim3(n_jobs), dim3(WG), SMEM_BYTES, stream, jobs_dev, step0, n_steps,
+                       flags & (NM_F_PROFILE | NM_F_TRACE | NM_F_GRADS | NM_F_BNSTATS), n_jobs, 1);
+}
+
+/* The same launch with `parts` workgroups per model, one per decoder, the head on part 0 (include/nmhip.h).  Arguments are
+ * judged before the device is asked for its CU count. */
+int nm_train_steps_head_split(const nm_job_t* jobs_dev, int n_jobs, int parts, int step0, int n_steps, int flags, void* stream) {
+  if (int bad = check_launch_geometry(jobs_dev, n_jobs, 1, n_steps, step0, flags)) return bad;
+  if (parts < 2 || parts > NM_MAX_MOD) return NM_E_GEOMETRY;
+  if ((flags & NM_F_GRADS) && n_steps != 1) return NM_E_GEOMETRY;
+  // the parts of a model wait for each other inside the launch: all must be resident at once, one workgroup per CU (LDS)
+  const int cus = cu_count();
+  if (cus < 1) return NM_E_GEOMETRY;
+  const int wgs = (n_jobs + 7) / 8 * 8 * parts;
+  if (wgs > cus) return NM_E_RESIDENCY;
+  if (int bad = nm_sync_reset(jobs_dev, n_jobs, stream)) return bad;
+  return launch_kernel(nm_head_step_kernel<true>, dim3(wgs), dim3(WG), SMEM_BYTES, stream, jobs_dev, step0, n_steps,
+                       flags & (NM_F_PROFILE | NM_F_TRACE | NM_F_GRADS | NM_F_BNSTATS), n_jobs, parts);
 }
 
 int nm_train_steps(const nm_job_t* jobs_dev, int n_jobs, int step0, int n_steps, void* stream) {

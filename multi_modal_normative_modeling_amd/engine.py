@@ -461,7 +461,8 @@ class Job:
 
 
 # the launches that leave hand-off error words behind (nm_split_errors), by the kind their error message names
-_HANDOFF_KINDS = {"nm_launch_split": "split", "nm_launch_rowsplit": "rowsplit", "nm_launch_rowsplit_mixed": "rowsplit"}
+_HANDOFF_KINDS = {"nm_launch_split": "split", "nm_launch_rowsplit": "rowsplit", "nm_launch_rowsplit_mixed": "rowsplit",
+                  "nm_train_steps_head_split": "split"}
 
 
 class JobSet:
@@ -757,9 +758,52 @@ class JobSet:
                 (_lib.NM_F_ADAM if adam and backward else 0) | (_lib.NM_F_BNSTATS if bn_stats else 0)
         self._issue("nm_head_classifier", max(n_tiles, 1), step, tile0, n_tiles, flags)
 
-    def _train_head(self, step0: int, n_steps: int, flags: int = 0):
-        """nm_train_steps_head: all n_steps in one persistent launch, the trunk's forward evaluated once per step."""
-        self._issue("nm_train_steps_head", 1, step0, n_steps, flags)
+    def _train_head(self, step0: int, n_steps: int, flags: int = 0, parts: int = 1):
+        """nm_train_steps_head: all n_steps in one persistent launch, the trunk's forward evaluated once per step.
+        parts > 1: nm_train_steps_head_split, one workgroup per decoder of every model (head_split_parts)."""
+        if parts > 1:
+            self._issue("nm_train_steps_head_split", 1, parts, step0, n_steps, flags)
+        else:
+            self._issue("nm_train_steps_head", 1, step0, n_steps, flags)
+
+    def _head_split_refusal(self, fused: bool = True) -> Optional[str]:
+        """Why the set's head models cannot run one workgroup per decoder (nm_train_steps_head_split); None: they can."""
+        M = len(self.jobs[0].kmods)
+        if self.wide:
+            return "a trunk on the general-shape path trains in the three-launch form"
+        if not fused:
+            return "fused=False asks for the three-launch form"
+        if any(w > 128 for j in self.jobs for w in (j.spec.classifier_layers or ())):
+            return "a classifier with blocks wider than 128 trains in the three-launch form"
+        if any(len(j.kmods) != M for j in self.jobs):
+            return "the models of the set differ in their number of decoders"
+        if M < 2:
+            return "the models have a single decoder"
+        if (len(self.jobs) + 7) // 8 * 8 * M > self._cus:
+            return (f"{len(self.jobs)} models x {M} workgroups (sets are padded to a multiple of 8 models) exceed the "
+                    f"device's {self._cus} CUs: the parts of a model must all be resident at once")
+        return None
+
+    def head_split_parts(self, fused: bool = True) -> int:
+        """Workgroups per model for a head-model training launch (train_regression / train_endtoend): one per decoder
+        (regression: 3; end-to-end: 6, two decoder banks) when split_parts() allows it -- NMHIP_SPLIT, the same number of
+        decoders in every model, all workgroups resident at once, not the general-shape path -- and the persistent head
+        kernel runs the step at all (fused, one-tile classifier); else 1."""
+        parts = self.split_parts()
+        if parts < 2 or self._head_split_refusal(fused) is not None:
+            return 1
+        return parts
+
+    def _head_parts(self, split: Optional[bool], fused: bool = True) -> int:
+        """split=None: head_split_parts(); True: insist (ValueError with the reason if the set cannot); False: 1."""
+        if split is None:
+            return self.head_split_parts(fused)
+        if not split:
+            return 1
+        why = self._head_split_refusal(fused)
+        if why is not None:
+            raise ValueError(f"split=True: this set cannot run one workgroup per decoder (nm_train_steps_head_split): {why}")
+        return len(self.jobs[0].kmods)
 
     def _head_step(self, head: str, s: int, adam: bool):
         """One head-model step as three launches -- the form a trunk on the general-shape path or a classifier with blocks
@@ -773,7 +817,7 @@ class JobSet:
             self.head_classifier(backward=True, grads=not adam, adam=adam, bn_stats=True, step=s, tile0=tile0)
         self._launch(s, 1, 1, _lib.NM_F_BACKWARD | (_lib.NM_F_ADAM if adam else _lib.NM_F_GRADS))
 
-    def train_endtoend(self, n_steps: int, fused: bool = True):
+    def train_endtoend(self, n_steps: int, fused: bool = True, split: Optional[bool] = None):
         """n_steps train steps of cVAE_multimodal_endtoend jobs on the device, no host sync (the loop of
         multimodal_kfold_cvae_nmpmcont.py:257-303): per step (i) forward with latent and per-subject deviations
         exported, (ii) the classifier head: forward (train-mode BatchNorm / Dropout), cross entropy, contrastive
@@ -781,43 +825,55 @@ class JobSet:
         with those extra gradients.  fused (default): one persistent launch for all steps (nm_train_steps_head);
         fused=False: the three-launches-per-step form it replaced (trunk forward twice), kept as a cross-check -- and the
         form a trunk on the general-shape path or a classifier with blocks wider than 128 (-Layers "256 128 64") runs in:
-        the persistent head kernel holds the one-tile classifier only."""
+        the persistent head kernel holds the one-tile classifier only.  Small sets run the persistent launch with one
+        workgroup per decoder (split=None: head_split_parts(); bit-identical to the one-workgroup launch)."""
         step0 = self._check_jobs("endtoend", "train_endtoend")
+        parts = self._head_parts(split, fused)
         for j in self.jobs:
             j.cls_train, j.cls_use_mu = True, False
             j.prepare_classifier()
         tiled_head = any(w > 128 for j in self.jobs for w in j.spec.classifier_layers)
         if fused and not self.wide and not tiled_head:
-            self._train_head(step0, n_steps, _lib.NM_F_BNSTATS)
+            self._train_head(step0, n_steps, _lib.NM_F_BNSTATS, parts)
         else:
             for s in range(step0, step0 + n_steps):
                 self._head_step("endtoend", s, adam=True)
         self._advance(n_steps)
 
-    def train_regression(self, n_steps: int):
+    def train_regression(self, n_steps: int, split: Optional[bool] = None):
         """n_steps train steps of cVAE_multimodal_regression jobs in one persistent launch, no host sync (the loop of
         multimodal_kfold_train_cvae_supervised_regression.py:112-125): per step (i) the trunk's forward, leaving the
         residuals as bf16 chunk images, (ii) the regressor: forward, MSE, backward, its Adam update, d MSE / d x_hat,
         (iii) the trunk's backward + Adam with that extra gradient (nm_train_steps_head).  A trunk on the general-shape
-        path runs the three-launch form (_head_step)."""
+        path runs the three-launch form (_head_step).  Small sets run the launch with one workgroup per decoder
+        (split=None: head_split_parts(); bit-identical to the one-workgroup launch)."""
         step0 = self._check_jobs("regression", "train_regression")
+        parts = self._head_parts(split)
         for j in self.jobs:
             j.prepare_regression()
         if self.wide:
             for s in range(step0, step0 + n_steps):
                 self._head_step("regression", s, adam=True)
         else:
-            self._train_head(step0, n_steps)
+            self._train_head(step0, n_steps, 0, parts)
         self._advance(n_steps)
 
-    def grads_head(self, step: int = 0):
-        """Gradients of one regression-model step's total loss into job.grads, no update (the eager facade's backward);
-        a trunk on the general-shape path runs the three-launch form."""
-        self._check_jobs("regression", "grads_head", at_step=False)
-        if self.wide:
-            self._head_step("regression", step, adam=False)
+    def grads_head(self, step: int = 0, split: bool = False):
+        """Gradients of one head-model step's total loss into job.grads, no update (regression sets: the eager facade's
+        backward; end-to-end sets: the classifier as the jobs have it set up, running statistics untouched); a trunk on the
+        general-shape path or a classifier with blocks wider than 128 runs the three-launch form.  split=True: one
+        workgroup per decoder (the same gradients bit for bit); the default stays the one-workgroup launch, the eager
+        facade's path."""
+        head = "endtoend" if self.jobs[0].spec.kind == "endtoend" else "regression"
+        self._check_jobs(head, "grads_head", at_step=False)
+        parts = self._head_parts(bool(split))
+        if head == "endtoend":
+            for j in self.jobs:
+                j.prepare_classifier()
+        if self.wide or (head == "endtoend" and any(w > 128 for j in self.jobs for w in j.spec.classifier_layers)):
+            self._head_step(head, step, adam=False)
         else:
-            self._train_head(step, 1, _lib.NM_F_GRADS)
+            self._train_head(step, 1, _lib.NM_F_GRADS, parts)
 
     def losses(self) -> torch.Tensor:
         """[n_jobs, loss_cap, 8] on the host."""
