@@ -221,9 +221,9 @@ def test_multi_step_single_launch_equals_stepwise():
             for _ in range(7):
                 js.train(1)
         torch.cuda.synchronize()
-        res.append((job.params.cpu().clone(), job.loss_log[:7].cpu().clone()))
-    assert torch.equal(res[0][0], res[1][0])
-    assert torch.equal(res[0][1], res[1][1])
+        res.append((job.params.cpu().clone(), job.loss_log[:7].cpu().clone(), job.adam_m.cpu().clone(), job.adam_v.cpu().clone()))
+    for a, b, what in zip(res[0], res[1], ("params", "loss_log", "adam_m", "adam_v")):
+        assert torch.equal(a, b), what
 
 
 def test_many_jobs_one_launch_are_independent():
