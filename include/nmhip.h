@@ -352,6 +352,20 @@ int nm_sync_reset(const nm_job_t* jobs_dev, int n_jobs, void* stream);
 int nm_devpass(const nm_job_t* jobs_dev, int n_jobs, int tile0, int n_tiles, int flags, void* stream);   /* flags: 0 or NM_F_TRACE */
 int nm_trace_read_dv(unsigned long long* out512, int reset);
 int nm_devpass_ok(const nm_job_t* job_host);
+/* The same pass for models with SEVERAL experts (csrc/nm_devpass.hip: nm_devpass_multi_kernel): pred_recon with the joint
+ * latent followed by reconstruction_deviation_multimodal (multimodal_kfold_test_cvae_supervised.py:112-113) over table rows
+ * [tile0 * 128, (tile0 + n_tiles) * 128): every expert's encoder, the fusion (poe / gpoe / moe / mopoe), the latent draw,
+ * every decoder; writes mod[m].out_loc / out_sqerr / out_rowdev of EVERY modality and nothing else (no loss log, no latent
+ * exports).  128-row tiles, 79 KB of LDS: two workgroups per CU.  The experts' statistics pass through the workspace as in
+ * nm_forward and are fused by the same code, so the exports equal nm_forward's bit for bit (out_rowdev: to the order of
+ * four partial sums).  Each job needs one workspace tile per 256-row batch the launch touches; the two 128-row tiles of a
+ * batch share that tile on disjoint rows.  Every job must pass nm_devpass_multi_ok: the caller checks on the host (the
+ * descriptors are in device memory), as for nm_devpass; the kernel makes the workgroups of a refused job leave at once, its
+ * exports untouched.  nm_devpass_multi_ok: NM_OK for a job that is not wide, has 2..NM_MAX_EXP modalities, each with an
+ * encoder (M_enc 0 or M), n_private == 0, tc_weight == 0, w_off < 0, out_kind == 0, H[0] <= 112 and Z rounded to 16 <= 32;
+ * NM_E_DEVPASS otherwise (such a job runs on nm_forward); NM_E_NULL for a null pointer. */
+int nm_devpass_multi(const nm_job_t* jobs_dev, int n_jobs, int tile0, int n_tiles, int flags, void* stream);   /* flags: 0 or NM_F_TRACE */
+int nm_devpass_multi_ok(const nm_job_t* job_host);
 /* NM_F_TRACE read-out of the row-split kernels ([8 waves][64 tags], as nm_trace_read) */
 int nm_trace_read_rs(unsigned long long* out512, int reset);
 /* out_dev[j] (device, n_jobs ints) != 0: a hand-off of job j timed out in a split launch since the word was last

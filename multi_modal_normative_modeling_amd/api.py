@@ -215,7 +215,10 @@ class _Base(nn.Module):
         return self._device
 
     def _run(self, xes: Sequence[torch.Tensor], cs: Sequence[torch.Tensor], combine: str, flags: int, eps=None,
-             kl_w=None, ll_w=1.0):
+             kl_w=None, ll_w=1.0, recon_only: bool = False):
+        """recon_only (forward-only calls that read the reconstruction alone -- pred_recon): the job's latent exports are
+        switched off for the call and the launch goes through JobSet.forward(loss=False), i.e. on the compact kernels where
+        the model's shape allows (same reconstruction, bit for bit); the next call that wants the latent switches them back."""
         self._ensure_device(xes[0])
         # One Job, one JobSet, one set of table buffers from call to call: a batch of the same shape is packed into the
         # existing tables (Table.repack) and the draw into the existing buffer, so the descriptor on the device stays
@@ -233,6 +236,7 @@ class _Base(nn.Module):
                 self._js = JobSet([j])
             j.tables = tables
             j.touch()
+        j.set_latent_exports(not recon_only)
         self.layout.nat_to_kernel(self._flat.data, j.params)     # the module's parameters (views, maybe edited) -> kernel layout
         j.params_changed()
         if int(all(t.c_key == j.tables[0].c_key for t in j.tables)) != getattr(j, "_shared_cov", -1):
@@ -266,6 +270,8 @@ class _Base(nn.Module):
             # through _publish_grads, every gradient -- then carries; the NmError itself is raised by the next call's upload.
             j.loss_log[0].fill_(float("nan"))
             self._js._launch_split(0, 1, flags | getattr(self, "_fault_inject", 0))
+        elif recon_only and flags == _lib.NM_F_EXPORT:
+            self._js.forward(0, nt, loss=False)
         else:
             self._js._launch(0, 1, nt, flags)
         return j, B
@@ -469,7 +475,7 @@ class cVAE_multimodal(_ExpertOps, _Base):
         xs = [torch.tensor(np.asarray(x.values if hasattr(x, "values") else x), dtype=torch.float32) for x in xes]
         ct = torch.tensor(np.asarray(c), dtype=torch.long)
         self._dev()
-        j, B = self._run(xs, [ct] * self.modalities, combine, _lib.NM_F_EXPORT)
+        j, B = self._run(xs, [ct] * self.modalities, combine, _lib.NM_F_EXPORT, recon_only=True)
         return [j.out_loc[m][:B].cpu().numpy() for m in range(self.modalities)]
 
     def reconstruction_deviation_multimodal(self, xes, x_preds):

@@ -16,7 +16,8 @@
 // rounded to 16, not 5 x 256), and the export epilogue makes one pass: residual, its square (stored), row sum.
 // Arithmetic, draws (keyed by absolute row) and exports are those of the general kernel, row by row: the two agree bit for
 // bit on out_sqerr / out_rowdev / out_loc (tests/test_gpu_devpass.py).  No loss log, no latent exports: launches that want
-// those, models with several experts, a first hidden layer wider than 112 or a latent wider than 32 stay on nm_forward.
+// those, a first hidden layer wider than 112 or a latent wider than 32 stay on nm_forward.  Models with several experts
+// run on nm_devpass_multi_kernel, further down in this file.
 #include "nm_core.inc"
 
 // export stores: plain, not non-temporal ("written once, read by another kernel"), as the A/B decided: 458 us per pass
@@ -272,6 +273,307 @@ __global__ __launch_bounds__(WG, 4) void nm_devpass_kernel(const nm_job_t* __res
   tr(c, 8);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// nm_devpass_multi_kernel -- the same pass for models with several experts (SE: 3, UCA: 4): pred_recon with the joint
+// latent, then reconstruction_deviation_multimodal (multimodal_kfold_test_cvae_supervised.py:112-113).
+//
+// A workgroup owns 128 rows as above.  Per tile: every expert's encoder chain (first layer, dv_layer, heads), the fusion
+// of the experts and the latent draw, then every decoder (z | c | 1, hidden layers, 64-ROI output chunks with the export
+// epilogue of nm_devpass_kernel -- that kernel's source stays as it is, so the chunk loop is repeated here per decoder).
+//
+// Expert statistics: [M][128][Zs] fp32 x 2 is 128 KB at M = 4, Zs = 32 -- it does not fit beside P and W.  As in the
+// general kernel, fwd_heads stores mu_m / logvar_m to the workspace tile of the 256-row batch and the fusion reads them
+// back through the SAME fuse_fwd / softmax_alpha (fp contraction off), so the joint statistics agree bit for bit by
+// construction.  The two workgroups of one batch share that batch's workspace tile on disjoint row halves (rloc0 = row0 %
+// 256; a row's statistics are whole cache lines); neither touches the tile's hand-off words.  The traffic stays in L2.
+//
+// LDS: P, W, the two vector slots and the scalars as above, plus Z [128][32] bf16 (8 KB): the sampled z, which every
+// decoder's z | c | 1 build reads (the covariates may differ per modality, so each decoder builds its own).  79.3 KB.
+// z = mu_j + eps exp(logvar_j / 2) is formed in one register with the addition kept apart from the product (the general
+// kernel adds two values it reloads from the workspace: no fused multiply-add there).
+//
+// A job nm_devpass_multi_ok refuses must not reach this kernel (the caller checks on the host, as for nm_devpass); its
+// workgroups leave at once, exports untouched, because its shapes would not fit the LDS plan.
+constexpr int DVM_Z_BYTES = DV_ROWS * 32 * 2;                         // 8,192
+constexpr int DVM_SMEM = DV_SMEM + DVM_Z_BYTES;
+static_assert(2 * DVM_SMEM <= 160 * 1024, "two workgroups per CU");
+static_assert((DV_SMEM & 15) == 0, "z buffer alignment");
+
+__host__ __device__ inline int dvm_refused(const nm_job_t* j) {
+  const int Me = j->M_enc > 0 ? j->M_enc : j->M;
+  if (j->wide || j->M < 2 || j->M > NM_MAX_EXP || Me != j->M) return NM_E_DEVPASS;
+  if (j->n_private != 0 || j->tc_weight != 0.f || j->w_off >= 0 || j->out_kind != 0) return NM_E_DEVPASS;
+  if (j->H[0] > DV_MAX_H0 || rup(j->Z, 16) > 32) return NM_E_DEVPASS;
+  return 0;
+}
+
+// the sum the general kernel forms in build_zc from two reloaded values: never a fused multiply-add
+__device__ __forceinline__ float dvm_add(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
+__global__ __launch_bounds__(WG, 4) void nm_devpass_multi_kernel(const nm_job_t* __restrict__ jobs, int tile0, int flags) {
+  constexpr int RT = DV_RT, ROWS = DV_ROWS;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const nm_job_t* J = jobs + blockIdx.x;
+  if (dvm_refused(J) || !J->workspace) return;
+  const int M = J->M;
+  const int t128 = tile0 + (int)blockIdx.y;
+  const int row0 = t128 * ROWS;
+  if (row0 >= J->n_rows) {
+    // the second half of a ragged last 256-row tile: every modality's export rows come back as zeros
+    if (row0 < (J->n_rows + TROWS - 1) / TROWS * TROWS) {
+      for (int m = 0; m < M; ++m) {
+        const nm_modality_t& mm = J->mod[m];
+        const int xpm = mm.x_pitch;
+        for (int e = threadIdx.x; e < ROWS * (xpm >> 2); e += WG) {
+          const int64_t gi = (int64_t)row0 * xpm + (int64_t)e * 4;
+          if (mm.out_loc) *(GAS f32x4*)(asg(mm.out_loc) + gi) = f32x4{0.f, 0.f, 0.f, 0.f};
+          if (mm.out_sqerr) *(GAS f32x4*)(asg(mm.out_sqerr) + gi) = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+      }
+    }
+    return;
+  }
+  Ctx c;
+  c.job = J;
+  c.part = -1; c.nparts = 1; c.lstep = 0;
+  c.slope = J->act_slope;
+  dv_carve(c, smem);
+  relaunder(c);
+  c.flags = NM_F_EXPORT | (flags & NM_F_TRACE);
+  c.t_last = 0;
+  // the workspace tile of this tile's 256-row batch (tiles of the launch are counted from the batch tile0 falls in)
+  c.ws = (GAS char*)J->workspace + (int64_t)(t128 / 2 - tile0 / 2) * J->workspace_stride;
+  for (int i = c.tid; i < DVM_SMEM / 4; i += WG) reinterpret_cast<uint32_t*>(smem)[i] = 0u;
+  __syncthreads();
+  if (c.flags & 64) c.tlast[c.wave_s] = clock64();
+  c.row0 = row0;
+  c.rloc0 = row0 % TROWS;
+  c.nrows = min(ROWS, J->n_rows - row0);
+  c.inv_b = 1.0f / (float)c.nrows;
+  const int live = c.nrows;
+  const int step = row0 / TROWS;
+  const int L = J->L, Z = J->Z, C = J->C;
+  const int Zs = rup(Z, 16);
+  const bool nl = J->non_linear != 0;
+  const bool vec4 = (Z & 3) == 0;
+  GAS char* const wsh = (GAS char*)J->wsh;
+  char* const Wb = reinterpret_cast<char*>(c.Q);
+  __bf16* const zlds = reinterpret_cast<__bf16*>(smem + DV_SMEM);
+  const WsLayout wl = ws_layout(M, L, Z);
+  // this workgroup's rows of the batch's expert statistics; expert m at + m * 256 * Zs
+  gf32 ws_mu_m = (gf32)(c.ws + wl.mu_m) + c.rloc0 * Zs;
+  gf32 ws_lv_m = (gf32)(c.ws + wl.lv_m) + c.rloc0 * Zs;
+  auto to_W = [&](const GAS char* blob, int vs, int rows, int K) {
+    return Next{blob, Wb, IMG_BYTES >> 10, blob + cimg_bytes(rows, K), reinterpret_cast<char*>(c.vec) + vs * VEC_BYTES, rows, blob_kp(K)};
+  };
+
+  // ---- encoders: every expert's chain, statistics to the workspace ----
+  for (int m = 0; m < M; ++m) {
+    relaunder(c);
+    const nm_modality_t& md = J->mod[m];
+    const int nch = (md.Kx + XCH - 1) / XCH;
+    const GAS char* after0 = wsh + (L > 1 ? md.enc_s[1] : md.heads_s);
+    fwd_first_layer<RT>(c, (const GAS char*)asg(md.xb) + (int64_t)(row0 / TROWS) * nch * XIMG_TILE_BYTES + (int64_t)c.rloc0 * (LDX * 2),
+                        md.Kx, wsh + md.enc_s[0], to_W(after0, 0, L > 1 ? J->H[1] : 2 * Zs, J->H[0]), J->H[0], nl, (gbf16)nullptr, true,
+                        DV_W0_PIECES, live);
+    int vs = 0;
+    for (int e = 1; e < L; ++e) {
+      const GAS char* nxt = wsh + (e + 1 < L ? md.enc_s[e + 1] : md.heads_s);
+      dv_layer(c, vs, to_W(nxt, vs ^ 1, e + 1 < L ? J->H[e + 1] : 2 * Zs, J->H[e]), J->H[e], J->H[e - 1], nl, live);
+      vs ^= 1;
+    }
+    tr(c, 1);
+    wait_vm(0);
+    fwd_heads<RT>(c, 0, no_next(), Z, J->H[L - 1], ws_mu_m + (int64_t)m * TROWS * Zs, ws_lv_m + (int64_t)m * TROWS * Zs, Zs, 0,
+                  (__bf16*)nullptr, step, vec4, (float*)nullptr, c.vec + vs * (VEC_BYTES / 4));
+  }
+
+  // ---- fusion + the latent draw: z -> LDS ----
+  handoff_barrier();                               // the heads' stores are complete for every thread of the workgroup
+  // W and P are free: the first decoder's image lands during the latent arithmetic
+  issue_next(c, to_W(wsh + J->mod[0].dec_s[0], 0, J->H[L - 1], Z + C));
+  {
+    float al[NM_MAX_EXP] = {0.f, 0.f, 0.f, 0.f};
+    if (J->combine == NM_COMBINE_GPOE) softmax_alpha(J, al);
+    relaunder(c);
+    if (vec4) {
+      const int nq4 = (Z + 3) >> 2;
+      const float rq4 = 1.0f / (float)nq4;
+#pragma unroll 2
+      for (int e = c.tid; e < ROWS * nq4; e += WG) {
+        const int r = idiv(e, nq4, rq4), z0 = 4 * (e - r * nq4);
+        f32x4 mu4[NM_MAX_EXP], lv4[NM_MAX_EXP];
+#pragma unroll
+        for (int m = 0; m < NM_MAX_EXP; ++m) {
+          mu4[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+          lv4[m] = mu4[m];
+          if (m < M) {
+            mu4[m] = *(const GAS f32x4*)(ws_mu_m + ((int64_t)m * TROWS + r) * Zs + z0);
+            lv4[m] = *(const GAS f32x4*)(ws_lv_m + ((int64_t)m * TROWS + r) * Zs + z0);
+          }
+        }
+        float ep[4];
+        if (J->eps) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) ep[i] = asg(J->eps)[((int64_t)(step % J->eps_cap) * TROWS + c.rloc0 + r) * Z + min(z0 + i, Z - 1)];
+        } else {
+          randn2_ctr(J->seed, (uint32_t)step, (uint32_t)(c.row0 + r), (uint32_t)(z0 >> 1), ep[0], ep[1]);
+          randn2_ctr(J->seed, (uint32_t)step, (uint32_t)(c.row0 + r), (uint32_t)(z0 >> 1) + 1u, ep[2], ep[3]);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ep[i] = (z0 + i < Z) ? ep[i] : 0.f;
+        bf16x4 zk;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          Lat Lt;
+#pragma unroll
+          for (int m = 0; m < NM_MAX_EXP; ++m) { Lt.mu[m] = mu4[m][i]; Lt.lv[m] = lv4[m][i]; }
+          const Fuse f = fuse_fwd(J, Lt, al);
+          const float es = ep[i] * fx_exp(0.5f * f.lv);
+          zk[i] = (__bf16)dvm_add(f.mu, es);
+        }
+        *reinterpret_cast<bf16x4*>(zlds + r * 32 + z0) = zk;
+      }
+    } else {
+      const float rZ = 1.0f / (float)Z;
+#pragma unroll 2
+      for (int e = c.tid; e < ROWS * Z; e += WG) {
+        const int r = idiv(e, Z, rZ), z = e - r * Z;
+        Lat Lt;
+#pragma unroll
+        for (int m = 0; m < NM_MAX_EXP; ++m) {
+          Lt.mu[m] = (m < M) ? ws_mu_m[((int64_t)m * TROWS + r) * Zs + z] : 0.f;
+          Lt.lv[m] = (m < M) ? ws_lv_m[((int64_t)m * TROWS + r) * Zs + z] : 0.f;
+        }
+        const Fuse f = fuse_fwd(J, Lt, al);
+        const float ep = J->eps ? asg(J->eps)[((int64_t)(step % J->eps_cap) * TROWS + c.rloc0 + r) * Z + z]
+                                : randn_ctr(J->seed, (uint32_t)step, (uint32_t)(c.row0 + r), (uint32_t)z);
+        const float es = ep * fx_exp(0.5f * f.lv);
+        zlds[r * 32 + z] = (__bf16)dvm_add(f.mu, es);
+      }
+    }
+  }
+  lds_barrier();                                   // z is complete (the decoder image requested above stays in flight)
+  tr(c, 3);
+
+  // ---- decoders ----
+  const int Hl = J->H[0];
+  const int ob = L & 1;                            // (see nm_devpass_kernel: chunk 0's vectors avoid the last hidden layer's bias)
+  for (int m = 0; m < M; ++m) {
+    relaunder(c);
+    const nm_modality_t& md = J->mod[m];
+    const int D = md.D;
+    if (m > 0) {
+      lds_barrier();                               // the previous decoder's last chunk is finished everywhere: P, W, vectors free
+      issue_next(c, to_W(wsh + md.dec_s[0], 0, J->H[L - 1], Z + C));
+    }
+    build_zc<RT>(c, c.P, md, (gcf32)nullptr, (gcf32)nullptr, Z, C, Zs, 0, (gcf32)nullptr, zlds);
+    tr(c, 4);
+    int vs = 0;
+    const GAS char* oblob = wsh + md.out_s;
+    const int nck = (D + OCH - 1) / OCH;
+    auto out_blob = [&](int ch) {
+      return Next{oblob + (int64_t)ch * OBLOB_BYTES, Wb + (ch & 1) * OIMG_BYTES, OIMG_BYTES >> 10,
+                  oblob + (int64_t)ch * OBLOB_BYTES + OIMG_BYTES, reinterpret_cast<char*>(c.vec) + ((ch + ob) & 1) * VEC_BYTES, 0, 0};
+    };
+    for (int d = 0; d < L; ++d) {
+      const int Kin = (d == 0) ? Z + C : J->H[L - d], Nout = J->H[L - 1 - d];
+      const Next nx = (d + 1 < L) ? to_W(wsh + md.dec_s[d + 1], vs ^ 1, J->H[L - 2 - d], Nout) : out_blob(0);
+      dv_layer(c, vs, nx, Nout, Kin, nl, live);    // (its first barrier also publishes z | c | 1)
+      vs ^= 1;
+    }
+    tr(c, 5);
+    // output layer in 64-ROI chunks, wave w owns rows [16 w, 16 w + 16) and all 64 columns: see nm_devpass_kernel
+    gcf32 xf = asg(md.x_f32);
+    const int xp = md.x_pitch;
+    float rdev = 0.f;
+    const int orow = c.wave * 16 + c.c16;
+    const bool wave_live = c.wave * 16 < live;
+    auto load_xin = [&](int chx, f32x4 (&xv)[4]) {
+#pragma unroll
+      for (int ft = 0; ft < 4; ++ft) {
+        const int dcl = min(chx * OCH + ft * 16 + 4 * c.g, xp - 4);
+        xv[ft] = *(const GAS f32x4*)(xf + (int64_t)(row0 + orow) * xp + dcl);
+      }
+    };
+    int stores_prev = 0;
+    auto chunk = [&](const int ch, f32x4 (&xin)[4], f32x4 (&xnx)[4]) {
+      relaunder(c);
+      const int d0 = ch * OCH;
+      const __bf16* Wc = reinterpret_cast<const __bf16*>(Wb + (ch & 1) * OIMG_BYTES);
+      const float* vb = c.vec + ((ch + ob) & 1) * (VEC_BYTES / 4);
+      wait_vm(ch > 0 ? stores_prev : 0);
+      lds_barrier();
+      if (ch + 1 < nck) { issue_next(c, out_blob(ch + 1)); if (wave_live) load_xin(ch + 1, xnx); }
+      stores_prev = 0;
+      if (!wave_live) return;
+      f32x4 acc[4];
+#pragma unroll
+      for (int ft = 0; ft < 4; ++ft) acc[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
+      const int ksteps = wpad(Hl) / 32;
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        if (ks < ksteps) {
+          const bf16x8 a = lds_frag(c.P, LDP, orow, ks * 32 + 8 * c.g);
+#pragma unroll
+          for (int ft = 0; ft < 4; ++ft) acc[ft] = mfma(lds_frag(Wc, LDP, ft * 16 + c.c16, ks * 32 + 8 * c.g), a, acc[ft]);
+        }
+      }
+      tr(c, 6);
+      const bool rv = orow < c.nrows;
+      const bool full = live == ROWS && d0 + OCH <= D;                   // no row / column masks needed (wave-uniform)
+#pragma unroll
+      for (int ft = 0; ft < 4; ++ft) {
+        const int dg0 = d0 + ft * 16 + 4 * c.g;
+        const f32x4 bo = *reinterpret_cast<const f32x4*>(vb + ft * 16 + 4 * c.g);
+        f32x4 lo, sq;
+        if (full) {
+          lo = acc[ft] + bo;
+          const f32x4 diff = lo - xin[ft];
+          sq = diff * diff;
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float xh = acc[ft][i] + bo[i];
+            const bool dv = rv && dg0 + i < D;
+            const float diff = xh - xin[ft][i];
+            lo[i] = dv ? xh : 0.f;
+            sq[i] = dv ? diff * diff : 0.f;
+          }
+        }
+        rdev += ((sq[0] + sq[1]) + sq[2]) + sq[3];
+        if (d0 + ft * 16 < xp) {                      // wave-uniform
+          if (dg0 < xp) {
+            const int64_t gi = (int64_t)(row0 + orow) * xp + dg0;
+            if (md.out_loc) *(GAS f32x4*)(asg(md.out_loc) + gi) = lo;
+            if (md.out_sqerr) *(GAS f32x4*)(asg(md.out_sqerr) + gi) = sq;
+          }
+          stores_prev += (md.out_loc ? 1 : 0) + (md.out_sqerr ? 1 : 0);
+        }
+      }
+      tr(c, 7);
+    };
+    {
+      f32x4 xa[4], xb[4];
+      if (wave_live) load_xin(0, xa);
+      for (int ch = 0; ch < nck; ch += 2) {
+        chunk(ch, xa, xb);
+        if (ch + 1 < nck) chunk(ch + 1, xb, xa);
+      }
+    }
+    if (md.out_rowdev && wave_live) {
+      float v = rdev;
+      v += __shfl_xor(v, 16, 64);
+      v += __shfl_xor(v, 32, 64);
+      if (c.g == 0 && orow < c.nrows) asg(md.out_rowdev)[row0 + orow] = v / (float)D;
+    }
+    tr(c, 8);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -292,6 +594,24 @@ int nm_devpass_ok(const nm_job_t* j) {
 int nm_devpass(const nm_job_t* jobs_dev, int n_jobs, int tile0, int n_tiles, int flags, void* stream) {
   if (int bad = check_launch_geometry(jobs_dev, n_jobs, n_tiles, 1, tile0, 0)) return bad;
   return launch_kernel(nm_devpass_kernel, dim3(n_jobs, n_tiles), dim3(WG), DV_SMEM, stream, jobs_dev, tile0, flags & NM_F_TRACE);
+}
+
+/* 0: the job's multi-expert deviation pass can run on the compact kernel (not wide; 2..NM_MAX_EXP modalities, every one with
+ * an encoder; no private latent / learnable weights / total correlation; Gaussian output; first hidden width <= 112, latent
+ * <= 32 after rounding to 16); NM_E_DEVPASS otherwise.  single_bypass plays no part: it only acts on one-expert models. */
+int nm_devpass_multi_ok(const nm_job_t* j) {
+  if (!j) return NM_E_NULL;
+  return dvm_refused(j);
+}
+
+/* pred_recon with the joint latent + reconstruction_deviation_multimodal (multimodal_kfold_test_cvae_supervised.py:112-113)
+ * over table rows [tile0 * 128, (tile0 + n_tiles) * 128): out_loc / out_sqerr / out_rowdev of EVERY modality, nothing else.
+ * Every job must pass nm_devpass_multi_ok -- checked by the caller on the host, as for nm_devpass (the descriptors are in
+ * device memory here); the kernel makes a refused job's workgroups leave at once, its exports untouched.  Every job needs
+ * one workspace tile per 256-row batch the launch touches: (tile0 + n_tiles + 1) / 2 - tile0 / 2 of them. */
+int nm_devpass_multi(const nm_job_t* jobs_dev, int n_jobs, int tile0, int n_tiles, int flags, void* stream) {
+  if (int bad = check_launch_geometry(jobs_dev, n_jobs, n_tiles, 1, tile0, 0)) return bad;
+  return launch_kernel(nm_devpass_multi_kernel, dim3(n_jobs, n_tiles), dim3(WG), DVM_SMEM, stream, jobs_dev, tile0, flags & NM_F_TRACE);
 }
 
 /* NM_F_TRACE read-out of nm_devpass ([8 waves][64 tags] interval cycles of workgroup (0, 0), as nm_trace_read) */

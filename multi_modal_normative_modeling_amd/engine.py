@@ -22,6 +22,11 @@ from .layout import ModelSpec, ParamLayout, rowsplit_limit
 
 BATCH = _lib.NM_BATCH
 
+# nm_devpass_multi as the automatic pick of JobSet.forward(loss=False), per number of experts: on only where the compact
+# kernel's slowest repeat beat the general kernel's fastest at every set size measured (tools/bench_devpass_multi.py,
+# profiles/devpass_multi.json)
+DEVPASS_MULTI_AUTO = {2: True, 3: True, 4: True}
+
 
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
@@ -252,6 +257,15 @@ class Job:
                 and self.tc_weight == 0.0 and s.kind != "weighted_dmvae" and s.hidden[0] <= 112 and (s.latent + 15) // 16 * 16 <= 32
                 and self.out_mu is None and self.out_logvar is None and self.out_z is None)
 
+    def devpass_multi_ok(self) -> bool:
+        """nm_devpass_multi_ok for this job -- several experts, every modality with an encoder, no private latent /
+        learnable weights / total correlation, Gaussian output, first hidden width <= 112, latent <= 32 -- plus: no latent
+        exports asked for (the general forward kernel writes those)."""
+        s = self.spec
+        return (not s.wide and len(self.kmods) == s.M and 2 <= s.M <= _lib.NM_MAX_EXP and s.n_private == 0 and not s.is_dm
+                and self.tc_weight == 0.0 and s.kind != "weighted_dmvae" and s.hidden[0] <= 112 and (s.latent + 15) // 16 * 16 <= 32
+                and self.out_mu is None and self.out_logvar is None and self.out_z is None)
+
     def rowsplit_ok(self) -> bool:
         """Can this model run row-split (nm_rowsplit_ok: plain cVAE / cVAE_multimodal-type models on the fused kernel whose
         modalities fit the Adam sweep's tables, layout.rowsplit_limit)?"""
@@ -357,6 +371,22 @@ class Job:
             self.out_loc[j] = torch.zeros(ra, t.x_pitch, device=self.device)[:, :t.D] if loc else None
             self.out_sqerr[j] = torch.zeros(ra, t.x_pitch, device=self.device)[:, :t.D] if sqerr else None
             self.out_rowdev[j] = torch.zeros(ra, device=self.device) if rowdev else None
+
+    def set_latent_exports(self, on: bool):
+        """Switch the joint-latent exports (out_mu / out_logvar / out_z) of a job that has them off and back on; the
+        buffers are kept.  Off, a reconstruction-only forward (JobSet.forward(loss=False)) can run on the compact kernels."""
+        if on == (self.out_mu is not None):
+            return
+        if on:
+            stash = getattr(self, "_latent_stash", None)
+            if stash is None:
+                ra, Z = self.tables[0].rows_alloc, self.spec.latent
+                stash = tuple(torch.zeros(ra, Z, device=self.device) for _ in range(3))
+            self.out_mu, self.out_logvar, self.out_z = stash
+        else:
+            self._latent_stash = (self.out_mu, self.out_logvar, self.out_z)
+            self.out_mu = self.out_logvar = self.out_z = None
+        self._version += 1
 
     # -- descriptor ----------------------------------------------------------------------------
     def struct(self) -> _lib.NmJob:
@@ -728,14 +758,42 @@ class JobSet:
             return False
         return all(j.devpass_ok() for j in self.jobs)
 
-    def forward(self, tile0: int = 0, n_tiles: Optional[int] = None, loss: bool = True, trace: bool = False):
+    def devpass_multi_ok(self) -> bool:
+        """Can the set's multi-expert reconstruction / deviation pass run on the compact kernel (nm_devpass_multi)?  The
+        conditions of nm_devpass_multi_ok, read off the jobs as in devpass_ok (tests/test_cabi_devpass_multi_cpu.py holds
+        the two to each other); NMHIP_DEVPASS=0 switches both compact kernels off."""
+        if self.wide or os.environ.get("NMHIP_DEVPASS", "1") == "0":
+            return False
+        return all(j.devpass_multi_ok() for j in self.jobs)
+
+    def devpass_multi_pick(self) -> bool:
+        """The automatic pick of nm_devpass_multi for this set: devpass_multi_ok() and a shape class in which the compact
+        kernel's slowest measured repeat beat the general kernel's fastest (DEVPASS_MULTI_AUTO).
+        NMHIP_DEVPASS_MULTI=1 / 0 forces the pick on (where the set passes devpass_multi_ok) / off."""
+        env = os.environ.get("NMHIP_DEVPASS_MULTI", "auto")
+        if env == "0" or not self.devpass_multi_ok():
+            return False
+        return env == "1" or all(DEVPASS_MULTI_AUTO.get(len(j.kmods), False) for j in self.jobs)
+
+    def forward(self, tile0: int = 0, n_tiles: Optional[int] = None, loss: bool = True, trace: bool = False,
+                compact: Optional[bool] = None):
         """forward-only over row tiles (one workgroup per (job, 256-row tile)); fills the exports.  loss=False: only the
         per-ROI / per-subject deviations and the reconstruction are wanted (the deviation pass of
-        ..._regression.py:163-192) -- one-expert sets then run on the compact kernel, two workgroups per CU.  trace: the
-        compact kernel records its phase cycles (nm_trace_read_dv)."""
+        ..._regression.py:163-192, pred_recon + reconstruction_deviation_multimodal of ..._test_cvae_supervised.py:112-113)
+        -- sets of one-expert models (nm_devpass) and sets of several-expert models (nm_devpass_multi) then run on the
+        compact kernels, two workgroups of 128 rows per CU.  compact (several-expert sets): None = the automatic pick
+        (devpass_multi_pick), True = insist on nm_devpass_multi (ValueError if a job of the set cannot run there), False =
+        the general kernel.  trace: the compact kernel records its phase cycles (nm_trace_read_dv)."""
         nt = self.jobs[0].tables[0].n_tiles if n_tiles is None else n_tiles
         if not loss and self.devpass_ok():
             self._issue("nm_devpass", 1, tile0 * 2, nt * 2, _lib.NM_F_TRACE if trace else 0)
+            return
+        if compact and (loss or not self.devpass_multi_ok()):
+            raise ValueError("compact=True: the set cannot run on nm_devpass_multi (loss wanted, latent exports on, "
+                             "NMHIP_DEVPASS=0, or a shape nm_devpass_multi_ok refuses)")
+        if not loss and (compact or (compact is None and self.devpass_multi_pick())):
+            # (one workspace tile per 256-row batch: the two 128-row workgroups of a batch share it on disjoint rows)
+            self._issue("nm_devpass_multi", nt, tile0 * 2, nt * 2, _lib.NM_F_TRACE if trace else 0)
             return
         self._launch(tile0, 1, nt, _lib.NM_F_EXPORT)
 

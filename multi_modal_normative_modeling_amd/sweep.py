@@ -436,13 +436,11 @@ def load_model(fold_dir, tables: Sequence[Table], device, seed: int = 0) -> Job:
                n_tiles_ws=tables[0].n_tiles)
 
 
-def test_fold(job: Job, cohort: prep.SyntheticCohort, train_rows: np.ndarray, test_rows: np.ndarray, modalities: Sequence[str],
-              combine: str, device, out_dir=None, roi_columns: Optional[Dict[str, Sequence[str]]] = None):
-    """One fold of multimodal_kfold_test_cvae_supervised.py:64-153 for a trained model: per modality a RobustScaler
-    fit on the fold's train rows and applied to the test rows (:86-92), covariates re-binned on the TEST rows
-    (:94-99), `pred_recon` (joint latent, sampled z; one workgroup per 256-row tile) and
-    `reconstruction_deviation_multimodal`, then the five CSV kinds per modality (:121-153).  Returns
-    {modality: per-subject reconstruction error} (what the group analysis averages and scores)."""
+def _fold_eval_job(job: Job, cohort: prep.SyntheticCohort, train_rows: np.ndarray, test_rows: np.ndarray,
+                   modalities: Sequence[str], combine: str, device):
+    """The evaluation job of one fold (test_fold / test_folds): per modality a RobustScaler fit on the fold's train rows and
+    applied to its test rows, covariates re-binned on the TEST rows, the trained model on those tables with the
+    reconstruction and per-subject deviation exports.  Returns (job, scaled test tables on the host)."""
     xs = []
     for m in modalities:
         src = prep.source_table(cohort, m)
@@ -455,8 +453,13 @@ def test_fold(job: Job, cohort: prep.SyntheticCohort, train_rows: np.ndarray, te
     ev = Job(job.spec, tables, combine=combine, state=job.state_dict(), seed=job.seed + 31, n_tiles_ws=tables[0].n_tiles,
              single_bypass=job.single_bypass)
     ev.enable_exports(loc=True, sqerr=False, rowdev=True, latent=False)
-    JobSet([ev]).forward()
-    torch.cuda.synchronize(device)
+    return ev, xs
+
+
+def _fold_results(ev: Job, xs, cohort: prep.SyntheticCohort, test_rows: np.ndarray, modalities: Sequence[str], out_dir,
+                  roi_columns: Optional[Dict[str, Sequence[str]]]):
+    """{modality: per-subject reconstruction error} of an evaluation job whose forward pass has run, and -- out_dir given --
+    the five CSV kinds per modality (multimodal_kfold_test_cvae_supervised.py:121-153)."""
     n = len(test_rows)
     errors = {}
     for i, m in enumerate(modalities):
@@ -469,6 +472,44 @@ def test_fold(job: Job, cohort: prep.SyntheticCohort, train_rows: np.ndarray, te
             cols = list(roi_columns[m]) if roi_columns and m in roi_columns else [f"{m}_{k}" for k in range(xs[i].shape[1])]
             io.write_test_csvs(Path(out_dir) / m, m, meta, cols, xs[i], x_hat)
     return errors
+
+
+def test_fold(job: Job, cohort: prep.SyntheticCohort, train_rows: np.ndarray, test_rows: np.ndarray, modalities: Sequence[str],
+              combine: str, device, out_dir=None, roi_columns: Optional[Dict[str, Sequence[str]]] = None):
+    """One fold of multimodal_kfold_test_cvae_supervised.py:64-153 for a trained model: per modality a RobustScaler
+    fit on the fold's train rows and applied to the test rows (:86-92), covariates re-binned on the TEST rows
+    (:94-99), `pred_recon` (joint latent, sampled z) and `reconstruction_deviation_multimodal`, then the five CSV kinds
+    per modality (:121-153).  Neither the loss nor the latent is wanted: the pass runs on the compact kernels where the
+    model's shape allows (JobSet.forward(loss=False)).  Returns {modality: per-subject reconstruction error} (what the
+    group analysis averages and scores).  test_folds runs all folds of a procedure in one launch; this is the
+    fold-by-fold form and its cross-check."""
+    ev, xs = _fold_eval_job(job, cohort, train_rows, test_rows, modalities, combine, device)
+    JobSet([ev]).forward(loss=False)
+    torch.cuda.synchronize(device)
+    return _fold_results(ev, xs, cohort, test_rows, modalities, out_dir, roi_columns)
+
+
+def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequence[tuple], modalities: Sequence[str],
+               combines, device, out_dirs: Optional[Sequence] = None,
+               roi_columns: Optional[Dict[str, Sequence[str]]] = None) -> List[Dict[str, np.ndarray]]:
+    """test_fold for ALL folds of a procedure as one launch: jobs[i] is the trained model of fold i, folds[i] its
+    (train_rows, test_rows); one evaluation job per fold, each on its own test tables (seed, scaler and covariates per fold
+    exactly as test_fold), all in ONE JobSet -- a fold's ~N / K test rows are a single workgroup, K of them in a row leave
+    the chip idle.  `combines`: one fusion name for all folds or one per fold; out_dirs: one directory per fold (or None).
+    Folds whose test tables differ in their number of 256-row tiles run as one launch per height (the folds of a K-fold
+    split differ by at most one row).  Returns test_fold's result per fold; bit-identical to the fold-by-fold form."""
+    if len(jobs) != len(folds):
+        raise ValueError(f"{len(jobs)} models for {len(folds)} folds")
+    combs = [combines] * len(jobs) if isinstance(combines, str) else list(combines)
+    dirs = [None] * len(jobs) if out_dirs is None else list(out_dirs)
+    evs = [_fold_eval_job(j, cohort, tr, te, modalities, cb, device) for j, (tr, te), cb in zip(jobs, folds, combs)]
+    by_tiles: Dict[tuple, List[int]] = {}
+    for i, (ev, _) in enumerate(evs):
+        by_tiles.setdefault((ev.tables[0].n_tiles, bool(ev.spec.wide)), []).append(i)
+    for idxs in by_tiles.values():
+        JobSet([evs[i][0] for i in idxs]).forward(loss=False)
+    torch.cuda.synchronize(device)
+    return [_fold_results(ev, xs, cohort, te, modalities, d, roi_columns) for (ev, xs), (_, te), d in zip(evs, folds, dirs)]
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -749,10 +790,11 @@ def main_test(argv=None):
     dc = DeviceCohort(cohort, device)
     errors: Dict[str, list] = {m: [] for m in mods}
     my = _my_folds(args)
+    fold_jobs, fold_rows, fold_combines, fold_dirs = [], [], [], []
     for k in my:
         tr, te = folds[k]
         fold_dir = root / f"{k:03d}"
-        # (the model is rebuilt on any tables of the right widths; test_fold puts it on the fold's test tables)
+        # (the model is rebuilt on any tables of the right widths; test_folds puts it on the fold's test tables)
         meta = torch.load(fold_dir / "cVAE_model_state.pt", map_location="cpu", weights_only=True)
         no_cov = MODEL_KINDS[meta["model"]][0] in ("dmvae", "weighted_dmvae", "mmvaeplus")
         # the fold's subjects as the train entry recorded them (its -O / -TrainingClass recipe may differ from the
@@ -760,11 +802,14 @@ def main_test(argv=None):
         if (fold_dir / "train_ids.csv").exists() and (fold_dir / "test_ids.csv").exists():
             tr = prep.rows_of_ids(cohort.iid, pd.read_csv(fold_dir / "train_ids.csv")["IID"].to_numpy())
             te = prep.rows_of_ids(cohort.iid, pd.read_csv(fold_dir / "test_ids.csv")["IID"].to_numpy())
-        job = load_model(fold_dir, dc.fold_tables_cached(k, mods, tr, with_covariates=not no_cov), device, seed=1000 * k)
+        fold_jobs.append(load_model(fold_dir, dc.fold_tables_cached(k, mods, tr, with_covariates=not no_cov), device, seed=1000 * k))
         # models whose class fixes the fusion (mmJSD, the DMVAE family: MODEL_KINDS[...][2]) reconstruct with the saved
         # one, whatever the procedure name says (mmJSD.pred_recon ignores its combine argument, cVAE.py:1405-1420)
-        fold_combine = str(meta["combine"]).lower() if MODEL_KINDS[meta["model"]][2] else combine
-        err = test_fold(job, cohort, tr, te, mods, fold_combine, device, out_dir=fold_dir)
+        fold_combines.append(str(meta["combine"]).lower() if MODEL_KINDS[meta["model"]][2] else combine)
+        fold_rows.append((tr, te))
+        fold_dirs.append(fold_dir)
+    # all folds of this rank in one launch (one job per fold on its own test tables)
+    for err in (test_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs) if my else []):
         for m in mods:
             errors[m].append(err[m])
     for m in mods:                                   # all folds of this rank, one table per CSV kind (:147-175)
