@@ -366,6 +366,18 @@ int nm_devpass_ok(const nm_job_t* job_host);
  * NM_E_DEVPASS otherwise (such a job runs on nm_forward); NM_E_NULL for a null pointer. */
 int nm_devpass_multi(const nm_job_t* jobs_dev, int n_jobs, int tile0, int n_tiles, int flags, void* stream);   /* flags: 0 or NM_F_TRACE */
 int nm_devpass_multi_ok(const nm_job_t* job_host);
+/* The encoder half alone (csrc/nm_devpass.hip: nm_latent_kernel): the joint posterior of every row, what cVAE.pred_latent
+ * returns (cVAE.py:539-545), over table rows [tile0 * 128, (tile0 + n_tiles) * 128).  Every expert's encoder and the fusion
+ * of nm_forward, no latent draw and no decoder; writes out_mu / out_logvar and nothing else -- bit for bit nm_forward's
+ * exports on the table's rows, zeros on the rows of the launch's tiles past the table's end.  128-row tiles, 75 KB of LDS:
+ * two workgroups per CU.  A job with several experts needs one workspace tile per 256-row batch the launch touches (as
+ * nm_devpass_multi); a one-expert job needs none.  Every job must pass nm_latent_pass_ok (checked by the caller on the
+ * host; the kernel makes the workgroups of a refused job leave at once): NM_OK for a job that is not wide, has
+ * 1..NM_MAX_EXP modalities, each with an encoder (M_enc 0 or M), n_private == 0, tc_weight == 0, w_off < 0, out_kind == 0,
+ * H[0] <= 112 and Z rounded to 16 <= 32; NM_E_DEVPASS otherwise (such a job gets its latent exports from nm_forward);
+ * NM_E_NULL for a null pointer.  NM_F_TRACE: read out by nm_trace_read_dv. */
+int nm_latent_pass(const nm_job_t* jobs_dev, int n_jobs, int tile0, int n_tiles, int flags, void* stream);   /* flags: 0 or NM_F_TRACE */
+int nm_latent_pass_ok(const nm_job_t* job_host);
 /* NM_F_TRACE read-out of the row-split kernels ([8 waves][64 tags], as nm_trace_read) */
 int nm_trace_read_rs(unsigned long long* out512, int reset);
 /* out_dev[j] (device, n_jobs ints) != 0: a hand-off of job j timed out in a split launch since the word was last
@@ -442,6 +454,21 @@ int nm_posthoc_metrics(const float* scores, const int32_t* labels, const int32_t
  * out = {accuracy, auroc, sensitivity, specificity, f1_score, precision, n_pos, n_neg}. */
 int nm_confusion_metrics(const int32_t* pred, const int32_t* labels, const int32_t* offsets, int n_sets, double* out,
                          void* stream);
+/* The latent deviation (utils_vae.py:155-161) on exported joint statistics: device arrays [rows][pitch] fp32 (pitch >= Z,
+ * 1 <= Z <= NM_MAX_LATENT) whose sets are the row segments [offsets[s], offsets[s+1]) (offsets: n_sets + 1 device ints).
+ * nm_latent_stats: per set the column means and POPULATION variances (np.mean / np.var over axis 0) of mu -> mean_out /
+ *   var_out [n_sets][Z]; fp64 partials per 128 rows merged in row order, rounded once to fp32, no atomics (the same bits
+ *   on every run); an empty set's statistics are NaN.
+ * nm_latent_score: against mean / var [n_sets][Z] (set s of the rows scored with row s of the statistics):
+ *   zsep_out [rows][pitch] = (mu - mean) / sqrt(var + exp(logvar))              separate_latent_deviation
+ *   score_out [rows]       = sum_z |mu - mean| / sqrt(var + exp(logvar)) / Z    latent_deviation
+ *   (either output may be NULL, not both).
+ * Status NM_E_NULL: a required pointer missing; NM_E_LATENT: Z outside 1..NM_MAX_LATENT; NM_E_METRICS: n_sets < 1 (no set
+ * at all) or pitch < Z. */
+int nm_latent_stats(const float* mu, const int32_t* offsets, int n_sets, int Z, int pitch, float* mean_out, float* var_out,
+                    void* stream);
+int nm_latent_score(const float* mu, const float* logvar, const int32_t* offsets, int n_sets, int Z, int pitch,
+                    const float* mean, const float* var, float* zsep_out, float* score_out, void* stream);
 
 /* The expert-fusion operators the reference exposes as public methods, as forward-only launches (elementwise over
  * [M][n] fp32 device tensors; csrc/nm_fusion.hip):

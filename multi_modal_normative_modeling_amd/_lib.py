@@ -175,6 +175,10 @@ def load():
     lib.nm_devpass_ok.argtypes = [C.POINTER(NmJob)]
     lib.nm_devpass_multi.argtypes = [vp, i32, i32, i32, i32, vp]
     lib.nm_devpass_multi_ok.argtypes = [C.POINTER(NmJob)]
+    lib.nm_latent_pass.argtypes = [vp, i32, i32, i32, i32, vp]
+    lib.nm_latent_pass_ok.argtypes = [C.POINTER(NmJob)]
+    lib.nm_latent_stats.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
+    lib.nm_latent_score.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.nm_combine_latent.argtypes = [vp, vp, i32, i64, i32, vp, i32, i32, i32, f32, vp, vp, vp]
     lib.nm_total_correlation.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.nm_train_steps.argtypes = [vp, i32, i32, i32, vp]
@@ -216,6 +220,7 @@ EXPORTED_SYMBOLS = [
     "nm_prep_scaler_fit", "nm_prep_onehot", "nm_pack_table_raw",
     "nm_launch_rowsplit", "nm_rowsplit_ok", "nm_sync_reset", "nm_trace_read_rs", "nm_devpass", "nm_devpass_ok", "nm_trace_read_dv", "nm_workspace_offset",
     "nm_launch_rowsplit_mixed", "nm_rowsplit_groups", "nm_devpass_multi", "nm_devpass_multi_ok",
+    "nm_latent_pass", "nm_latent_pass_ok", "nm_latent_stats", "nm_latent_score",
 ]
 
 

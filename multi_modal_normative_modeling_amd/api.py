@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .engine import Job, JobSet, Table, adam_step, require_gpu
+from .engine import Job, JobSet, Table, adam_step, latent_scores, latent_stats, require_gpu
 from .layout import ModelSpec, ParamLayout
 
 
@@ -215,8 +215,11 @@ class _Base(nn.Module):
         return self._device
 
     def _run(self, xes: Sequence[torch.Tensor], cs: Sequence[torch.Tensor], combine: str, flags: int, eps=None,
-             kl_w=None, ll_w=1.0, recon_only: bool = False):
-        """recon_only (forward-only calls that read the reconstruction alone -- pred_recon): the job's latent exports are
+             kl_w=None, ll_w=1.0, recon_only: bool = False, latent_only: bool = False):
+        """latent_only (forward-only calls that read the joint posterior alone -- pred_latent of the multimodal classes): the
+        launch goes through JobSet.latent(), i.e. on the encoder-only kernel where the model's shape allows (same out_mu /
+        out_logvar, bit for bit).
+        recon_only (forward-only calls that read the reconstruction alone -- pred_recon): the job's latent exports are
         switched off for the call and the launch goes through JobSet.forward(loss=False), i.e. on the compact kernels where
         the model's shape allows (same reconstruction, bit for bit); the next call that wants the latent switches them back."""
         self._ensure_device(xes[0])
@@ -272,9 +275,49 @@ class _Base(nn.Module):
             self._js._launch_split(0, 1, flags | getattr(self, "_fault_inject", 0))
         elif recon_only and flags == _lib.NM_F_EXPORT:
             self._js.forward(0, nt, loss=False)
+        elif latent_only and flags == _lib.NM_F_EXPORT:
+            self._js.latent(0, nt)
         else:
             self._js._launch(0, 1, nt, flags)
         return j, B
+
+    # -- the latent deviation (utils_vae.py:155-161) ----------------------------------------------------
+    def _latent_joint(self, xes, c, combine: str = "poe"):
+        """Joint posterior (mu, logvar) of a cohort as device tensors: DataFrames / arrays in (one, or one per modality)."""
+        many = isinstance(xes, (list, tuple))
+        xs = [torch.tensor(np.asarray(x.values if hasattr(x, "values") else x), dtype=torch.float32) for x in (xes if many else [xes])]
+        ct = torch.tensor(np.asarray(c), dtype=torch.long)
+        self._dev()
+        j, B = self._run(xs, [ct] * len(xs), combine, _lib.NM_F_EXPORT, latent_only=True,
+                         eps=torch.zeros(int(xs[0].shape[0]), self.spec.latent, device=self._device))
+        return j.out_mu[:B].clone(), j.out_logvar[:B].clone()
+
+    def _latent_of(self, what):
+        """`what`: (mu, var) as pred_latent returns them, or the arguments of a pred_latent call -- (x, c) / (xes, c, combine)
+        with DataFrames -- for which the latent pass runs here.  -> (mu, logvar) device tensors."""
+        first = what[0]
+        if isinstance(first, (list, tuple)) or hasattr(first, "to_numpy"):
+            return self._latent_joint(*what)
+        mu = torch.as_tensor(np.asarray(what[0]), dtype=torch.float32).to(self._dev())
+        var = torch.as_tensor(np.asarray(what[1]), dtype=torch.float32).to(self._dev())
+        return mu, var.log()
+
+    def _latent_scores(self, train, sample):
+        mu_t, _ = self._latent_of(train)
+        mu_s, lv_s = self._latent_of(sample)
+        mean, var = latent_stats([mu_t])
+        zsep, score = latent_scores([mu_s], [lv_s], mean, var)
+        return zsep[0], score[0]
+
+    def latent_deviation(self, train, sample):
+        """utils_vae.py:155-157 on the device: per subject of `sample` the mean absolute z-score of its latent mean against
+        the `train` cohort's latent distribution, the subject's own posterior variance in the denominator.  train / sample:
+        (mu, var) as pred_latent returns them, or pred_latent's own arguments without the device ((x, c) / (xes, c, combine))."""
+        return self._latent_scores(train, sample)[1].cpu().numpy()
+
+    def separate_latent_deviation(self, train, sample):
+        """utils_vae.py:159-161 on the device: the z-score per latent dimension, [N, Z]."""
+        return self._latent_scores(train, sample)[0].cpu().numpy()
 
     def _publish_grads(self, which: str, g: torch.Tensor):
         xes, cs, combine, eps = self._last
@@ -478,6 +521,11 @@ class cVAE_multimodal(_ExpertOps, _Base):
         j, B = self._run(xs, [ct] * self.modalities, combine, _lib.NM_F_EXPORT, recon_only=True)
         return [j.out_loc[m][:B].cpu().numpy() for m in range(self.modalities)]
 
+    def pred_latent(self, xes, c, DEVICE, combine):
+        """The joint counterpart of cVAE.pred_latent (cVAE.py:539-545): DataFrames in, (mu_joint, var_joint) as numpy out."""
+        mu, logvar = self._latent_joint(list(xes), c, combine)
+        return mu.cpu().numpy(), logvar.exp().cpu().numpy()
+
     def reconstruction_deviation_multimodal(self, xes, x_preds):
         return [np.sum((xes[m] - x_preds[m]) ** 2, axis=1) / xes[m].shape[1] for m in range(self.modalities)]
 
@@ -630,6 +678,9 @@ class mvtCAE(cVAE_multimodal):
     def pred_recon(self, xes, c, DEVICE, combine):
         return super().pred_recon(xes, c, DEVICE, self._kernel_combine(combine))
 
+    def pred_latent(self, xes, c, DEVICE, combine):
+        return super().pred_latent(xes, c, DEVICE, self._kernel_combine(combine))
+
 
 class mmJSD(cVAE_multimodal):
     """cVAE.py:1354-1448 (baseline zoo).  Same encoders / decoders / `alpha_m_list` and the same
@@ -651,6 +702,9 @@ class mmJSD(cVAE_multimodal):
 
     def pred_recon(self, xes, c, DEVICE, combine):
         return super().pred_recon(xes, c, DEVICE, "poe")
+
+    def pred_latent(self, xes, c, DEVICE, combine="poe"):
+        return super().pred_latent(xes, c, DEVICE, "poe")
 
     def reparameterize(self, mu, logvar):
         return self.reparameterise(mu, logvar)
@@ -791,6 +845,9 @@ class cVAE_multimodal_regression(_ExpertOps, _HeadBase):
         self._pending = j.grads
         self._grads_ready = True
         self._assign_grads()
+
+    def pred_latent(self, xes, c, DEVICE, combine):
+        return cVAE_multimodal.pred_latent(self, xes, c, DEVICE, combine)
 
     def encode(self, x, c, m):
         return cVAE_multimodal.encode(self, x, c, m)

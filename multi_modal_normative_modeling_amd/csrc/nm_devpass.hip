@@ -17,7 +17,8 @@
 // Arithmetic, draws (keyed by absolute row) and exports are those of the general kernel, row by row: the two agree bit for
 // bit on out_sqerr / out_rowdev / out_loc (tests/test_gpu_devpass.py).  No loss log, no latent exports: launches that want
 // those, a first hidden layer wider than 112 or a latent wider than 32 stay on nm_forward.  Models with several experts
-// run on nm_devpass_multi_kernel, further down in this file.
+// run on nm_devpass_multi_kernel, further down in this file; the joint latent statistics alone (no decoder) come from
+// nm_latent_kernel, at its end.
 #include "nm_core.inc"
 
 // export stores: plain, not non-temporal ("written once, read by another kernel"), as the A/B decided: 458 us per pass
@@ -574,6 +575,225 @@ __global__ __launch_bounds__(WG, 4) void nm_devpass_multi_kernel(const nm_job_t*
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// nm_latent_kernel -- the encoder half of the pass above and nothing else: the joint posterior (mu, logvar) of every row,
+// what cVAE.pred_latent returns (cVAE.py:539-545) and latent_deviation / separate_latent_deviation score against the
+// training cohort (utils_vae.py:155-161).  No latent draw, no z | c | 1, no decoder, no output chunks.
+//
+// A workgroup owns 128 rows, two workgroups share a CU (LDS: P, W, the two vector slots and the scalars of nm_devpass_kernel,
+// 75 KB; no z buffer).  Per tile: every expert's encoder chain (first layer, dv_layer, heads), then the fusion.
+//   several experts: the heads store mu_m / logvar_m to this tile's rows of the batch's workspace tile, and the fusion reads
+//     them back through fuse_fwd / softmax_alpha exactly as nm_devpass_multi_kernel and the general kernel do;
+//   one expert (SM models, cVAE): the heads' accumulators go through the same fuse_fwd (its single-expert bypass, or the
+//     one-expert product with the prior where the job has the bypass off) straight to the exports: no workspace tile.
+// out_mu / out_logvar agree bit for bit with the general kernel's exports on the table's rows; the rows of the launch's
+// 128-row tiles past the table's end -- the empty half of a ragged 256-row batch included -- come back as zeros.
+// A job lat_refused refuses must not reach this kernel; its workgroups leave at once, exports untouched.
+__host__ __device__ inline int lat_refused(const nm_job_t* j) {
+  const int Me = j->M_enc > 0 ? j->M_enc : j->M;
+  if (j->wide || j->M < 1 || j->M > NM_MAX_EXP || Me != j->M) return NM_E_DEVPASS;
+  if (j->n_private != 0 || j->tc_weight != 0.f || j->w_off >= 0 || j->out_kind != 0) return NM_E_DEVPASS;
+  if (j->H[0] > DV_MAX_H0 || rup(j->Z, 16) > 32) return NM_E_DEVPASS;
+  return 0;
+}
+
+// One expert: the heads GEMM of fwd_heads (same fragments, same order of accumulation), its epilogue the fusion of that
+// one expert and the export.  Lane (c16, g) of a unit holds row r, latent columns f0 .. f0 + 3.
+__device__ __forceinline__ void lat_heads_export(const Ctx& cc, int Z, int K, int Zs, bool vec4, const float (&alpha)[NM_MAX_EXP],
+                                                 const float* bias) {
+  constexpr int RT = DV_RT, WROWS = DV_RT * 16;
+  Ctx c = cc;
+  relaunder(c);
+  const nm_job_t* J = c.job;
+  const int ksteps = wpad(K) / 32;
+  const int nzt = Zs / 16;
+  const __bf16* Wt = c.Q;
+  gf32 omu = asg(J->out_mu), olv = asg(J->out_logvar);
+  wait_vm(0);
+  lds_barrier();
+  for (int u = c.wn; u < nzt * RT; u += NWN) {
+    const int ft = u / RT, rt = u - ft * RT;
+    const int f0 = ft * 16 + 4 * c.g;
+    f32x4 am = {0.f, 0.f, 0.f, 0.f}, al = am;
+    for (int ks = 0; ks < ksteps; ++ks) {
+      const bf16x8 fm = lds_frag(Wt, LDP, ft * 16 + c.c16, ks * 32 + 8 * c.g);
+      const bf16x8 fl = lds_frag(Wt, LDP, Zs + ft * 16 + c.c16, ks * 32 + 8 * c.g);
+      const bf16x8 a = lds_frag(c.P, LDP, c.wm * WROWS + rt * 16 + c.c16, ks * 32 + 8 * c.g);
+      am = mfma(fm, a, am);
+      al = mfma(fl, a, al);
+    }
+    const int r = c.wm * WROWS + rt * 16 + c.c16;
+    am += *reinterpret_cast<const f32x4*>(bias + f0);
+    al += *reinterpret_cast<const f32x4*>(bias + Zs + f0);
+    const bool rv = r < c.nrows;
+    f32x4 jm, jl;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      Lat Lt;
+#pragma unroll
+      for (int m = 0; m < NM_MAX_EXP; ++m) { Lt.mu[m] = 0.f; Lt.lv[m] = 0.f; }
+      Lt.mu[0] = am[i]; Lt.lv[0] = al[i];
+      const Fuse f = fuse_fwd(J, Lt, alpha);
+      jm[i] = rv ? f.mu : 0.f;
+      jl[i] = rv ? f.lv : 0.f;
+    }
+    const int64_t gr = (int64_t)(c.row0 + r) * Z + f0;
+    if (vec4) {
+      if (f0 < Z) {
+        if (omu) *(GAS f32x4*)(omu + gr) = jm;
+        if (olv) *(GAS f32x4*)(olv + gr) = jl;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        if (f0 + i < Z) {
+          if (omu) omu[gr + i] = jm[i];
+          if (olv) olv[gr + i] = jl[i];
+        }
+      }
+    }
+  }
+  lds_barrier();
+  tr(c, 2);
+}
+
+__global__ __launch_bounds__(WG, 4) void nm_latent_kernel(const nm_job_t* __restrict__ jobs, int tile0, int flags) {
+  constexpr int RT = DV_RT, ROWS = DV_ROWS;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const nm_job_t* J = jobs + blockIdx.x;
+  const int M = J->M;
+  if (lat_refused(J) || (M > 1 && !J->workspace)) return;
+  const int Z = J->Z;
+  const int t128 = tile0 + (int)blockIdx.y;
+  const int row0 = t128 * ROWS;
+  gf32 omu = asg(J->out_mu), olv = asg(J->out_logvar);
+  if (row0 >= J->n_rows) {
+    // the second half of a ragged last 256-row tile: its export rows come back as zeros ([128][Z] floats: whole 16-byte words)
+    if (row0 < (J->n_rows + TROWS - 1) / TROWS * TROWS) {
+      for (int e = threadIdx.x; e < ROWS * Z / 4; e += WG) {
+        const int64_t gi = (int64_t)row0 * Z + (int64_t)e * 4;
+        if (omu) *(GAS f32x4*)(omu + gi) = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (olv) *(GAS f32x4*)(olv + gi) = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+    return;
+  }
+  Ctx c;
+  c.job = J;
+  c.part = -1; c.nparts = 1; c.lstep = 0;
+  c.slope = J->act_slope;
+  dv_carve(c, smem);
+  relaunder(c);
+  c.flags = NM_F_EXPORT | (flags & NM_F_TRACE);
+  c.t_last = 0;
+  // several experts: the workspace tile of this tile's 256-row batch (counted from the batch tile0 falls in)
+  c.ws = M > 1 ? (GAS char*)J->workspace + (int64_t)(t128 / 2 - tile0 / 2) * J->workspace_stride : nullptr;
+  for (int i = c.tid; i < DV_SMEM / 4; i += WG) reinterpret_cast<uint32_t*>(smem)[i] = 0u;
+  __syncthreads();
+  if (c.flags & 64) c.tlast[c.wave_s] = clock64();
+  c.row0 = row0;
+  c.rloc0 = row0 % TROWS;
+  c.nrows = min(ROWS, J->n_rows - row0);
+  c.inv_b = 1.0f / (float)c.nrows;
+  const int live = c.nrows;
+  const int L = J->L;
+  const int Zs = rup(Z, 16);
+  const bool nl = J->non_linear != 0;
+  const bool vec4 = (Z & 3) == 0;
+  GAS char* const wsh = (GAS char*)J->wsh;
+  char* const Wb = reinterpret_cast<char*>(c.Q);
+  const WsLayout wl = ws_layout(M, L, Z);
+  gf32 ws_mu_m = (gf32)(c.ws + wl.mu_m) + c.rloc0 * Zs;
+  gf32 ws_lv_m = (gf32)(c.ws + wl.lv_m) + c.rloc0 * Zs;
+  auto to_W = [&](const GAS char* blob, int vs, int rows, int K) {
+    return Next{blob, Wb, IMG_BYTES >> 10, blob + cimg_bytes(rows, K), reinterpret_cast<char*>(c.vec) + vs * VEC_BYTES, rows, blob_kp(K)};
+  };
+  float al[NM_MAX_EXP] = {0.f, 0.f, 0.f, 0.f};
+  if (J->combine == NM_COMBINE_GPOE && !(M == 1 && J->single_bypass)) softmax_alpha(J, al);
+
+  // ---- encoders: every expert's chain ----
+  for (int m = 0; m < M; ++m) {
+    relaunder(c);
+    const nm_modality_t& md = J->mod[m];
+    const int nch = (md.Kx + XCH - 1) / XCH;
+    const GAS char* after0 = wsh + (L > 1 ? md.enc_s[1] : md.heads_s);
+    fwd_first_layer<RT>(c, (const GAS char*)asg(md.xb) + (int64_t)(row0 / TROWS) * nch * XIMG_TILE_BYTES + (int64_t)c.rloc0 * (LDX * 2),
+                        md.Kx, wsh + md.enc_s[0], to_W(after0, 0, L > 1 ? J->H[1] : 2 * Zs, J->H[0]), J->H[0], nl, (gbf16)nullptr, true,
+                        DV_W0_PIECES, live);
+    int vs = 0;
+    for (int e = 1; e < L; ++e) {
+      const GAS char* nxt = wsh + (e + 1 < L ? md.enc_s[e + 1] : md.heads_s);
+      dv_layer(c, vs, to_W(nxt, vs ^ 1, e + 1 < L ? J->H[e + 1] : 2 * Zs, J->H[e]), J->H[e], J->H[e - 1], nl, live);
+      vs ^= 1;
+    }
+    tr(c, 1);
+    if (M == 1) {
+      lat_heads_export(c, Z, J->H[L - 1], Zs, vec4, al, c.vec + vs * (VEC_BYTES / 4));
+      return;
+    }
+    wait_vm(0);
+    fwd_heads<RT>(c, 0, no_next(), Z, J->H[L - 1], ws_mu_m + (int64_t)m * TROWS * Zs, ws_lv_m + (int64_t)m * TROWS * Zs, Zs, 0,
+                  (__bf16*)nullptr, 0, vec4, (float*)nullptr, c.vec + vs * (VEC_BYTES / 4));
+  }
+
+  // ---- fusion: the joint statistics to the exports ----
+  handoff_barrier();                               // the heads' stores are complete for every thread of the workgroup
+  relaunder(c);
+  if (vec4) {
+    const int nq4 = Z >> 2;
+    const float rq4 = 1.0f / (float)nq4;
+#pragma unroll 2
+    for (int e = c.tid; e < ROWS * nq4; e += WG) {
+      const int r = idiv(e, nq4, rq4), z0 = 4 * (e - r * nq4);
+      f32x4 jm = {0.f, 0.f, 0.f, 0.f}, jl = jm;
+      if (r < live) {
+        f32x4 mu4[NM_MAX_EXP], lv4[NM_MAX_EXP];
+#pragma unroll
+        for (int m = 0; m < NM_MAX_EXP; ++m) {
+          mu4[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+          lv4[m] = mu4[m];
+          if (m < M) {
+            mu4[m] = *(const GAS f32x4*)(ws_mu_m + ((int64_t)m * TROWS + r) * Zs + z0);
+            lv4[m] = *(const GAS f32x4*)(ws_lv_m + ((int64_t)m * TROWS + r) * Zs + z0);
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          Lat Lt;
+#pragma unroll
+          for (int m = 0; m < NM_MAX_EXP; ++m) { Lt.mu[m] = mu4[m][i]; Lt.lv[m] = lv4[m][i]; }
+          const Fuse f = fuse_fwd(J, Lt, al);
+          jm[i] = f.mu; jl[i] = f.lv;
+        }
+      }
+      const int64_t gr = (int64_t)(row0 + r) * Z + z0;
+      if (omu) *(GAS f32x4*)(omu + gr) = jm;
+      if (olv) *(GAS f32x4*)(olv + gr) = jl;
+    }
+  } else {
+    const float rZ = 1.0f / (float)Z;
+#pragma unroll 2
+    for (int e = c.tid; e < ROWS * Z; e += WG) {
+      const int r = idiv(e, Z, rZ), z = e - r * Z;
+      float jm = 0.f, jl = 0.f;
+      if (r < live) {
+        Lat Lt;
+#pragma unroll
+        for (int m = 0; m < NM_MAX_EXP; ++m) {
+          Lt.mu[m] = (m < M) ? ws_mu_m[((int64_t)m * TROWS + r) * Zs + z] : 0.f;
+          Lt.lv[m] = (m < M) ? ws_lv_m[((int64_t)m * TROWS + r) * Zs + z] : 0.f;
+        }
+        const Fuse f = fuse_fwd(J, Lt, al);
+        jm = f.mu; jl = f.lv;
+      }
+      const int64_t gr = (int64_t)(row0 + r) * Z + z;
+      if (omu) omu[gr] = jm;
+      if (olv) olv[gr] = jl;
+    }
+  }
+  tr(c, 3);
+}
+
 }  // namespace
 
 extern "C" {
@@ -612,6 +832,23 @@ int nm_devpass_multi_ok(const nm_job_t* j) {
 int nm_devpass_multi(const nm_job_t* jobs_dev, int n_jobs, int tile0, int n_tiles, int flags, void* stream) {
   if (int bad = check_launch_geometry(jobs_dev, n_jobs, n_tiles, 1, tile0, 0)) return bad;
   return launch_kernel(nm_devpass_multi_kernel, dim3(n_jobs, n_tiles), dim3(WG), DVM_SMEM, stream, jobs_dev, tile0, flags & NM_F_TRACE);
+}
+
+/* 0: the job's joint latent statistics can come from the encoder-only kernel (not wide; 1..NM_MAX_EXP modalities, every one
+ * with an encoder; no private latent / learnable weights / total correlation; Gaussian output; first hidden width <= 112,
+ * latent <= 32 after rounding to 16); NM_E_DEVPASS otherwise.  One-expert jobs pass with the bypass on or off. */
+int nm_latent_pass_ok(const nm_job_t* j) {
+  if (!j) return NM_E_NULL;
+  return lat_refused(j);
+}
+
+/* The joint posterior of every row (cVAE.pred_latent, cVAE.py:539-545) over table rows [tile0 * 128, (tile0 + n_tiles) * 128):
+ * out_mu / out_logvar, nothing else (out_z and the per-modality exports stay as they are).  Every job must pass
+ * nm_latent_pass_ok -- checked by the caller on the host; the kernel makes a refused job's workgroups leave at once.  A job
+ * with several experts needs one workspace tile per 256-row batch the launch touches, as for nm_devpass_multi. */
+int nm_latent_pass(const nm_job_t* jobs_dev, int n_jobs, int tile0, int n_tiles, int flags, void* stream) {
+  if (int bad = check_launch_geometry(jobs_dev, n_jobs, n_tiles, 1, tile0, 0)) return bad;
+  return launch_kernel(nm_latent_kernel, dim3(n_jobs, n_tiles), dim3(WG), DV_SMEM, stream, jobs_dev, tile0, flags & NM_F_TRACE);
 }
 
 /* NM_F_TRACE read-out of nm_devpass ([8 waves][64 tags] interval cycles of workgroup (0, 0), as nm_trace_read) */

@@ -6,6 +6,9 @@
 //                          sklearn.metrics.roc_curve / auc as called there at :125-126)
 //   nm_confusion_metrics  hard predictions + labels -> accuracy, auroc, sensitivity, specificity, f1, precision
 //                         (evaluate, multimodal_kfold_cvae_nmpmcont.py:29-70)
+//   nm_latent_stats       exported joint latent means of a cohort -> column means and population variances
+//   nm_latent_score       ... and a cohort's (mu, logvar) against them -> z-score per latent dimension, its mean |z|
+//                         (latent_deviation / separate_latent_deviation, utils_vae.py:155-161)
 //
 // One workgroup per score set (a (fold, procedure) cell); sets are segments of one concatenated array.  The
 // whole set lives in LDS: order-preserving 64-bit keys (score, label) are bitonic-sorted descending, label
@@ -234,6 +237,80 @@ __global__ __launch_bounds__(MT) void confusion_kernel(const int32_t* __restrict
 
 constexpr int METRICS_SMEM = MAXN * (8 + 4 + 4);
 
+// ---- latent deviation (utils_vae.py:155-161): cohort statistics of the exported joint mu, then the z-scores -------------
+// nm_latent_stats: one workgroup per cohort (a segment of the concatenated [rows][pitch] array).  A thread owns one
+// (128-row chunk, column) pair at a time: the chunk's mean and its sum of squared deviations from that mean, two passes in
+// fp64; thread z < Z then merges the chunks' partials in row order with Chan's formula.  No atomics, a fixed order of
+// every sum: the result is the same run to run.  Rounded once to fp32 at the end.
+constexpr int LAT_CHUNK = 128;
+
+__global__ __launch_bounds__(MT) void latent_stats_kernel(const float* __restrict__ mu, const int32_t* __restrict__ offsets, int Z,
+                                                          int pitch, float* __restrict__ mean_out, float* __restrict__ var_out) {
+  __shared__ double pmean[MT], pm2[MT];
+  const int s = blockIdx.x, t = threadIdx.x;
+  const int base = offsets[s], n = offsets[s + 1] - base;
+  if (n <= 0) {                                                 // an empty cohort has no statistics
+    if (t < Z) { mean_out[(int64_t)s * Z + t] = __int_as_float(0x7FC00000); var_out[(int64_t)s * Z + t] = __int_as_float(0x7FC00000); }
+    return;
+  }
+  const int per = MT / Z;                                       // chunks per round (Z <= 64: at least 4)
+  const int nchunks = (n + LAT_CHUNK - 1) / LAT_CHUNK;
+  const int cl = t / Z, z = t - cl * Z;
+  double cnt = 0.0, mean = 0.0, m2 = 0.0;                       // thread z < Z: the running statistics of column z
+  for (int c0 = 0; c0 < nchunks; c0 += per) {
+    const int ch = c0 + cl;
+    if (cl < per && ch < nchunks) {
+      const int r0 = ch * LAT_CHUNK, r1 = min(r0 + LAT_CHUNK, n);
+      const float* col = mu + (int64_t)(base + r0) * pitch + z;
+      double sum = 0.0;
+      for (int r = 0; r < r1 - r0; ++r) sum += (double)col[(int64_t)r * pitch];
+      const double cm = sum / (double)(r1 - r0);
+      double q = 0.0;
+      for (int r = 0; r < r1 - r0; ++r) { const double d = (double)col[(int64_t)r * pitch] - cm; q += d * d; }
+      pmean[t] = cm; pm2[t] = q;
+    }
+    __syncthreads();
+    if (t < Z) {
+      for (int k = 0; k < per && c0 + k < nchunks; ++k) {
+        const double nb = (double)(min((c0 + k + 1) * LAT_CHUNK, n) - (c0 + k) * LAT_CHUNK);
+        const double delta = pmean[k * Z + t] - mean, tot = cnt + nb;
+        mean += delta * (nb / tot);
+        m2 += pm2[k * Z + t] + delta * delta * (cnt * nb / tot);
+        cnt = tot;
+      }
+    }
+    __syncthreads();
+  }
+  if (t < Z) {
+    mean_out[(int64_t)s * Z + t] = (float)mean;
+    var_out[(int64_t)s * Z + t] = (float)(m2 / cnt);            // population variance (np.var, ddof 0)
+  }
+}
+
+// nm_latent_score: one workgroup per set, a thread per row.  The library's expf / sqrtf / division (<= 1 ulp, correctly
+// rounded, correctly rounded); no product anywhere, so nothing for the compiler to contract.
+__global__ __launch_bounds__(MT) void latent_score_kernel(const float* __restrict__ mu, const float* __restrict__ logvar,
+                                                          const int32_t* __restrict__ offsets, int Z, int pitch,
+                                                          const float* __restrict__ mean, const float* __restrict__ var,
+                                                          float* __restrict__ zsep_out, float* __restrict__ score_out) {
+  __shared__ float smean[NM_MAX_LATENT], svar[NM_MAX_LATENT];
+  const int s = blockIdx.x, t = threadIdx.x;
+  const int base = offsets[s], n = offsets[s + 1] - base;
+  if (t < Z) { smean[t] = mean[(int64_t)s * Z + t]; svar[t] = var[(int64_t)s * Z + t]; }
+  __syncthreads();
+  for (int r = t; r < n; r += MT) {
+    const int64_t row = (int64_t)(base + r) * pitch;
+    float acc = 0.f;
+    for (int z = 0; z < Z; ++z) {
+      const float a = mu[row + z] - smean[z];
+      const float d = sqrtf(svar[z] + expf(logvar[row + z]));
+      if (zsep_out) zsep_out[row + z] = a / d;
+      acc += fabsf(a) / d;
+    }
+    if (score_out) score_out[base + r] = acc / (float)Z;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -250,6 +327,23 @@ int nm_confusion_metrics(const int32_t* pred, const int32_t* labels, const int32
   if (!pred || !labels || !offsets || !out) return NM_E_NULL;
   if (n_sets < 1) return NM_E_METRICS;
   return launch_kernel(confusion_kernel, dim3(n_sets), dim3(MT), 0, stream, pred, labels, offsets, out);
+}
+
+int nm_latent_stats(const float* mu, const int32_t* offsets, int n_sets, int Z, int pitch, float* mean_out, float* var_out,
+                    void* stream) {
+  if (!mu || !offsets || !mean_out || !var_out) return NM_E_NULL;
+  if (Z < 1 || Z > NM_MAX_LATENT) return NM_E_LATENT;
+  if (n_sets < 1 || pitch < Z) return NM_E_METRICS;
+  return launch_kernel(latent_stats_kernel, dim3(n_sets), dim3(MT), 0, stream, mu, offsets, Z, pitch, mean_out, var_out);
+}
+
+int nm_latent_score(const float* mu, const float* logvar, const int32_t* offsets, int n_sets, int Z, int pitch, const float* mean,
+                    const float* var, float* zsep_out, float* score_out, void* stream) {
+  if (!mu || !logvar || !offsets || !mean || !var || (!zsep_out && !score_out)) return NM_E_NULL;
+  if (Z < 1 || Z > NM_MAX_LATENT) return NM_E_LATENT;
+  if (n_sets < 1 || pitch < Z) return NM_E_METRICS;
+  return launch_kernel(latent_score_kernel, dim3(n_sets), dim3(MT), 0, stream, mu, logvar, offsets, Z, pitch, mean, var, zsep_out,
+                       score_out);
 }
 
 }  // extern "C"

@@ -27,6 +27,12 @@ BATCH = _lib.NM_BATCH
 # profiles/devpass_multi.json)
 DEVPASS_MULTI_AUTO = {2: True, 3: True, 4: True}
 
+# nm_latent_pass as the automatic pick of JobSet.latent(), per number of experts: on only where the encoder-only kernel's
+# slowest repeat beat the general forward kernel's fastest at every set size measured (tools/bench_latent.py,
+# profiles/latent_pass.json).  Two experts: the record holds no set of that class yet, so the class
+# stays on the general kernel until it does (JobSet.latent(compact=True) reaches nm_latent_pass all the same)
+LATENT_AUTO = {1: True, 2: False, 3: True, 4: True}
+
 
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
@@ -265,6 +271,14 @@ class Job:
         return (not s.wide and len(self.kmods) == s.M and 2 <= s.M <= _lib.NM_MAX_EXP and s.n_private == 0 and not s.is_dm
                 and self.tc_weight == 0.0 and s.kind != "weighted_dmvae" and s.hidden[0] <= 112 and (s.latent + 15) // 16 * 16 <= 32
                 and self.out_mu is None and self.out_logvar is None and self.out_z is None)
+
+    def latent_ok(self) -> bool:
+        """nm_latent_pass_ok for this job: 1..NM_MAX_EXP experts, every modality with an encoder, no private latent /
+        learnable weights / total correlation, Gaussian output, first hidden width <= 112, latent <= 32.  (The latent exports
+        are what the pass writes: they play no part here.)"""
+        s = self.spec
+        return (not s.wide and len(self.kmods) == s.M and 1 <= s.M <= _lib.NM_MAX_EXP and s.n_private == 0 and not s.is_dm
+                and self.tc_weight == 0.0 and s.kind != "weighted_dmvae" and s.hidden[0] <= 112 and (s.latent + 15) // 16 * 16 <= 32)
 
     def rowsplit_ok(self) -> bool:
         """Can this model run row-split (nm_rowsplit_ok: plain cVAE / cVAE_multimodal-type models on the fused kernel whose
@@ -797,6 +811,73 @@ class JobSet:
             return
         self._launch(tile0, 1, nt, _lib.NM_F_EXPORT)
 
+    def latent_ok(self) -> bool:
+        """Can the set's joint latent statistics come from the encoder-only kernel (nm_latent_pass)?  The conditions of
+        nm_latent_pass_ok, read off the jobs as in devpass_ok (tests/test_cabi_latent_cpu.py holds the two to each other);
+        NMHIP_LATENT=0 switches the kernel off."""
+        if self.wide or os.environ.get("NMHIP_LATENT", "1") == "0":
+            return False
+        return all(j.latent_ok() for j in self.jobs)
+
+    def latent_pick(self) -> bool:
+        """The automatic pick of nm_latent_pass for this set: latent_ok() and a shape class in which the encoder-only
+        kernel's slowest measured repeat beat the general kernel's fastest (LATENT_AUTO)."""
+        return self.latent_ok() and all(LATENT_AUTO.get(len(j.kmods), False) for j in self.jobs)
+
+    def latent(self, tile0: int = 0, n_tiles: Optional[int] = None, compact: Optional[bool] = None, trace: bool = False):
+        """The joint posterior of every row -- out_mu / out_logvar of every job, what cVAE.pred_latent returns
+        (cVAE.py:539-545) -- over row tiles.  Through the encoder-only kernel (nm_latent_pass: 128-row tiles, two workgroups
+        per CU, no draw, no decoder) where every job passes latent_ok(); else through the general forward kernel, which
+        computes the decoders as well.  compact: None = the automatic pick (latent_pick), True = insist on nm_latent_pass
+        (ValueError with the reason if the set cannot run there), False = the general kernel.  A job whose latent exports
+        are off gets them switched on (set_latent_exports).  trace: nm_latent_pass records its phase cycles
+        (nm_trace_read_dv)."""
+        for j in self.jobs:
+            if j.out_mu is None or j.out_logvar is None:
+                j.set_latent_exports(True)
+        nt = self.jobs[0].tables[0].n_tiles if n_tiles is None else n_tiles
+        if compact and not self.latent_ok():
+            raise ValueError("compact=True: the set cannot run on nm_latent_pass: " + self._latent_refusal())
+        if compact or (compact is None and self.latent_pick()):
+            # (several experts: one workspace tile per 256-row batch, shared by the batch's two 128-row workgroups)
+            ws_tiles = nt if any(len(j.kmods) > 1 for j in self.jobs) else 1
+            self._issue("nm_latent_pass", ws_tiles, tile0 * 2, nt * 2, _lib.NM_F_TRACE if trace else 0)
+            return
+        self._launch(tile0, 1, nt, _lib.NM_F_EXPORT)
+
+    def _latent_refusal(self) -> str:
+        if os.environ.get("NMHIP_LATENT", "1") == "0":
+            return "NMHIP_LATENT=0"
+        if self.wide:
+            return "general-shape path (a hidden width or latent beyond the fused kernel's tile)"
+        for i, j in enumerate(self.jobs):
+            if not j.latent_ok():
+                s = j.spec
+                return (f"job {i}: nm_latent_pass_ok refuses its shape (kind {s.kind!r}, {s.M} modalities of which "
+                        f"{len(j.kmods)} in the kernel, hidden {list(s.hidden)}, latent {s.latent}, private {s.n_private}, "
+                        f"tc_weight {j.tc_weight})")
+        return "nothing"
+
+    def latent_stats(self):
+        """Per job the column means and population variances of its exported joint mu over the table's rows (the training
+        cohort's latent distribution, utils_vae.py:156-157) -- all jobs of the set in ONE launch of nm_latent_stats.
+        Returns (mean, var), device tensors [n_jobs, Z]."""
+        return latent_stats([j.out_mu[:j.tables[0].N] for j in self._latent_jobs()])
+
+    def latent_scores(self, mean: torch.Tensor, var: torch.Tensor):
+        """Per job separate_latent_deviation and latent_deviation (utils_vae.py:155-161) of its exported joint (mu, logvar)
+        against row k of mean / var [n_jobs, Z] -- all jobs in ONE launch of nm_latent_score.  Returns (zsep, score): lists
+        of device tensors [N_k, Z] / [N_k]."""
+        jobs = self._latent_jobs()
+        return latent_scores([j.out_mu[:j.tables[0].N] for j in jobs], [j.out_logvar[:j.tables[0].N] for j in jobs], mean, var)
+
+    def _latent_jobs(self):
+        if any(j.out_mu is None or j.out_logvar is None for j in self.jobs):
+            raise ValueError("latent exports are off: run JobSet.latent() (or forward() with enable_exports(latent=True)) first")
+        if any(j.spec.latent != self.jobs[0].spec.latent for j in self.jobs):
+            raise ValueError("jobs of one set must have the same latent size")
+        return self.jobs
+
     def head_regression(self, backward: bool, grads: bool = True, adam: bool = False, step: int = 0, tile0: int = 0,
                         n_tiles: int = 1):
         """nm_head_regression on the residual images a preceding forward() / NM_F_EXPORT launch left in job.reg_resid:
@@ -952,6 +1033,53 @@ class JobSet:
         if not bool(ok.all()):
             bad = int((~ok).nonzero()[0])
             raise _lib.NmError(f"non-finite loss in job {bad} of {len(self.jobs)} (step {self.jobs[bad].step})")
+
+
+def _latent_sets(arrays: Sequence[torch.Tensor]):
+    """[N_k, Z] fp32 device arrays -> (their rows concatenated, the offsets table on the device, Z)."""
+    if not arrays:
+        raise ValueError("no set")
+    Z = int(arrays[0].shape[1])
+    if any(a.dim() != 2 or int(a.shape[1]) != Z for a in arrays):
+        raise ValueError("every set must be [rows, Z] with the same Z")
+    dev = arrays[0].device
+    cat = arrays[0].contiguous() if len(arrays) == 1 else torch.cat(list(arrays), 0)
+    offs = np.zeros(len(arrays) + 1, dtype=np.int32)
+    offs[1:] = np.cumsum([int(a.shape[0]) for a in arrays])
+    return cat.float(), torch.from_numpy(offs).to(dev), Z
+
+
+def latent_stats(mus: Sequence[torch.Tensor]):
+    """nm_latent_stats over several cohorts in one launch: per cohort the column means and population variances (np.mean /
+    np.var, axis 0) of its [N_k, Z] fp32 device array.  Returns (mean, var), device tensors [n_sets, Z]; an empty cohort's
+    rows are NaN."""
+    require_gpu(mus[0].device)
+    cat, offs, Z = _latent_sets(mus)
+    mean = torch.empty(len(mus), Z, dtype=torch.float32, device=cat.device)
+    var = torch.empty_like(mean)
+    _lib.check(_lib.load().nm_latent_stats(cat.data_ptr(), offs.data_ptr(), len(mus), Z, Z, mean.data_ptr(), var.data_ptr(),
+                                           _stream_ptr(cat.device)), "nm_latent_stats")
+    return mean, var
+
+
+def latent_scores(mus: Sequence[torch.Tensor], logvars: Sequence[torch.Tensor], mean: torch.Tensor, var: torch.Tensor):
+    """nm_latent_score over several sets in one launch: set k's (mu, logvar) [N_k, Z] against row k of mean / var
+    [n_sets, Z].  Returns (zsep, score): per set (mu - mean) / sqrt(var + exp(logvar)) [N_k, Z] and the row mean of its
+    absolute values [N_k] (separate_latent_deviation / latent_deviation, utils_vae.py:155-161)."""
+    require_gpu(mus[0].device)
+    cat_mu, offs, Z = _latent_sets(mus)
+    cat_lv, _, Zl = _latent_sets(logvars)
+    if Zl != Z or cat_lv.shape != cat_mu.shape or tuple(mean.shape) != (len(mus), Z) or tuple(var.shape) != (len(mus), Z):
+        raise ValueError("mu / logvar must have equal shapes per set, mean / var must be [n_sets, Z]")
+    mean = mean.to(device=cat_mu.device, dtype=torch.float32).contiguous()
+    var = var.to(device=cat_mu.device, dtype=torch.float32).contiguous()
+    zsep = torch.empty_like(cat_mu)
+    score = torch.empty(cat_mu.shape[0], dtype=torch.float32, device=cat_mu.device)
+    _lib.check(_lib.load().nm_latent_score(cat_mu.data_ptr(), cat_lv.data_ptr(), offs.data_ptr(), len(mus), Z, Z, mean.data_ptr(),
+                                           var.data_ptr(), zsep.data_ptr(), score.data_ptr(), _stream_ptr(cat_mu.device)),
+               "nm_latent_score")
+    sizes = [int(m.shape[0]) for m in mus]
+    return list(torch.split(zsep, sizes)), list(torch.split(score, sizes))
 
 
 def adam_step(params: torch.Tensor, grads: torch.Tensor, m: torch.Tensor, v: torch.Tensor, t: int, lr=1e-4,

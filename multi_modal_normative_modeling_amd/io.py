@@ -64,6 +64,26 @@ def write_test_csvs(out_dir, dataset_name: str, covariates: pd.DataFrame, roi_co
     return paths
 
 
+def write_latent_csvs(out_dir, name: str, covariates: pd.DataFrame, mu: np.ndarray, var: np.ndarray, score: np.ndarray,
+                      zsep: np.ndarray) -> Dict[str, Path]:
+    """The latent-space deviation of one fold's test subjects (pred_latent + latent_deviation / separate_latent_deviation,
+    utils_vae.py:155-161), with the metadata columns of write_test_csvs:
+      latent_{name}.csv            participant_id, DIA, AGE, PTGENDER, mu_0.., var_0..   (the joint posterior)
+      latent_deviation_{name}.csv  participant_id, DIA, AGE, PTGENDER, Latent deviation, z_0..z_{Z-1}"""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    cov = covariates[META_COLS].copy().reset_index(drop=True)
+    Z = int(np.asarray(mu).shape[1])
+    paths = {"latent": out_dir / f"latent_{name}.csv", "latent_deviation": out_dir / f"latent_deviation_{name}.csv"}
+    pd.concat([cov, pd.DataFrame(np.asarray(mu), columns=[f"mu_{i}" for i in range(Z)]),
+               pd.DataFrame(np.asarray(var), columns=[f"var_{i}" for i in range(Z)])], axis=1).to_csv(paths["latent"], index=False)
+    dev = cov.copy()
+    dev["Latent deviation"] = np.asarray(score)
+    pd.concat([dev, pd.DataFrame(np.asarray(zsep), columns=[f"z_{i}" for i in range(Z)])], axis=1).to_csv(
+        paths["latent_deviation"], index=False)
+    return paths
+
+
 # ---- the reference's input layout (SURVEY.md appendix A) -----------------------------------------------------------
 # data/<resource>/y.csv: IID, participant_id, DIA, AGE, PTGENDER (+ FI for HCPimage); data/<resource>/<modality>.csv:
 # IID + the ROI columns.  multimodal_kfold_train_cvae_supervised.py:49-50, 84-91 and utils.py:110-168 read them per

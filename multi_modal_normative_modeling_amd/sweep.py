@@ -512,6 +512,61 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
     return [_fold_results(ev, xs, cohort, te, modalities, d, roi_columns) for (ev, xs), (_, te), d in zip(evs, folds, dirs)]
 
 
+def _fold_latent_jobs(job: Job, cohort: prep.SyntheticCohort, train_rows: np.ndarray, test_rows: np.ndarray,
+                      modalities: Sequence[str], combine: str, device):
+    """The two jobs the latent deviation of one fold needs: the trained model on the fold's TRAIN tables as training saw them
+    (scaler fit on the train rows, covariates binned on the train rows) and on its TEST tables as _fold_eval_job builds them
+    (same scaler, covariates re-binned on the test rows), both with the joint-latent exports on."""
+    xs, cov = prep.fold_train_tables(cohort, modalities, train_rows)
+    if job.spec.net_c_dim == 0:
+        cov = np.zeros((len(train_rows), 0), dtype=np.float32)
+    tables = [Table(np.asarray(x, dtype=np.float32), cov, device) for x in xs]
+    trn = Job(job.spec, tables, combine=combine, state=job.state_dict(), seed=job.seed + 31, n_tiles_ws=tables[0].n_tiles,
+              single_bypass=job.single_bypass)
+    trn.set_latent_exports(True)
+    ev, _ = _fold_eval_job(job, cohort, train_rows, test_rows, modalities, combine, device)
+    ev.set_latent_exports(True)
+    return trn, ev
+
+
+def latent_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequence[tuple], modalities: Sequence[str],
+                 combines, device, out_dirs: Optional[Sequence] = None, name: str = "joint") -> List[Dict[str, np.ndarray]]:
+    """The latent-space deviation (latent_deviation / separate_latent_deviation, utils_vae.py:155-161, on what pred_latent
+    returns) for ALL folds of a procedure: jobs[i] is the trained model of fold i, folds[i] its (train_rows, test_rows).
+    One latent launch over the folds' train tables, one over their test tables (JobSet.latent: the encoder-only kernel where
+    the shape allows; folds whose tables differ in their number of 256-row tiles run as one launch per height), then ONE
+    nm_latent_stats launch (every fold's train cohort a set) and ONE nm_latent_score launch (every fold's test subjects
+    against their own fold's statistics).  Returns per fold {"mu", "var" [N, Z], "z" [N, Z], "score" [N]} of the test
+    subjects; out_dirs: one directory per fold for latent_<name>.csv / latent_deviation_<name>.csv."""
+    from . import engine
+    if len(jobs) != len(folds):
+        raise ValueError(f"{len(jobs)} models for {len(folds)} folds")
+    combs = [combines] * len(jobs) if isinstance(combines, str) else list(combines)
+    dirs = [None] * len(jobs) if out_dirs is None else list(out_dirs)
+    pairs = [_fold_latent_jobs(j, cohort, tr, te, modalities, cb, device) for j, (tr, te), cb in zip(jobs, folds, combs)]
+    for side in (0, 1):
+        by_tiles: Dict[tuple, List[int]] = {}
+        for i, pr in enumerate(pairs):
+            by_tiles.setdefault((pr[side].tables[0].n_tiles, bool(pr[side].spec.wide)), []).append(i)
+        for idxs in by_tiles.values():
+            JobSet([pairs[i][side] for i in idxs]).latent()
+    mean, var = engine.latent_stats([trn.out_mu[:len(tr)] for (trn, _), (tr, _) in zip(pairs, folds)])
+    mus = [ev.out_mu[:len(te)] for (_, ev), (_, te) in zip(pairs, folds)]
+    lvs = [ev.out_logvar[:len(te)] for (_, ev), (_, te) in zip(pairs, folds)]
+    zsep, score = engine.latent_scores(mus, lvs, mean, var)
+    torch.cuda.synchronize(device)
+    out = []
+    for mu, lv, z, sc, (_, te), d in zip(mus, lvs, zsep, score, folds, dirs):
+        res = {"mu": mu.cpu().numpy(), "var": lv.exp().cpu().numpy(), "z": z.cpu().numpy(), "score": sc.cpu().numpy()}
+        if d is not None:
+            import pandas as pd
+            meta = pd.DataFrame({"participant_id": cohort.iid[te], "DIA": cohort.dia[te], "AGE": cohort.age[te],
+                                 "PTGENDER": cohort.gender[te]})
+            io.write_latent_csvs(d, name, meta, res["mu"], res["var"], res["score"], res["z"])
+        out.append(res)
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # Entry point: the reference's train script as ONE sharded sweep,
 #     python -m torch.distributed.run --nproc-per-node N -m multi_modal_normative_modeling_amd.sweep -R HCPimage \
@@ -777,6 +832,8 @@ def main_test(argv=None):
     ap.add_argument("-P", "--procedure", dest="procedure", type=str, default="SE-gPoE")
     ap.add_argument("-K", "--n_splits", dest="n_splits", type=int, default=10)
     ap.add_argument("--models-dir", type=str, required=True, help="the --out-dir of the train entry (run with --save-models)")
+    ap.add_argument("--latent", action="store_true",
+                    help="also the latent-space deviation: per fold latent_<P>.csv (joint mu / var) and latent_deviation_<P>.csv")
     _driver_common(ap)
     args = ap.parse_args(argv)
     cohort = _cohort_from_args(args)
@@ -818,6 +875,15 @@ def main_test(argv=None):
             parts = [pd.read_csv(root / f"{k:03d}" / m / f"{kind}_{m}.csv") for k in my]
             if parts:
                 pd.concat(parts, ignore_index=True).to_csv(out_root / m / f"{kind}_{m}.csv", index=False)
+    if args.latent and my:
+        # the folds' train cohorts and test subjects in one latent launch each, one statistics and one score launch
+        lat = latent_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs, name=args.procedure)
+        out_root.mkdir(parents=True, exist_ok=True)
+        for kind in ("latent", "latent_deviation"):
+            parts = [pd.read_csv(root / f"{k:03d}" / f"{kind}_{args.procedure}.csv") for k in my]
+            pd.concat(parts, ignore_index=True).to_csv(out_root / f"{kind}_{args.procedure}.csv", index=False)
+        sc = np.concatenate([r["score"] for r in lat])
+        print(f"[test] {args.procedure} latent: {len(sc)} subjects, mean latent deviation {float(sc.mean()):.5f}", flush=True)
     out = {m: np.concatenate(v) if v else np.empty(0) for m, v in errors.items()}
     for m, v in out.items():
         print(f"[test] {args.procedure} {m}: {len(v)} subjects, mean reconstruction error {float(v.mean()) if len(v) else float('nan'):.5f}", flush=True)
@@ -839,29 +905,40 @@ def main_analysis(argv=None):
     ap.add_argument("-E", "--epochs", dest="epochs", type=int, default=None)
     ap.add_argument("-K", "--n_splits", dest="n_splits", type=int, default=10)
     ap.add_argument("--models-dir", type=str, required=True, help="where the `test` subcommand wrote its per-fold CSVs")
+    ap.add_argument("--score", choices=("reconstruction", "latent"), default="reconstruction",
+                    help="the per-subject score: the modality-averaged reconstruction error, or the `Latent deviation` column "
+                         "of latent_deviation_<P>.csv (`test --latent`); latent writes group_analysis_latent.csv")
     args = ap.parse_args(argv)
     mods, _ = workload.procedure_modalities(args.procedure, args.dataset_resourse)
     root = Path(args.models_dir) / args.dataset_resourse / args.procedure
     hc = prep.HC_LABEL.get(args.dataset_resourse, 1)
     scores, positive, folds = [], [], []
     for k in range(args.n_splits):
-        files = [root / f"{k:03d}" / m / f"reconstruction_error_{m}.csv" for m in mods]
+        if args.score == "latent":
+            files = [root / f"{k:03d}" / f"latent_deviation_{args.procedure}.csv"]
+        else:
+            files = [root / f"{k:03d}" / m / f"reconstruction_error_{m}.csv" for m in mods]
         if not all(f.exists() for f in files):
             continue
         dfs = [pd.read_csv(f) for f in files]
-        err = sum(d["Reconstruction error"].to_numpy(dtype=np.float64) for d in dfs) / len(dfs)
+        if args.score == "latent":
+            err = dfs[0]["Latent deviation"].to_numpy(dtype=np.float64)
+        else:
+            err = sum(d["Reconstruction error"].to_numpy(dtype=np.float64) for d in dfs) / len(dfs)
         dia = dfs[0]["DIA"].to_numpy()
         # (files written from a prep.Cohort carry DIA in the cohort's convention 1 = healthy; raw tables the resource's label)
         healthy = (dia == 1) if set(np.unique(dia)) <= {0, 1} else (dia == hc)
         scores.append(torch.as_tensor(err, dtype=torch.float32))
         positive.append(torch.as_tensor(~healthy, dtype=torch.int32))
         folds.append(k)
+    if not folds and args.score == "latent":
+        raise FileNotFoundError(f"no latent_deviation_{args.procedure}.csv under {root}/<fold>/ -- run the `test` subcommand with --latent first")
     if not folds:
         raise FileNotFoundError(f"no reconstruction_error_*.csv of {mods} under {root}/<fold>/ -- run the `test` subcommand first")
     table = metrics.posthoc_metrics(scores, positive).cpu()
     df = pd.DataFrame(table.numpy(), columns=list(metrics.POSTHOC_COLUMNS))
     df.insert(0, "fold", folds)
-    df.to_csv(root / "group_analysis.csv", index=False)
+    df.to_csv(root / ("group_analysis_latent.csv" if args.score == "latent" else "group_analysis.csv"), index=False)
     for _, r in df.iterrows():
         print(f"[analysis] fold {int(r['fold'])}: AUC {r['roc_auc']:.4f}  accuracy {r['accuracy']:.4f}  sensitivity {r['recall']:.4f}  "
               f"specificity {r['specificity']:.4f}  significance ratio {r['significance_ratio']:.3f}", flush=True)

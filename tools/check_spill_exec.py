@@ -66,6 +66,8 @@ LIMITS = {
     "nm_devpass_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 64, "vgpr_count": 128},
     # (the build shows 49 SGPR spills -- the loops over experts and decoders keep more scalars alive -- plus the margin of 64 above)
     "nm_devpass_multi_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 112, "vgpr_count": 128},
+    # (the encoder half of the kernel above: the build shows 76 VGPRs and 30 SGPR spills -- plus the same margin of 64)
+    "nm_latent_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 94, "vgpr_count": 128},
     "nm_rs_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 540},
     "nm_wide_step_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 400},
     # (both instantiations: one workgroup per model / one per decoder, nm_train_steps_head_split)
