@@ -17,7 +17,8 @@ the gradient's own comparison with the oracle this closes the chain: each single
   b. 8 isolated steps on every training form -- whole, scalar_tr, split, rowsplit 2 / 4 with 0, 3 and the default number of
      helpers, the general-shape path -- on six goldens (a fresh batch per step), six fuzz shapes over a 531-row table
      (walking batch index, ragged 19-row tail), two general-shape fuzz shapes, the full size 3 x 379 / [110, 110] / B = 256,
-     and mvtCAE from the zoo.  A mixed set (one- and three-modality model in one launch) runs the mixed row-split entry:
+     mvtCAE from the zoo, and 3 steps on the general-shape path at its limits (W1, W3, W4 of tests/grad_check.py: width
+     4096 with latent 128, the block boundaries, eight layers).  A mixed set (one- and three-modality model in one launch) runs the mixed row-split entry:
      grads() drives it whenever the set's modality counts differ.
   c. the flat-buffer invariants above, after those 8 steps.
   d. optimizer step 1001.. (job.t = 1000) and the cyclic learning-rate table: the checker is given t and the step's rate.
@@ -256,10 +257,27 @@ def test_fuzz_shapes_walking_batches(seed, form):
 
 @pytest.mark.parametrize("seed", [0, 1])
 def test_general_shape_path(seed):
+    """Two shapes of the general-shape fuzz over a 531-row table."""
     dims, Z, combine, _, hidden, c_dim, non_linear = _draw_wide(seed)
     job = table_job(dims, hidden, Z, c_dim, combine, non_linear, 531, seed)
     assert job.spec.wide
     isolated_steps(nm.JobSet([job]), "whole", f"wide {seed} {dims} {hidden} Z={Z} {combine}", label="general")
+
+
+@pytest.mark.parametrize("cid", ["W1", "W3", "W4"])
+def test_general_shape_path_at_limits(cid):
+    """The cases of tests/test_gpu_grad_exact.py at the path's limits (W1: width 4096 and latent 128; W3: the block
+    boundaries, latent 65; W4: eight layers): there the update is pinned to the very gradient that module pins to the
+    oracle.  Three steps, not eight: a case carries ONE batch of draws, so every step sees the same data and only the Adam
+    state moves on -- first step (zero moments), second and third (bias corrections, moments in use) are the distinct
+    states; and the fp64 restatement of W1's flat buffers takes its time per step.  (W2 is left out: the restatement of
+    its 2 x 4096 x 4096 buffers is slow.)"""
+    from tests import grad_check as G
+    job = G.data(cid).job(True, DEV)
+    job.grads.zero_()
+    assert job.spec.wide
+    isolated_steps(nm.JobSet([job]), "whole", f"wide {cid}", n_steps=3, label="general")
+    G.clear_cache()
 
 
 @pytest.mark.parametrize("form", forms_for(3))
