@@ -470,6 +470,22 @@ int nm_latent_stats(const float* mu, const int32_t* offsets, int n_sets, int Z, 
 int nm_latent_score(const float* mu, const float* logvar, const int32_t* offsets, int n_sets, int Z, int pitch,
                     const float* mean, const float* var, float* zsep_out, float* score_out, void* stream);
 
+/* ROI-wise group effect sizes: cliff_delta(X, Y) of utils.py:97-109 for every column of a table at once.  Set s of the
+ * device array sets_dev is a matrix x[rows][pitch] (fp32, pitch >= D; the out_sqerr export of an evaluation job, read where
+ * it lies) with one group word per row: 1 = X (the patients), 0 = Y (the controls), any other value leaves the row out.
+ * max_rows (1..NM_METRICS_MAX_N) is the host's bound on every set's rows.  out is [n_sets][D][NM_METRICS_STRIDE] fp64, per
+ * (set, column) = {cliff_delta, auc, n_more, n_less, n_x, n_y, mean_x, mean_y}:
+ *   n_more / n_less  pairs (i in X, j in Y) with x_i > y_j / x_i < y_j; a NaN compares false both ways, its pairs are ties
+ *   cliff_delta      (n_more - n_less) / (n_x n_y)            auc  (2 n_more + ties) / (2 n_x n_y) = (delta + 1) / 2
+ *   mean_x / mean_y  fp64 sums in a fixed order over the group size (NaN propagates, as in np.mean)
+ * An empty group: zero counts, NaN for delta, auc and that mean.  Every element is written on every call, without atomics:
+ * two runs give the same bits.  A set with rows > max_rows, rows < 0, pitch < D or (rows > 0) a null pointer gets NaN rows;
+ * nothing of it is read.  Status NM_E_NULL: sets_dev or out missing; NM_E_METRICS: n_sets < 1, D < 1, max_rows outside
+ * 1..NM_METRICS_MAX_N (or more than 2^31 - 1 workgroups).  NM_ROI_Y_CHUNK: the Y rows the kernel stages at a time. */
+#define NM_ROI_Y_CHUNK 128
+typedef struct { const float* x; const int32_t* group; int32_t rows; int32_t pitch; } nm_roi_set_t;
+int nm_roi_effect(const nm_roi_set_t* sets_dev, int n_sets, int D, int max_rows, double* out, void* stream);
+
 /* The expert-fusion operators the reference exposes as public methods, as forward-only launches (elementwise over
  * [M][n] fp32 device tensors; csrc/nm_fusion.hip):
  *   cVAE_multimodal.combine_latent(mus, variances, combine)                      cVAE.py:1144-1164   (also :2292-2307)

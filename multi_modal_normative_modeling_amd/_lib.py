@@ -51,6 +51,8 @@ NM_SYNC_ERR_TIMEOUT = 1
 NM_SYNC_ERR_SHAPE = 2
 NM_METRICS_MAX_N = 8192
 NM_METRICS_STRIDE = 8
+# nm_roi_effect: the Y rows its kernel stages in LDS at a time (tests put group sizes around it)
+NM_ROI_Y_CHUNK = 128
 
 # status codes (nmhip.h; nm_status_string gives the text)
 NM_OK = 0
@@ -127,6 +129,11 @@ class NmJob(C.Structure):
     ]
 
 
+class NmRoiSet(C.Structure):
+    """nm_roi_set_t: one matrix of nm_roi_effect's pointer table."""
+    _fields_ = [("x", C.c_void_p), ("group", C.c_void_p), ("rows", C.c_int32), ("pitch", C.c_int32)]
+
+
 class NmError(RuntimeError):
     pass
 
@@ -194,6 +201,7 @@ def load():
     lib.nm_train_steps_head_split.restype = i32
     lib.nm_posthoc_metrics.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
     lib.nm_confusion_metrics.argtypes = [vp, vp, vp, i32, vp, vp]
+    lib.nm_roi_effect.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.nm_adam_step.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, i64, vp]
     lib.nm_pack_table.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp]
     lib.nm_prep_scaler_fit.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp]
@@ -221,6 +229,7 @@ EXPORTED_SYMBOLS = [
     "nm_launch_rowsplit", "nm_rowsplit_ok", "nm_sync_reset", "nm_trace_read_rs", "nm_devpass", "nm_devpass_ok", "nm_trace_read_dv", "nm_workspace_offset",
     "nm_launch_rowsplit_mixed", "nm_rowsplit_groups", "nm_devpass_multi", "nm_devpass_multi_ok",
     "nm_latent_pass", "nm_latent_pass_ok", "nm_latent_stats", "nm_latent_score",
+    "nm_roi_effect",
 ]
 
 

@@ -9,6 +9,8 @@
 //   nm_latent_stats       exported joint latent means of a cohort -> column means and population variances
 //   nm_latent_score       ... and a cohort's (mu, logvar) against them -> z-score per latent dimension, its mean |z|
 //                         (latent_deviation / separate_latent_deviation, utils_vae.py:155-161)
+//   nm_roi_effect         ROI-wise squared errors of two groups -> Cliff's delta, ROC-AUC, pair counts, group means per ROI
+//                         (cliff_delta, utils.py:97-109, once per column; further down in this file)
 //
 // One workgroup per score set (a (fold, procedure) cell); sets are segments of one concatenated array.  The
 // whole set lives in LDS: order-preserving 64-bit keys (score, label) are bitonic-sorted descending, label
@@ -311,6 +313,133 @@ __global__ __launch_bounds__(MT) void latent_score_kernel(const float* __restric
   }
 }
 
+// ---- ROI-wise group effect sizes (cliff_delta, utils.py:97-109, for every column of a table at once) --------------------
+// nm_roi_effect: one workgroup per (set, 64-column tile), a lane per column, so a wave reads 64 consecutive floats of a row.
+// The group words are read first: the set's X rows (group 1) are listed from the front of an LDS index array, its Y rows
+// (group 0) from its back, both in row order; every other row is on neither list.  The Y rows then pass through LDS in
+// chunks of NM_ROI_Y_CHUNK rows ([row][column]: consecutive lanes on consecutive banks); the four waves take every fourth
+// X row, ROI_XR of them at a time in registers, so one LDS read serves ROI_XR pairs and each pair is two compares whose
+// results are added to int32 counters (a thread sees at most 8192 / 4 x 8192 pairs).  A NaN compares false both ways: its
+// pairs are ties.  Group sums in fp64, per thread in the order of its rows; counters and sums of the four waves are merged
+// through LDS in wave order -- no atomics, the same bits on every run -- and the two quotients are single IEEE divisions
+// of exactly represented integers.
+constexpr int ROI_TILE = 64;                      // columns per workgroup
+constexpr int ROI_WAVES = MT / 64;
+constexpr int ROI_XR = 8;                         // X rows a thread holds while a Y chunk streams past
+constexpr int ROI_YCH = NM_ROI_Y_CHUNK;
+static_assert(sizeof(nm_roi_set_t) == 24, "nm_roi_set_t is mirrored by _lib.NmRoiSet");
+static_assert(ROI_YCH * ROI_TILE * 4 >= ROI_WAVES * ROI_TILE * (4 + 4 + 8 + 8), "the merge arrays reuse the Y chunk");
+
+__global__ __launch_bounds__(MT) void roi_effect_kernel(const nm_roi_set_t* __restrict__ sets, int D, int max_rows, int tiles,
+                                                        double* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) float ys[ROI_YCH * ROI_TILE];      // the Y chunk; at the end the merge arrays
+  __shared__ uint16_t idx[MAXN];                                             // X rows from [0] up, Y rows from [MAXN - 1] down
+  __shared__ int32_t part[2][MT];
+
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int s = blockIdx.x / tiles, tile = blockIdx.x - s * tiles;
+  const nm_roi_set_t S = sets[s];
+  const int col = tile * ROI_TILE + lane;
+  const bool cv = col < D;
+  double* o = out + ((int64_t)s * D + col) * NM_METRICS_STRIDE;
+  const double qnan = __longlong_as_double(0x7FF8000000000000ll);
+  const int rows = S.rows, pitch = S.pitch;
+  if (rows < 0 || rows > max_rows || pitch < D || (rows > 0 && (!S.x || !S.group))) {
+    if (w == 0 && cv)
+      for (int k = 0; k < NM_METRICS_STRIDE; ++k) o[k] = qnan;
+    return;
+  }
+  // the two row lists: a thread counts its stretch of rows, takes its place from the counts before it, writes its rows
+  const int per = (rows + MT - 1) / MT;
+  const int lo = min(t * per, rows), hi = min(lo + per, rows);
+  {
+    int cx = 0, cy = 0;
+    for (int r = lo; r < hi; ++r) { const int32_t g = S.group[r]; cx += (g == 1); cy += (g == 0); }
+    part[0][t] = cx; part[1][t] = cy;
+  }
+  __syncthreads();
+  int nx = 0, ny = 0;
+  {
+    int bx = 0, by = 0;
+    for (int q = 0; q < MT; ++q) {
+      const int cx = part[0][q], cy = part[1][q];
+      if (q < t) { bx += cx; by += cy; }
+      nx += cx; ny += cy;
+    }
+    for (int r = lo; r < hi; ++r) {
+      const int32_t g = S.group[r];
+      if (g == 1) idx[bx++] = (uint16_t)r;
+      else if (g == 0) idx[MAXN - 1 - by++] = (uint16_t)r;
+    }
+  }
+  const float* xc = S.x + col;                     // (read only where cv: beyond D lies padding, or the next row)
+  int32_t more[ROI_XR], less[ROI_XR];
+#pragma unroll
+  for (int k = 0; k < ROI_XR; ++k) { more[k] = 0; less[k] = 0; }
+  double sumx = 0.0, sumy = 0.0;
+  for (int y0 = 0; y0 == 0 || y0 < ny; y0 += ROI_YCH) {          // (once with an empty chunk when there is no Y row: X's sums)
+    const int yn = min(ROI_YCH, ny - y0);
+    __syncthreads();                               // the lists are written / the chunk before this one is used up
+    for (int r = w; r < yn; r += ROI_WAVES) {
+      const float v = cv ? xc[(int64_t)idx[MAXN - 1 - (y0 + r)] * pitch] : 0.f;
+      ys[r * ROI_TILE + lane] = v;
+      sumy += (double)v;
+    }
+    __syncthreads();
+    for (int p0 = w; p0 < nx; p0 += ROI_WAVES * ROI_XR) {
+      float xv[ROI_XR];
+#pragma unroll
+      for (int k = 0; k < ROI_XR; ++k) {
+        const int p = p0 + ROI_WAVES * k;
+        xv[k] = (p < nx && cv) ? xc[(int64_t)idx[min(p, nx - 1)] * pitch] : __int_as_float(0x7FC00000);   // NaN: counts nothing
+      }
+      if (y0 == 0) {
+#pragma unroll
+        for (int k = 0; k < ROI_XR; ++k)
+          if (p0 + ROI_WAVES * k < nx) sumx += (double)xv[k];
+      }
+#pragma unroll 4
+      for (int j = 0; j < yn; ++j) {
+        const float y = ys[j * ROI_TILE + lane];
+#pragma unroll
+        for (int k = 0; k < ROI_XR; ++k) {
+          more[k] += (xv[k] > y) ? 1 : 0;
+          less[k] += (xv[k] < y) ? 1 : 0;
+        }
+      }
+    }
+  }
+  __syncthreads();                                 // the last chunk is used up: its place takes the waves' partial results
+  int32_t* pm = reinterpret_cast<int32_t*>(ys);                         // [ROI_WAVES][ROI_TILE] each
+  int32_t* pl = pm + ROI_WAVES * ROI_TILE;
+  double* px = reinterpret_cast<double*>(pl + ROI_WAVES * ROI_TILE);
+  double* py = px + ROI_WAVES * ROI_TILE;
+  {
+    int32_t m = 0, l = 0;
+#pragma unroll
+    for (int k = 0; k < ROI_XR; ++k) { m += more[k]; l += less[k]; }
+    pm[t] = m; pl[t] = l; px[t] = sumx; py[t] = sumy;
+  }
+  __syncthreads();
+  if (w == 0 && cv) {
+    long long M = 0, L = 0;
+    double sx = 0.0, sy = 0.0;
+    for (int q = 0; q < ROI_WAVES; ++q) {
+      M += pm[q * ROI_TILE + lane]; L += pl[q * ROI_TILE + lane];
+      sx += px[q * ROI_TILE + lane]; sy += py[q * ROI_TILE + lane];
+    }
+    const long long pairs = (long long)nx * ny, ties = pairs - M - L;
+    o[0] = pairs ? (double)(M - L) / (double)pairs : qnan;              // cliff_delta
+    o[1] = pairs ? (double)(2 * M + ties) / (double)(2 * pairs) : qnan; // ROC-AUC of the column as a patient score
+    o[2] = (double)M;
+    o[3] = (double)L;
+    o[4] = (double)nx;
+    o[5] = (double)ny;
+    o[6] = nx ? sx / (double)nx : qnan;
+    o[7] = ny ? sy / (double)ny : qnan;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -344,6 +473,14 @@ int nm_latent_score(const float* mu, const float* logvar, const int32_t* offsets
   if (n_sets < 1 || pitch < Z) return NM_E_METRICS;
   return launch_kernel(latent_score_kernel, dim3(n_sets), dim3(MT), 0, stream, mu, logvar, offsets, Z, pitch, mean, var, zsep_out,
                        score_out);
+}
+
+int nm_roi_effect(const nm_roi_set_t* sets_dev, int n_sets, int D, int max_rows, double* out, void* stream) {
+  if (!sets_dev || !out) return NM_E_NULL;
+  if (n_sets < 1 || D < 1 || max_rows < 1 || max_rows > MAXN) return NM_E_METRICS;
+  const int tiles = (D + ROI_TILE - 1) / ROI_TILE;
+  if ((int64_t)n_sets * tiles > 0x7FFFFFFFll) return NM_E_METRICS;
+  return launch_kernel(roi_effect_kernel, dim3(n_sets * tiles), dim3(MT), 0, stream, sets_dev, D, max_rows, tiles, out);
 }
 
 }  // extern "C"

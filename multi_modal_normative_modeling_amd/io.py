@@ -84,6 +84,22 @@ def write_latent_csvs(out_dir, name: str, covariates: pd.DataFrame, mu: np.ndarr
     return paths
 
 
+def write_roi_effect_csv(out_dir, dataset_name: str, roi_columns: Sequence[str], table: np.ndarray) -> Path:
+    """roi_effect_{name}.csv: one row per ROI -- its column name, then metrics.ROI_EFFECT_COLUMNS (Cliff's delta of patients
+    against controls on the ROI's squared error, its ROC-AUC, the pair counts, group sizes and group means)."""
+    from .metrics import ROI_EFFECT_COLUMNS
+    table = np.asarray(table, dtype=np.float64)
+    if table.shape != (len(roi_columns), len(ROI_EFFECT_COLUMNS)):
+        raise ValueError(f"a [{len(roi_columns)}, {len(ROI_EFFECT_COLUMNS)}] table is needed, got {table.shape}")
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    df = pd.DataFrame(table, columns=list(ROI_EFFECT_COLUMNS))
+    df.insert(0, "ROI", list(roi_columns))
+    path = out_dir / f"roi_effect_{dataset_name}.csv"
+    df.to_csv(path, index=False)
+    return path
+
+
 # ---- the reference's input layout (SURVEY.md appendix A) -----------------------------------------------------------
 # data/<resource>/y.csv: IID, participant_id, DIA, AGE, PTGENDER (+ FI for HCPimage); data/<resource>/<modality>.csv:
 # IID + the ROI columns.  multimodal_kfold_train_cvae_supervised.py:49-50, 84-91 and utils.py:110-168 read them per

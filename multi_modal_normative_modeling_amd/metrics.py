@@ -5,11 +5,16 @@ multimodal_kfold_cvae_group_analysis_1x1.py:105-157 for many score sets at once 
 `confusion_metrics` = evaluate() of multimodal_kfold_cvae_nmpmcont.py:29-70 from hard predictions.
 Scores stay on the GPU (they are the per-subject mean deviations the forward pass exported); only the
 [n_sets, 8] fp64 result table comes back.
+`roi_effect` = cliff_delta of utils.py:97-109 for every ROI column of many tables at once (one workgroup per table and
+64 columns), on the ROI-wise squared errors where the evaluation jobs exported them; `cliff_delta` is the reference's
+signature on top of it.
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -17,6 +22,7 @@ from .engine import _stream_ptr, require_gpu
 
 POSTHOC_COLUMNS = ("roc_auc", "threshold", "accuracy", "recall", "specificity", "significance_ratio", "n_pos", "n_neg")
 CONFUSION_COLUMNS = ("accuracy", "auroc", "sensitivity", "specificity", "f1_score", "precision", "n_pos", "n_neg")
+ROI_EFFECT_COLUMNS = ("cliff_delta", "auc", "n_more", "n_less", "n_x", "n_y", "mean_x", "mean_y")
 
 
 def _segments(parts: Sequence[torch.Tensor], device, dtype):
@@ -67,3 +73,69 @@ def confusion_metrics(pred: Sequence[torch.Tensor], labels: Sequence[torch.Tenso
     _lib.check(_lib.load().nm_confusion_metrics(p.data_ptr(), l.data_ptr(), off.data_ptr(), len(sizes), out.data_ptr(),
                                                  _stream_ptr(dev)), "nm_confusion_metrics")
     return out
+
+
+def _roi_table(mats: Sequence[torch.Tensor], groups: Sequence[torch.Tensor]):
+    """nm_roi_effect's pointer table on the host: every matrix where it lies (data_ptr of the view, its row stride as pitch)."""
+    table = (_lib.NmRoiSet * len(mats))()
+    for k, (m, g) in enumerate(zip(mats, groups)):
+        rows = int(m.shape[0])
+        table[k].x, table[k].group = (m.data_ptr(), g.data_ptr()) if rows else (None, None)
+        table[k].rows, table[k].pitch = rows, (int(m.stride(0)) if rows > 1 else int(m.shape[1]))
+    return table
+
+
+def roi_effect(mats: Sequence[torch.Tensor], groups: Sequence, device=None) -> torch.Tensor:
+    """[n_sets, D, 8] fp64 on the device, per (set, ROI column): cliff_delta, auc, n_more, n_less, n_x, n_y, mean_x, mean_y
+    (ROI_EFFECT_COLUMNS; include/nmhip.h has the definitions).  mats[k]: a [n_k, D] fp32 device tensor of any row stride
+    and unit column stride -- a view such as job.out_sqerr[m][:n] is read where it lies; groups[k]: n_k entries, 1 = X
+    (the patients), 0 = Y (the controls), any other value leaves the row out.  One launch for all sets."""
+    if len(mats) == 0:
+        raise ValueError("no ROI tables")
+    if len(mats) != len(groups):
+        raise ValueError("mats and groups must have the same number of sets")
+    D = None
+    for k, m in enumerate(mats):
+        if not isinstance(m, torch.Tensor) or m.dim() != 2 or m.dtype != torch.float32:
+            raise ValueError(f"set {k}: a 2-D float32 tensor is needed")
+        if D is None:
+            D = int(m.shape[1])
+        if int(m.shape[1]) != D or D < 1:
+            raise ValueError(f"set {k}: {int(m.shape[1])} columns, every set needs the same number (>= 1; set 0 has {D})")
+        if m.shape[0] > _lib.NM_METRICS_MAX_N:
+            raise ValueError(f"set {k}: at most {_lib.NM_METRICS_MAX_N} rows per set, got {int(m.shape[0])}")
+        if m.shape[0] > 0 and m.stride(1) != 1:
+            raise ValueError(f"set {k}: columns must be contiguous (stride(1) == 1), got {m.stride(1)}")
+        if m.shape[0] > 1 and m.stride(0) < D:
+            raise ValueError(f"set {k}: row stride {m.stride(0)} below the {D} columns")
+        if int(torch.as_tensor(groups[k]).numel()) != int(m.shape[0]):
+            raise ValueError(f"set {k}: one group entry per row is needed")
+    dev = require_gpu(device if device is not None else (mats[0].device if mats[0].is_cuda else None))
+    if dev.index is None:
+        dev = torch.device(dev.type, torch.cuda.current_device())
+    for k, m in enumerate(mats):
+        if m.device != dev:
+            raise ValueError(f"set {k} is on {m.device}, not on {dev}: the tables are read where they lie")
+    grp = [torch.as_tensor(g).reshape(-1).to(device=dev, dtype=torch.int32).contiguous() for g in groups]
+    sets = torch.frombuffer(bytearray(bytes(_roi_table(mats, grp))), dtype=torch.uint8).to(dev)
+    out = torch.empty(len(mats), D, _lib.NM_METRICS_STRIDE, dtype=torch.float64, device=dev)
+    _lib.check(_lib.load().nm_roi_effect(sets.data_ptr(), len(mats), D, max(max(int(m.shape[0]) for m in mats), 1),
+                                          out.data_ptr(), _stream_ptr(dev)), "nm_roi_effect")
+    return out
+
+
+def cliff_delta(X, Y, device=None):
+    """cliff_delta(X, Y) of utils.py:97-109 on the device: 1-D inputs give a float, [n, D] inputs a [D] numpy array (one
+    delta per column).  len(X) + len(Y) <= NM_METRICS_MAX_N."""
+    x = torch.as_tensor(np.asarray(X.detach().cpu() if isinstance(X, torch.Tensor) else X, dtype=np.float32))
+    y = torch.as_tensor(np.asarray(Y.detach().cpu() if isinstance(Y, torch.Tensor) else Y, dtype=np.float32))
+    if x.dim() != y.dim() or x.dim() not in (1, 2) or (x.dim() == 2 and x.shape[1] != y.shape[1]):
+        raise ValueError(f"X and Y must both be 1-D, or 2-D with the same columns; got {tuple(x.shape)} and {tuple(y.shape)}")
+    flat = x.dim() == 1
+    both = torch.cat([x.reshape(len(x), -1), y.reshape(len(y), -1)])
+    if both.shape[0] > _lib.NM_METRICS_MAX_N:
+        raise ValueError(f"at most {_lib.NM_METRICS_MAX_N} observations in X and Y together, got {both.shape[0]}")
+    dev = require_gpu(device)
+    group = torch.cat([torch.ones(len(x), dtype=torch.int32), torch.zeros(len(y), dtype=torch.int32)])
+    delta = roi_effect([both.to(dev)], [group], device=dev)[0, :, 0].cpu().numpy()
+    return float(delta[0]) if flat else delta

@@ -437,10 +437,11 @@ def load_model(fold_dir, tables: Sequence[Table], device, seed: int = 0) -> Job:
 
 
 def _fold_eval_job(job: Job, cohort: prep.SyntheticCohort, train_rows: np.ndarray, test_rows: np.ndarray,
-                   modalities: Sequence[str], combine: str, device):
+                   modalities: Sequence[str], combine: str, device, sqerr: bool = False):
     """The evaluation job of one fold (test_fold / test_folds): per modality a RobustScaler fit on the fold's train rows and
     applied to its test rows, covariates re-binned on the TEST rows, the trained model on those tables with the
-    reconstruction and per-subject deviation exports.  Returns (job, scaled test tables on the host)."""
+    reconstruction and per-subject deviation exports (sqerr: the ROI-wise squared errors too, what metrics.roi_effect
+    reads).  Returns (job, scaled test tables on the host)."""
     xs = []
     for m in modalities:
         src = prep.source_table(cohort, m)
@@ -452,7 +453,7 @@ def _fold_eval_job(job: Job, cohort: prep.SyntheticCohort, train_rows: np.ndarra
     tables = [Table(x, cov, device) for x in xs]
     ev = Job(job.spec, tables, combine=combine, state=job.state_dict(), seed=job.seed + 31, n_tiles_ws=tables[0].n_tiles,
              single_bypass=job.single_bypass)
-    ev.enable_exports(loc=True, sqerr=False, rowdev=True, latent=False)
+    ev.enable_exports(loc=True, sqerr=sqerr, rowdev=True, latent=False)
     return ev, xs
 
 
@@ -469,7 +470,7 @@ def _fold_results(ev: Job, xs, cohort: prep.SyntheticCohort, test_rows: np.ndarr
             import pandas as pd
             meta = pd.DataFrame({"participant_id": cohort.iid[test_rows], "DIA": cohort.dia[test_rows],
                                  "AGE": cohort.age[test_rows], "PTGENDER": cohort.gender[test_rows]})
-            cols = list(roi_columns[m]) if roi_columns and m in roi_columns else [f"{m}_{k}" for k in range(xs[i].shape[1])]
+            cols = _roi_columns(roi_columns, m, xs[i].shape[1])
             io.write_test_csvs(Path(out_dir) / m, m, meta, cols, xs[i], x_hat)
     return errors
 
@@ -489,27 +490,79 @@ def test_fold(job: Job, cohort: prep.SyntheticCohort, train_rows: np.ndarray, te
     return _fold_results(ev, xs, cohort, test_rows, modalities, out_dir, roi_columns)
 
 
+def roi_groups(dia: np.ndarray, disease_label=None) -> np.ndarray:
+    """The group words of metrics.roi_effect from diagnoses in the cohort's convention (1 = healthy control): controls 0 (Y),
+    every other label -- or, with disease_label given, only that one -- 1 (X, the patients), the rest -1 (left out)."""
+    dia = np.asarray(dia)
+    patient = (dia != 1) if disease_label is None else (dia == disease_label)
+    return np.where(dia == 1, 0, np.where(patient, 1, -1)).astype(np.int32)
+
+
+def _roi_effect_sets(mats: Sequence[torch.Tensor], groups: Sequence[np.ndarray], device) -> List[torch.Tensor]:
+    """metrics.roi_effect for tables of any widths: one launch per distinct width (an SE procedure's modalities share one, a
+    UCA procedure adds the early-fusion table's), every table read where it lies.  Returns one [D_k, 8] device tensor per
+    table, in the order given."""
+    by_width: Dict[int, List[int]] = {}
+    for j, x in enumerate(mats):
+        by_width.setdefault(int(x.shape[1]), []).append(j)
+    out: List[Optional[torch.Tensor]] = [None] * len(mats)
+    for idxs in by_width.values():
+        tab = metrics.roi_effect([mats[j] for j in idxs], [groups[j] for j in idxs], device=device)
+        for a, j in enumerate(idxs):
+            out[j] = tab[a]
+    return out
+
+
+def _roi_columns(roi_columns, m: str, d: int):
+    return list(roi_columns[m]) if roi_columns and m in roi_columns else [f"{m}_{k}" for k in range(d)]
+
+
 def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequence[tuple], modalities: Sequence[str],
                combines, device, out_dirs: Optional[Sequence] = None,
-               roi_columns: Optional[Dict[str, Sequence[str]]] = None) -> List[Dict[str, np.ndarray]]:
+               roi_columns: Optional[Dict[str, Sequence[str]]] = None, roi_effect: bool = False,
+               disease_label=None) -> List[Dict[str, np.ndarray]]:
     """test_fold for ALL folds of a procedure as one launch: jobs[i] is the trained model of fold i, folds[i] its
     (train_rows, test_rows); one evaluation job per fold, each on its own test tables (seed, scaler and covariates per fold
     exactly as test_fold), all in ONE JobSet -- a fold's ~N / K test rows are a single workgroup, K of them in a row leave
     the chip idle.  `combines`: one fusion name for all folds or one per fold; out_dirs: one directory per fold (or None).
     Folds whose test tables differ in their number of 256-row tiles run as one launch per height (the folds of a K-fold
-    split differ by at most one row).  Returns test_fold's result per fold; bit-identical to the fold-by-fold form."""
+    split differ by at most one row).  Returns test_fold's result per fold; bit-identical to the fold-by-fold form.
+
+    roi_effect: the evaluation jobs also export their ROI-wise squared errors, and after the forward launches ONE
+    metrics.roi_effect launch over all folds x modalities (one per table width, where the modalities' widths differ) gives
+    every ROI's Cliff's delta / ROC-AUC of patients against controls (roi_groups on cohort.dia; disease_label picks one
+    diagnosis as the patients), one more the same on the pooled set per modality (all folds' test rows, concatenated on the
+    device: the all-folds tables of the test script, :157-178; at most NM_METRICS_MAX_N subjects in all).
+    Each fold's dict gains "roi_effect": {modality: [D, 8]} (metrics.ROI_EFFECT_COLUMNS) and "roi_effect_pooled": the pooled
+    tables (the same dict in every fold's result); with out_dirs, roi_effect_<m>.csv next to the five kinds."""
     if len(jobs) != len(folds):
         raise ValueError(f"{len(jobs)} models for {len(folds)} folds")
     combs = [combines] * len(jobs) if isinstance(combines, str) else list(combines)
     dirs = [None] * len(jobs) if out_dirs is None else list(out_dirs)
-    evs = [_fold_eval_job(j, cohort, tr, te, modalities, cb, device) for j, (tr, te), cb in zip(jobs, folds, combs)]
+    evs = [_fold_eval_job(j, cohort, tr, te, modalities, cb, device, sqerr=roi_effect)
+           for j, (tr, te), cb in zip(jobs, folds, combs)]
     by_tiles: Dict[tuple, List[int]] = {}
     for i, (ev, _) in enumerate(evs):
         by_tiles.setdefault((ev.tables[0].n_tiles, bool(ev.spec.wide)), []).append(i)
     for idxs in by_tiles.values():
         JobSet([evs[i][0] for i in idxs]).forward(loss=False)
+    if roi_effect:
+        nm_ = len(modalities)
+        grp = [roi_groups(cohort.dia[te], disease_label) for _, te in folds]
+        mats = [ev.out_sqerr[i][:len(te)] for (ev, _), (_, te) in zip(evs, folds) for i in range(nm_)]
+        per_fold = _roi_effect_sets(mats, [g for g in grp for _ in range(nm_)], device)
+        pooled = _roi_effect_sets([torch.cat(mats[i::nm_]) for i in range(nm_)], [np.concatenate(grp)] * nm_, device)
     torch.cuda.synchronize(device)
-    return [_fold_results(ev, xs, cohort, te, modalities, d, roi_columns) for (ev, xs), (_, te), d in zip(evs, folds, dirs)]
+    out = [_fold_results(ev, xs, cohort, te, modalities, d, roi_columns) for (ev, xs), (_, te), d in zip(evs, folds, dirs)]
+    if roi_effect:
+        pooled = {m: pooled[i].cpu().numpy() for i, m in enumerate(modalities)}
+        for f, (res, d) in enumerate(zip(out, dirs)):
+            res["roi_effect"] = {m: per_fold[f * nm_ + i].cpu().numpy() for i, m in enumerate(modalities)}
+            res["roi_effect_pooled"] = pooled
+            if d is not None:
+                for m, tab in res["roi_effect"].items():
+                    io.write_roi_effect_csv(Path(d) / m, m, _roi_columns(roi_columns, m, tab.shape[0]), tab)
+    return out
 
 
 def _fold_latent_jobs(job: Job, cohort: prep.SyntheticCohort, train_rows: np.ndarray, test_rows: np.ndarray,
@@ -834,6 +887,12 @@ def main_test(argv=None):
     ap.add_argument("--models-dir", type=str, required=True, help="the --out-dir of the train entry (run with --save-models)")
     ap.add_argument("--latent", action="store_true",
                     help="also the latent-space deviation: per fold latent_<P>.csv (joint mu / var) and latent_deviation_<P>.csv")
+    ap.add_argument("--roi-effect", dest="roi_effect", action="store_true",
+                    help="also every ROI's Cliff's delta / ROC-AUC of patients against controls on its squared error: per fold "
+                         "roi_effect_<m>.csv, and the same on all folds' subjects pooled next to the all-folds tables")
+    ap.add_argument("--disease-label", dest="disease_label", type=int, default=None,
+                    help="with --roi-effect: the one diagnosis (the cohort's DIA value) that counts as patients; default: every "
+                         "subject who is not a healthy control")
     _driver_common(ap)
     args = ap.parse_args(argv)
     cohort = _cohort_from_args(args)
@@ -866,7 +925,9 @@ def main_test(argv=None):
         fold_rows.append((tr, te))
         fold_dirs.append(fold_dir)
     # all folds of this rank in one launch (one job per fold on its own test tables)
-    for err in (test_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs) if my else []):
+    results = test_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs,
+                         roi_effect=args.roi_effect, disease_label=args.disease_label) if my else []
+    for err in results:
         for m in mods:
             errors[m].append(err[m])
     for m in mods:                                   # all folds of this rank, one table per CSV kind (:147-175)
@@ -875,6 +936,12 @@ def main_test(argv=None):
             parts = [pd.read_csv(root / f"{k:03d}" / m / f"{kind}_{m}.csv") for k in my]
             if parts:
                 pd.concat(parts, ignore_index=True).to_csv(out_root / m / f"{kind}_{m}.csv", index=False)
+        if args.roi_effect and results:              # the pooled table: this rank's folds' test subjects as one set
+            tab = results[0]["roi_effect_pooled"][m]
+            io.write_roi_effect_csv(out_root / m, m, _roi_columns(None, m, tab.shape[0]), tab)
+            top = int(np.nanargmax(np.abs(tab[:, 0]))) if np.isfinite(tab[:, 0]).any() else 0
+            print(f"[test] {args.procedure} {m}: pooled ROI effect, largest |delta| {tab[top, 0]:+.4f} (AUC {tab[top, 1]:.4f}) at ROI {top}",
+                  flush=True)
     if args.latent and my:
         # the folds' train cohorts and test subjects in one latent launch each, one statistics and one score launch
         lat = latent_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs, name=args.procedure)
@@ -887,6 +954,48 @@ def main_test(argv=None):
     out = {m: np.concatenate(v) if v else np.empty(0) for m, v in errors.items()}
     for m, v in out.items():
         print(f"[test] {args.procedure} {m}: {len(v)} subjects, mean reconstruction error {float(v.mean()) if len(v) else float('nan'):.5f}", flush=True)
+    return out
+
+
+def _analysis_roi(root: Path, mods: Sequence[str], n_splits: int, hc: int, procedure: str) -> Dict[str, np.ndarray]:
+    """`analysis --roi`: the per-fold reconstruction_error_roi_<m>.csv files (this package's or the reference's: the four
+    metadata columns, then one column per ROI) uploaded, ONE metrics.roi_effect launch over all folds and modalities (one per
+    table width), and
+    per modality group_analysis_roi_<m>.csv: per ROI the mean and population std over folds of cliff_delta and auc.
+    Prints the ten ROIs with the largest mean |delta|; returns {modality: [folds, D, 8]}."""
+    import os
+    import pandas as pd
+    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+    mats, groups, cols, folds = [], [], {}, []
+    for k in range(n_splits):
+        files = [root / f"{k:03d}" / m / f"reconstruction_error_roi_{m}.csv" for m in mods]
+        if not all(f.exists() for f in files):
+            continue
+        folds.append(k)
+        for m, f in zip(mods, files):
+            df = pd.read_csv(f, float_precision="round_trip")      # (the float32 values the file was written from, exactly)
+            dia = df["DIA"].to_numpy()
+            # (DIA as in the reconstruction analysis: the cohort's convention 1 = healthy, or the resource's raw label)
+            healthy = (dia == 1) if set(np.unique(dia)) <= {0, 1} else (dia == hc)
+            roi = [c for c in df.columns if c not in io.META_COLS]
+            if cols.setdefault(m, roi) != roi:
+                raise ValueError(f"{f}: ROI columns differ from the first fold's")
+            mats.append(torch.as_tensor(np.ascontiguousarray(df[roi].to_numpy(dtype=np.float32))).to(device))   # (row-major)
+            groups.append(np.where(healthy, 0, 1).astype(np.int32))
+    if not folds:
+        raise FileNotFoundError(f"no reconstruction_error_roi_*.csv of {list(mods)} under {root}/<fold>/ -- run the `test` subcommand first")
+    tabs = _roi_effect_sets(mats, groups, device)
+    out = {m: torch.stack(tabs[i::len(mods)]).cpu().numpy() for i, m in enumerate(mods)}
+    for m in mods:
+        delta, auc = out[m][:, :, 0], out[m][:, :, 1]
+        df = pd.DataFrame({"ROI": cols[m], "cliff_delta_mean": delta.mean(0), "cliff_delta_std": delta.std(0),
+                           "auc_mean": auc.mean(0), "auc_std": auc.std(0)})
+        df.to_csv(root / f"group_analysis_roi_{m}.csv", index=False)
+        order = np.argsort(-np.nan_to_num(np.abs(df["cliff_delta_mean"].to_numpy()), nan=-1.0), kind="stable")[:10]
+        print(f"[analysis] {procedure} {m}: {len(folds)} folds, {len(cols[m])} ROIs; largest mean |Cliff's delta|:", flush=True)
+        for r in order:
+            print(f"[analysis]   {df['ROI'][r]}: delta {df['cliff_delta_mean'][r]:+.4f} +- {df['cliff_delta_std'][r]:.4f}  "
+                  f"AUC {df['auc_mean'][r]:.4f} +- {df['auc_std'][r]:.4f}", flush=True)
     return out
 
 
@@ -908,10 +1017,15 @@ def main_analysis(argv=None):
     ap.add_argument("--score", choices=("reconstruction", "latent"), default="reconstruction",
                     help="the per-subject score: the modality-averaged reconstruction error, or the `Latent deviation` column "
                          "of latent_deviation_<P>.csv (`test --latent`); latent writes group_analysis_latent.csv")
+    ap.add_argument("--roi", action="store_true",
+                    help="instead: which ROIs separate patients from controls -- per fold and modality every ROI's Cliff's delta and "
+                         "ROC-AUC on reconstruction_error_roi_<m>.csv, their mean and std over folds to group_analysis_roi_<m>.csv")
     args = ap.parse_args(argv)
     mods, _ = workload.procedure_modalities(args.procedure, args.dataset_resourse)
     root = Path(args.models_dir) / args.dataset_resourse / args.procedure
     hc = prep.HC_LABEL.get(args.dataset_resourse, 1)
+    if args.roi:
+        return _analysis_roi(root, mods, args.n_splits, hc, args.procedure)
     scores, positive, folds = [], [], []
     for k in range(args.n_splits):
         if args.score == "latent":

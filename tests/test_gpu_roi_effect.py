@@ -1,0 +1,225 @@
+"""nm_roi_effect on the device against the yardstick (tests/roi_effect_ref.py).  In every case the output buffer starts out
+poisoned, the pad columns D..pitch of the inputs hold NaN / inf, the four counts must be the yardstick's integers, cliff_delta
+and auc its bits, and the means within the fp64 summation bound of both sides,
+|mean - ref| <= 2 n 2^-53 mean(|x|) with n the group's size.  Inputs are squares of values quantised to 1/4: ties are common."""
+import numpy as np
+import pytest
+import torch
+
+from multi_modal_normative_modeling_amd import _lib, metrics
+from multi_modal_normative_modeling_amd.engine import _stream_ptr
+from tests import roi_effect_ref as R
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+POISON = -1.2345e300
+YCH = _lib.NM_ROI_Y_CHUNK
+
+
+def _values(rng, rows, D):
+    return ((np.round(rng.normal(size=(rows, D)) * 4) / 4) ** 2).astype(np.float32)
+
+
+def _groups(rng, rows):
+    """X, Y and left-out rows interleaved; -1 and 7 both mean `left out`."""
+    g = rng.choice([1, 0, -1, 7], size=rows, p=[0.42, 0.38, 0.1, 0.1]).astype(np.int32)
+    g[:4] = [1, 0, -1, 7][:rows]
+    return g
+
+
+def _upload(x, pitch):
+    """[rows, D] view of a [rows, pitch] device buffer whose pad columns hold NaN and +-inf."""
+    rows, D = x.shape
+    assert pitch >= D
+    buf = torch.empty(rows, pitch, dtype=torch.float32)
+    pad = torch.tensor([float("nan"), float("inf"), float("-inf")]).repeat(pitch)[:pitch]
+    buf[:] = pad
+    buf[:, :D] = torch.from_numpy(x)
+    return buf.to(DEV)[:, :D]
+
+
+def _launch(views, groups, max_rows=None, rows=None, pitches=None):
+    """The C entry point on a poisoned output; rows / pitches override what the table declares (the refusal cases)."""
+    D = int(views[0].shape[1])
+    grp = [torch.as_tensor(np.asarray(g, dtype=np.int32)).to(DEV) for g in groups]
+    table = metrics._roi_table(views, grp)
+    for k in range(len(views)):
+        if rows is not None and rows[k] is not None:
+            table[k].rows = rows[k]
+        if pitches is not None and pitches[k] is not None:
+            table[k].pitch = pitches[k]
+    sets = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(DEV)
+    out = torch.full((len(views), D, _lib.NM_METRICS_STRIDE), POISON, dtype=torch.float64, device=DEV)
+    if max_rows is None:
+        max_rows = max(max(int(v.shape[0]) for v in views), 1)
+    _lib.check(_lib.load().nm_roi_effect(sets.data_ptr(), len(views), D, max_rows, out.data_ptr(), _stream_ptr(DEV)), "nm_roi_effect")
+    torch.cuda.synchronize()
+    return out.cpu().numpy()
+
+
+def _same_bits(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    nan = np.isnan(a)
+    return np.array_equal(nan, np.isnan(b)) and np.array_equal(a[~nan].view(np.int64), b[~nan].view(np.int64))
+
+
+def _check(got, x, group, counts=R.counts_broadcast):
+    ref = R.table(x, group, counts)
+    assert got.shape == ref.shape
+    assert not np.any(got == POISON)
+    print("counts", got[:, 2:6].max(0), "max |delta diff|", np.nanmax(np.abs(got[:, 0] - ref[:, 0]), initial=0.0))
+    assert np.array_equal(got[:, 2:6].astype(np.int64), ref[:, 2:6].astype(np.int64)) and np.array_equal(got[:, 2:6], np.rint(got[:, 2:6]))
+    assert _same_bits(got[:, 0], ref[:, 0])
+    assert _same_bits(got[:, 1], ref[:, 1])
+    X, Y = R.split(x, group)
+    for col, part in ((6, X), (7, Y)):
+        n = part.shape[0]
+        fin = np.isfinite(ref[:, col])
+        # where the yardstick's mean is NaN or infinite (an empty group, a NaN / inf entry) the kernel's is the same
+        assert np.array_equal(np.isnan(got[:, col]), np.isnan(ref[:, col]))
+        assert np.array_equal(got[~fin, col], ref[~fin, col], equal_nan=True)
+        if n:
+            bound = 2 * n * 2.0 ** -53 * np.abs(part[:, fin]).mean(0)
+            err = np.abs(got[fin, col] - ref[fin, col])
+            print("mean column", col, "max err", err.max(initial=0.0), "bound min", bound.min(initial=np.inf))
+            assert np.all(err <= bound)
+    return ref
+
+
+@pytest.mark.parametrize("D", [1, 63, 64, 65, 379])
+def test_widths_around_the_tile(D):
+    rng = np.random.default_rng(100 + D)
+    rows = 171
+    x, g = _values(rng, rows, D), _groups(rng, rows)
+    if D > 1:                                            # (the single column stays finite: its means are compared as numbers)
+        x[rng.integers(0, rows, 6), rng.integers(0, D, 6)] = np.nan
+        x[rng.integers(0, rows, 3), rng.integers(0, D, 3)] = np.inf
+        x[rng.integers(0, rows, 3), rng.integers(0, D, 3)] = -np.inf
+    got = _launch([_upload(x, D + 3)], [g])
+    _check(got[0], x, g)
+
+
+def test_one_against_one():
+    for xv, yv, delta in ((2.25, 0.0625, 1.0), (0.25, 0.25, 0.0), (0.0, 4.0, -1.0)):
+        x = np.array([[yv, 9.0], [xv, 1.0]], dtype=np.float32)
+        got = _launch([_upload(x, 5)], [[0, 1]])
+        ref = _check(got[0], x, [0, 1])
+        assert ref[0, 0] == delta and got[0, 0, 4] == 1 and got[0, 0, 5] == 1
+
+
+@pytest.mark.parametrize("n_y", [YCH - 1, YCH, YCH + 1, 2 * YCH + 1])
+def test_y_rows_around_the_chunk(n_y):
+    rng = np.random.default_rng(n_y)
+    n_x = 37                                            # no multiple of the four waves, nor of the rows a thread holds
+    g = np.concatenate([np.ones(n_x, dtype=np.int32), np.zeros(n_y, dtype=np.int32), np.full(5, -1, dtype=np.int32)])
+    rng.shuffle(g)
+    x = _values(rng, len(g), 65)
+    got = _launch([_upload(x, 68)], [g])
+    ref = _check(got[0], x, g)
+    assert ref[0, 4] == n_x and ref[0, 5] == n_y
+
+
+@pytest.mark.parametrize("n_x", [1, 3, 4, 5, 31, 32, 33, 67])
+def test_x_rows_around_the_interleave(n_x):
+    rng = np.random.default_rng(1000 + n_x)
+    g = np.concatenate([np.ones(n_x, dtype=np.int32), np.zeros(19, dtype=np.int32)])
+    rng.shuffle(g)
+    x = _values(rng, len(g), 7)
+    got = _launch([_upload(x, 8)], [g])
+    _check(got[0], x, g)
+
+
+def test_empty_groups():
+    rng = np.random.default_rng(3)
+    x = _values(rng, 40, 66)
+    for g in (np.where(np.arange(40) % 3 == 0, 0, 7), np.where(np.arange(40) % 3 == 0, 1, -1), np.full(40, 2)):
+        got = _launch([_upload(x, 70)], [g])[0]
+        ref = _check(got, x, g)
+        assert np.all(ref[:, 2:4] == 0) and np.all(np.isnan(got[:, :2]))
+        assert np.all(np.isnan(got[:, 6]) == (not np.any(g == 1))) and np.all(np.isnan(got[:, 7]) == (not np.any(g == 0)))
+    # a table without rows: the same, nothing is read
+    got = _launch([_upload(x, 70)[:0]], [np.zeros(0, dtype=np.int32)])
+    assert np.all(got[0, :, 2:6] == 0) and np.all(np.isnan(got[0][:, [0, 1, 6, 7]]))
+
+
+def test_ties_signed_zeros_and_non_finite_values():
+    rng = np.random.default_rng(4)
+    rows = 90
+    x, g = _values(rng, rows, 6), _groups(rng, rows)
+    x[:, 0] = 2.25                                       # all equal: delta 0, auc 0.5
+    x[:, 1] = np.where(g == 1, 0.0, -0.0)                # +0 against -0: ties
+    x[:, 2] = np.where(rng.random(rows) < 0.3, np.nan, x[:, 2])
+    x[:, 3] = np.where(rng.random(rows) < 0.3, np.inf, x[:, 3])
+    x[:, 4] = np.where(rng.random(rows) < 0.3, -np.inf, x[:, 4])
+    x[:, 5] = rng.choice([np.nan, np.inf, -np.inf, 0.25], size=rows)
+    got = _launch([_upload(x, 9)], [g])
+    ref = _check(got[0], x, g)
+    for c in (0, 1):
+        assert got[0, c, 0] == 0.0 and got[0, c, 1] == 0.5 and got[0, c, 2] == 0 and got[0, c, 3] == 0
+    assert np.signbit(x[g == 0, 1]).all() and not np.signbit(x[g == 1, 1]).any()
+    assert ref[2, 2] + ref[2, 3] < ref[2, 4] * ref[2, 5]
+
+
+def _mixed():
+    """Five sets of different heights and pitches; the third a row slice out of the middle of a taller buffer."""
+    rng = np.random.default_rng(77)
+    D = 70
+    shapes = [(33, 70), (YCH + 9, 72), (58, 80), (2, 71), (301, 76)]
+    xs = [_values(rng, r, D) for r, _ in shapes]
+    gs = [_groups(rng, r) for r, _ in shapes]
+    views = [_upload(x, p) for x, (_, p) in zip(xs, shapes)]
+    tall = _upload(np.concatenate([_values(rng, 11, D), xs[2], _values(rng, 6, D)]), 80)
+    views[2] = tall[11:11 + 58]
+    assert not views[2].is_contiguous() and views[2].data_ptr() == tall.data_ptr() + 11 * 80 * 4
+    return views, xs, gs
+
+
+def test_five_sets_in_one_launch_through_the_host_function():
+    views, xs, gs = _mixed()
+    ptrs = [v.data_ptr() for v in views]
+    got = metrics.roi_effect(views, gs, device=DEV)
+    assert got.dtype == torch.float64 and got.is_cuda and tuple(got.shape) == (5, 70, 8)
+    assert [v.data_ptr() for v in views] == ptrs
+    got = got.cpu().numpy()
+    for k in range(5):
+        _check(got[k], xs[k], gs[k])
+    # the same table, pointer for pointer, on a poisoned output; twice: the same bytes
+    a = _launch(views, gs)
+    b = _launch(views, gs)
+    assert a.tobytes() == b.tobytes() == got.tobytes()
+
+
+def test_full_height_set_where_every_x_exceeds_every_y():
+    rng = np.random.default_rng(8192)
+    n, D = _lib.NM_METRICS_MAX_N, 65
+    g = np.concatenate([np.ones(n // 2, dtype=np.int32), np.zeros(n // 2, dtype=np.int32)])
+    rng.shuffle(g)
+    x = _values(rng, n, D)
+    x = np.where(g[:, None] == 1, x + np.float32(64.0), np.minimum(x, np.float32(63.0))).astype(np.float32)
+    got = _launch([_upload(x, 68)], [g])
+    ref = _check(got[0], x, g, counts=R.counts_sorted)
+    assert np.all(ref[:, 2] == 2 ** 24) and np.all(got[0, :, 2] == 2 ** 24) and np.all(got[0, :, 0] == 1.0)
+
+
+def test_a_refused_set_gets_nan_rows_and_its_neighbours_their_results():
+    views, xs, gs = _mixed()
+    # set 4 (301 rows) is taller than max_rows; set 1 declares a pitch below D; set 3 a negative height
+    got = _launch(views, gs, max_rows=YCH + 9, pitches=[None, 69, None, None, None], rows=[None, None, None, -1, None])
+    for k in (1, 3, 4):
+        assert np.all(np.isnan(got[k])), k
+    for k in (0, 2):
+        _check(got[k], xs[k], gs[k])
+
+
+def test_cliff_delta_is_the_double_loop():
+    rng = np.random.default_rng(5)
+    X, Y = _values(rng, 97, 1)[:, 0], _values(rng, 131, 1)[:, 0]
+    X[13] = np.nan
+    d = metrics.cliff_delta(X, Y)
+    assert isinstance(d, float) and np.float64(d).tobytes() == np.float64(R.literal_delta(X, Y)).tobytes()
+    X2, Y2 = _values(rng, 40, 5), _values(rng, 23, 5)
+    d2 = metrics.cliff_delta(torch.from_numpy(X2), Y2)
+    assert isinstance(d2, np.ndarray) and d2.shape == (5,)
+    for c in range(5):
+        assert np.float64(d2[c]).tobytes() == np.float64(R.literal_delta(X2[:, c], Y2[:, c])).tobytes()
