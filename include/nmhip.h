@@ -25,6 +25,7 @@
 #ifndef NMHIP_H
 #define NMHIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -485,6 +486,42 @@ int nm_latent_score(const float* mu, const float* logvar, const int32_t* offsets
 #define NM_ROI_Y_CHUNK 128
 typedef struct { const float* x; const int32_t* group; int32_t rows; int32_t pitch; } nm_roi_set_t;
 int nm_roi_effect(const nm_roi_set_t* sets_dev, int n_sets, int D, int max_rows, double* out, void* stream);
+
+/* ROI-wise significance of the same tables (sets_dev, D, max_rows as for nm_roi_effect; n_perm 0..NM_ROI_MAX_PERM label
+ * permutations, a 64-bit seed).  The included rows of set k are its rows with group 0 or 1, in row order, at positions
+ * i = 0..n-1; n_x of them have group 1 (X), n_y group 0 (Y).  A column is valid if n_x >= 1, n_y >= 1 and no included row
+ * holds a NaN in it; a column that is not valid gets NaN in all eight outputs and takes no part in the BH count or in the
+ * maximum.  Equality is IEEE ==: -0 == +0, inf == inf is a tie.  Rows are taken as independent observations.
+ *   r2[i]     twice the mid-rank of row i in its column (2..2n, tied rows share it)
+ *   tie_term  sum over tie groups of t^3 - t                S = sum_{i in X} r2[i] - n_x (n + 1)  (= n_more - n_less)
+ *   u_x       (S + n_x n_y) / 2, the Mann-Whitney U of X
+ *   fp64, every operation on its own:  a = double(n_x n_y) / 12;  b = double(tie_term) / (double(n) double(n - 1));
+ *     s = sqrt(a (double(n + 1) - b));  zabs = s > 0 ? max(|S| 0.5 - 0.5, 0) / s : 0;  z = copysign(zabs, S);
+ *     p_mwu = erfc(zabs / sqrt(2))     (scipy.stats.mannwhitneyu, two-sided, asymptotic, with continuity correction)
+ *   q_bh      over the m valid columns of the set, p_mwu ascending as p_(1..m): min(1, min_{j >= i} p_(j) (double(m) / double(j)))
+ *   permutation t = 1..n_perm of set k:  h = splitmix64(seed ^ 0x5160C0DE ^ (k << 40) ^ (t << 16) ^ i), the sort key
+ *     (h & ~0x1FFF) | i; the n_x positions with the smallest keys are X*;  S*_t,c = sum_{i in X*} r2[i, c] - n_x (n + 1);
+ *     maxstat_t = max over valid c of |S*_t,c|
+ *   p_perm    (1 + #{t: |S*_t,c| >= |S_c|}) / (1 + n_perm)      p_maxt  (1 + #{t: maxstat_t >= |S_c|}) / (1 + n_perm)
+ *             (one fp64 division each; NaN with n_perm = 0)
+ * out is [n_sets][D][NM_METRICS_STRIDE] fp64 = {u_x, tie_term, z, p_mwu, q_bh, p_perm, p_maxt, n_perm}; maxstat_out (may
+ * be NULL) [n_sets][n_perm] int32 is the null distribution of the maximum, -1 for a set without a valid column.  A set
+ * refused as nm_roi_effect refuses it gets NaN rows and -1 in maxstat_out; nothing of it is read.  Every output element is
+ * written on every call, without atomics: two runs give the same bytes.  workspace: device memory of at least
+ * nm_roi_significance_workspace(...) bytes (0 for arguments no launch accepts), 256-byte aligned, contents irrelevant.
+ * Set k's index in the hash is its index in sets_dev.  A caller that splits its sets over several calls passes the offset
+ * in the seed: with a group of 2^b sets that starts at a multiple k0 of 2^b, seed ^ (k0 << 40) gives set j of the group the
+ * hash of set k0 + j (k0 | j = k0 ^ j); there is no first-set argument.
+ * Status, decided before the device is asked anything: NM_E_NULL: sets_dev, out or workspace missing; NM_E_METRICS: n_sets
+ * < 1, D outside 1..8192 (the BH sort's limit), max_rows outside 1..NM_METRICS_MAX_N, n_perm outside 0..NM_ROI_MAX_PERM,
+ * workspace_bytes below the query's answer, or a grid beyond 2^31 - 1 workgroups.  NM_ROI_PERM_CHUNK: the permutations one
+ * workgroup of the sum pass takes; NM_ROI_ROW_CHUNK: the rank rows it stages at a time. */
+#define NM_ROI_MAX_PERM   65535
+#define NM_ROI_PERM_CHUNK 64
+#define NM_ROI_ROW_CHUNK  256
+size_t nm_roi_significance_workspace(int n_sets, int D, int max_rows, int n_perm);
+int nm_roi_significance(const nm_roi_set_t* sets_dev, int n_sets, int D, int max_rows, int n_perm, uint64_t seed,
+                        void* workspace, size_t workspace_bytes, double* out, int32_t* maxstat_out, void* stream);
 
 /* The expert-fusion operators the reference exposes as public methods, as forward-only launches (elementwise over
  * [M][n] fp32 device tensors; csrc/nm_fusion.hip):

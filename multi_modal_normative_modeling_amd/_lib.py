@@ -53,6 +53,11 @@ NM_METRICS_MAX_N = 8192
 NM_METRICS_STRIDE = 8
 # nm_roi_effect: the Y rows its kernel stages in LDS at a time (tests put group sizes around it)
 NM_ROI_Y_CHUNK = 128
+# nm_roi_significance: the most label permutations, the permutations a workgroup of its sum pass takes, the rank rows it
+# stages at a time (tests put n_perm and the heights around them)
+NM_ROI_MAX_PERM = 65535
+NM_ROI_PERM_CHUNK = 64
+NM_ROI_ROW_CHUNK = 256
 
 # status codes (nmhip.h; nm_status_string gives the text)
 NM_OK = 0
@@ -202,6 +207,9 @@ def load():
     lib.nm_posthoc_metrics.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
     lib.nm_confusion_metrics.argtypes = [vp, vp, vp, i32, vp, vp]
     lib.nm_roi_effect.argtypes = [vp, i32, i32, i32, vp, vp]
+    lib.nm_roi_significance_workspace.restype = C.c_size_t
+    lib.nm_roi_significance_workspace.argtypes = [i32, i32, i32, i32]
+    lib.nm_roi_significance.argtypes = [vp, i32, i32, i32, i32, C.c_uint64, vp, C.c_size_t, vp, vp, vp]
     lib.nm_adam_step.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, i64, vp]
     lib.nm_pack_table.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp]
     lib.nm_prep_scaler_fit.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp]
@@ -229,7 +237,7 @@ EXPORTED_SYMBOLS = [
     "nm_launch_rowsplit", "nm_rowsplit_ok", "nm_sync_reset", "nm_trace_read_rs", "nm_devpass", "nm_devpass_ok", "nm_trace_read_dv", "nm_workspace_offset",
     "nm_launch_rowsplit_mixed", "nm_rowsplit_groups", "nm_devpass_multi", "nm_devpass_multi_ok",
     "nm_latent_pass", "nm_latent_pass_ok", "nm_latent_stats", "nm_latent_score",
-    "nm_roi_effect",
+    "nm_roi_effect", "nm_roi_significance_workspace", "nm_roi_significance",
 ]
 
 

@@ -11,6 +11,8 @@
 //                         (latent_deviation / separate_latent_deviation, utils_vae.py:155-161)
 //   nm_roi_effect         ROI-wise squared errors of two groups -> Cliff's delta, ROC-AUC, pair counts, group means per ROI
 //                         (cliff_delta, utils.py:97-109, once per column; further down in this file)
+//   nm_roi_significance   the same tables -> Mann-Whitney U, z and asymptotic p per ROI, Benjamini-Hochberg q, and the
+//                         label-permutation p-values, per ROI and against the maximum over the ROIs (at the end)
 //
 // One workgroup per score set (a (fold, procedure) cell); sets are segments of one concatenated array.  The
 // whole set lives in LDS: order-preserving 64-bit keys (score, label) are bitonic-sorted descending, label
@@ -440,6 +442,379 @@ __global__ __launch_bounds__(MT) void roi_effect_kernel(const nm_roi_set_t* __re
   }
 }
 
+// ---- ROI-wise significance (Mann-Whitney p, Benjamini-Hochberg q, max-statistic label permutations) --------------------
+// nm_roi_significance, six launches on one stream over a workspace (include/nmhip.h has the definitions):
+//   rank   one workgroup per (set, column): the included rows' (order-preserving key of the value, position, is-X) as 64-bit
+//          keys, bitonic-sorted in LDS as posthoc_kernel sorts; a thread that finds the first key of a tie run walks the run
+//          and writes twice its mid-rank for every member to r2 [set][position][D] (uint16), and the column's tie term, S
+//          and validity.  -0 and +0 share a key.
+//   label  one workgroup per (set, permutation): the n hash keys sorted the same way, the n_x smallest marked in a byte
+//          array, the bytes gathered into ceil(max_rows / 32) label words.
+//   sum    one workgroup per (set, 64-column tile, NM_ROI_PERM_CHUNK permutations), a lane per column.  The tile's rank rows
+//          pass through LDS NM_ROI_ROW_CHUNK rows at a time ([row][column] uint16: a wave reads 128 consecutive bytes); each
+//          of the four waves carries SIG_PW permutations in int32 accumulators, reads a row once and adds it SIG_PW times
+//          as v * bit, the bit taken from a label word that is the same for the whole wave (a scalar operand: one multiply-
+//          add per row and permutation).  Per permutation the tile's largest |S*| over valid columns (a wave reduction), per
+//          column the chunk's count of |S*| >= |S| (the waves' counts merged through LDS in wave order).
+//   max    the tiles' maxima -> maxstat_t;  count: per column the chunks' counts added in chunk order and the number of
+//          maxstat_t >= |S|;  close: one workgroup per set -- z and p per column, the BH sort over the columns in LDS, the
+//          suffix minimum, the table.
+// No atomics; integers until the last divisions.
+constexpr int SIG_PW = 16;                         // permutations a wave carries through a row chunk
+constexpr int SIG_PCH = NM_ROI_PERM_CHUNK;
+constexpr int SIG_RCH = NM_ROI_ROW_CHUNK;
+constexpr int SIG_MAX_D = 8192;                    // the BH sort's limit
+static_assert(SIG_PCH == ROI_WAVES * SIG_PW, "a chunk is what the four waves carry");
+static_assert(SIG_RCH % 32 == 0 && MAXN % SIG_RCH == 0, "row chunks are whole label words");
+
+struct SigPlan {                                   // byte offsets into the workspace, each a multiple of 256
+  size_t r2, colS, coltie, info, lab, tmax, ccnt, ms, cnt, total;
+  int W, tiles, chunks;
+};
+inline SigPlan sig_plan(int n_sets, int D, int max_rows, int n_perm) {
+  SigPlan p;
+  p.W = (max_rows + 31) / 32;
+  p.tiles = (D + ROI_TILE - 1) / ROI_TILE;
+  p.chunks = (n_perm + SIG_PCH - 1) / SIG_PCH;
+  const size_t ns = (size_t)n_sets, sd = ns * (size_t)D, sp = ns * (size_t)n_perm;
+  size_t o = 0;
+  auto take = [&o](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
+  p.r2 = take(sd * (size_t)max_rows * 2);          // uint16 [set][position][D]
+  p.colS = take(sd * 4);                           // int32  [set][D]
+  p.coltie = take(sd * 8);                         // double [set][D]: the tie term, -1 where the column is not valid
+  p.info = take(ns * 16);                          // int32  [set][4]: n, n_x, usable
+  p.lab = take(sp * (size_t)p.W * 4);              // uint32 [set][perm][W]
+  p.tmax = take(sp * (size_t)p.tiles * 4);         // int32  [set][perm][tile]
+  p.ccnt = take(ns * (size_t)p.chunks * (size_t)D * 4);   // int32 [set][chunk][D]
+  p.ms = take(sp * 4);                             // int32  [set][perm]
+  p.cnt = take(sd * 8);                            // int32  [set][D][2]: #|S*| >= |S|, #maxstat >= |S|
+  p.total = o;
+  return p;
+}
+inline int pow2_at_least(int n) { int p = 2; while (p < n) p <<= 1; return p; }
+
+__device__ __forceinline__ uint64_t sig_splitmix64(uint64_t x) {      // splitmix64 of nm_core.inc
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+__device__ __forceinline__ uint32_t asc_key(float x) {
+  if (x == 0.0f) x = 0.0f;                               // -0 and +0 are one value
+  const uint32_t b = __float_as_uint(x);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+// ascending bitonic sort of key[0..npad), npad a power of two; all threads call
+__device__ __forceinline__ void sort_keys(uint64_t* key, int npad) {
+  const int t = threadIdx.x;
+  for (int k = 2; k <= npad; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = t; i < npad; i += MT) {
+        const int p = i ^ j;
+        if (p > i) {
+          const uint64_t a = key[i], b = key[p];
+          if ((a > b) == ((i & k) == 0)) { key[i] = b; key[p] = a; }
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+__global__ __launch_bounds__(MT) void roi_rank_kernel(const nm_roi_set_t* __restrict__ sets, int D, int max_rows,
+                                                      uint16_t* __restrict__ r2, int32_t* __restrict__ colS,
+                                                      double* __restrict__ coltie, int32_t* __restrict__ info) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint64_t* key = reinterpret_cast<uint64_t*>(smem);            // [npad]: value key << 32 | position << 1 | is X
+  __shared__ int32_t part[2][MT];
+  __shared__ long long red[2][MT];
+  const int t = threadIdx.x;
+  const int s = blockIdx.x / D, col = blockIdx.x - s * D;
+  const nm_roi_set_t S = sets[s];
+  const int64_t ci = (int64_t)s * D + col;
+  const int rows = S.rows, pitch = S.pitch;
+  if (rows < 0 || rows > max_rows || pitch < D || (rows > 0 && (!S.x || !S.group))) {
+    if (t == 0) {
+      colS[ci] = 0; coltie[ci] = -1.0;
+      if (col == 0) { info[4 * s] = 0; info[4 * s + 1] = 0; info[4 * s + 2] = 0; info[4 * s + 3] = 0; }
+    }
+    return;
+  }
+  const int per = (rows + MT - 1) / MT;
+  const int lo = min(t * per, rows), hi = min(lo + per, rows);
+  {
+    int cn = 0, cx = 0;
+    for (int r = lo; r < hi; ++r) { const int32_t g = S.group[r]; cn += (g == 1 || g == 0); cx += (g == 1); }
+    part[0][t] = cn; part[1][t] = cx;
+  }
+  __syncthreads();
+  int n = 0, nx = 0, pos = 0;
+  for (int q = 0; q < MT; ++q) {
+    const int cn = part[0][q];
+    if (q < t) pos += cn;
+    n += cn; nx += part[1][q];
+  }
+  const bool usable = nx >= 1 && n - nx >= 1;
+  if (t == 0 && col == 0) { info[4 * s] = n; info[4 * s + 1] = nx; info[4 * s + 2] = usable ? 1 : 0; info[4 * s + 3] = 0; }
+  if (!usable) {
+    if (t == 0) { colS[ci] = 0; coltie[ci] = -1.0; }
+    return;
+  }
+  const int npad = [n] { int p = 2; while (p < n) p <<= 1; return p; }();
+  for (int i = n + t; i < npad; i += MT) key[i] = ~0ull;
+  int nan = 0;
+  for (int r = lo; r < hi; ++r) {
+    const int32_t g = S.group[r];
+    if (g == 1 || g == 0) {
+      const float v = S.x[(int64_t)r * pitch + col];
+      nan |= (v != v);
+      key[pos] = ((uint64_t)asc_key(v) << 32) | ((uint64_t)pos << 1) | (uint64_t)(g == 1);
+      ++pos;
+    }
+  }
+  if (__syncthreads_or(nan)) {                     // a NaN in an included row: the column is not valid
+    if (t == 0) { colS[ci] = 0; coltie[ci] = -1.0; }
+    return;
+  }
+  sort_keys(key, npad);
+  long long sumx = 0, tie = 0;
+  uint16_t* rc = r2 + (int64_t)s * max_rows * D + col;
+  for (int j = t; j < n; j += MT) {
+    const uint32_t v = (uint32_t)(key[j] >> 32);
+    if (j > 0 && (uint32_t)(key[j - 1] >> 32) == v) continue;   // not the first of its tie run
+    int e = j + 1;
+    while (e < n && (uint32_t)(key[e] >> 32) == v) ++e;
+    const long long tn = e - j;
+    tie += tn * tn * tn - tn;
+    const int rr = j + 1 + e;                      // twice the mid-rank of ranks j + 1 .. e
+    for (int q = j; q < e; ++q) {
+      const uint32_t low = (uint32_t)key[q];
+      rc[(int64_t)((low >> 1) & 0x1FFFu) * D] = (uint16_t)rr;
+      if (low & 1u) sumx += rr;
+    }
+  }
+  red[0][t] = sumx; red[1][t] = tie;
+  __syncthreads();
+  if (t == 0) {
+    long long sx = 0, tt = 0;
+    for (int q = 0; q < MT; ++q) { sx += red[0][q]; tt += red[1][q]; }
+    colS[ci] = (int32_t)(sx - (long long)nx * (n + 1));
+    coltie[ci] = (double)tt;
+  }
+}
+
+__global__ __launch_bounds__(MT) void roi_label_kernel(const int32_t* __restrict__ info, int n_perm, int W, uint64_t seed,
+                                                       uint32_t* __restrict__ lab) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint64_t* key = reinterpret_cast<uint64_t*>(smem);            // [npad]
+  __shared__ uint8_t flag[MAXN];
+  const int t = threadIdx.x;
+  const int s = blockIdx.x / n_perm, p = blockIdx.x - s * n_perm;
+  const int n = info[4 * s], nx = info[4 * s + 1];
+  if (!info[4 * s + 2]) return;                    // no valid column in this set: nothing reads its labels
+  int npad = 2;
+  while (npad < n) npad <<= 1;
+  const uint64_t base = seed ^ 0x5160C0DEull ^ ((uint64_t)s << 40) ^ ((uint64_t)(p + 1) << 16);
+  for (int i = t; i < npad; i += MT)
+    key[i] = (i < n) ? ((sig_splitmix64(base ^ (uint64_t)i) & ~0x1FFFull) | (uint64_t)i) : ~0ull;
+  for (int i = t; i < W * 32; i += MT) flag[i] = 0;
+  __syncthreads();
+  sort_keys(key, npad);
+  for (int j = t; j < nx; j += MT) flag[(uint32_t)key[j] & 0x1FFFu] = 1;
+  __syncthreads();
+  for (int wd = t; wd < W; wd += MT) {
+    uint32_t word = 0;
+#pragma unroll
+    for (int b = 0; b < 32; ++b) word |= (uint32_t)flag[wd * 32 + b] << b;
+    lab[((int64_t)s * n_perm + p) * W + wd] = word;
+  }
+}
+
+// acc + v * bit with the bit in a scalar register: one v_mad_u32_u24 per (row, permutation).  (Left to itself the compiler
+// forms a 0 / -1 mask, an AND and an add3 over two rows: three instructions for two.)
+__device__ __forceinline__ int32_t mad_bit(uint32_t v, uint32_t bit, int32_t acc) {
+  int32_t r;
+  asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(v), "s"(bit), "v"(acc));
+  return r;
+}
+
+__global__ __launch_bounds__(MT) void roi_sum_kernel(const int32_t* __restrict__ info, const uint16_t* __restrict__ r2,
+                                                     const int32_t* __restrict__ colS, const double* __restrict__ coltie,
+                                                     const uint32_t* __restrict__ lab, int D, int max_rows, int n_perm, int W,
+                                                     int tiles, int chunks, int32_t* __restrict__ tmax,
+                                                     int32_t* __restrict__ ccnt) {
+  __shared__ uint16_t rs[SIG_RCH * ROI_TILE];
+  __shared__ int32_t pc[ROI_WAVES][ROI_TILE];
+  const int t = threadIdx.x, lane = t & 63;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  int b = blockIdx.x;
+  const int chunk = b % chunks; b /= chunks;
+  const int tile = b % tiles, s = b / tiles;
+  const int n = info[4 * s], nx = info[4 * s + 1];
+  if (!info[4 * s + 2]) return;                    // (the max and close kernels know it from the same word)
+  const int col = tile * ROI_TILE + lane;
+  const bool cv = col < D;
+  const int64_t ci = (int64_t)s * D + (cv ? col : 0);
+  const bool valid = cv && coltie[ci] >= 0.0;
+  const int absS = valid ? abs(colS[ci]) : 0;
+  const int p0 = chunk * SIG_PCH + w * SIG_PW;     // this wave's first permutation (0-based)
+  const int pw = max(0, min(SIG_PW, n_perm - p0));
+  const uint32_t* lw[SIG_PW];
+#pragma unroll
+  for (int k = 0; k < SIG_PW; ++k) lw[k] = lab + ((int64_t)s * n_perm + min(p0 + k, n_perm - 1)) * W;
+  int32_t acc[SIG_PW];
+#pragma unroll
+  for (int k = 0; k < SIG_PW; ++k) acc[k] = 0;
+  const uint16_t* rc = r2 + (int64_t)s * max_rows * D + col;
+  for (int r0 = 0; r0 < n; r0 += SIG_RCH) {
+    const int rn = min(SIG_RCH, n - r0);
+    __syncthreads();                               // the chunk before this one is used up
+    for (int r = w; r < rn; r += ROI_WAVES) rs[r * ROI_TILE + lane] = cv ? rc[(int64_t)(r0 + r) * D] : (uint16_t)0;
+    __syncthreads();
+    if (pw > 0) {
+      const int ng = (rn + 31) >> 5;               // (rows past rn within the last word: their label bits are 0)
+      for (int g = 0; g < ng; ++g) {
+        uint32_t wk[SIG_PW];
+#pragma unroll
+        for (int k = 0; k < SIG_PW; ++k) wk[k] = lw[k][(r0 >> 5) + g];
+#pragma unroll
+        for (int bit = 0; bit < 32; ++bit) {
+          const uint32_t v = rs[((g << 5) + bit) * ROI_TILE + lane];
+#pragma unroll
+          for (int k = 0; k < SIG_PW; ++k) acc[k] = mad_bit(v, (wk[k] >> bit) & 1u, acc[k]);
+        }
+      }
+    }
+  }
+  const int center = nx * (n + 1);
+  int cnt = 0;
+#pragma unroll
+  for (int k = 0; k < SIG_PW; ++k) {
+    const int a = abs(acc[k] - center);
+    const bool live = k < pw;
+    cnt += (live && valid && a >= absS) ? 1 : 0;
+    int m = valid ? a : -1;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = max(m, __shfl_xor(m, off, 64));
+    if (live && lane == 0) tmax[((int64_t)s * n_perm + p0 + k) * tiles + tile] = m;
+  }
+  pc[w][lane] = cnt;
+  __syncthreads();
+  if (w == 0 && cv) ccnt[((int64_t)s * chunks + chunk) * D + col] = pc[0][lane] + pc[1][lane] + pc[2][lane] + pc[3][lane];
+}
+
+__global__ __launch_bounds__(MT) void roi_max_kernel(const int32_t* __restrict__ info, const int32_t* __restrict__ tmax,
+                                                     int n_perm, int tiles, int pblocks, int32_t* __restrict__ ms,
+                                                     int32_t* __restrict__ maxstat_out) {
+  const int s = blockIdx.x / pblocks, p = (blockIdx.x - s * pblocks) * MT + threadIdx.x;
+  if (p >= n_perm) return;
+  int m = -1;
+  if (info[4 * s + 2])
+    for (int tile = 0; tile < tiles; ++tile) m = max(m, tmax[((int64_t)s * n_perm + p) * tiles + tile]);
+  ms[(int64_t)s * n_perm + p] = m;
+  if (maxstat_out) maxstat_out[(int64_t)s * n_perm + p] = m;
+}
+
+__global__ __launch_bounds__(MT) void roi_count_kernel(const int32_t* __restrict__ info, const int32_t* __restrict__ colS,
+                                                       const int32_t* __restrict__ ccnt, const int32_t* __restrict__ ms, int D,
+                                                       int n_perm, int chunks, int dblocks, int32_t* __restrict__ cnt) {
+  const int s = blockIdx.x / dblocks, col = (blockIdx.x - s * dblocks) * MT + threadIdx.x;
+  if (col >= D) return;
+  const int64_t ci = (int64_t)s * D + col;
+  int cp = 0, cm = 0;
+  if (info[4 * s + 2]) {
+    const int absS = abs(colS[ci]);
+    for (int c = 0; c < chunks; ++c) cp += ccnt[((int64_t)s * chunks + c) * D + col];
+    const int32_t* m = ms + (int64_t)s * n_perm;
+    for (int p = 0; p < n_perm; ++p) cm += (m[p] >= absS) ? 1 : 0;
+  }
+  cnt[2 * ci] = cp; cnt[2 * ci + 1] = cm;
+}
+
+// z and the asymptotic p of one column: every operation on its own, in the order of the definitions
+#pragma clang fp contract(off)
+__device__ __forceinline__ void mwu_z_p(int n, int nx, int S, double tie, double& z, double& p) {
+  const double a = (double)((long long)nx * (n - nx)) / 12.0;
+  const double b = tie / ((double)n * (double)(n - 1));
+  const double sd = __dsqrt_rn(a * ((double)(n + 1) - b));
+  const double zabs = sd > 0.0 ? fmax(fabs((double)S) * 0.5 - 0.5, 0.0) / sd : 0.0;
+  z = copysign(zabs, (double)S);
+  p = erfc(zabs / 1.4142135623730951);              // sqrt(2.0), correctly rounded
+}
+
+__global__ __launch_bounds__(MT) void roi_close_kernel(const int32_t* __restrict__ info, const int32_t* __restrict__ colS,
+                                                       const double* __restrict__ coltie, const int32_t* __restrict__ cnt, int D,
+                                                       int npad, int n_perm, double* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint64_t* key = reinterpret_cast<uint64_t*>(smem);            // [npad]: the bits of p (p >= 0: their order is p's)
+  uint16_t* idx = reinterpret_cast<uint16_t*>(key + npad);      // [npad]: the column of key[j]
+  __shared__ int32_t part[MT];
+  __shared__ double dpart[MT];
+  const int s = blockIdx.x, t = threadIdx.x;
+  const int n = info[4 * s], nx = info[4 * s + 1], usable = info[4 * s + 2];
+  const double qnan = __longlong_as_double(0x7FF8000000000000ll);
+  int mine = 0;
+  for (int c = t; c < npad; c += MT) {
+    uint64_t k = ~0ull;
+    if (c < D) {
+      const int64_t ci = (int64_t)s * D + c;
+      double* o = out + ci * NM_METRICS_STRIDE;
+      const double tie = usable ? coltie[ci] : -1.0;
+      if (tie >= 0.0) {
+        const int S = colS[ci];
+        double z, p;
+        mwu_z_p(n, nx, S, tie, z, p);
+        o[0] = (double)((long long)S + (long long)nx * (n - nx)) * 0.5;
+        o[1] = tie; o[2] = z; o[3] = p;
+        o[5] = n_perm ? (double)(1 + cnt[2 * ci]) / (double)(1 + n_perm) : qnan;
+        o[6] = n_perm ? (double)(1 + cnt[2 * ci + 1]) / (double)(1 + n_perm) : qnan;
+        o[7] = (double)n_perm;
+        k = (uint64_t)__double_as_longlong(p);
+        ++mine;
+      } else {
+        for (int q = 0; q < NM_METRICS_STRIDE; ++q) o[q] = qnan;
+      }
+    }
+    key[c] = k; idx[c] = (uint16_t)c;
+  }
+  part[t] = mine;
+  __syncthreads();
+  int m = 0;
+  for (int q = 0; q < MT; ++q) m += part[q];
+  // ascending in p, the column riding along
+  for (int k = 2; k <= npad; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = t; i < npad; i += MT) {
+        const int p = i ^ j;
+        if (p > i) {
+          const uint64_t a = key[i], b = key[p];
+          if ((a > b) == ((i & k) == 0)) {
+            key[i] = b; key[p] = a;
+            const uint16_t ia = idx[i]; idx[i] = idx[p]; idx[p] = ia;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  // q_(i) = min(1, min_{j >= i} p_(j) * (m / j)): the products in place, then the suffix minimum by stretches
+  double* v = reinterpret_cast<double*>(key);
+  const int per = (m + MT - 1) / MT;
+  const int lo = min(t * per, m), hi = min(lo + per, m);
+  double run = __longlong_as_double(0x7FF0000000000000ll);
+  for (int j = hi - 1; j >= lo; --j) {
+    const double pj = __longlong_as_double((long long)key[j]);
+    run = fmin(run, pj * ((double)m / (double)(j + 1)));
+    v[j] = run;
+  }
+  dpart[t] = run;
+  __syncthreads();
+  double tail = __longlong_as_double(0x7FF0000000000000ll);
+  for (int q = t + 1; q < MT; ++q) tail = fmin(tail, dpart[q]);
+  for (int j = lo; j < hi; ++j)
+    out[((int64_t)s * D + idx[j]) * NM_METRICS_STRIDE + 4] = fmin(1.0, fmin(v[j], tail));
+}
+
 }  // namespace
 
 extern "C" {
@@ -481,6 +856,54 @@ int nm_roi_effect(const nm_roi_set_t* sets_dev, int n_sets, int D, int max_rows,
   const int tiles = (D + ROI_TILE - 1) / ROI_TILE;
   if ((int64_t)n_sets * tiles > 0x7FFFFFFFll) return NM_E_METRICS;
   return launch_kernel(roi_effect_kernel, dim3(n_sets * tiles), dim3(MT), 0, stream, sets_dev, D, max_rows, tiles, out);
+}
+
+size_t nm_roi_significance_workspace(int n_sets, int D, int max_rows, int n_perm) {
+  if (n_sets < 1 || D < 1 || max_rows < 1 || n_perm < 0) return 0;
+  return sig_plan(n_sets, D, max_rows, n_perm).total;
+}
+
+int nm_roi_significance(const nm_roi_set_t* sets_dev, int n_sets, int D, int max_rows, int n_perm, uint64_t seed,
+                        void* workspace, size_t workspace_bytes, double* out, int32_t* maxstat_out, void* stream) {
+  if (!sets_dev || !out || !workspace) return NM_E_NULL;
+  if (n_sets < 1 || D < 1 || D > SIG_MAX_D || max_rows < 1 || max_rows > MAXN || n_perm < 0 || n_perm > NM_ROI_MAX_PERM)
+    return NM_E_METRICS;
+  const SigPlan P = sig_plan(n_sets, D, max_rows, n_perm);
+  if (workspace_bytes < P.total) return NM_E_METRICS;
+  const int pblocks = (n_perm + MT - 1) / MT, dblocks = (D + MT - 1) / MT;
+  if ((int64_t)n_sets * D > 0x7FFFFFFFll || (int64_t)n_sets * n_perm > 0x7FFFFFFFll ||
+      (int64_t)n_sets * P.tiles * P.chunks > 0x7FFFFFFFll)
+    return NM_E_METRICS;
+  char* ws = static_cast<char*>(workspace);
+  uint16_t* r2 = reinterpret_cast<uint16_t*>(ws + P.r2);
+  int32_t* colS = reinterpret_cast<int32_t*>(ws + P.colS);
+  double* coltie = reinterpret_cast<double*>(ws + P.coltie);
+  int32_t* info = reinterpret_cast<int32_t*>(ws + P.info);
+  uint32_t* lab = reinterpret_cast<uint32_t*>(ws + P.lab);
+  int32_t* tmax = reinterpret_cast<int32_t*>(ws + P.tmax);
+  int32_t* ccnt = reinterpret_cast<int32_t*>(ws + P.ccnt);
+  int32_t* ms = reinterpret_cast<int32_t*>(ws + P.ms);
+  int32_t* cnt = reinterpret_cast<int32_t*>(ws + P.cnt);
+  const int sort_lds = pow2_at_least(max_rows) * 8;
+  int e = launch_kernel(roi_rank_kernel, dim3(n_sets * D), dim3(MT), sort_lds, stream, sets_dev, D, max_rows, r2, colS, coltie, info);
+  if (e) return e;
+  if (n_perm > 0) {
+    e = launch_kernel(roi_label_kernel, dim3(n_sets * n_perm), dim3(MT), sort_lds, stream, (const int32_t*)info, n_perm, P.W, seed, lab);
+    if (e) return e;
+    e = launch_kernel(roi_sum_kernel, dim3(n_sets * P.tiles * P.chunks), dim3(MT), 0, stream, (const int32_t*)info,
+                      (const uint16_t*)r2, (const int32_t*)colS, (const double*)coltie, (const uint32_t*)lab, D, max_rows, n_perm,
+                      P.W, P.tiles, P.chunks, tmax, ccnt);
+    if (e) return e;
+    e = launch_kernel(roi_max_kernel, dim3(n_sets * pblocks), dim3(MT), 0, stream, (const int32_t*)info, (const int32_t*)tmax,
+                      n_perm, P.tiles, pblocks, ms, maxstat_out);
+    if (e) return e;
+  }
+  e = launch_kernel(roi_count_kernel, dim3(n_sets * dblocks), dim3(MT), 0, stream, (const int32_t*)info, (const int32_t*)colS,
+                    (const int32_t*)ccnt, (const int32_t*)ms, D, n_perm, P.chunks, dblocks, cnt);
+  if (e) return e;
+  const int npad = pow2_at_least(D);
+  return launch_kernel(roi_close_kernel, dim3(n_sets), dim3(MT), npad * (8 + 2), stream, (const int32_t*)info, (const int32_t*)colS,
+                       (const double*)coltie, (const int32_t*)cnt, D, npad, n_perm, out);
 }
 
 }  // extern "C"

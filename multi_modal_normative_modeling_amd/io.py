@@ -100,6 +100,24 @@ def write_roi_effect_csv(out_dir, dataset_name: str, roi_columns: Sequence[str],
     return path
 
 
+def write_roi_significance_csv(out_dir, dataset_name: str, roi_columns: Sequence[str], table: np.ndarray) -> Path:
+    """roi_significance_{name}.csv: one row per ROI -- its column name, then metrics.ROI_SIGNIFICANCE_COLUMNS (the
+    Mann-Whitney U of patients against controls on the ROI's squared error, its tie term, z and asymptotic p, the
+    Benjamini-Hochberg q over the ROIs, the label-permutation p of the ROI and against the maximum over the ROIs, and the
+    number of permutations).  The subjects are taken as independent."""
+    from .metrics import ROI_SIGNIFICANCE_COLUMNS
+    table = np.asarray(table, dtype=np.float64)
+    if table.shape != (len(roi_columns), len(ROI_SIGNIFICANCE_COLUMNS)):
+        raise ValueError(f"a [{len(roi_columns)}, {len(ROI_SIGNIFICANCE_COLUMNS)}] table is needed, got {table.shape}")
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    df = pd.DataFrame(table, columns=list(ROI_SIGNIFICANCE_COLUMNS))
+    df.insert(0, "ROI", list(roi_columns))
+    path = out_dir / f"roi_significance_{dataset_name}.csv"
+    df.to_csv(path, index=False)
+    return path
+
+
 # ---- the reference's input layout (SURVEY.md appendix A) -----------------------------------------------------------
 # data/<resource>/y.csv: IID, participant_id, DIA, AGE, PTGENDER (+ FI for HCPimage); data/<resource>/<modality>.csv:
 # IID + the ROI columns.  multimodal_kfold_train_cvae_supervised.py:49-50, 84-91 and utils.py:110-168 read them per

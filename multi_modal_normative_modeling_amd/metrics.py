@@ -7,7 +7,8 @@ Scores stay on the GPU (they are the per-subject mean deviations the forward pas
 [n_sets, 8] fp64 result table comes back.
 `roi_effect` = cliff_delta of utils.py:97-109 for every ROI column of many tables at once (one workgroup per table and
 64 columns), on the ROI-wise squared errors where the evaluation jobs exported them; `cliff_delta` is the reference's
-signature on top of it.
+signature on top of it.  `roi_significance` = the Mann-Whitney test per ROI column of the same tables with its
+Benjamini-Hochberg q and the max-statistic label-permutation test; `mann_whitney` is scipy's two-sample signature on top of it.
 """
 from __future__ import annotations
 
@@ -23,6 +24,7 @@ from .engine import _stream_ptr, require_gpu
 POSTHOC_COLUMNS = ("roc_auc", "threshold", "accuracy", "recall", "specificity", "significance_ratio", "n_pos", "n_neg")
 CONFUSION_COLUMNS = ("accuracy", "auroc", "sensitivity", "specificity", "f1_score", "precision", "n_pos", "n_neg")
 ROI_EFFECT_COLUMNS = ("cliff_delta", "auc", "n_more", "n_less", "n_x", "n_y", "mean_x", "mean_y")
+ROI_SIGNIFICANCE_COLUMNS = ("u_x", "tie_term", "z", "p_mwu", "q_bh", "p_perm", "p_maxt", "n_perm")
 
 
 def _segments(parts: Sequence[torch.Tensor], device, dtype):
@@ -85,11 +87,8 @@ def _roi_table(mats: Sequence[torch.Tensor], groups: Sequence[torch.Tensor]):
     return table
 
 
-def roi_effect(mats: Sequence[torch.Tensor], groups: Sequence, device=None) -> torch.Tensor:
-    """[n_sets, D, 8] fp64 on the device, per (set, ROI column): cliff_delta, auc, n_more, n_less, n_x, n_y, mean_x, mean_y
-    (ROI_EFFECT_COLUMNS; include/nmhip.h has the definitions).  mats[k]: a [n_k, D] fp32 device tensor of any row stride
-    and unit column stride -- a view such as job.out_sqerr[m][:n] is read where it lies; groups[k]: n_k entries, 1 = X
-    (the patients), 0 = Y (the controls), any other value leaves the row out.  One launch for all sets."""
+def _roi_check(mats: Sequence[torch.Tensor], groups: Sequence) -> int:
+    """The argument checks nm_roi_effect's and nm_roi_significance's host functions share (no device is looked for); D."""
     if len(mats) == 0:
         raise ValueError("no ROI tables")
     if len(mats) != len(groups):
@@ -110,6 +109,11 @@ def roi_effect(mats: Sequence[torch.Tensor], groups: Sequence, device=None) -> t
             raise ValueError(f"set {k}: row stride {m.stride(0)} below the {D} columns")
         if int(torch.as_tensor(groups[k]).numel()) != int(m.shape[0]):
             raise ValueError(f"set {k}: one group entry per row is needed")
+    return D
+
+
+def _roi_upload(mats: Sequence[torch.Tensor], groups: Sequence, device):
+    """The device, the group words on it and the pointer table's bytes (host) of checked inputs."""
     dev = require_gpu(device if device is not None else (mats[0].device if mats[0].is_cuda else None))
     if dev.index is None:
         dev = torch.device(dev.type, torch.cuda.current_device())
@@ -117,25 +121,108 @@ def roi_effect(mats: Sequence[torch.Tensor], groups: Sequence, device=None) -> t
         if m.device != dev:
             raise ValueError(f"set {k} is on {m.device}, not on {dev}: the tables are read where they lie")
     grp = [torch.as_tensor(g).reshape(-1).to(device=dev, dtype=torch.int32).contiguous() for g in groups]
-    sets = torch.frombuffer(bytearray(bytes(_roi_table(mats, grp))), dtype=torch.uint8).to(dev)
+    return dev, grp, bytes(_roi_table(mats, grp))
+
+
+def roi_effect(mats: Sequence[torch.Tensor], groups: Sequence, device=None) -> torch.Tensor:
+    """[n_sets, D, 8] fp64 on the device, per (set, ROI column): cliff_delta, auc, n_more, n_less, n_x, n_y, mean_x, mean_y
+    (ROI_EFFECT_COLUMNS; include/nmhip.h has the definitions).  mats[k]: a [n_k, D] fp32 device tensor of any row stride
+    and unit column stride -- a view such as job.out_sqerr[m][:n] is read where it lies; groups[k]: n_k entries, 1 = X
+    (the patients), 0 = Y (the controls), any other value leaves the row out.  One launch for all sets."""
+    D = _roi_check(mats, groups)
+    dev, grp, table = _roi_upload(mats, groups, device)
+    sets = torch.frombuffer(bytearray(table), dtype=torch.uint8).to(dev)
     out = torch.empty(len(mats), D, _lib.NM_METRICS_STRIDE, dtype=torch.float64, device=dev)
     _lib.check(_lib.load().nm_roi_effect(sets.data_ptr(), len(mats), D, max(max(int(m.shape[0]) for m in mats), 1),
                                           out.data_ptr(), _stream_ptr(dev)), "nm_roi_effect")
     return out
 
 
-def cliff_delta(X, Y, device=None):
-    """cliff_delta(X, Y) of utils.py:97-109 on the device: 1-D inputs give a float, [n, D] inputs a [D] numpy array (one
-    delta per column).  len(X) + len(Y) <= NM_METRICS_MAX_N."""
+# nm_roi_significance's workspace above this many bytes: the sets run in consecutive groups that fit
+ROI_SIGNIFICANCE_WORKSPACE_CAP = 1 << 30
+
+
+ROI_SIGNIFICANCE_MAX_D = 8192
+
+
+def _perm_args(n_perm, seed):
+    n_perm, seed = int(n_perm), int(seed)
+    if not 0 <= n_perm <= _lib.NM_ROI_MAX_PERM:
+        raise ValueError(f"n_perm must lie in 0..{_lib.NM_ROI_MAX_PERM}, got {n_perm}")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must be an unsigned 64-bit integer, got {seed}")
+    return n_perm, seed
+
+
+def roi_significance(mats: Sequence[torch.Tensor], groups: Sequence, n_perm: int = 0, seed: int = 0, device=None,
+                     return_maxstat: bool = False):
+    """[n_sets, D, 8] fp64 on the device, per (set, ROI column): u_x, tie_term, z, p_mwu, q_bh, p_perm, p_maxt, n_perm
+    (ROI_SIGNIFICANCE_COLUMNS; include/nmhip.h has the definitions): the Mann-Whitney U of X with its tie-corrected,
+    continuity-corrected asymptotic two-sided p, the Benjamini-Hochberg q over the set's valid columns, and with n_perm > 0
+    (at most NM_ROI_MAX_PERM) the label-permutation p-values of |S| per column and against the maximum over the columns
+    (family-wise error control over the ROIs).  mats and groups as for roi_effect; a column with a NaN in an included row,
+    and every column of a set with an empty group, is NaN throughout.  return_maxstat: also the [n_sets, n_perm] int32
+    null distribution of the maximum (-1 for a set without a valid column).
+
+    The rows of a set are taken as independent observations: a cohort recipe that repeats a subject across folds makes the
+    p-values of the pooled rows too small.
+
+    The workspace comes from nm_roi_significance_workspace; above ROI_SIGNIFICANCE_WORKSPACE_CAP the sets run in
+    consecutive groups of a power of two that fit, set k keeping its own index in the permutation hash (the group's
+    offset goes into the seed, as include/nmhip.h describes).  The same seed gives the same bytes."""
+    D = _roi_check(mats, groups)
+    n_perm, seed = _perm_args(n_perm, seed)
+    if D > ROI_SIGNIFICANCE_MAX_D:
+        raise ValueError(f"at most {ROI_SIGNIFICANCE_MAX_D} columns (the Benjamini-Hochberg sort's limit), got {D}")
+    dev, grp, table = _roi_upload(mats, groups, device)
+    lib, n_sets, entry = _lib.load(), len(mats), C.sizeof(_lib.NmRoiSet)
+    max_rows = max(max(int(m.shape[0]) for m in mats), 1)
+    per = 1 << (n_sets - 1).bit_length()                   # sets per launch: the largest power of two whose workspace fits
+    while per > 1 and lib.nm_roi_significance_workspace(min(per, n_sets), D, max_rows, n_perm) > ROI_SIGNIFICANCE_WORKSPACE_CAP:
+        per >>= 1
+    need = int(lib.nm_roi_significance_workspace(min(per, n_sets), D, max_rows, n_perm))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    out = torch.empty(n_sets, D, _lib.NM_METRICS_STRIDE, dtype=torch.float64, device=dev)
+    maxstat = torch.empty(n_sets, n_perm, dtype=torch.int32, device=dev) if return_maxstat else None
+    for k0 in range(0, n_sets, per):
+        k1 = min(k0 + per, n_sets)
+        sets = torch.frombuffer(bytearray(table[k0 * entry:k1 * entry]), dtype=torch.uint8).to(dev)
+        _lib.check(lib.nm_roi_significance(sets.data_ptr(), k1 - k0, D, max_rows, n_perm, seed ^ ((k0 << 40) & ((1 << 64) - 1)),
+                                           ws.data_ptr(), need, out[k0:k1].data_ptr(),
+                                           maxstat[k0:k1].data_ptr() if maxstat is not None and n_perm else None,
+                                           _stream_ptr(dev)), "nm_roi_significance")
+    return (out, maxstat) if return_maxstat else out
+
+
+def _two_groups(X, Y):
+    """X over Y as one fp32 [n, D] host matrix with its group words, and whether the inputs were 1-D."""
     x = torch.as_tensor(np.asarray(X.detach().cpu() if isinstance(X, torch.Tensor) else X, dtype=np.float32))
     y = torch.as_tensor(np.asarray(Y.detach().cpu() if isinstance(Y, torch.Tensor) else Y, dtype=np.float32))
     if x.dim() != y.dim() or x.dim() not in (1, 2) or (x.dim() == 2 and x.shape[1] != y.shape[1]):
         raise ValueError(f"X and Y must both be 1-D, or 2-D with the same columns; got {tuple(x.shape)} and {tuple(y.shape)}")
-    flat = x.dim() == 1
     both = torch.cat([x.reshape(len(x), -1), y.reshape(len(y), -1)])
     if both.shape[0] > _lib.NM_METRICS_MAX_N:
         raise ValueError(f"at most {_lib.NM_METRICS_MAX_N} observations in X and Y together, got {both.shape[0]}")
-    dev = require_gpu(device)
     group = torch.cat([torch.ones(len(x), dtype=torch.int32), torch.zeros(len(y), dtype=torch.int32)])
+    return both, group, x.dim() == 1
+
+
+def mann_whitney(X, Y, n_perm: int = 0, seed: int = 0, device=None):
+    """scipy.stats.mannwhitneyu(X, Y, alternative='two-sided', method='asymptotic', use_continuity=True) on the device, with
+    the Benjamini-Hochberg q over the columns and (n_perm > 0) the permutation p-values of roi_significance: a dict of
+    ROI_SIGNIFICANCE_COLUMNS -- floats for 1-D inputs, [D] numpy arrays for [n, D] inputs (one test per column).
+    len(X) + len(Y) <= NM_METRICS_MAX_N; the observations are taken as independent."""
+    both, group, flat = _two_groups(X, Y)
+    n_perm, seed = _perm_args(n_perm, seed)
+    dev = require_gpu(device)
+    tab = roi_significance([both.to(dev)], [group], n_perm=n_perm, seed=seed, device=dev)[0].cpu().numpy()
+    return {name: (float(tab[0, j]) if flat else tab[:, j].copy()) for j, name in enumerate(ROI_SIGNIFICANCE_COLUMNS)}
+
+
+def cliff_delta(X, Y, device=None):
+    """cliff_delta(X, Y) of utils.py:97-109 on the device: 1-D inputs give a float, [n, D] inputs a [D] numpy array (one
+    delta per column).  len(X) + len(Y) <= NM_METRICS_MAX_N."""
+    both, group, flat = _two_groups(X, Y)
+    dev = require_gpu(device)
     delta = roi_effect([both.to(dev)], [group], device=dev)[0, :, 0].cpu().numpy()
     return float(delta[0]) if flat else delta

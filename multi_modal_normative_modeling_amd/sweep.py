@@ -513,6 +513,21 @@ def _roi_effect_sets(mats: Sequence[torch.Tensor], groups: Sequence[np.ndarray],
     return out
 
 
+def _roi_significance_sets(mats: Sequence[torch.Tensor], groups: Sequence[np.ndarray], n_perm: int, seed: int,
+                           device) -> List[torch.Tensor]:
+    """metrics.roi_significance for tables of any widths, as _roi_effect_sets: one call per distinct width; a table's index in
+    the permutation hash is its place among the tables of its width."""
+    by_width: Dict[int, List[int]] = {}
+    for j, x in enumerate(mats):
+        by_width.setdefault(int(x.shape[1]), []).append(j)
+    out: List[Optional[torch.Tensor]] = [None] * len(mats)
+    for idxs in by_width.values():
+        tab = metrics.roi_significance([mats[j] for j in idxs], [groups[j] for j in idxs], n_perm=n_perm, seed=seed, device=device)
+        for a, j in enumerate(idxs):
+            out[j] = tab[a]
+    return out
+
+
 def _roi_columns(roi_columns, m: str, d: int):
     return list(roi_columns[m]) if roi_columns and m in roi_columns else [f"{m}_{k}" for k in range(d)]
 
@@ -520,7 +535,8 @@ def _roi_columns(roi_columns, m: str, d: int):
 def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequence[tuple], modalities: Sequence[str],
                combines, device, out_dirs: Optional[Sequence] = None,
                roi_columns: Optional[Dict[str, Sequence[str]]] = None, roi_effect: bool = False,
-               disease_label=None) -> List[Dict[str, np.ndarray]]:
+               disease_label=None, roi_significance: bool = False, roi_perm: int = 0,
+               roi_seed: int = 0) -> List[Dict[str, np.ndarray]]:
     """test_fold for ALL folds of a procedure as one launch: jobs[i] is the trained model of fold i, folds[i] its
     (train_rows, test_rows); one evaluation job per fold, each on its own test tables (seed, scaler and covariates per fold
     exactly as test_fold), all in ONE JobSet -- a fold's ~N / K test rows are a single workgroup, K of them in a row leave
@@ -534,7 +550,16 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
     diagnosis as the patients), one more the same on the pooled set per modality (all folds' test rows, concatenated on the
     device: the all-folds tables of the test script, :157-178; at most NM_METRICS_MAX_N subjects in all).
     Each fold's dict gains "roi_effect": {modality: [D, 8]} (metrics.ROI_EFFECT_COLUMNS) and "roi_effect_pooled": the pooled
-    tables (the same dict in every fold's result); with out_dirs, roi_effect_<m>.csv next to the five kinds."""
+    tables (the same dict in every fold's result); with out_dirs, roi_effect_<m>.csv next to the five kinds.
+
+    roi_significance (needs roi_effect): metrics.roi_significance on the same tables with roi_perm label permutations and the
+    seed roi_seed -- per ROI the Mann-Whitney U, z and asymptotic p, the Benjamini-Hochberg q over the ROIs and the
+    permutation p-values of the ROI and against the maximum over the ROIs.  Each fold's dict gains "roi_significance":
+    {modality: [D, 8]} (metrics.ROI_SIGNIFICANCE_COLUMNS) and "roi_significance_pooled"; with out_dirs,
+    roi_significance_<m>.csv.  The subjects are taken as independent: a cohort recipe that repeats a subject across folds
+    makes the pooled p-values too small."""
+    if roi_significance and not roi_effect:
+        raise ValueError("roi_significance needs roi_effect=True (the evaluation jobs export the ROI-wise squared errors for it)")
     if len(jobs) != len(folds):
         raise ValueError(f"{len(jobs)} models for {len(folds)} folds")
     combs = [combines] * len(jobs) if isinstance(combines, str) else list(combines)
@@ -551,7 +576,11 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
         grp = [roi_groups(cohort.dia[te], disease_label) for _, te in folds]
         mats = [ev.out_sqerr[i][:len(te)] for (ev, _), (_, te) in zip(evs, folds) for i in range(nm_)]
         per_fold = _roi_effect_sets(mats, [g for g in grp for _ in range(nm_)], device)
-        pooled = _roi_effect_sets([torch.cat(mats[i::nm_]) for i in range(nm_)], [np.concatenate(grp)] * nm_, device)
+        pooled_mats = [torch.cat(mats[i::nm_]) for i in range(nm_)]
+        pooled = _roi_effect_sets(pooled_mats, [np.concatenate(grp)] * nm_, device)
+        if roi_significance:
+            sig_fold = _roi_significance_sets(mats, [g for g in grp for _ in range(nm_)], roi_perm, roi_seed, device)
+            sig_pooled = _roi_significance_sets(pooled_mats, [np.concatenate(grp)] * nm_, roi_perm, roi_seed, device)
     torch.cuda.synchronize(device)
     out = [_fold_results(ev, xs, cohort, te, modalities, d, roi_columns) for (ev, xs), (_, te), d in zip(evs, folds, dirs)]
     if roi_effect:
@@ -562,6 +591,14 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
             if d is not None:
                 for m, tab in res["roi_effect"].items():
                     io.write_roi_effect_csv(Path(d) / m, m, _roi_columns(roi_columns, m, tab.shape[0]), tab)
+    if roi_significance:
+        sig_pooled = {m: sig_pooled[i].cpu().numpy() for i, m in enumerate(modalities)}
+        for f, (res, d) in enumerate(zip(out, dirs)):
+            res["roi_significance"] = {m: sig_fold[f * nm_ + i].cpu().numpy() for i, m in enumerate(modalities)}
+            res["roi_significance_pooled"] = sig_pooled
+            if d is not None:
+                for m, tab in res["roi_significance"].items():
+                    io.write_roi_significance_csv(Path(d) / m, m, _roi_columns(roi_columns, m, tab.shape[0]), tab)
     return out
 
 
@@ -893,8 +930,15 @@ def main_test(argv=None):
     ap.add_argument("--disease-label", dest="disease_label", type=int, default=None,
                     help="with --roi-effect: the one diagnosis (the cohort's DIA value) that counts as patients; default: every "
                          "subject who is not a healthy control")
+    ap.add_argument("--roi-significance", dest="roi_significance", action="store_true",
+                    help="with --roi-effect: also every ROI's Mann-Whitney p, Benjamini-Hochberg q and (with --roi-perm) the "
+                         "max-statistic permutation p: per fold and pooled roi_significance_<m>.csv")
+    ap.add_argument("--roi-perm", dest="roi_perm", type=int, default=0, help="label permutations of --roi-significance (0: none)")
+    ap.add_argument("--roi-seed", dest="roi_seed", type=int, default=0, help="the seed of those permutations")
     _driver_common(ap)
     args = ap.parse_args(argv)
+    if args.roi_significance and not args.roi_effect:
+        ap.error("--roi-significance needs --roi-effect")
     cohort = _cohort_from_args(args)
     mods, combine = workload.procedure_modalities(args.procedure, args.dataset_resourse)
     combine = (args.combine or combine).lower()
@@ -926,7 +970,8 @@ def main_test(argv=None):
         fold_dirs.append(fold_dir)
     # all folds of this rank in one launch (one job per fold on its own test tables)
     results = test_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs,
-                         roi_effect=args.roi_effect, disease_label=args.disease_label) if my else []
+                         roi_effect=args.roi_effect, disease_label=args.disease_label, roi_significance=args.roi_significance,
+                         roi_perm=args.roi_perm, roi_seed=args.roi_seed) if my else []
     for err in results:
         for m in mods:
             errors[m].append(err[m])
@@ -942,6 +987,12 @@ def main_test(argv=None):
             top = int(np.nanargmax(np.abs(tab[:, 0]))) if np.isfinite(tab[:, 0]).any() else 0
             print(f"[test] {args.procedure} {m}: pooled ROI effect, largest |delta| {tab[top, 0]:+.4f} (AUC {tab[top, 1]:.4f}) at ROI {top}",
                   flush=True)
+        if args.roi_significance and results:
+            tab = results[0]["roi_significance_pooled"][m]
+            io.write_roi_significance_csv(out_root / m, m, _roi_columns(None, m, tab.shape[0]), tab)
+            col = 6 if args.roi_perm else 4
+            print(f"[test] {args.procedure} {m}: pooled ROI significance, {int(np.nansum(tab[:, col] <= 0.05))} of {tab.shape[0]} ROIs with "
+                  f"{metrics.ROI_SIGNIFICANCE_COLUMNS[col]} <= 0.05", flush=True)
     if args.latent and my:
         # the folds' train cohorts and test subjects in one latent launch each, one statistics and one score launch
         lat = latent_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs, name=args.procedure)
@@ -999,6 +1050,53 @@ def _analysis_roi(root: Path, mods: Sequence[str], n_splits: int, hc: int, proce
     return out
 
 
+def _analysis_roi_significance(root: Path, mods: Sequence[str], n_splits: int, hc: int, procedure: str, n_perm: int,
+                               seed: int) -> Dict[str, np.ndarray]:
+    """`analysis --roi --roi-significance`: the rows of all folds' reconstruction_error_roi_<m>.csv pooled per modality (at
+    most NM_METRICS_MAX_N in all), one metrics.roi_significance call per table width, and per modality
+    group_analysis_roi_significance_<m>.csv: every ROI with metrics.ROI_SIGNIFICANCE_COLUMNS, sorted by p_maxt, then by q_bh,
+    under a comment line with n_x, n_y, n_perm and seed.  The pooled rows are taken as independent: a cohort recipe that
+    repeats a subject across folds makes these p-values too small.  Returns {modality: [D, 8]} in the files' ROI order."""
+    import os
+    import pandas as pd
+    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+    rows: Dict[str, list] = {m: [] for m in mods}
+    grp: Dict[str, list] = {m: [] for m in mods}
+    cols: Dict[str, list] = {}
+    for k in range(n_splits):
+        files = [root / f"{k:03d}" / m / f"reconstruction_error_roi_{m}.csv" for m in mods]
+        if not all(f.exists() for f in files):
+            continue
+        for m, f in zip(mods, files):
+            df = pd.read_csv(f, float_precision="round_trip")
+            dia = df["DIA"].to_numpy()
+            healthy = (dia == 1) if set(np.unique(dia)) <= {0, 1} else (dia == hc)
+            roi = [c for c in df.columns if c not in io.META_COLS]
+            if cols.setdefault(m, roi) != roi:
+                raise ValueError(f"{f}: ROI columns differ from the first fold's")
+            rows[m].append(np.ascontiguousarray(df[roi].to_numpy(dtype=np.float32)))
+            grp[m].append(np.where(healthy, 0, 1).astype(np.int32))
+    if not cols:
+        raise FileNotFoundError(f"no reconstruction_error_roi_*.csv of {list(mods)} under {root}/<fold>/ -- run the `test` subcommand first")
+    mats = [torch.as_tensor(np.concatenate(rows[m])).to(device) for m in mods]
+    groups = [np.concatenate(grp[m]) for m in mods]
+    tabs = _roi_significance_sets(mats, groups, n_perm, seed, device)      # (more than NM_METRICS_MAX_N rows: its ValueError)
+    out = {}
+    for m, tab, g in zip(mods, tabs, groups):
+        out[m] = tab = tab.cpu().numpy()
+        df = pd.DataFrame(tab, columns=list(metrics.ROI_SIGNIFICANCE_COLUMNS))
+        df.insert(0, "ROI", cols[m])
+        big = np.finfo(np.float64).max                                     # (NaN last: no permutations, or a column that is not valid)
+        order = np.lexsort((np.nan_to_num(tab[:, 4], nan=big), np.nan_to_num(tab[:, 6], nan=big)))
+        with open(root / f"group_analysis_roi_significance_{m}.csv", "w", newline="") as fh:
+            fh.write(f"# n_x={int((g == 1).sum())} n_y={int((g == 0).sum())} n_perm={n_perm} seed={seed}\n")
+            df.iloc[order].to_csv(fh, index=False)
+        print(f"[analysis] {procedure} {m}: {len(g)} pooled subjects, {len(cols[m])} ROIs, {n_perm} permutations; smallest p-values:", flush=True)
+        for r in order[:10]:
+            print(f"[analysis]   {cols[m][r]}: z {tab[r, 2]:+.3f}  p {tab[r, 3]:.3g}  q_bh {tab[r, 4]:.3g}  p_maxt {tab[r, 6]:.3g}", flush=True)
+    return out
+
+
 def main_analysis(argv=None):
     """multimodal_kfold_cvae_group_analysis_1x1.py:160-235 on the files the `test` subcommand wrote: per fold the subjects'
     reconstruction errors averaged over the procedure's modalities (:205-209), healthy vs disease ROC-AUC, Youden-J
@@ -1020,10 +1118,19 @@ def main_analysis(argv=None):
     ap.add_argument("--roi", action="store_true",
                     help="instead: which ROIs separate patients from controls -- per fold and modality every ROI's Cliff's delta and "
                          "ROC-AUC on reconstruction_error_roi_<m>.csv, their mean and std over folds to group_analysis_roi_<m>.csv")
+    ap.add_argument("--roi-significance", dest="roi_significance", action="store_true",
+                    help="with --roi: on the pooled rows of all folds every ROI's Mann-Whitney p, Benjamini-Hochberg q and (with "
+                         "--roi-perm) max-statistic permutation p, to group_analysis_roi_significance_<m>.csv")
+    ap.add_argument("--roi-perm", dest="roi_perm", type=int, default=0, help="label permutations of --roi-significance (0: none)")
+    ap.add_argument("--roi-seed", dest="roi_seed", type=int, default=0, help="the seed of those permutations")
     args = ap.parse_args(argv)
+    if args.roi_significance and not args.roi:
+        ap.error("--roi-significance needs --roi")
     mods, _ = workload.procedure_modalities(args.procedure, args.dataset_resourse)
     root = Path(args.models_dir) / args.dataset_resourse / args.procedure
     hc = prep.HC_LABEL.get(args.dataset_resourse, 1)
+    if args.roi and args.roi_significance:
+        return _analysis_roi_significance(root, mods, args.n_splits, hc, args.procedure, args.roi_perm, args.roi_seed)
     if args.roi:
         return _analysis_roi(root, mods, args.n_splits, hc, args.procedure)
     scores, positive, folds = [], [], []
