@@ -523,6 +523,49 @@ size_t nm_roi_significance_workspace(int n_sets, int D, int max_rows, int n_perm
 int nm_roi_significance(const nm_roi_set_t* sets_dev, int n_sets, int D, int max_rows, int n_perm, uint64_t seed,
                         void* workspace, size_t workspace_bytes, double* out, int32_t* maxstat_out, void* stream);
 
+/* Bootstrap of the per-subject ROC-AUC and the paired comparison of two procedures' AUCs.  Sets are the segments
+ * [offsets[k], offsets[k+1]) of scores (fp32) and labels (int32, != 0 = positive), as for nm_posthoc_metrics; n is a set's size.
+ * A set is valid if 1 <= n <= max_set <= NM_METRICS_MAX_N, n_pos >= 1, n_neg >= 1, no score is NaN and its stream id lies
+ * in 0..2^24 - 1.  Equality is IEEE ==: -0 == +0, inf == inf is a tie.  Positives in row order are p[0..n_pos), negatives
+ * in row order q[0..n_neg).
+ *   A2        sum over (i in P, j in Q) of 2 [s_i > s_j] + [s_i == s_j], an integer <= 2 n_pos n_neg <= 2^25
+ *   roc_auc   double(A2) / double(2 n_pos n_neg), one division
+ *   resample b = 1..n_boot (1 <= n_boot <= NM_BOOT_MAX) of a set with stream id sigma, stratified (the denominator stays
+ *     fixed, a resample is never one-class): draw u = 0..n-1 takes h = splitmix64(seed ^ 0xB0075712A9 ^ (sigma << 40) ^
+ *     (b << 16) ^ u), hi = h >> 32; for u < n_pos the positive p[(hi n_pos) >> 32], otherwise the negative
+ *     q[(hi n_neg) >> 32].  A2*_b = A2 of the drawn multiset, an int32.
+ *   streams[k] (NULL: k) is set k's stream id: sets with the same stream id and the same labels draw the same subjects in
+ *     every resample.  A set's result depends on (scores, labels, seed, stream id) only, not on its place in the launch.
+ * out [n_sets][NM_METRICS_STRIDE] fp64 = {roc_auc, ci_lo, ci_hi, boot_mean, boot_se, n_boot, n_pos, n_neg}:
+ *   ci_lo / ci_hi  double(sorted(A2*)[lo_index]) / double(2 n_pos n_neg), and [hi_index]; 0 <= lo_index <= hi_index < n_boot
+ *                  are the caller's (no quantile position is rounded on the device)
+ *   boot_mean      double(sum_b A2*_b) / double(n_boot 2 n_pos n_neg), integers until the one division
+ *   boot_se        sqrt(double(T) / double(n_boot (n_boot - 1))) / double(2 n_pos n_neg) with the integer
+ *                  T = n_boot sum_b (A2*_b)^2 - (sum_b A2*_b)^2 (the sample standard deviation, ddof 1; NaN for n_boot = 1)
+ *   A set that is not valid gets NaN in all eight columns.
+ * pairs [n_pairs][2] (device int32; may be NULL with n_pairs = 0) are set indices (a, c).  A pair is valid if both indices
+ * lie in 0..n_sets-1, both sets are valid, their stream ids and their n are equal and their labels agree row by row (all
+ * checked on the device); d_b = A2*_{a,b} - A2*_{c,b}.
+ * pairs_out [n_pairs][NM_METRICS_STRIDE] fp64 = {delta_auc, ci_lo, ci_hi, boot_mean, boot_se, p_boot, n_le0, n_ge0}:
+ *   delta_auc  double(A2_a - A2_c) / double(2 n_pos n_neg);  ci, mean and se as above, of d_b
+ *   n_le0 = #{d_b <= 0}, n_ge0 = #{d_b >= 0};  p_boot = min(1, double(2 (1 + min(n_le0, n_ge0))) / double(1 + n_boot))
+ *   An invalid pair gets a NaN row.
+ * boot_out (may be NULL) [n_sets][n_boot] int32: the A2*_b in resample order, -1 for a set that is not valid.
+ * Every output element is written on every call; no floating-point atomics (integer LDS atomics only, whose sum has no
+ * order): two runs give the same bytes.  workspace: device memory of at least nm_auc_bootstrap_workspace(...) bytes (0 for
+ * arguments no launch accepts), 256-byte aligned, contents irrelevant.
+ * Status, decided before the device is asked anything: NM_E_NULL: scores, labels, offsets, workspace or out missing, pairs
+ * or pairs_out missing with n_pairs > 0; NM_E_METRICS: n_sets < 1, max_set outside 1..NM_METRICS_MAX_N, n_boot outside
+ * 1..NM_BOOT_MAX, n_pairs < 0, the indices not 0 <= lo_index <= hi_index < n_boot, workspace_bytes below the query's
+ * answer, or a grid beyond 2^31 - 1 workgroups.  NM_BOOT_CHUNK: the resamples one workgroup of the resample pass takes. */
+#define NM_BOOT_MAX   16384
+#define NM_BOOT_CHUNK 64
+size_t nm_auc_bootstrap_workspace(int n_sets, int max_set, int n_boot, int n_pairs);
+int nm_auc_bootstrap(const float* scores, const int32_t* labels, const int32_t* offsets, const int32_t* streams,
+                     int n_sets, int max_set, int n_boot, int lo_index, int hi_index, uint64_t seed,
+                     const int32_t* pairs, int n_pairs, void* workspace, size_t workspace_bytes,
+                     double* out, double* pairs_out, int32_t* boot_out, void* stream);
+
 /* The expert-fusion operators the reference exposes as public methods, as forward-only launches (elementwise over
  * [M][n] fp32 device tensors; csrc/nm_fusion.hip):
  *   cVAE_multimodal.combine_latent(mus, variances, combine)                      cVAE.py:1144-1164   (also :2292-2307)

@@ -58,6 +58,10 @@ NM_ROI_Y_CHUNK = 128
 NM_ROI_MAX_PERM = 65535
 NM_ROI_PERM_CHUNK = 64
 NM_ROI_ROW_CHUNK = 256
+# nm_auc_bootstrap: the most resamples (the close pass holds them in LDS), the resamples a workgroup of its resample pass
+# takes (tests put n_boot around it)
+NM_BOOT_MAX = 16384
+NM_BOOT_CHUNK = 64
 
 # status codes (nmhip.h; nm_status_string gives the text)
 NM_OK = 0
@@ -210,6 +214,9 @@ def load():
     lib.nm_roi_significance_workspace.restype = C.c_size_t
     lib.nm_roi_significance_workspace.argtypes = [i32, i32, i32, i32]
     lib.nm_roi_significance.argtypes = [vp, i32, i32, i32, i32, C.c_uint64, vp, C.c_size_t, vp, vp, vp]
+    lib.nm_auc_bootstrap_workspace.restype = C.c_size_t
+    lib.nm_auc_bootstrap_workspace.argtypes = [i32, i32, i32, i32]
+    lib.nm_auc_bootstrap.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, C.c_uint64, vp, i32, vp, C.c_size_t, vp, vp, vp, vp]
     lib.nm_adam_step.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, i64, vp]
     lib.nm_pack_table.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp]
     lib.nm_prep_scaler_fit.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp]
@@ -238,6 +245,7 @@ EXPORTED_SYMBOLS = [
     "nm_launch_rowsplit_mixed", "nm_rowsplit_groups", "nm_devpass_multi", "nm_devpass_multi_ok",
     "nm_latent_pass", "nm_latent_pass_ok", "nm_latent_stats", "nm_latent_score",
     "nm_roi_effect", "nm_roi_significance_workspace", "nm_roi_significance",
+    "nm_auc_bootstrap_workspace", "nm_auc_bootstrap",
 ]
 
 

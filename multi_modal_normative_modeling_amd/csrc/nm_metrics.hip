@@ -12,7 +12,9 @@
 //   nm_roi_effect         ROI-wise squared errors of two groups -> Cliff's delta, ROC-AUC, pair counts, group means per ROI
 //                         (cliff_delta, utils.py:97-109, once per column; further down in this file)
 //   nm_roi_significance   the same tables -> Mann-Whitney U, z and asymptotic p per ROI, Benjamini-Hochberg q, and the
-//                         label-permutation p-values, per ROI and against the maximum over the ROIs (at the end)
+//                         label-permutation p-values, per ROI and against the maximum over the ROIs
+//   nm_auc_bootstrap      score sets -> the ROC-AUC with its stratified-bootstrap percentile interval, mean and standard error,
+//                         and for pairs of sets on the same subjects the difference with its interval and p (at the end)
 //
 // One workgroup per score set (a (fold, procedure) cell); sets are segments of one concatenated array.  The
 // whole set lives in LDS: order-preserving 64-bit keys (score, label) are bitonic-sorted descending, label
@@ -815,6 +817,308 @@ __global__ __launch_bounds__(MT) void roi_close_kernel(const int32_t* __restrict
     out[((int64_t)s * D + idx[j]) * NM_METRICS_STRIDE + 4] = fmin(1.0, fmin(v[j], tail));
 }
 
+// ---- bootstrap of the per-subject ROC-AUC, paired comparison (include/nmhip.h has the definitions) ---------------------
+// nm_auc_bootstrap, three launches on one stream over a workspace:
+//   prepare   one workgroup per set: the (value key, ordinal within its class, is-positive) triples as 64-bit keys, sorted
+//             once in LDS; the distinct values numbered g = 0..G-1 (a scan over the boundaries); per positive ordinal and per
+//             negative ordinal its value group (uint16, positives first); G, n_pos, n_neg, A2 and the validity to info.
+//   resample  one workgroup per (set, NM_BOOT_CHUNK resamples), a wave per resample in flight.  With V the histogram of the
+//             resample's negative draws over the value groups and C its inclusive prefix sum (C[-1] = 0),
+//             A2* = sum over positive draws of C[g - 1] + C[g]  (= 2 #{smaller negatives} + #{equal negatives}):
+//             n_neg hashed increments into the wave's LDS histogram, one wave scan over G bins, n_pos hashed gathers.  No
+//             sort and no float per resample.  The LDS is sized from max_set: the set's groups once, a histogram per wave.
+//   close     one workgroup per set and per pair: the n_boot integers (differences) as biased uint32 keys in LDS, the two
+//             order statistics by radix selection over them (no sort: two of n_boot ranks are asked for), the counts, and the
+//             sums as integers: sum d in int64, sum (d - m)^2 about the integer
+//             m = sum d / n_boot in 128 bits, so T = n_boot sum (d - m)^2 - (sum d - n_boot m)^2 is exact.
+// Integer LDS atomics only (their sum has no order).
+constexpr int BOOT_CHUNK = NM_BOOT_CHUNK;
+constexpr int BOOT_WAVES = MT / 64;
+constexpr int BOOT_INFO = 8;                       // int32 per set: n, n_pos, n_neg, G, A2, valid, stream id, 0
+static_assert(BOOT_CHUNK % BOOT_WAVES == 0, "every wave of the resample pass makes the same number of rounds");
+static_assert(NM_BOOT_MAX * 4 <= 64 * 1024, "the close pass holds n_boot int32 in LDS");
+static_assert(MT == 256, "the close pass's radix selection has a bin per thread");
+
+struct BootPlan {                                  // byte offsets into the workspace, each a multiple of 256
+  size_t info, grp, boot, total;
+  int chunks, hpitch, grp_lds, resample_lds;
+};
+inline BootPlan boot_plan(int n_sets, int max_set, int n_boot) {
+  BootPlan p;
+  const size_t ns = (size_t)n_sets;
+  size_t o = 0;
+  auto take = [&o](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
+  p.info = take(ns * BOOT_INFO * 4);               // int32  [set][BOOT_INFO]
+  p.grp = take(ns * (size_t)max_set * 2);          // uint16 [set][max_set]: the positives' groups, then the negatives'
+  p.boot = take(ns * (size_t)n_boot * 4);          // int32  [set][n_boot]
+  p.total = o;
+  p.chunks = (n_boot + BOOT_CHUNK - 1) / BOOT_CHUNK;
+  p.hpitch = max_set + 1;                          // a wave's histogram: C[-1] and at most max_set groups
+  p.grp_lds = (max_set * 2 + 15) & ~15;
+  p.resample_lds = p.grp_lds + BOOT_WAVES * p.hpitch * 4;
+  return p;
+}
+
+__global__ __launch_bounds__(MT) void boot_prepare_kernel(const float* __restrict__ scores, const int32_t* __restrict__ labels,
+                                                          const int32_t* __restrict__ offsets, const int32_t* __restrict__ streams,
+                                                          int max_set, int npad_max, uint16_t* __restrict__ grp,
+                                                          int32_t* __restrict__ info) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint64_t* key = reinterpret_cast<uint64_t*>(smem);            // [npad_max]: value key << 32 | ordinal << 1 | is positive
+  int32_t* arr = reinterpret_cast<int32_t*>(key + npad_max);    // [npad_max]: label prefix sums, then the group numbers
+  __shared__ int32_t part[MT];
+  __shared__ long long red[MT];
+  const int s = blockIdx.x, t = threadIdx.x;
+  const int base = offsets[s], n = offsets[s + 1] - base;
+  int32_t* inf = info + (int64_t)s * BOOT_INFO;
+  const int32_t sg = streams ? streams[s] : s;
+  if (n < 1 || n > max_set || sg < 0 || sg >= (1 << 24)) {
+    if (t < BOOT_INFO) inf[t] = 0;
+    return;
+  }
+  int npad = 2;
+  while (npad < n) npad <<= 1;
+  for (int i = t; i < npad; i += MT) arr[i] = (i < n && labels[base + i] != 0) ? 1 : 0;
+  __syncthreads();
+  block_scan(arr, npad, part);
+  const int npos = arr[n - 1], nneg = n - npos;
+  int nan = 0;
+  for (int i = t; i < npad; i += MT) {
+    uint64_t k = ~0ull;
+    if (i < n) {
+      const float v = scores[base + i];
+      nan |= (v != v);
+      const int c = arr[i], before = (i > 0) ? arr[i - 1] : 0;
+      const uint32_t pos = (uint32_t)(c - before);
+      const uint32_t ord = pos ? (uint32_t)(c - 1) : (uint32_t)(i - c);
+      k = ((uint64_t)asc_key(v) << 32) | (uint64_t)(ord << 1) | (uint64_t)pos;
+    }
+    key[i] = k;
+  }
+  const int bad = __syncthreads_or(nan);
+  if (bad || npos < 1 || nneg < 1) {
+    if (t < BOOT_INFO) inf[t] = 0;
+    return;
+  }
+  sort_keys(key, npad);
+  for (int i = t; i < npad; i += MT)
+    arr[i] = (i > 0 && i < n && (uint32_t)(key[i] >> 32) != (uint32_t)(key[i - 1] >> 32)) ? 1 : 0;
+  __syncthreads();
+  block_scan(arr, npad, part);                     // arr[j]: the value group of sorted position j
+  const int G = arr[n - 1] + 1;
+  __syncthreads();
+  uint16_t* gs = grp + (int64_t)s * max_set;
+  for (int j = t; j < n; j += MT) {
+    const uint32_t low = (uint32_t)key[j], pos = low & 1u, ord = (low >> 1) & 0x1FFFu;
+    gs[pos ? ord : (uint32_t)npos + ord] = (uint16_t)arr[j];
+    arr[j] = (arr[j] << 1) | (int32_t)pos;
+  }
+  __syncthreads();                                 // the keys are used up: their place takes the histogram
+  int32_t* hist = reinterpret_cast<int32_t*>(key); // [G + 1] <= n + 1 <= 2 npad
+  for (int g = t; g <= G; g += MT) hist[g] = 0;
+  __syncthreads();
+  for (int j = t; j < n; j += MT)
+    if (!(arr[j] & 1)) atomicAdd(&hist[(arr[j] >> 1) + 1], 1);
+  __syncthreads();
+  block_scan(hist, G + 1, part);                   // hist[g + 1] = C[g], hist[0] = C[-1] = 0
+  long long a2 = 0;
+  for (int j = t; j < n; j += MT)
+    if (arr[j] & 1) { const int g = arr[j] >> 1; a2 += hist[g] + hist[g + 1]; }
+  red[t] = a2;
+  __syncthreads();
+  if (t == 0) {
+    long long A2 = 0;
+    for (int q = 0; q < MT; ++q) A2 += red[q];
+    inf[0] = n; inf[1] = npos; inf[2] = nneg; inf[3] = G; inf[4] = (int32_t)A2; inf[5] = 1; inf[6] = sg; inf[7] = 0;
+  }
+}
+
+__global__ __launch_bounds__(MT) void boot_resample_kernel(const int32_t* __restrict__ info, const uint16_t* __restrict__ grp,
+                                                           int max_set, int grp_lds, int hpitch, int n_boot, int chunks,
+                                                           uint64_t seed, int32_t* __restrict__ boot) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int s = blockIdx.x / chunks, chunk = blockIdx.x - s * chunks;
+  const int32_t* inf = info + (int64_t)s * BOOT_INFO;
+  const int b0 = chunk * BOOT_CHUNK;               // the chunk's first resample, 0-based
+  const int nb = min(BOOT_CHUNK, n_boot - b0);
+  int32_t* bo = boot + (int64_t)s * n_boot + b0;
+  if (!inf[5]) {
+    if (t < nb) bo[t] = -1;
+    return;
+  }
+  const int n = inf[0], npos = inf[1], nneg = inf[2], G = inf[3];
+  uint16_t* gl = reinterpret_cast<uint16_t*>(smem);                              // [n]: positives' groups, then negatives'
+  int32_t* hist = reinterpret_cast<int32_t*>(smem + grp_lds) + w * hpitch;       // this wave's [G + 1]
+  const uint16_t* gs = grp + (int64_t)s * max_set;
+  for (int i = t; i < n; i += MT) gl[i] = gs[i];
+  const uint64_t fixed = seed ^ 0xB0075712A9ull ^ ((uint64_t)(uint32_t)inf[6] << 40);
+  for (int r = 0; r < BOOT_CHUNK / BOOT_WAVES; ++r) {
+    const int q = r * BOOT_WAVES + w;              // this wave's resample within the chunk
+    const bool live = q < nb;
+    const uint64_t hb = fixed ^ ((uint64_t)(b0 + q + 1) << 16);
+    for (int g = lane; g <= G; g += 64) hist[g] = 0;
+    __syncthreads();                               // (in the first round also: the groups are in place)
+    if (live) {
+      for (int u = lane; u < nneg; u += 64) {
+        const uint32_t hi = (uint32_t)(sig_splitmix64(hb ^ (uint64_t)(npos + u)) >> 32);
+        atomicAdd(&hist[(int)gl[npos + (int)__umulhi(hi, (uint32_t)nneg)] + 1], 1);
+      }
+    }
+    __syncthreads();
+    int carry = 0;                                 // inclusive prefix sums of hist[1..G], 64 bins at a time
+    for (int g0 = 1; g0 <= G; g0 += 64) {
+      const int g = g0 + lane;
+      int v = (g <= G) ? hist[g] : 0;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const int o = __shfl_up(v, off, 64);
+        if (lane >= off) v += o;
+      }
+      v += carry;
+      if (g <= G) hist[g] = v;
+      carry = __shfl(v, 63, 64);
+    }
+    __syncthreads();
+    int acc = 0;
+    if (live) {
+      for (int u = lane; u < npos; u += 64) {
+        const uint32_t hi = (uint32_t)(sig_splitmix64(hb ^ (uint64_t)u) >> 32);
+        const int g = gl[__umulhi(hi, (uint32_t)npos)];
+        acc += hist[g] + hist[g + 1];
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if (live && lane == 0) bo[q] = acc;
+    __syncthreads();                               // every gather is done before the next round clears the histogram
+  }
+}
+
+__global__ __launch_bounds__(MT) void boot_close_kernel(const int32_t* __restrict__ info, const int32_t* __restrict__ boot,
+                                                        const int32_t* __restrict__ labels, const int32_t* __restrict__ offsets,
+                                                        const int32_t* __restrict__ pairs, int n_sets, int n_boot,
+                                                        int lo_index, int hi_index, double* __restrict__ out,
+                                                        double* __restrict__ pairs_out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint32_t* key = reinterpret_cast<uint32_t*>(smem);            // [n_boot]: d ^ 0x80000000 (unsigned order = d's order)
+  __shared__ long long rsum[MT];
+  __shared__ unsigned long long rsq[MT];
+  __shared__ int32_t rle[MT], rge[MT], bins[MT];
+  const int t = threadIdx.x;
+  const bool is_pair = (int)blockIdx.x >= n_sets;
+  const double qnan = __longlong_as_double(0x7FF8000000000000ll);
+  int a = blockIdx.x, c = -1;
+  double* o = out + (int64_t)a * NM_METRICS_STRIDE;
+  bool ok;
+  if (!is_pair) {
+    ok = info[(int64_t)a * BOOT_INFO + 5] != 0;
+  } else {
+    const int p = (int)blockIdx.x - n_sets;
+    a = pairs[2 * (int64_t)p]; c = pairs[2 * (int64_t)p + 1];
+    o = pairs_out + (int64_t)p * NM_METRICS_STRIDE;
+    ok = a >= 0 && a < n_sets && c >= 0 && c < n_sets;
+    if (ok) {
+      const int32_t* ia = info + (int64_t)a * BOOT_INFO;
+      const int32_t* ic = info + (int64_t)c * BOOT_INFO;
+      ok = ia[5] && ic[5] && ia[6] == ic[6] && ia[0] == ic[0];
+    }
+    if (ok) {                                      // (the same for every thread so far) the labels, row by row
+      const int n = info[(int64_t)a * BOOT_INFO];
+      const int32_t* la = labels + offsets[a];
+      const int32_t* lc = labels + offsets[c];
+      int diff = 0;
+      for (int i = t; i < n; i += MT) diff |= ((la[i] != 0) != (lc[i] != 0)) ? 1 : 0;
+      ok = !__syncthreads_or(diff);
+    }
+  }
+  if (!ok) {
+    if (t < NM_METRICS_STRIDE) o[t] = qnan;
+    return;
+  }
+  const int32_t* ia = info + (int64_t)a * BOOT_INFO;
+  const int32_t* va = boot + (int64_t)a * n_boot;
+  const int32_t* vc = is_pair ? boot + (int64_t)c * n_boot : nullptr;
+  long long sum = 0;
+  int le = 0, ge = 0;
+  for (int i = t; i < n_boot; i += MT) {
+    const int d = va[i] - (vc ? vc[i] : 0);
+    sum += d; le += (d <= 0) ? 1 : 0; ge += (d >= 0) ? 1 : 0;
+    key[i] = (uint32_t)d ^ 0x80000000u;
+  }
+  rsum[t] = sum; rle[t] = le; rge[t] = ge;
+  __syncthreads();
+  long long total = 0;
+  for (int q = 0; q < MT; ++q) total += rsum[q];
+  const long long m = total / n_boot;              // an integer near the mean: |d - m| <= 2^26
+  unsigned long long sq = 0;                       // at most 64 squares below 2^52 each
+  for (int i = t; i < n_boot; i += MT) {
+    const long long e = (long long)(int32_t)(key[i] ^ 0x80000000u) - m;
+    sq += (unsigned long long)(e * e);
+  }
+  rsq[t] = sq;
+  __syncthreads();
+  // the two order statistics by radix selection, a byte of the key per pass from the top: the histogram of that byte over
+  // the keys that share the bytes chosen so far (LDS integer atomics), then every thread walks the 256 bins alike
+  uint32_t stat_lo = 0, stat_hi = 0;
+  for (int which = 0; which < 2; ++which) {
+    int rank = which ? hi_index : lo_index;        // 0-based, among the keys that still match
+    uint32_t prefix = 0, mask = 0;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+      bins[t] = 0;
+      __syncthreads();
+      for (int i = t; i < n_boot; i += MT) {
+        const uint32_t k = key[i];
+        if ((k & mask) == prefix) atomicAdd(&bins[(k >> shift) & 0xFFu], 1);
+      }
+      __syncthreads();
+      int b = 0, below = 0;
+      for (; b < 255; ++b) {
+        const int c = bins[b];
+        if (below + c > rank) break;
+        below += c;
+      }
+      rank -= below;
+      prefix |= (uint32_t)b << shift;
+      mask |= 0xFFu << shift;
+      __syncthreads();                             // everyone has read the bins before the next pass clears them
+    }
+    if (which) stat_hi = prefix; else stat_lo = prefix;
+  }
+  if (t == 0) {
+    int LE = 0, GE = 0;
+    unsigned long long qlo = 0, qhi = 0;           // sum (d - m)^2 in 128 bits
+    for (int q = 0; q < MT; ++q) {
+      LE += rle[q]; GE += rge[q];
+      const unsigned long long before = qlo;
+      qlo += rsq[q];
+      qhi += (qlo < before) ? 1ull : 0ull;
+    }
+    // T = n_boot * sum (d - m)^2 - r^2, r = sum d - n_boot m (|r| < n_boot): never negative, below 2^81
+    const unsigned long long nb = (unsigned long long)n_boot;
+    unsigned long long tlo = qlo * nb, thi = __umul64hi(qlo, nb) + qhi * nb;
+    const long long r = total - m * (long long)n_boot;
+    const unsigned long long r2 = (unsigned long long)(r * r);
+    thi -= (tlo < r2) ? 1ull : 0ull;
+    tlo -= r2;
+    const double T = (double)thi * 18446744073709551616.0 + (double)tlo;
+    const double den = (double)(2ll * ia[1] * ia[2]);
+    const double lo = (double)(int32_t)(stat_lo ^ 0x80000000u) / den;
+    const double hi = (double)(int32_t)(stat_hi ^ 0x80000000u) / den;
+    const double mean = (double)total / (double)(2ll * ia[1] * ia[2] * (long long)n_boot);
+    const double se = n_boot > 1 ? __dsqrt_rn(T / (double)((long long)n_boot * (n_boot - 1))) / den : qnan;
+    o[1] = lo; o[2] = hi; o[3] = mean; o[4] = se;
+    if (!is_pair) {
+      o[0] = (double)ia[4] / den;
+      o[5] = (double)n_boot; o[6] = (double)ia[1]; o[7] = (double)ia[2];
+    } else {
+      o[0] = (double)(ia[4] - info[(int64_t)c * BOOT_INFO + 4]) / den;
+      o[5] = fmin(1.0, (double)(2ll * (1 + min(LE, GE))) / (double)(1 + n_boot));
+      o[6] = (double)LE; o[7] = (double)GE;
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -904,6 +1208,36 @@ int nm_roi_significance(const nm_roi_set_t* sets_dev, int n_sets, int D, int max
   const int npad = pow2_at_least(D);
   return launch_kernel(roi_close_kernel, dim3(n_sets), dim3(MT), npad * (8 + 2), stream, (const int32_t*)info, (const int32_t*)colS,
                        (const double*)coltie, (const int32_t*)cnt, D, npad, n_perm, out);
+}
+
+size_t nm_auc_bootstrap_workspace(int n_sets, int max_set, int n_boot, int n_pairs) {
+  if (n_sets < 1 || max_set < 1 || max_set > MAXN || n_boot < 1 || n_boot > NM_BOOT_MAX || n_pairs < 0) return 0;
+  return boot_plan(n_sets, max_set, n_boot).total;
+}
+
+int nm_auc_bootstrap(const float* scores, const int32_t* labels, const int32_t* offsets, const int32_t* streams, int n_sets,
+                     int max_set, int n_boot, int lo_index, int hi_index, uint64_t seed, const int32_t* pairs, int n_pairs,
+                     void* workspace, size_t workspace_bytes, double* out, double* pairs_out, int32_t* boot_out, void* stream) {
+  if (!scores || !labels || !offsets || !workspace || !out) return NM_E_NULL;
+  if (n_pairs > 0 && (!pairs || !pairs_out)) return NM_E_NULL;
+  if (n_sets < 1 || max_set < 1 || max_set > MAXN || n_boot < 1 || n_boot > NM_BOOT_MAX || n_pairs < 0) return NM_E_METRICS;
+  if (lo_index < 0 || lo_index > hi_index || hi_index >= n_boot) return NM_E_METRICS;
+  const BootPlan P = boot_plan(n_sets, max_set, n_boot);
+  if (workspace_bytes < P.total) return NM_E_METRICS;
+  if ((int64_t)n_sets * P.chunks > 0x7FFFFFFFll || (int64_t)n_sets + n_pairs > 0x7FFFFFFFll) return NM_E_METRICS;
+  char* ws = static_cast<char*>(workspace);
+  int32_t* info = reinterpret_cast<int32_t*>(ws + P.info);
+  uint16_t* grp = reinterpret_cast<uint16_t*>(ws + P.grp);
+  int32_t* boot = boot_out ? boot_out : reinterpret_cast<int32_t*>(ws + P.boot);
+  const int npad_set = pow2_at_least(max_set);
+  int e = launch_kernel(boot_prepare_kernel, dim3(n_sets), dim3(MT), npad_set * (8 + 4), stream, scores, labels, offsets, streams,
+                        max_set, npad_set, grp, info);
+  if (e) return e;
+  e = launch_kernel(boot_resample_kernel, dim3(n_sets * P.chunks), dim3(MT), P.resample_lds, stream, (const int32_t*)info,
+                    (const uint16_t*)grp, max_set, P.grp_lds, P.hpitch, n_boot, P.chunks, seed, boot);
+  if (e) return e;
+  return launch_kernel(boot_close_kernel, dim3(n_sets + n_pairs), dim3(MT), n_boot * 4, stream, (const int32_t*)info,
+                       (const int32_t*)boot, labels, offsets, pairs, n_sets, n_boot, lo_index, hi_index, out, pairs_out);
 }
 
 }  // extern "C"

@@ -9,6 +9,8 @@ Scores stay on the GPU (they are the per-subject mean deviations the forward pas
 64 columns), on the ROI-wise squared errors where the evaluation jobs exported them; `cliff_delta` is the reference's
 signature on top of it.  `roi_significance` = the Mann-Whitney test per ROI column of the same tables with its
 Benjamini-Hochberg q and the max-statistic label-permutation test; `mann_whitney` is scipy's two-sample signature on top of it.
+`auc_bootstrap` = the per-subject ROC-AUC of many score sets with its stratified-bootstrap percentile interval, and the paired
+comparison of sets that share subjects; `auc_compare` is the two-procedure convenience on top of it.
 """
 from __future__ import annotations
 
@@ -226,3 +228,97 @@ def cliff_delta(X, Y, device=None):
     dev = require_gpu(device)
     delta = roi_effect([both.to(dev)], [group], device=dev)[0, :, 0].cpu().numpy()
     return float(delta[0]) if flat else delta
+
+
+AUC_BOOTSTRAP_COLUMNS = ("roc_auc", "ci_lo", "ci_hi", "boot_mean", "boot_se", "n_boot", "n_pos", "n_neg")
+AUC_COMPARE_COLUMNS = ("delta_auc", "ci_lo", "ci_hi", "boot_mean", "boot_se", "p_boot", "n_le0", "n_ge0")
+AUC_BOOTSTRAP_MAX_STREAM = (1 << 24) - 1
+
+
+def boot_indices(n_boot: int, ci: float):
+    """The two order statistics of a `ci` interval over n_boot resamples: lo = floor((1 - ci) / 2 * (n_boot - 1)) and
+    hi = n_boot - 1 - lo -- np.quantile's method='lower' at (1 - ci) / 2 and method='higher' at (1 + ci) / 2."""
+    lo = int(np.floor((1.0 - ci) / 2.0 * (n_boot - 1)))
+    return lo, n_boot - 1 - lo
+
+
+def _boot_check(scores, positive, n_boot, ci, seed, streams, pairs):
+    """nm_auc_bootstrap's argument checks on the host (no device is looked for): the sizes, n_boot, the two indices, the
+    seed, the stream ids and the pairs as host values."""
+    if len(scores) == 0:
+        raise ValueError("no score sets")
+    if len(scores) != len(positive):
+        raise ValueError("scores and positive must have the same number of sets")
+    sizes = [int(torch.as_tensor(s).numel()) for s in scores]
+    if sizes != [int(torch.as_tensor(p).numel()) for p in positive]:
+        raise ValueError("every score set needs one label per score")
+    if max(sizes) > _lib.NM_METRICS_MAX_N:
+        raise ValueError(f"at most {_lib.NM_METRICS_MAX_N} scores per set, got {max(sizes)}")
+    n_boot, seed, ci = int(n_boot), int(seed), float(ci)
+    if not 1 <= n_boot <= _lib.NM_BOOT_MAX:
+        raise ValueError(f"n_boot must lie in 1..{_lib.NM_BOOT_MAX}, got {n_boot}")
+    if not 0.0 < ci < 1.0:
+        raise ValueError(f"ci must lie in (0, 1), got {ci}")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must be an unsigned 64-bit integer, got {seed}")
+    if streams is not None:
+        streams = [int(v) for v in np.asarray(streams).reshape(-1)]
+        if len(streams) != len(sizes):
+            raise ValueError("one stream id per set")
+        if any(not 0 <= v <= AUC_BOOTSTRAP_MAX_STREAM for v in streams):
+            raise ValueError(f"stream ids must lie in 0..{AUC_BOOTSTRAP_MAX_STREAM}")
+    elif len(sizes) - 1 > AUC_BOOTSTRAP_MAX_STREAM:
+        raise ValueError(f"more than {AUC_BOOTSTRAP_MAX_STREAM + 1} sets need explicit stream ids")
+    if pairs is not None:
+        pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2) if len(pairs) else np.zeros((0, 2), dtype=np.int64)
+        if pairs.size and (pairs.min() < 0 or pairs.max() >= len(sizes)):
+            raise ValueError(f"pair indices must lie in 0..{len(sizes) - 1}")
+    lo, hi = boot_indices(n_boot, ci)
+    return sizes, n_boot, lo, hi, seed, streams, pairs
+
+
+def auc_bootstrap(scores: Sequence[torch.Tensor], positive: Sequence[torch.Tensor], n_boot: int = 2000, ci: float = 0.95,
+                  seed: int = 0, streams=None, pairs=None, device="cuda:0", return_boot: bool = False):
+    """[n_sets, 8] fp64 on the device, per set: roc_auc, ci_lo, ci_hi, boot_mean, boot_se, n_boot, n_pos, n_neg
+    (AUC_BOOTSTRAP_COLUMNS; include/nmhip.h has the definitions): the set's ROC-AUC with the percentile interval, mean and
+    standard error of n_boot stratified bootstrap resamples (positives and negatives are redrawn within their class, as
+    pROC does by default).  scores / positive as for posthoc_metrics.  streams[k] (default k, 0..2^24 - 1) names set k's
+    random stream: sets with the same stream id and the same labels draw the same subjects in every resample.  pairs: a list
+    of set index pairs (a, c); then also [n_pairs, 8] fp64 = delta_auc, ci_lo, ci_hi, boot_mean, boot_se, p_boot, n_le0,
+    n_ge0 (AUC_COMPARE_COLUMNS) of the resamples' differences AUC_a - AUC_c -- NaN unless the two sets share the stream id
+    and the labels.  return_boot: also the [n_sets, n_boot] int32 distribution of A2* = AUC* x 2 n_pos n_neg (-1 for a
+    set that is not valid: one class only, a NaN score, an empty set).
+
+    The rows of a set are taken as independent subjects: a cohort recipe that repeats a subject across folds makes the
+    interval of the pooled rows too narrow.  The same seed gives the same bytes."""
+    sizes, n_boot, lo, hi, seed, streams, pairs = _boot_check(scores, positive, n_boot, ci, seed, streams, pairs)
+    dev = require_gpu(device)
+    s, off, _ = _segments([torch.as_tensor(p) for p in scores], dev, torch.float32)
+    l, _, _ = _segments([torch.as_tensor(p) for p in positive], dev, torch.int32)
+    n_sets, max_set = len(sizes), max(max(sizes), 1)
+    n_pairs = 0 if pairs is None else int(pairs.shape[0])
+    st = torch.tensor(streams, dtype=torch.int32, device=dev) if streams is not None else None
+    pr = torch.as_tensor(pairs, dtype=torch.int32).contiguous().to(dev) if n_pairs else None
+    lib = _lib.load()
+    need = int(lib.nm_auc_bootstrap_workspace(n_sets, max_set, n_boot, n_pairs))
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    out = torch.empty(n_sets, _lib.NM_METRICS_STRIDE, dtype=torch.float64, device=dev)
+    pout = torch.empty(n_pairs, _lib.NM_METRICS_STRIDE, dtype=torch.float64, device=dev) if pairs is not None else None
+    boot = torch.empty(n_sets, n_boot, dtype=torch.int32, device=dev) if return_boot else None
+    _lib.check(lib.nm_auc_bootstrap(s.data_ptr(), l.data_ptr(), off.data_ptr(), st.data_ptr() if st is not None else None,
+                                    n_sets, max_set, n_boot, lo, hi, seed, pr.data_ptr() if pr is not None else None, n_pairs,
+                                    ws.data_ptr(), need, out.data_ptr(), pout.data_ptr() if n_pairs else None,
+                                    boot.data_ptr() if boot is not None else None, _stream_ptr(dev)), "nm_auc_bootstrap")
+    res = (out,) + ((pout,) if pairs is not None else ()) + ((boot,) if return_boot else ())
+    return res if len(res) > 1 else out
+
+
+def auc_compare(scores_a, scores_c, positive, n_boot: int = 2000, ci: float = 0.95, seed: int = 0, device="cuda:0"):
+    """Two procedures' scores of the same subjects: the difference of their ROC-AUCs with its paired stratified-bootstrap
+    interval and two-sided p -- a dict of AUC_COMPARE_COLUMNS (floats)."""
+    a, c, p = (torch.as_tensor(v).reshape(-1) for v in (scores_a, scores_c, positive))
+    if a.numel() != c.numel():
+        raise ValueError(f"both procedures need the same subjects, got {a.numel()} and {c.numel()} scores")
+    _, prs = auc_bootstrap([a, c], [p, p], n_boot=n_boot, ci=ci, seed=seed, streams=[0, 0], pairs=[(0, 1)], device=device)
+    row = prs[0].cpu().numpy()
+    return {name: float(row[j]) for j, name in enumerate(AUC_COMPARE_COLUMNS)}

@@ -18,7 +18,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import io, metrics, prep, workload
+from . import _lib, io, metrics, prep, workload
 from .engine import Job, JobSet, Table
 from .layout import ModelSpec
 
@@ -1097,12 +1097,106 @@ def _analysis_roi_significance(root: Path, mods: Sequence[str], n_splits: int, h
     return out
 
 
+def _analysis_scores(root: Path, mods: Sequence[str], procedure: str, score: str, n_splits: int, hc: int):
+    """The per-subject scores `analysis` works on, read from the files of `test`: per fold present the fp32 score tensor (the
+    modality-averaged reconstruction error, or the latent deviation), the int32 patient flags, the fold number and the
+    participant ids."""
+    import pandas as pd
+    scores, positive, folds, ids = [], [], [], []
+    for k in range(n_splits):
+        if score == "latent":
+            files = [root / f"{k:03d}" / f"latent_deviation_{procedure}.csv"]
+        else:
+            files = [root / f"{k:03d}" / m / f"reconstruction_error_{m}.csv" for m in mods]
+        if not all(f.exists() for f in files):
+            continue
+        dfs = [pd.read_csv(f) for f in files]
+        if score == "latent":
+            err = dfs[0]["Latent deviation"].to_numpy(dtype=np.float64)
+        else:
+            err = sum(d["Reconstruction error"].to_numpy(dtype=np.float64) for d in dfs) / len(dfs)
+        dia = dfs[0]["DIA"].to_numpy()
+        # (files written from a prep.Cohort carry DIA in the cohort's convention 1 = healthy; raw tables the resource's label)
+        healthy = (dia == 1) if set(np.unique(dia)) <= {0, 1} else (dia == hc)
+        scores.append(torch.as_tensor(err, dtype=torch.float32))
+        positive.append(torch.as_tensor(~healthy, dtype=torch.int32))
+        folds.append(k)
+        ids.append(dfs[0]["participant_id"].to_numpy())
+    if not folds and score == "latent":
+        raise FileNotFoundError(f"no latent_deviation_{procedure}.csv under {root}/<fold>/ -- run the `test` subcommand with --latent first")
+    if not folds:
+        raise FileNotFoundError(f"no reconstruction_error_*.csv of {mods} under {root}/<fold>/ -- run the `test` subcommand first")
+    return scores, positive, folds, ids
+
+
+def _analysis_bootstrap(root: Path, args, hc: int, scores, positive, folds, ids):
+    """`analysis --bootstrap B [--against Q ...]`: every fold's set and the pooled rows of all folds, of the procedure and of
+    every procedure it is compared against, in ONE metrics.auc_bootstrap call.  Fold k draws from stream k, the pooled rows
+    from stream n_splits, for every procedure alike: a comparison resamples the same subjects on both sides.  Writes
+    group_analysis_bootstrap.csv (`fold` column, `pooled` as the last row) and per Q
+    group_analysis_compare_<P>_vs_<Q>.csv; prints AUC [lo, hi] per row."""
+    import pandas as pd
+
+    def with_pooled(sc, po):
+        return list(sc) + [torch.cat(list(sc))], list(po) + [torch.cat(list(po))]
+
+    total = sum(int(s.numel()) for s in scores)
+    if total > _lib.NM_METRICS_MAX_N:
+        raise ValueError(f"--bootstrap: the pooled rows of all folds are {total} subjects, a set holds at most {_lib.NM_METRICS_MAX_N}")
+    sets, labs = with_pooled(scores, positive)
+    per = len(folds) + 1
+    streams = list(folds) + [args.n_splits]
+    pairs, others = [], list(args.against or [])
+    for qi, q in enumerate(others):
+        qmods, _ = workload.procedure_modalities(q, args.dataset_resourse)
+        qroot = Path(args.models_dir) / args.dataset_resourse / q
+        qs, qp, qf, qid = _analysis_scores(qroot, qmods, q, args.score, args.n_splits, hc)
+        if qf != folds:
+            raise ValueError(f"--against {q}: its folds {qf} are not {args.procedure}'s {folds}: no paired comparison")
+        for k, a, b, la, lb in zip(folds, ids, qid, positive, qp):
+            if len(a) != len(b) or not np.array_equal(a, b) or not torch.equal(la, lb):
+                raise ValueError(f"--against {q}: fold {k} does not hold {args.procedure}'s subjects with their DIA in the same order "
+                                 f"({qroot / f'{k:03d}'}): the comparison is paired subject by subject -- evaluate both procedures "
+                                 f"on the same folds of the same cohort")
+        qs, qp = with_pooled(qs, qp)
+        sets += qs
+        labs += qp
+        pairs += [(i, (qi + 1) * per + i) for i in range(per)]
+    streams = streams * (1 + len(others))
+    res = metrics.auc_bootstrap(sets, labs, n_boot=args.bootstrap, ci=args.ci, seed=args.boot_seed, streams=streams,
+                                pairs=pairs if others else None)
+    tab, cmp_tab = (res[0].cpu().numpy(), res[1].cpu().numpy()) if others else (res.cpu().numpy(), None)
+    names = [str(k) for k in folds] + ["pooled"]
+    tag = "latent_" if args.score == "latent" else ""
+    df = pd.DataFrame(tab[:per], columns=list(metrics.AUC_BOOTSTRAP_COLUMNS))
+    df.insert(0, "fold", names)
+    df.to_csv(root / f"group_analysis_{tag}bootstrap.csv", index=False)
+    pct = f"{100 * args.ci:g}%"
+    for name, r in zip(names, tab[:per]):
+        print(f"[analysis] {args.procedure} {'fold ' if name != 'pooled' else ''}{name}: AUC {r[0]:.4f} [{r[1]:.4f}, {r[2]:.4f}]  "
+              f"({pct} interval of {args.bootstrap} stratified resamples, se {r[4]:.4f})", flush=True)
+    for qi, q in enumerate(others):
+        rows = cmp_tab[qi * per:(qi + 1) * per]
+        dq = pd.DataFrame(rows, columns=list(metrics.AUC_COMPARE_COLUMNS))
+        dq.insert(0, "fold", names)
+        dq.insert(1, "auc_a", tab[:per, 0])
+        dq.insert(2, "auc_c", tab[(qi + 1) * per:(qi + 2) * per, 0])
+        dq.to_csv(root / f"group_analysis_{tag}compare_{args.procedure}_vs_{q}.csv", index=False)
+        for name, r in zip(names, rows):
+            print(f"[analysis] {args.procedure} - {q} {'fold ' if name != 'pooled' else ''}{name}: delta AUC {r[0]:+.4f} "
+                  f"[{r[1]:+.4f}, {r[2]:+.4f}]  p {r[5]:.3g}", flush=True)
+    return tab[:per], cmp_tab
+
+
 def main_analysis(argv=None):
     """multimodal_kfold_cvae_group_analysis_1x1.py:160-235 on the files the `test` subcommand wrote: per fold the subjects'
     reconstruction errors averaged over the procedure's modalities (:205-209), healthy vs disease ROC-AUC, Youden-J
     threshold, accuracy / sensitivity / specificity (compute_classification_performance, :105-157, on the device:
     nm_posthoc_metrics) and the significance ratio auc / (1 - auc) (:231); prints the per-fold rows and mean +- std,
-    writes <models-dir>/<resource>/<procedure>/group_analysis.csv.  Returns the [folds, 8] metric table."""
+    writes <models-dir>/<resource>/<procedure>/group_analysis.csv.  Returns the [folds, 8] metric table.
+    --bootstrap B adds the stratified-bootstrap interval of every fold's AUC and of the pooled rows (nm_auc_bootstrap),
+    --against Q the paired comparison with other procedures evaluated on the same folds; neither changes what is
+    written and returned without them."""
     import pandas as pd
     ap = argparse.ArgumentParser(prog="python -m multi_modal_normative_modeling_amd.sweep analysis", description=main_analysis.__doc__)
     ap.add_argument("-R", "--dataset_resourse", dest="dataset_resourse", type=str, default="HCPimage")
@@ -1123,9 +1217,30 @@ def main_analysis(argv=None):
                          "--roi-perm) max-statistic permutation p, to group_analysis_roi_significance_<m>.csv")
     ap.add_argument("--roi-perm", dest="roi_perm", type=int, default=0, help="label permutations of --roi-significance (0: none)")
     ap.add_argument("--roi-seed", dest="roi_seed", type=int, default=0, help="the seed of those permutations")
+    ap.add_argument("--bootstrap", type=int, default=0, metavar="B",
+                    help="besides everything above: B stratified bootstrap resamples (1..%d) of every fold's AUC and of the pooled "
+                         "rows of all folds, to group_analysis_bootstrap.csv (`fold` column, `pooled` last) and as `AUC x [lo, hi]` "
+                         "lines.  The rows of a set are taken as independent subjects: under k-fold recipes a subject is in exactly "
+                         "one test fold, but a cohort recipe that repeats a subject across folds makes the pooled interval too "
+                         "narrow and the pooled p-values too small" % _lib.NM_BOOT_MAX)
+    ap.add_argument("--boot-seed", dest="boot_seed", type=int, default=0, help="the seed of those resamples")
+    ap.add_argument("--ci", type=float, default=0.95, help="the coverage of the percentile interval (default 0.95)")
+    ap.add_argument("--against", nargs="+", type=str, default=None, metavar="Q",
+                    help="with --bootstrap: the paired comparison of -P with every procedure Q, per fold and pooled, in the same "
+                         "call (fold k draws from stream k, the pooled rows from stream n_splits, on both sides): delta AUC, its "
+                         "interval and the two-sided bootstrap p to group_analysis_compare_<P>_vs_<Q>.csv.  Q's files are read from "
+                         "the same --models-dir and must hold the same folds with the same subjects and DIA in the same order")
     args = ap.parse_args(argv)
     if args.roi_significance and not args.roi:
         ap.error("--roi-significance needs --roi")
+    if args.against and not args.bootstrap:
+        ap.error("--against needs --bootstrap")
+    if args.bootstrap and args.roi:
+        ap.error("--bootstrap resamples the per-subject score: it does not go with --roi")
+    if args.bootstrap and not 1 <= args.bootstrap <= _lib.NM_BOOT_MAX:
+        ap.error(f"--bootstrap must lie in 1..{_lib.NM_BOOT_MAX}")
+    if not 0.0 < args.ci < 1.0:
+        ap.error("--ci must lie in (0, 1)")
     mods, _ = workload.procedure_modalities(args.procedure, args.dataset_resourse)
     root = Path(args.models_dir) / args.dataset_resourse / args.procedure
     hc = prep.HC_LABEL.get(args.dataset_resourse, 1)
@@ -1133,29 +1248,7 @@ def main_analysis(argv=None):
         return _analysis_roi_significance(root, mods, args.n_splits, hc, args.procedure, args.roi_perm, args.roi_seed)
     if args.roi:
         return _analysis_roi(root, mods, args.n_splits, hc, args.procedure)
-    scores, positive, folds = [], [], []
-    for k in range(args.n_splits):
-        if args.score == "latent":
-            files = [root / f"{k:03d}" / f"latent_deviation_{args.procedure}.csv"]
-        else:
-            files = [root / f"{k:03d}" / m / f"reconstruction_error_{m}.csv" for m in mods]
-        if not all(f.exists() for f in files):
-            continue
-        dfs = [pd.read_csv(f) for f in files]
-        if args.score == "latent":
-            err = dfs[0]["Latent deviation"].to_numpy(dtype=np.float64)
-        else:
-            err = sum(d["Reconstruction error"].to_numpy(dtype=np.float64) for d in dfs) / len(dfs)
-        dia = dfs[0]["DIA"].to_numpy()
-        # (files written from a prep.Cohort carry DIA in the cohort's convention 1 = healthy; raw tables the resource's label)
-        healthy = (dia == 1) if set(np.unique(dia)) <= {0, 1} else (dia == hc)
-        scores.append(torch.as_tensor(err, dtype=torch.float32))
-        positive.append(torch.as_tensor(~healthy, dtype=torch.int32))
-        folds.append(k)
-    if not folds and args.score == "latent":
-        raise FileNotFoundError(f"no latent_deviation_{args.procedure}.csv under {root}/<fold>/ -- run the `test` subcommand with --latent first")
-    if not folds:
-        raise FileNotFoundError(f"no reconstruction_error_*.csv of {mods} under {root}/<fold>/ -- run the `test` subcommand first")
+    scores, positive, folds, ids = _analysis_scores(root, mods, args.procedure, args.score, args.n_splits, hc)
     table = metrics.posthoc_metrics(scores, positive).cpu()
     df = pd.DataFrame(table.numpy(), columns=list(metrics.POSTHOC_COLUMNS))
     df.insert(0, "fold", folds)
@@ -1165,6 +1258,8 @@ def main_analysis(argv=None):
               f"specificity {r['specificity']:.4f}  significance ratio {r['significance_ratio']:.3f}", flush=True)
     print(f"[analysis] {args.procedure}: AUC {df['roc_auc'].mean():.4f} +- {df['roc_auc'].std(ddof=0):.4f}  accuracy {df['accuracy'].mean():.4f}  "
           f"sensitivity {df['recall'].mean():.4f}  specificity {df['specificity'].mean():.4f}", flush=True)
+    if args.bootstrap:
+        _analysis_bootstrap(root, args, hc, scores, positive, folds, ids)
     return table
 
 
