@@ -566,6 +566,50 @@ int nm_auc_bootstrap(const float* scores, const int32_t* labels, const int32_t* 
                      const int32_t* pairs, int n_pairs, void* workspace, size_t workspace_bytes,
                      double* out, double* pairs_out, int32_t* boot_out, void* stream);
 
+/* One regression per column of a table: latent_pvalues(latent, target, type) of utils_vae.py:163-174 (statsmodels OLS /
+ * Logit of target ~ const + latent_i, the p-values of both parameters) for every column of many tables at once, with
+ * optional nuisance covariates.  Set s of the device array sets_dev is a matrix x[rows][pitch] (fp32, pitch >= D, read
+ * where it lies), target[rows] (fp32), cov[rows][cov_pitch] (fp32, cov_pitch >= n_cov; NULL with n_cov = 0) and include[rows]
+ * (int32, != 0: the row takes part; NULL: all rows).  A value in an excluded row is never looked at.  n = the included
+ * rows; the model of column j is target ~ const + x_j + cov_1..cov_q with P = 2 + q parameters, q = n_cov.
+ * Arithmetic: fp32 inputs, fp64 from the load on.  The fit runs on the design whose non-constant columns are centred on
+ * their fp64 means m over the included rows (the slopes are those of the raw design); the intercept and its variance are
+ * mapped back with g = (1, -m): const = b0 - m.b, var_const = g' C g.  The P x P systems are solved by Cholesky; a pivot
+ * d_j <= 1e-12 A_jj (or NaN) means `not positive definite`.
+ *   NM_REG_OLS    least squares; s^2 = RSS / (n - P), C = s^2 (Z'Z)^-1, p = the two-sided Student-t tail of est / se with
+ *                 n - P degrees of freedom; n_iter = 0
+ *   NM_REG_LOGIT  maximum likelihood by Newton steps from zero (in the centred parameters): step = H^-1 Z'(y - p), H = Z'WZ,
+ *                 W = p (1 - p); converged when every |step_i| <= NM_REG_TOL, after at most NM_REG_MAX_ITER steps; C = H^-1
+ *                 at the final parameters; p = erfc(|est / se| / sqrt 2); n_iter = the steps taken
+ * out is [n_sets][D][NM_METRICS_STRIDE] fp64 = {const, coef, se_const, se_coef, p_const, p_coef, n_obs, n_iter}; the
+ * covariates' coefficients are not reported.  Status through n_iter, the six statistics NaN:
+ *   -1  a Logit that did not converge or whose Hessian lost positive definiteness after the first step (perfect separation
+ *       ends here; statsmodels raises or warns instead)
+ *   -2  invalid input: a non-finite value of the column in an included row; a non-finite target or covariate in an included
+ *       row (every column of the set); n <= P; a constant column; a singular design (the Gram matrix of the centred design
+ *       is not positive definite); for Logit a target that is not 0 or 1, or one class only.  A set with rows < 0, rows >
+ *       max_rows, pitch < D, cov_pitch < n_cov or a missing pointer is refused the same way with n_obs = 0; nothing of it is read.
+ * One workgroup per (set, 64 columns), the rows in a fixed order, no atomics: two runs give the same bytes, and a column's
+ * row depends on its own values alone, not on its neighbours, its tile or its set's place in the launch.
+ * Status, decided before the device is asked anything: NM_E_NULL: sets_dev or out missing; NM_E_METRICS: n_sets < 1, D < 1,
+ * max_rows outside 1..NM_METRICS_MAX_N, n_cov outside 0..NM_REG_MAX_COV, an unknown kind (or more than 2^31 - 1 workgroups).
+ * nm_student_t_two_sided (host): P(|T_df| >= |t|) = I_{df / (df + t^2)}(df / 2, 1 / 2), the function the kernel calls. */
+#define NM_REG_OLS      0
+#define NM_REG_LOGIT    1
+#define NM_REG_MAX_COV  4        /* nuisance covariates next to const and the column */
+#define NM_REG_MAX_ITER 35       /* statsmodels' Newton default */
+#define NM_REG_TOL      1e-8     /* every |Newton step| <= tol */
+typedef struct nm_reg_set {
+  const float*   x;              /* [rows][pitch], the D columns to test, read where they lie */
+  const float*   target;         /* [rows] */
+  const float*   cov;            /* [rows][cov_pitch] or NULL when n_cov == 0 */
+  const int32_t* include;        /* [rows], != 0: the row takes part; NULL: all rows */
+  int32_t rows, pitch, cov_pitch, pad;
+} nm_reg_set_t;
+int nm_column_regress(const nm_reg_set_t* sets_dev, int n_sets, int D, int max_rows, int n_cov, int kind,
+                      double* out /* [n_sets][D][NM_METRICS_STRIDE] */, void* stream);
+double nm_student_t_two_sided(double t, double df);
+
 /* The expert-fusion operators the reference exposes as public methods, as forward-only launches (elementwise over
  * [M][n] fp32 device tensors; csrc/nm_fusion.hip):
  *   cVAE_multimodal.combine_latent(mus, variances, combine)                      cVAE.py:1144-1164   (also :2292-2307)

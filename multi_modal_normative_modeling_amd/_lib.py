@@ -62,6 +62,12 @@ NM_ROI_ROW_CHUNK = 256
 # takes (tests put n_boot around it)
 NM_BOOT_MAX = 16384
 NM_BOOT_CHUNK = 64
+# nm_column_regress: the model kinds, the most nuisance covariates, the Newton steps a Logit may take and their tolerance
+NM_REG_OLS = 0
+NM_REG_LOGIT = 1
+NM_REG_MAX_COV = 4
+NM_REG_MAX_ITER = 35
+NM_REG_TOL = 1e-8
 
 # status codes (nmhip.h; nm_status_string gives the text)
 NM_OK = 0
@@ -143,6 +149,12 @@ class NmRoiSet(C.Structure):
     _fields_ = [("x", C.c_void_p), ("group", C.c_void_p), ("rows", C.c_int32), ("pitch", C.c_int32)]
 
 
+class NmRegSet(C.Structure):
+    """nm_reg_set_t: one table of nm_column_regress's pointer table."""
+    _fields_ = [("x", C.c_void_p), ("target", C.c_void_p), ("cov", C.c_void_p), ("include", C.c_void_p),
+                ("rows", C.c_int32), ("pitch", C.c_int32), ("cov_pitch", C.c_int32), ("pad", C.c_int32)]
+
+
 class NmError(RuntimeError):
     pass
 
@@ -217,6 +229,9 @@ def load():
     lib.nm_auc_bootstrap_workspace.restype = C.c_size_t
     lib.nm_auc_bootstrap_workspace.argtypes = [i32, i32, i32, i32]
     lib.nm_auc_bootstrap.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, C.c_uint64, vp, i32, vp, C.c_size_t, vp, vp, vp, vp]
+    lib.nm_column_regress.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]
+    lib.nm_student_t_two_sided.restype = C.c_double
+    lib.nm_student_t_two_sided.argtypes = [C.c_double, C.c_double]
     lib.nm_adam_step.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, i64, vp]
     lib.nm_pack_table.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp]
     lib.nm_prep_scaler_fit.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp]
@@ -246,6 +261,7 @@ EXPORTED_SYMBOLS = [
     "nm_latent_pass", "nm_latent_pass_ok", "nm_latent_stats", "nm_latent_score",
     "nm_roi_effect", "nm_roi_significance_workspace", "nm_roi_significance",
     "nm_auc_bootstrap_workspace", "nm_auc_bootstrap",
+    "nm_column_regress", "nm_student_t_two_sided",
 ]
 
 

@@ -15,6 +15,9 @@
 //                         label-permutation p-values, per ROI and against the maximum over the ROIs
 //   nm_auc_bootstrap      score sets -> the ROC-AUC with its stratified-bootstrap percentile interval, mean and standard error,
 //                         and for pairs of sets on the same subjects the difference with its interval and p (at the end)
+//   nm_column_regress     tables and a target per set -> per column the OLS or Logit fit target ~ const + column + covariates:
+//                         both reported parameters, their standard errors and p-values
+//                         (latent_pvalues, utils_vae.py:163-174, once per column; after the bootstrap)
 //
 // One workgroup per score set (a (fold, procedure) cell); sets are segments of one concatenated array.  The
 // whole set lives in LDS: order-preserving 64-bit keys (score, label) are bitonic-sorted descending, label
@@ -1119,9 +1122,355 @@ __global__ __launch_bounds__(MT) void boot_close_kernel(const int32_t* __restric
   }
 }
 
+// ---- one regression per column (latent_pvalues, utils_vae.py:163-174, for every column of a table at once) -------------
+// nm_column_regress: one workgroup per (set, 64-column tile), a lane per column, as roi_effect_kernel; the four waves take
+// every fourth row, and the target, covariates and include word of a row are wave-uniform loads.  Every pass over the rows
+// ends with the waves' partial sums merged through LDS in wave order, and every wave then does the same P x P algebra on the
+// same sums, so all four hold the same parameters for the next pass without a broadcast.  Pass 0 gives n, the means and the
+// validity of the column; OLS takes two more (normal equations of the centred design, residuals), Logit one per Newton step
+// and one for the Hessian at the final parameters.  The tile is re-read from L2 in every pass.  A lane that has finished
+// keeps its state; the workgroup leaves the Newton loop when no lane is still iterating.  Templated on q and the kind: every
+// index into the register arrays is a compile-time constant after unrolling.
+
+// Continued fraction of the incomplete beta function (modified Lentz), converging fast for x < (a + 1) / (a + b + 2).
+__host__ __device__ inline double reg_betacf(double a, double b, double x) {
+  const double tiny = 1e-300, eps = 1e-15;
+  const double qab = a + b, qap = a + 1.0, qam = a - 1.0;
+  double c = 1.0, d = 1.0 - qab * x / qap;
+  if (fabs(d) < tiny) d = tiny;
+  d = 1.0 / d;
+  double h = d;
+  for (int m = 1; m <= 4000; ++m) {
+    const double m2 = 2.0 * m;
+    double aa = m * (b - m) * x / ((qam + m2) * (a + m2));
+    d = 1.0 + aa * d; if (fabs(d) < tiny) d = tiny;
+    c = 1.0 + aa / c; if (fabs(c) < tiny) c = tiny;
+    d = 1.0 / d;
+    h *= d * c;
+    aa = -(a + m) * (qab + m) * x / ((a + m2) * (qap + m2));
+    d = 1.0 + aa * d; if (fabs(d) < tiny) d = tiny;
+    c = 1.0 + aa / c; if (fabs(c) < tiny) c = tiny;
+    d = 1.0 / d;
+    const double del = d * c;
+    h *= del;
+    if (fabs(del - 1.0) < eps) break;
+  }
+  return h;
+}
+
+// P(|T_df| >= |t|) = I_x(df / 2, 1 / 2) at x = df / (df + t^2); log x and log (1 - x) from t^2 / df, so neither tail cancels.
+__host__ __device__ inline double reg_student_t_two_sided(double t, double df) {
+  if (t != t || !(df > 0.0)) return NAN;
+  const double r = t * t / df;
+  if (r == 0.0) return 1.0;
+  if (r > 1.7e308) return 0.0;
+  const double a = 0.5 * df, b = 0.5;
+  const double l1p = log1p(r);
+  const double x = 1.0 / (1.0 + r), omx = r / (1.0 + r);
+  const double front = exp(lgamma(a + b) - lgamma(a) - lgamma(b) - a * l1p + b * (log(r) - l1p));
+  if (x < (a + 1.0) / (a + b + 2.0)) return front * reg_betacf(a, b, x) / a;
+  return 1.0 - front * reg_betacf(b, a, omx) / b;
+}
+
+constexpr int REG_TILE = 64;                       // columns per workgroup
+constexpr int REG_WAVES = MT / 64;
+constexpr double REG_PIVOT = 1e-12;                // a Cholesky pivot at or below this share of its diagonal entry: not positive definite
+static_assert(sizeof(nm_reg_set_t) == 48, "nm_reg_set_t is mirrored by _lib.NmRegSet");
+
+// A = L L' (A's upper triangle is read, L's lower written); false where a pivot fails
+template <int P>
+__device__ __forceinline__ bool reg_chol(const double (&A)[P][P], double (&L)[P][P]) {
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < P; ++j) {
+    double d = A[j][j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
+    ok = ok && (d > REG_PIVOT * A[j][j]);
+    const double l = sqrt(d);
+    L[j][j] = l;
+#pragma unroll
+    for (int i = j + 1; i < P; ++i) {
+      double v = A[j][i];
+#pragma unroll
+      for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
+      L[i][j] = v / l;
+    }
+  }
+  return ok;
+}
+template <int P>
+__device__ __forceinline__ void reg_forward(const double (&L)[P][P], double (&y)[P]) {      // y := L^-1 y
+#pragma unroll
+  for (int i = 0; i < P; ++i) {
+    double v = y[i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
+    y[i] = v / L[i][i];
+  }
+}
+template <int P>
+__device__ __forceinline__ void reg_backward(const double (&L)[P][P], double (&y)[P]) {     // y := L'^-1 y
+#pragma unroll
+  for (int i = P - 1; i >= 0; --i) {
+    double v = y[i];
+#pragma unroll
+    for (int k = i + 1; k < P; ++k) v -= L[k][i] * y[k];
+    y[i] = v / L[i][i];
+  }
+}
+
+// v[k] := the four waves' v[k] added in wave order (all threads call; every wave gets the same sums)
+template <int N>
+__device__ __forceinline__ void reg_merge(double (&v)[N], double* part, int w, int lane) {
+#pragma unroll
+  for (int k = 0; k < N; ++k) part[(w * N + k) * REG_TILE + lane] = v[k];
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    double s = part[k * REG_TILE + lane];
+#pragma unroll
+    for (int q = 1; q < REG_WAVES; ++q) s += part[(q * N + k) * REG_TILE + lane];
+    v[k] = s;
+  }
+  __syncthreads();
+}
+
+// One pass over the set's included rows at the parameters beta of the centred design z = (1, x - m1, cov - m2..).
+// MODE 0: A = Z'Z, g = Z'y.   MODE 1: p = 1 / (1 + exp(-z.beta)), A = Z' diag(p (1 - p)) Z, g = Z'(y - p).
+// MODE 2: rss = sum (y - z.beta)^2, A and g untouched.
+template <int Q, int MODE>
+__device__ __forceinline__ void reg_pass(const nm_reg_set_t& S, const float* xc, bool cv, int w, int lane, const double (&m)[2 + Q],
+                                         const double (&beta)[2 + Q], double (&A)[2 + Q][2 + Q], double (&g)[2 + Q], double& rss,
+                                         double* part) {
+  constexpr int P = 2 + Q, NT = P * (P + 1) / 2;
+  double acc[MODE == 2 ? 1 : NT + P];
+#pragma unroll
+  for (int k = 0; k < (MODE == 2 ? 1 : NT + P); ++k) acc[k] = 0.0;
+  for (int r = w; r < S.rows; r += REG_WAVES) {
+    if (S.include && S.include[r] == 0) continue;
+    double z[P];
+    z[0] = 1.0;
+    z[1] = (cv ? (double)xc[(int64_t)r * S.pitch] : 0.0) - m[1];
+#pragma unroll
+    for (int k = 0; k < Q; ++k) z[2 + k] = (double)S.cov[(int64_t)r * S.cov_pitch + k] - m[2 + k];
+    const double y = (double)S.target[r];
+    double eta = beta[0];
+#pragma unroll
+    for (int i = 1; i < P; ++i) eta += z[i] * beta[i];
+    if (MODE == 2) {
+      const double e = y - eta;
+      acc[0] += e * e;
+    } else {
+      double wt = 1.0, res = y;
+      if (MODE == 1) {
+        const double p = 1.0 / (1.0 + exp(-eta));
+        wt = p * (1.0 - p);
+        res = y - p;
+      }
+      int k = 0;
+#pragma unroll
+      for (int i = 0; i < P; ++i) {
+        const double wz = MODE == 1 ? wt * z[i] : z[i];
+#pragma unroll
+        for (int j = i; j < P; ++j) acc[k++] += wz * z[j];
+      }
+#pragma unroll
+      for (int i = 0; i < P; ++i) acc[NT + i] += z[i] * res;
+    }
+  }
+  reg_merge(acc, part, w, lane);
+  if (MODE == 2) {
+    rss = acc[0];
+  } else {
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+#pragma unroll
+      for (int j = i; j < P; ++j) A[i][j] = acc[k++];
+    }
+#pragma unroll
+    for (int i = 0; i < P; ++i) g[i] = acc[NT + i];
+  }
+}
+
+template <int Q, int KIND>
+__global__ __launch_bounds__(MT) void column_regress_kernel(const nm_reg_set_t* __restrict__ sets, int D, int max_rows, int tiles,
+                                                            double* __restrict__ out) {
+  constexpr int P = 2 + Q;
+  constexpr int NT = P * (P + 1) / 2;
+  constexpr int N0 = P + 5;                        // pass 0: sums of target, column, covariates; n, ones, bad; min, max
+  constexpr int NL = (NT + P) > N0 ? (NT + P) : N0;
+  __shared__ double part[REG_WAVES * NL * REG_TILE];
+
+  const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int s = blockIdx.x / tiles, tile = blockIdx.x - s * tiles;
+  const nm_reg_set_t S = sets[s];
+  const int col = tile * REG_TILE + lane;
+  const bool cv = col < D;
+  double* o = out + ((int64_t)s * D + col) * NM_METRICS_STRIDE;
+  const double qnan = __longlong_as_double(0x7FF8000000000000ll);
+  const int rows = S.rows;
+  if (rows < 0 || rows > max_rows || S.pitch < D || (Q > 0 && S.cov_pitch < Q) ||
+      (rows > 0 && (!S.x || !S.target || (Q > 0 && !S.cov)))) {
+    if (w == 0 && cv) {
+      for (int k = 0; k < 6; ++k) o[k] = qnan;
+      o[6] = 0.0; o[7] = -2.0;
+    }
+    return;
+  }
+  const float* xc = S.x + col;                     // (read only where cv: beyond D lies padding, or the next row)
+
+  // pass 0: the included rows, the sums the means come from, what makes the column or the set invalid
+  double a0[N0];
+#pragma unroll
+  for (int k = 0; k < N0; ++k) a0[k] = 0.0;
+  double xmin = __longlong_as_double(0x7FF0000000000000ll), xmax = -xmin;
+  for (int r = w; r < rows; r += REG_WAVES) {
+    if (S.include && S.include[r] == 0) continue;
+    const float yf = S.target[r];
+    const float xf = cv ? xc[(int64_t)r * S.pitch] : 0.f;
+    bool bad = !isfinite(yf) || !isfinite(xf);
+    if (KIND == NM_REG_LOGIT) bad = bad || (yf != 0.f && yf != 1.f);
+    a0[0] += (double)yf;
+    a0[1] += (double)xf;
+#pragma unroll
+    for (int k = 0; k < Q; ++k) {
+      const float cf = S.cov[(int64_t)r * S.cov_pitch + k];
+      bad = bad || !isfinite(cf);
+      a0[2 + k] += (double)cf;
+    }
+    a0[P] += 1.0;
+    a0[P + 1] += (yf == 1.f) ? 1.0 : 0.0;
+    a0[P + 2] += bad ? 1.0 : 0.0;
+    xmin = fmin(xmin, (double)xf);
+    xmax = fmax(xmax, (double)xf);
+  }
+  a0[P + 3] = xmin; a0[P + 4] = xmax;
+#pragma unroll
+  for (int k = 0; k < N0; ++k) part[(w * N0 + k) * REG_TILE + lane] = a0[k];
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < N0; ++k) {
+    double v = part[k * REG_TILE + lane];
+#pragma unroll
+    for (int q = 1; q < REG_WAVES; ++q) {
+      const double u = part[(q * N0 + k) * REG_TILE + lane];
+      v = k == P + 3 ? fmin(v, u) : k == P + 4 ? fmax(v, u) : v + u;
+    }
+    a0[k] = v;
+  }
+  __syncthreads();
+  const double n = a0[P];
+  bool valid = cv && a0[P + 2] == 0.0 && n > (double)P && a0[P + 3] < a0[P + 4];
+  if (KIND == NM_REG_LOGIT) valid = valid && a0[P + 1] > 0.0 && a0[P + 1] < n;
+  double m[P];
+  m[0] = 0.0;
+#pragma unroll
+  for (int i = 1; i < P; ++i) m[i] = a0[i] / n;
+
+  double beta[P], A[P][P], g[P], L[P][P], rss = 0.0;
+#pragma unroll
+  for (int i = 0; i < P; ++i) beta[i] = 0.0;
+  int n_iter = 0;
+  int state = valid ? 0 : 4;                       // 0 iterating, 1 converged: the Hessian at the end is due, 2 done, 3 failed (-1), 4 invalid (-2)
+  if (KIND == NM_REG_OLS) {
+    reg_pass<Q, 0>(S, xc, cv, w, lane, m, beta, A, g, rss, part);
+    if (state == 0) {
+      if (reg_chol<P>(A, L)) {
+#pragma unroll
+        for (int i = 0; i < P; ++i) beta[i] = g[i];
+        reg_forward<P>(L, beta);
+        reg_backward<P>(L, beta);
+        state = 2;
+      } else {
+        state = 4;
+      }
+    }
+    reg_pass<Q, 2>(S, xc, cv, w, lane, m, beta, A, g, rss, part);
+  } else {
+    while (__syncthreads_or(state <= 1)) {
+      reg_pass<Q, 1>(S, xc, cv, w, lane, m, beta, A, g, rss, part);
+      if (state > 1) continue;
+      const bool pd = reg_chol<P>(A, L);
+      if (!pd) {
+        state = n_iter == 0 ? 4 : 3;               // at zero the Hessian is a quarter of the Gram matrix: a singular design
+      } else if (state == 1) {
+        state = 2;
+      } else {
+        reg_forward<P>(L, g);
+        reg_backward<P>(L, g);
+        double big = 0.0;
+#pragma unroll
+        for (int i = 0; i < P; ++i) { beta[i] += g[i]; big = fmax(big, fabs(g[i])); }
+        ++n_iter;
+        state = big <= NM_REG_TOL ? 1 : (n_iter >= NM_REG_MAX_ITER || big != big) ? 3 : 0;
+      }
+    }
+  }
+  if (w != 0 || !cv) return;
+  o[6] = n;
+  if (state != 2) {
+    for (int k = 0; k < 6; ++k) o[k] = qnan;
+    o[7] = state == 3 ? -1.0 : -2.0;
+    return;
+  }
+  // var(coef) = |L^-1 e1|^2 and var(const) = |L^-1 (1, -m)|^2 (times s^2 for OLS)
+  double u[P], v[P];
+  u[0] = 0.0; u[1] = 1.0; v[0] = 1.0; v[1] = -m[1];
+#pragma unroll
+  for (int i = 2; i < P; ++i) { u[i] = 0.0; v[i] = -m[i]; }
+  reg_forward<P>(L, u);
+  reg_forward<P>(L, v);
+  double vu = 0.0, vv = 0.0, b0 = beta[0];
+#pragma unroll
+  for (int i = 0; i < P; ++i) { vu += u[i] * u[i]; vv += v[i] * v[i]; }
+#pragma unroll
+  for (int i = 1; i < P; ++i) b0 -= m[i] * beta[i];
+  const double df = n - (double)P;
+  const double s2 = KIND == NM_REG_OLS ? rss / df : 1.0;
+  const double se0 = sqrt(s2 * vv), se1 = sqrt(s2 * vu);
+  o[0] = b0; o[1] = beta[1]; o[2] = se0; o[3] = se1;
+  if (KIND == NM_REG_OLS) {
+    o[4] = reg_student_t_two_sided(b0 / se0, df);
+    o[5] = reg_student_t_two_sided(beta[1] / se1, df);
+  } else {
+    o[4] = erfc(fabs(b0 / se0) * 0.70710678118654752440);
+    o[5] = erfc(fabs(beta[1] / se1) * 0.70710678118654752440);
+  }
+  o[7] = (double)n_iter;
+}
+
+template <int KIND>
+int launch_column_regress(int n_cov, dim3 grid, void* stream, const nm_reg_set_t* sets, int D, int max_rows, int tiles, double* out) {
+  switch (n_cov) {
+    case 0: return launch_kernel(column_regress_kernel<0, KIND>, grid, dim3(MT), 0, stream, sets, D, max_rows, tiles, out);
+    case 1: return launch_kernel(column_regress_kernel<1, KIND>, grid, dim3(MT), 0, stream, sets, D, max_rows, tiles, out);
+    case 2: return launch_kernel(column_regress_kernel<2, KIND>, grid, dim3(MT), 0, stream, sets, D, max_rows, tiles, out);
+    case 3: return launch_kernel(column_regress_kernel<3, KIND>, grid, dim3(MT), 0, stream, sets, D, max_rows, tiles, out);
+    default: return launch_kernel(column_regress_kernel<4, KIND>, grid, dim3(MT), 0, stream, sets, D, max_rows, tiles, out);
+  }
+}
+
 }  // namespace
 
 extern "C" {
+
+int nm_column_regress(const nm_reg_set_t* sets_dev, int n_sets, int D, int max_rows, int n_cov, int kind, double* out,
+                      void* stream) {
+  if (!sets_dev || !out) return NM_E_NULL;
+  if (n_sets < 1 || D < 1 || max_rows < 1 || max_rows > MAXN || n_cov < 0 || n_cov > NM_REG_MAX_COV ||
+      (kind != NM_REG_OLS && kind != NM_REG_LOGIT))
+    return NM_E_METRICS;
+  const int tiles = (D + REG_TILE - 1) / REG_TILE;
+  if ((int64_t)n_sets * tiles > 0x7FFFFFFFll) return NM_E_METRICS;
+  const dim3 grid(n_sets * tiles);
+  return kind == NM_REG_OLS ? launch_column_regress<NM_REG_OLS>(n_cov, grid, stream, sets_dev, D, max_rows, tiles, out)
+                            : launch_column_regress<NM_REG_LOGIT>(n_cov, grid, stream, sets_dev, D, max_rows, tiles, out);
+}
+
+double nm_student_t_two_sided(double t, double df) { return reg_student_t_two_sided(t, df); }
+
 
 int nm_posthoc_metrics(const float* scores, const int32_t* labels, const int32_t* offsets, int n_sets, int max_set,
                        const double* thr_in, double* out, void* stream) {

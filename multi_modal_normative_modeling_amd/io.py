@@ -118,6 +118,42 @@ def write_roi_significance_csv(out_dir, dataset_name: str, roi_columns: Sequence
     return path
 
 
+def write_roi_regress_csv(out_dir, dataset_name: str, roi_columns: Sequence[str], table: np.ndarray) -> Path:
+    """roi_regress_{name}.csv: one row per ROI -- its column name, then metrics.COLUMN_REGRESS_COLUMNS (the fit
+    target ~ const + the ROI's squared error + the adjustment covariates: both reported parameters, their standard errors
+    and p-values, the subjects that took part and the Newton steps; n_iter < 0 is a status, see metrics.column_regress)."""
+    from .metrics import COLUMN_REGRESS_COLUMNS
+    table = np.asarray(table, dtype=np.float64)
+    if table.shape != (len(roi_columns), len(COLUMN_REGRESS_COLUMNS)):
+        raise ValueError(f"a [{len(roi_columns)}, {len(COLUMN_REGRESS_COLUMNS)}] table is needed, got {table.shape}")
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    df = pd.DataFrame(table, columns=list(COLUMN_REGRESS_COLUMNS))
+    df.insert(0, "ROI", list(roi_columns))
+    path = out_dir / f"roi_regress_{dataset_name}.csv"
+    df.to_csv(path, index=False)
+    return path
+
+
+def latent_pvalues_frame(table: np.ndarray) -> pd.DataFrame:
+    """The DataFrame latent_pvalues returns (utils_vae.py:163-174) from a [Z, 8] metrics.column_regress table: labels =
+    ['const', 'latent'], one column 'latent i' per latent dimension with the two p-values."""
+    table = np.asarray(table, dtype=np.float64)
+    df = pd.DataFrame({"labels": ["const", "latent"]})
+    for i in range(table.shape[0]):
+        df["latent {0}".format(i)] = [float(table[i, 4]), float(table[i, 5])]
+    return df
+
+
+def write_latent_pvalues_csv(out_dir, name: str, target: str, table: np.ndarray) -> Path:
+    """latent_pvalues_{name}_{target}.csv: latent_pvalues_frame of the table, as the reference's frame goes to a file."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    path = out_dir / f"latent_pvalues_{name}_{target}.csv"
+    latent_pvalues_frame(table).to_csv(path, index=False)
+    return path
+
+
 # ---- the reference's input layout (SURVEY.md appendix A) -----------------------------------------------------------
 # data/<resource>/y.csv: IID, participant_id, DIA, AGE, PTGENDER (+ FI for HCPimage); data/<resource>/<modality>.csv:
 # IID + the ROI columns.  multimodal_kfold_train_cvae_supervised.py:49-50, 84-91 and utils.py:110-168 read them per

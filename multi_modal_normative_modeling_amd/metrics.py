@@ -11,6 +11,8 @@ signature on top of it.  `roi_significance` = the Mann-Whitney test per ROI colu
 Benjamini-Hochberg q and the max-statistic label-permutation test; `mann_whitney` is scipy's two-sample signature on top of it.
 `auc_bootstrap` = the per-subject ROC-AUC of many score sets with its stratified-bootstrap percentile interval, and the paired
 comparison of sets that share subjects; `auc_compare` is the two-procedure convenience on top of it.
+`column_regress` = one OLS or Logit fit per column of many tables at once (target ~ const + column + covariates, the Wald
+p-values of both reported parameters); `latent_pvalues` is the reference's signature (utils_vae.py:163-174) on top of it.
 """
 from __future__ import annotations
 
@@ -27,6 +29,8 @@ POSTHOC_COLUMNS = ("roc_auc", "threshold", "accuracy", "recall", "specificity", 
 CONFUSION_COLUMNS = ("accuracy", "auroc", "sensitivity", "specificity", "f1_score", "precision", "n_pos", "n_neg")
 ROI_EFFECT_COLUMNS = ("cliff_delta", "auc", "n_more", "n_less", "n_x", "n_y", "mean_x", "mean_y")
 ROI_SIGNIFICANCE_COLUMNS = ("u_x", "tie_term", "z", "p_mwu", "q_bh", "p_perm", "p_maxt", "n_perm")
+COLUMN_REGRESS_COLUMNS = ("const", "coef", "se_const", "se_coef", "p_const", "p_coef", "n_obs", "n_iter")
+COLUMN_REGRESS_KINDS = {"ols": _lib.NM_REG_OLS, "logit": _lib.NM_REG_LOGIT}
 
 
 def _segments(parts: Sequence[torch.Tensor], device, dtype):
@@ -322,3 +326,88 @@ def auc_compare(scores_a, scores_c, positive, n_boot: int = 2000, ci: float = 0.
     _, prs = auc_bootstrap([a, c], [p, p], n_boot=n_boot, ci=ci, seed=seed, streams=[0, 0], pairs=[(0, 1)], device=device)
     row = prs[0].cpu().numpy()
     return {name: float(row[j]) for j, name in enumerate(AUC_COMPARE_COLUMNS)}
+
+
+def _reg_table(mats, targets, covs, incs, n_cov: int):
+    """nm_column_regress's pointer table on the host: every matrix where it lies, as _roi_table; covs / incs entries may be None."""
+    table = (_lib.NmRegSet * len(mats))()
+    for k, m in enumerate(mats):
+        rows = int(m.shape[0])
+        e = table[k]
+        e.rows, e.pitch = rows, (int(m.stride(0)) if rows > 1 else int(m.shape[1]))
+        e.cov_pitch, e.pad = n_cov, 0
+        if rows:
+            e.x, e.target = m.data_ptr(), targets[k].data_ptr()
+            e.cov = covs[k].data_ptr() if n_cov else None
+            e.include = incs[k].data_ptr() if incs[k] is not None else None
+    return table
+
+
+def _reg_check(mats, targets, kind, covariates, include):
+    """nm_column_regress's argument checks on the host (no device is looked for): D, the kind's code, n_cov."""
+    if kind not in COLUMN_REGRESS_KINDS:
+        raise ValueError(f"kind must be one of {sorted(COLUMN_REGRESS_KINDS)}, got {kind!r}")
+    D = _roi_check(mats, targets)                           # (the same table rules; one target entry per row)
+    for name, seq in (("covariates", covariates), ("include", include)):
+        if seq is not None and len(seq) != len(mats):
+            raise ValueError(f"{name} must have one entry per set")
+    n_cov = 0
+    if covariates is not None:
+        for k, c in enumerate(covariates):
+            c = torch.as_tensor(c)
+            if c.dim() != 2 or int(c.shape[0]) != int(mats[k].shape[0]):
+                raise ValueError(f"set {k}: covariates must be [rows, q], got {tuple(c.shape)}")
+            if k == 0:
+                n_cov = int(c.shape[1])
+            if int(c.shape[1]) != n_cov:
+                raise ValueError(f"set {k}: {int(c.shape[1])} covariates, every set needs the same number (set 0 has {n_cov})")
+        if n_cov > _lib.NM_REG_MAX_COV:
+            raise ValueError(f"at most {_lib.NM_REG_MAX_COV} covariates, got {n_cov}")
+    if include is not None:
+        for k, w in enumerate(include):
+            if w is not None and int(torch.as_tensor(w).numel()) != int(mats[k].shape[0]):
+                raise ValueError(f"set {k}: one include word per row is needed")
+    return D, COLUMN_REGRESS_KINDS[kind], n_cov
+
+
+def column_regress(mats: Sequence[torch.Tensor], targets: Sequence, kind: str = "ols", covariates: Optional[Sequence] = None,
+                   include: Optional[Sequence] = None, device=None) -> torch.Tensor:
+    """[n_sets, D, 8] fp64 on the device, per (set, column): const, coef, se_const, se_coef, p_const, p_coef, n_obs, n_iter
+    (COLUMN_REGRESS_COLUMNS; include/nmhip.h has the definitions): the fit target ~ const + column + covariates, "ols" (least
+    squares, Student-t p-values) or "logit" (maximum likelihood by Newton steps, Wald p-values), one fit per column.
+    mats[k]: a [n_k, D] fp32 device tensor read where it lies, as for roi_effect; targets[k]: n_k values (0 / 1 for logit);
+    covariates[k]: [n_k, q] nuisance regressors, q <= NM_REG_MAX_COV, whose coefficients are not reported; include[k]: n_k
+    words (or None), a row with 0 is left out and never looked at.  n_iter < 0 is a status with NaN statistics: -1 a Logit
+    that did not converge (perfect separation ends here), -2 invalid input.  One launch for all sets."""
+    D, code, n_cov = _reg_check(mats, targets, kind, covariates, include)
+    dev = require_gpu(device if device is not None else (mats[0].device if mats[0].is_cuda else None))
+    if dev.index is None:
+        dev = torch.device(dev.type, torch.cuda.current_device())
+    for k, m in enumerate(mats):
+        if m.device != dev:
+            raise ValueError(f"set {k} is on {m.device}, not on {dev}: the tables are read where they lie")
+    tgt = [torch.as_tensor(v).reshape(-1).to(device=dev, dtype=torch.float32).contiguous() for v in targets]
+    cov = [torch.as_tensor(c).to(device=dev, dtype=torch.float32).contiguous() for c in covariates] if n_cov else None
+    inc = [None if (include is None or w is None) else torch.as_tensor(w).reshape(-1).ne(0).to(device=dev, dtype=torch.int32)
+           for w in (include if include is not None else [None] * len(mats))]
+    sets = torch.frombuffer(bytearray(bytes(_reg_table(mats, tgt, cov, inc, n_cov))), dtype=torch.uint8).to(dev)
+    out = torch.empty(len(mats), D, _lib.NM_METRICS_STRIDE, dtype=torch.float64, device=dev)
+    _lib.check(_lib.load().nm_column_regress(sets.data_ptr(), len(mats), D, max(max(int(m.shape[0]) for m in mats), 1), n_cov,
+                                              code, out.data_ptr(), _stream_ptr(dev)), "nm_column_regress")
+    return out
+
+
+def latent_pvalues(latent, target, type, device=None):
+    """latent_pvalues(latent, target, type) of utils_vae.py:163-174 on the device: a DataFrame with labels = ['const',
+    'latent'] and one column 'latent i' per latent dimension holding the p-values of target ~ const + latent_i;
+    type == 'continuous' is OLS, anything else Logit.  A fit that statsmodels would refuse (separation, a constant
+    column) gives NaN."""
+    lat = torch.as_tensor(np.asarray(latent.detach().cpu() if isinstance(latent, torch.Tensor) else latent, dtype=np.float32))
+    tgt = torch.as_tensor(np.asarray(target.detach().cpu() if isinstance(target, torch.Tensor) else target, dtype=np.float32))
+    if lat.dim() != 2 or tgt.dim() != 1 or tgt.numel() != lat.shape[0]:
+        raise ValueError(f"latent must be [n, Z] and target [n]; got {tuple(lat.shape)} and {tuple(tgt.shape)}")
+    _reg_check([lat], [tgt], "ols", None, None)
+    dev = require_gpu(device)
+    tab = column_regress([lat.to(dev)], [tgt], kind="ols" if type == "continuous" else "logit", device=dev)[0].cpu().numpy()
+    from .io import latent_pvalues_frame
+    return latent_pvalues_frame(tab)

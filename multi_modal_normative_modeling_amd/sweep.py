@@ -528,6 +528,47 @@ def _roi_significance_sets(mats: Sequence[torch.Tensor], groups: Sequence[np.nda
     return out
 
 
+REGRESS_TARGETS = {"DIA": "dia", "AGE": "age", "PTGENDER": "gender", "FI": "fi"}
+
+
+def regress_target(cohort: prep.SyntheticCohort, rows: np.ndarray, target: str, kind: str, disease_label=None):
+    """(values fp32, include int32 or None) of metrics.column_regress for the cohort column `target` (REGRESS_TARGETS) on
+    `rows`.  A Logit on DIA: 1 = the disease label (every patient when disease_label is None), 0 = the healthy controls,
+    every other class excluded through the include words (roi_groups).  Any other pair: the column as it stands."""
+    if target not in REGRESS_TARGETS:
+        raise ValueError(f"target must be one of {sorted(REGRESS_TARGETS)}, got {target!r}")
+    if kind not in metrics.COLUMN_REGRESS_KINDS:
+        raise ValueError(f"kind must be one of {sorted(metrics.COLUMN_REGRESS_KINDS)}, got {kind!r}")
+    if target == "DIA" and kind == "logit":
+        g = roi_groups(cohort.dia[rows], disease_label)
+        return (g == 1).astype(np.float32), (g >= 0).astype(np.int32)
+    return np.asarray(getattr(cohort, REGRESS_TARGETS[target])[rows], dtype=np.float32), None
+
+
+def parse_regress_spec(spec: str):
+    """'DIA:logit' -> ('DIA', 'logit'), checked as regress_target checks it."""
+    target, sep, kind = str(spec).partition(":")
+    if not sep or target not in REGRESS_TARGETS or kind not in metrics.COLUMN_REGRESS_KINDS:
+        raise ValueError(f"a TARGET:KIND pair is needed, TARGET one of {sorted(REGRESS_TARGETS)} and KIND one of "
+                         f"{sorted(metrics.COLUMN_REGRESS_KINDS)}; got {spec!r}")
+    return target, kind
+
+
+def _column_regress_sets(mats: Sequence[torch.Tensor], targets, kind: str, covs, incs, device) -> List[torch.Tensor]:
+    """metrics.column_regress for tables of any widths, as _roi_effect_sets: one launch per distinct width."""
+    by_width: Dict[int, List[int]] = {}
+    for j, x in enumerate(mats):
+        by_width.setdefault(int(x.shape[1]), []).append(j)
+    out: List[Optional[torch.Tensor]] = [None] * len(mats)
+    for idxs in by_width.values():
+        tab = metrics.column_regress([mats[j] for j in idxs], [targets[j] for j in idxs], kind=kind,
+                                     covariates=None if covs is None else [covs[j] for j in idxs],
+                                     include=[incs[j] for j in idxs], device=device)
+        for a, j in enumerate(idxs):
+            out[j] = tab[a]
+    return out
+
+
 def _roi_columns(roi_columns, m: str, d: int):
     return list(roi_columns[m]) if roi_columns and m in roi_columns else [f"{m}_{k}" for k in range(d)]
 
@@ -536,7 +577,8 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
                combines, device, out_dirs: Optional[Sequence] = None,
                roi_columns: Optional[Dict[str, Sequence[str]]] = None, roi_effect: bool = False,
                disease_label=None, roi_significance: bool = False, roi_perm: int = 0,
-               roi_seed: int = 0) -> List[Dict[str, np.ndarray]]:
+               roi_seed: int = 0, roi_regress: Optional[tuple] = None,
+               roi_adjust: Sequence[str] = ()) -> List[Dict[str, np.ndarray]]:
     """test_fold for ALL folds of a procedure as one launch: jobs[i] is the trained model of fold i, folds[i] its
     (train_rows, test_rows); one evaluation job per fold, each on its own test tables (seed, scaler and covariates per fold
     exactly as test_fold), all in ONE JobSet -- a fold's ~N / K test rows are a single workgroup, K of them in a row leave
@@ -557,9 +599,23 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
     permutation p-values of the ROI and against the maximum over the ROIs.  Each fold's dict gains "roi_significance":
     {modality: [D, 8]} (metrics.ROI_SIGNIFICANCE_COLUMNS) and "roi_significance_pooled"; with out_dirs,
     roi_significance_<m>.csv.  The subjects are taken as independent: a cohort recipe that repeats a subject across folds
-    makes the pooled p-values too small."""
+    makes the pooled p-values too small.
+
+    roi_regress = (kind, target) (needs roi_effect): metrics.column_regress on the same tables, every fold x modality and the
+    pooled sets in ONE launch (one per table width) -- per ROI the fit target ~ const + the ROI's squared error, kind "logit"
+    or "ols", target a cohort column (regress_target; a Logit on DIA is patients against controls as roi_groups picks them),
+    adjusted for the cohort columns named in roi_adjust (at most NM_REG_MAX_COV).  Each fold's dict gains "roi_regress":
+    {modality: [D, 8]} (metrics.COLUMN_REGRESS_COLUMNS) and "roi_regress_pooled"; with out_dirs, roi_regress_<m>.csv."""
     if roi_significance and not roi_effect:
         raise ValueError("roi_significance needs roi_effect=True (the evaluation jobs export the ROI-wise squared errors for it)")
+    if roi_regress is not None:
+        if not roi_effect:
+            raise ValueError("roi_regress needs roi_effect=True (the evaluation jobs export the ROI-wise squared errors for it)")
+        reg_kind, reg_target = roi_regress
+        regress_target(cohort, np.zeros(0, dtype=np.int64), reg_target, reg_kind)
+        roi_adjust = list(roi_adjust)
+        if any(a not in REGRESS_TARGETS for a in roi_adjust) or len(roi_adjust) > _lib.NM_REG_MAX_COV:
+            raise ValueError(f"roi_adjust: at most {_lib.NM_REG_MAX_COV} of {sorted(REGRESS_TARGETS)}, got {roi_adjust}")
     if len(jobs) != len(folds):
         raise ValueError(f"{len(jobs)} models for {len(folds)} folds")
     combs = [combines] * len(jobs) if isinstance(combines, str) else list(combines)
@@ -581,6 +637,15 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
         if roi_significance:
             sig_fold = _roi_significance_sets(mats, [g for g in grp for _ in range(nm_)], roi_perm, roi_seed, device)
             sig_pooled = _roi_significance_sets(pooled_mats, [np.concatenate(grp)] * nm_, roi_perm, roi_seed, device)
+        if roi_regress is not None:
+            # the folds' sets, then the pooled ones: one table list, one launch per width
+            rows_of = [te for _, te in folds] + [np.concatenate([te for _, te in folds])]
+            tg = [regress_target(cohort, r, reg_target, reg_kind, disease_label) for r in rows_of]
+            cv = [np.stack([np.asarray(getattr(cohort, REGRESS_TARGETS[a])[r], dtype=np.float32) for a in roi_adjust], 1)
+                  for r in rows_of] if roi_adjust else None
+            rep = lambda seq: [v for v in seq[:-1] for _ in range(nm_)] + [seq[-1]] * nm_
+            reg = _column_regress_sets(mats + pooled_mats, rep([t for t, _ in tg]), reg_kind,
+                                       None if cv is None else rep(cv), rep([w for _, w in tg]), device)
     torch.cuda.synchronize(device)
     out = [_fold_results(ev, xs, cohort, te, modalities, d, roi_columns) for (ev, xs), (_, te), d in zip(evs, folds, dirs)]
     if roi_effect:
@@ -599,6 +664,14 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
             if d is not None:
                 for m, tab in res["roi_significance"].items():
                     io.write_roi_significance_csv(Path(d) / m, m, _roi_columns(roi_columns, m, tab.shape[0]), tab)
+    if roi_regress is not None:
+        reg_pooled = {m: reg[len(mats) + i].cpu().numpy() for i, m in enumerate(modalities)}
+        for f, (res, d) in enumerate(zip(out, dirs)):
+            res["roi_regress"] = {m: reg[f * nm_ + i].cpu().numpy() for i, m in enumerate(modalities)}
+            res["roi_regress_pooled"] = reg_pooled
+            if d is not None:
+                for m, tab in res["roi_regress"].items():
+                    io.write_roi_regress_csv(Path(d) / m, m, _roi_columns(roi_columns, m, tab.shape[0]), tab)
     return out
 
 
@@ -620,17 +693,29 @@ def _fold_latent_jobs(job: Job, cohort: prep.SyntheticCohort, train_rows: np.nda
 
 
 def latent_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequence[tuple], modalities: Sequence[str],
-                 combines, device, out_dirs: Optional[Sequence] = None, name: str = "joint") -> List[Dict[str, np.ndarray]]:
+                 combines, device, out_dirs: Optional[Sequence] = None, name: str = "joint",
+                 pvalues: Optional[Sequence[tuple]] = None, disease_label=None,
+                 pooled_dir=None) -> List[Dict[str, np.ndarray]]:
     """The latent-space deviation (latent_deviation / separate_latent_deviation, utils_vae.py:155-161, on what pred_latent
     returns) for ALL folds of a procedure: jobs[i] is the trained model of fold i, folds[i] its (train_rows, test_rows).
     One latent launch over the folds' train tables, one over their test tables (JobSet.latent: the encoder-only kernel where
     the shape allows; folds whose tables differ in their number of 256-row tiles run as one launch per height), then ONE
     nm_latent_stats launch (every fold's train cohort a set) and ONE nm_latent_score launch (every fold's test subjects
     against their own fold's statistics).  Returns per fold {"mu", "var" [N, Z], "z" [N, Z], "score" [N]} of the test
-    subjects; out_dirs: one directory per fold for latent_<name>.csv / latent_deviation_<name>.csv."""
+    subjects; out_dirs: one directory per fold for latent_<name>.csv / latent_deviation_<name>.csv.
+
+    pvalues: (target, kind) pairs such as [("DIA", "logit"), ("AGE", "ols")] -- latent_pvalues (utils_vae.py:163-174) of the
+    test subjects' joint mu, still on the device: per pair ONE metrics.column_regress launch over every fold's set and the
+    pooled rows (regress_target picks the values; a Logit on DIA is disease_label -- default: every patient -- against the
+    healthy controls, the other classes excluded).  Each fold's dict gains "pvalues": {target: [Z, 8]}
+    (metrics.COLUMN_REGRESS_COLUMNS) and "pvalues_pooled" (the same dict in every fold's result); with out_dirs,
+    latent_pvalues_<name>_<target>.csv in the reference's layout per fold, and with pooled_dir the pooled one there."""
     from . import engine
     if len(jobs) != len(folds):
         raise ValueError(f"{len(jobs)} models for {len(folds)} folds")
+    pvalues = [tuple(p) for p in (pvalues or [])]
+    for target, kind in pvalues:
+        regress_target(cohort, np.zeros(0, dtype=np.int64), target, kind)
     combs = [combines] * len(jobs) if isinstance(combines, str) else list(combines)
     dirs = [None] * len(jobs) if out_dirs is None else list(out_dirs)
     pairs = [_fold_latent_jobs(j, cohort, tr, te, modalities, cb, device) for j, (tr, te), cb in zip(jobs, folds, combs)]
@@ -644,7 +729,19 @@ def latent_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Seque
     mus = [ev.out_mu[:len(te)] for (_, ev), (_, te) in zip(pairs, folds)]
     lvs = [ev.out_logvar[:len(te)] for (_, ev), (_, te) in zip(pairs, folds)]
     zsep, score = engine.latent_scores(mus, lvs, mean, var)
+    pv = {}
+    if pvalues and mus:
+        rows_of = [te for _, te in folds] + [np.concatenate([te for _, te in folds])]
+        sets = list(mus) + [torch.cat(list(mus))]
+        for target, kind in pvalues:
+            tg = [regress_target(cohort, r, target, kind, disease_label) for r in rows_of]
+            pv[target] = metrics.column_regress(sets, [t for t, _ in tg], kind=kind, include=[w for _, w in tg], device=device)
     torch.cuda.synchronize(device)
+    pv = {t: tab.cpu().numpy() for t, tab in pv.items()}
+    pv_pooled = {t: tab[-1] for t, tab in pv.items()}
+    if pv and pooled_dir is not None:
+        for target, tab in pv_pooled.items():
+            io.write_latent_pvalues_csv(pooled_dir, name, target, tab)
     out = []
     for mu, lv, z, sc, (_, te), d in zip(mus, lvs, zsep, score, folds, dirs):
         res = {"mu": mu.cpu().numpy(), "var": lv.exp().cpu().numpy(), "z": z.cpu().numpy(), "score": sc.cpu().numpy()}
@@ -653,6 +750,12 @@ def latent_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Seque
             meta = pd.DataFrame({"participant_id": cohort.iid[te], "DIA": cohort.dia[te], "AGE": cohort.age[te],
                                  "PTGENDER": cohort.gender[te]})
             io.write_latent_csvs(d, name, meta, res["mu"], res["var"], res["score"], res["z"])
+        if pv:
+            res["pvalues"] = {t: tab[len(out)] for t, tab in pv.items()}
+            res["pvalues_pooled"] = pv_pooled
+            if d is not None:
+                for target, tab in res["pvalues"].items():
+                    io.write_latent_pvalues_csv(d, name, target, tab)
         out.append(res)
     return out
 
@@ -935,10 +1038,29 @@ def main_test(argv=None):
                          "max-statistic permutation p: per fold and pooled roi_significance_<m>.csv")
     ap.add_argument("--roi-perm", dest="roi_perm", type=int, default=0, help="label permutations of --roi-significance (0: none)")
     ap.add_argument("--roi-seed", dest="roi_seed", type=int, default=0, help="the seed of those permutations")
+    ap.add_argument("--latent-pvalues", dest="latent_pvalues", nargs="+", type=str, default=None, metavar="TARGET:KIND",
+                    help="with --latent: which latent dimensions carry a cohort column (DIA:logit AGE:ols ...): per fold and pooled "
+                         "latent_pvalues_<P>_<TARGET>.csv, the p-values of TARGET ~ const + latent_i")
+    ap.add_argument("--roi-regress", dest="roi_regress", type=str, default=None, metavar="TARGET:KIND",
+                    help="with --roi-effect: the same fit per ROI on its squared error (DIA:logit ...): per fold and pooled "
+                         "roi_regress_<m>.csv")
+    ap.add_argument("--roi-adjust", dest="roi_adjust", nargs="+", type=str, default=[], metavar="COLUMN",
+                    help="with --roi-regress: cohort columns the fit is adjusted for (AGE PTGENDER)")
     _driver_common(ap)
     args = ap.parse_args(argv)
     if args.roi_significance and not args.roi_effect:
         ap.error("--roi-significance needs --roi-effect")
+    if args.latent_pvalues and not args.latent:
+        ap.error("--latent-pvalues needs --latent")
+    if args.roi_regress and not args.roi_effect:
+        ap.error("--roi-regress needs --roi-effect")
+    if args.roi_adjust and not args.roi_regress:
+        ap.error("--roi-adjust needs --roi-regress")
+    try:
+        lat_pvalues = [parse_regress_spec(v) for v in (args.latent_pvalues or [])]
+        roi_regress = tuple(reversed(parse_regress_spec(args.roi_regress))) if args.roi_regress else None
+    except ValueError as e:
+        ap.error(str(e))
     cohort = _cohort_from_args(args)
     mods, combine = workload.procedure_modalities(args.procedure, args.dataset_resourse)
     combine = (args.combine or combine).lower()
@@ -971,7 +1093,8 @@ def main_test(argv=None):
     # all folds of this rank in one launch (one job per fold on its own test tables)
     results = test_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs,
                          roi_effect=args.roi_effect, disease_label=args.disease_label, roi_significance=args.roi_significance,
-                         roi_perm=args.roi_perm, roi_seed=args.roi_seed) if my else []
+                         roi_perm=args.roi_perm, roi_seed=args.roi_seed, roi_regress=roi_regress,
+                         roi_adjust=args.roi_adjust) if my else []
     for err in results:
         for m in mods:
             errors[m].append(err[m])
@@ -993,9 +1116,15 @@ def main_test(argv=None):
             col = 6 if args.roi_perm else 4
             print(f"[test] {args.procedure} {m}: pooled ROI significance, {int(np.nansum(tab[:, col] <= 0.05))} of {tab.shape[0]} ROIs with "
                   f"{metrics.ROI_SIGNIFICANCE_COLUMNS[col]} <= 0.05", flush=True)
+        if roi_regress and results:
+            tab = results[0]["roi_regress_pooled"][m]
+            io.write_roi_regress_csv(out_root / m, m, _roi_columns(None, m, tab.shape[0]), tab)
+            print(f"[test] {args.procedure} {m}: pooled ROI regression {args.roi_regress}, {int(np.nansum(tab[:, 5] <= 0.05))} of "
+                  f"{tab.shape[0]} ROIs with p_coef <= 0.05", flush=True)
     if args.latent and my:
         # the folds' train cohorts and test subjects in one latent launch each, one statistics and one score launch
-        lat = latent_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs, name=args.procedure)
+        lat = latent_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs, name=args.procedure,
+                           pvalues=lat_pvalues, disease_label=args.disease_label, pooled_dir=out_root if lat_pvalues else None)
         out_root.mkdir(parents=True, exist_ok=True)
         for kind in ("latent", "latent_deviation"):
             parts = [pd.read_csv(root / f"{k:03d}" / f"{kind}_{args.procedure}.csv") for k in my]

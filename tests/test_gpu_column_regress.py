@@ -1,0 +1,248 @@
+"""nm_column_regress on the device against the yardstick (tests/column_regress_ref.py).  In every case the output buffer
+starts out poisoned and the pad columns D..pitch of the inputs hold NaN / inf.  The closeness rule (R.close): n_obs, the
+status codes and the NaN pattern exactly, a Logit's n_iter within 1 of the yardstick's and inside 1..35, an estimate within
+1e-9 x max(|ref|, its se), se and p within 1e-9 relative -- 3000 times the summation-order noise the CPU test measures on the
+yardstick, five orders below what a dropped row does."""
+import numpy as np
+import pytest
+import torch
+
+from multi_modal_normative_modeling_amd import _lib, metrics
+from multi_modal_normative_modeling_amd.engine import _stream_ptr
+from tests import column_regress_ref as R
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+POISON = -1.2345e300
+KINDS = {"ols": _lib.NM_REG_OLS, "logit": _lib.NM_REG_LOGIT}
+
+
+def _upload(x, pitch):
+    """[rows, D] view of a [rows, pitch] device buffer whose pad columns hold NaN and +-inf."""
+    rows, D = x.shape
+    assert pitch >= D
+    buf = torch.empty(rows, pitch, dtype=torch.float32)
+    buf[:] = torch.tensor([float("nan"), float("inf"), float("-inf")]).repeat(pitch)[:pitch]
+    buf[:, :D] = torch.from_numpy(np.ascontiguousarray(x))
+    return buf.to(DEV)[:, :D]
+
+
+def _launch(views, targets, covs, incs, kind, max_rows=None, rows=None, pitches=None):
+    """The C entry point on a poisoned output; rows / pitches override what the table declares (the refusal cases)."""
+    D = int(views[0].shape[1])
+    n_cov = 0 if covs is None else int(np.asarray(covs[0]).shape[1])
+    tg = [torch.as_tensor(np.asarray(v, dtype=np.float32)).to(DEV) for v in targets]
+    cv = [torch.as_tensor(np.ascontiguousarray(c, dtype=np.float32)).to(DEV) for c in covs] if n_cov else None
+    ic = [None if w is None else torch.as_tensor(np.asarray(w, dtype=np.int32)).to(DEV) for w in (incs or [None] * len(views))]
+    table = metrics._reg_table(views, tg, cv, ic, n_cov)
+    for k in range(len(views)):
+        if rows is not None and rows[k] is not None:
+            table[k].rows = rows[k]
+        if pitches is not None and pitches[k] is not None:
+            table[k].pitch = pitches[k]
+    sets = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(DEV)
+    out = torch.full((len(views), D, _lib.NM_METRICS_STRIDE), POISON, dtype=torch.float64, device=DEV)
+    if max_rows is None:
+        max_rows = max(max(int(v.shape[0]) for v in views), 1)
+    _lib.check(_lib.load().nm_column_regress(sets.data_ptr(), len(views), D, max_rows, n_cov, KINDS[kind], out.data_ptr(),
+                                              _stream_ptr(DEV)), "nm_column_regress")
+    torch.cuda.synchronize()
+    got = out.cpu().numpy()
+    assert not np.any(got == POISON)
+    return got
+
+
+def _one(x, y, cov, inc, kind, pitch=None):
+    return _launch([_upload(x, pitch or x.shape[1] + 3)], [y], None if cov is None else [cov], [inc], kind)[0]
+
+
+def _check(got, x, y, cov, inc, kind, what=""):
+    ref = R.table(x, y, cov, inc, kind)
+    worst = R.close(got, ref)
+    print(what, "worst error / bound:", worst, "n_iter", got[:, 7].min(), "..", got[:, 7].max())
+    assert worst <= 1.0, what
+    return ref
+
+
+@pytest.mark.parametrize("D", [1, 63, 64, 65, 130])
+@pytest.mark.parametrize("q", [0, 1, 4])
+@pytest.mark.parametrize("kind", ["ols", "logit"])
+def test_widths_heights_and_covariates(kind, q, D):
+    rng = np.random.default_rng(1000 * q + D + (7 if kind == "logit" else 0))
+    for rows in (2 + q + 1, 5, 63, 64, 65, 257, 1064):
+        x, y, cov = R.make_case(rng, rows, D, q, kind)
+        got = _one(x, y, cov, None, kind)
+        ref = _check(got, x, y, cov, None, kind, f"{kind} q={q} D={D} rows={rows}")
+        if rows >= 257:
+            assert np.all(ref[:, 7] >= (1 if kind == "logit" else 0))
+
+
+def _mixed(kind, q):
+    """Five sets of different heights and pitches, three with include words; the third a row slice out of a taller buffer."""
+    rng = np.random.default_rng(77 + q)
+    D = 70
+    shapes = [(33, 70), (137, 72), (58, 80), (9, 71), (301, 76)]
+    cases = [R.make_case(rng, r, D, q, kind) for r, _ in shapes]
+    xs, ys, covs = [c[0] for c in cases], [c[1] for c in cases], ([c[2] for c in cases] if q else None)
+    incs = [None, (rng.random(137) < 0.8).astype(np.int32), rng.choice([0, 1, -3, 7], size=58).astype(np.int32), None,
+            (rng.random(301) < 0.5).astype(np.int32)]
+    views = [_upload(x, p) for x, (_, p) in zip(xs, shapes)]
+    tall = _upload(np.concatenate([xs[0][:11], xs[2], xs[0][:6]]), 80)
+    views[2] = tall[11:11 + 58]
+    assert not views[2].is_contiguous() and views[2].data_ptr() == tall.data_ptr() + 11 * 80 * 4
+    return views, xs, ys, covs, incs
+
+
+@pytest.mark.parametrize("q", [0, 2])
+@pytest.mark.parametrize("kind", ["ols", "logit"])
+def test_five_sets_in_one_launch_through_the_host_function(kind, q):
+    views, xs, ys, covs, incs = _mixed(kind, q)
+    ptrs = [v.data_ptr() for v in views]
+    got = metrics.column_regress(views, ys, kind=kind, covariates=covs, include=incs, device=DEV)
+    assert got.dtype == torch.float64 and got.is_cuda and tuple(got.shape) == (5, 70, 8)
+    assert [v.data_ptr() for v in views] == ptrs
+    got = got.cpu().numpy()
+    for k in range(5):
+        _check(got[k], xs[k], ys[k], None if covs is None else covs[k], incs[k], kind, f"set {k}")
+    # the same table on a poisoned output, twice: the same bytes (any non-zero include word means `takes part`)
+    a = _launch(views, ys, covs, incs, kind)
+    b = _launch(views, ys, covs, incs, kind)
+    assert a.tobytes() == b.tobytes() == got.tobytes()
+
+
+@pytest.mark.parametrize("kind", ["ols", "logit"])
+def test_a_set_alone_and_at_either_end_of_twenty(kind):
+    rng = np.random.default_rng(20)
+    D, q = 65, 1
+    cases = [R.make_case(rng, int(r), D, q, kind) for r in rng.integers(20, 200, 20)]
+    cases[19] = cases[0]
+    views = [_upload(c[0], D + 1 + k % 3) for k, c in enumerate(cases)]
+    alone = _launch(views[:1], [cases[0][1]], [cases[0][2]], None, kind)
+    many = _launch(views, [c[1] for c in cases], [c[2] for c in cases], None, kind)
+    assert alone[0].tobytes() == many[0].tobytes() == many[19].tobytes()
+    _check(many[7], cases[7][0], cases[7][1], cases[7][2], None, kind)
+
+
+def test_a_separated_column_fails_alone():
+    rng = np.random.default_rng(8)
+    n, D = 120, 66
+    x, y, cov = R.make_case(rng, n, D, 1, "logit")
+    clean = _one(x, y, cov, None, "logit")
+    xs = x.copy()
+    for c in (3, 65):                                              # one in each tile
+        xs[:, c] = np.where(y == 1, 1.0 + rng.random(n), -1.0 - rng.random(n)).astype(np.float32)
+    got = _one(xs, y, cov, None, "logit")
+    _check(got, xs, y, cov, None, "logit")
+    others = np.setdiff1d(np.arange(D), [3, 65])
+    assert np.all(got[[3, 65], 7] == -1) and np.all(np.isnan(got[[3, 65], :6])) and np.all(got[:, 6] == n)
+    assert got[others].tobytes() == clean[others].tobytes()
+
+
+@pytest.mark.parametrize("kind", ["ols", "logit"])
+def test_invalid_columns_fail_alone(kind):
+    rng = np.random.default_rng(9)
+    n, D = 90, 67
+    x, y, cov = R.make_case(rng, n, D, 2, kind)
+    clean = _one(x, y, cov, None, kind)
+    xs = x.copy()
+    xs[17, 1] = np.nan
+    xs[40, 2] = np.inf
+    xs[89, 64] = -np.inf
+    xs[:, 5] = 2.5                                                 # a constant column
+    xs[:, 66] = cov[:, 1]                                          # the column is a covariate: a singular design
+    badc = [1, 2, 5, 64, 66]
+    got = _one(xs, y, cov, None, kind)
+    _check(got, xs, y, cov, None, kind)
+    assert np.all(got[badc, 7] == -2) and np.all(np.isnan(got[badc, :6])) and np.all(got[:, 6] == n)
+    others = np.setdiff1d(np.arange(D), badc)
+    assert np.all(got[others, 7] >= 0) and got[others].tobytes() == clean[others].tobytes()
+
+
+@pytest.mark.parametrize("kind", ["ols", "logit"])
+def test_invalid_sets(kind):
+    rng = np.random.default_rng(10)
+    n, D, q = 50, 65, 2
+    x, y, cov = R.make_case(rng, n, D, q, kind)
+    P = 2 + q
+
+    def all_invalid(xx, yy, cc, inc=None, n_obs=n):
+        got = _one(xx, yy, cc, inc, kind)
+        _check(got, xx, yy, cc, inc, kind)
+        assert np.all(got[:, 7] == -2) and np.all(np.isnan(got[:, :6])) and np.all(got[:, 6] == n_obs)
+
+    for bad in (np.nan, np.inf):
+        yb = y.copy(); yb[13] = bad
+        all_invalid(x, yb, cov)                                    # a non-finite target
+        cb = cov.copy(); cb[31, 1] = bad
+        all_invalid(x, y, cb)                                      # a non-finite covariate
+    inc = np.zeros(n, dtype=np.int32); inc[:P] = 1
+    if kind == "logit":
+        y[:2] = [0, 1]
+    all_invalid(x, y, cov, inc, n_obs=P)                           # n_obs <= P
+    cc = cov.copy(); cc[:, 0] = 4.0
+    all_invalid(x, y, cc)                                          # a constant covariate: a singular design
+    cc = cov.copy(); cc[:, 1] = cc[:, 0]
+    all_invalid(x, y, cc)                                          # two equal covariates
+    if kind == "logit":
+        all_invalid(x, 2 * y, cov)                                 # a target that is not 0 or 1
+        yb = y.copy(); yb[7] = 0.5
+        all_invalid(x, yb, cov)
+        all_invalid(x, np.ones_like(y), cov)                       # one class only
+        all_invalid(x, np.zeros_like(y), cov)
+    # sets the table itself rules out: nothing of them is read, their neighbour gets its result
+    v = _upload(x, D + 3)
+    got = _launch([v, v, v, v], [y] * 4, [cov] * 4, None, kind, max_rows=n, rows=[None, n + 1, -1, None], pitches=[None, None, None, D - 1])
+    for k in (1, 2, 3):
+        assert np.all(got[k, :, 7] == -2) and np.all(np.isnan(got[k, :, :6])) and np.all(got[k, :, 6] == 0)
+    _check(got[0], x, y, cov, None, kind)
+
+
+@pytest.mark.parametrize("kind", ["ols", "logit"])
+def test_an_excluded_row_is_never_looked_at(kind):
+    rng = np.random.default_rng(12)
+    n, D = 100, 65
+    x, y, cov = R.make_case(rng, n, D, 1, kind)
+    inc = np.ones(n, dtype=np.int32)
+    inc[[0, 41, 99]] = 0
+    clean = _one(x, y, cov, inc, kind)
+    xb, yb, cb = x.copy(), y.copy(), cov.copy()
+    xb[0, :] = np.nan; xb[41, 7] = np.inf
+    yb[41] = np.nan; yb[99] = 7.0
+    cb[99, 0] = -np.inf
+    got = _one(xb, yb, cb, inc, kind)
+    assert got.tobytes() == clean.tobytes()
+    _check(got, x, y, cov, inc, kind)
+    assert np.all(got[:, 6] == n - 3) and np.all(got[:, 7] >= 0)
+
+
+def test_a_column_offset_by_ten_thousand_stays_within_the_bound():
+    rng = np.random.default_rng(21)
+    n = 500
+    x = rng.normal(size=(n, 3)).astype(np.float32)
+    x[:, 1] = (x[:, 1] + 1e4).astype(np.float32)
+    true1 = x[:, 1].astype(np.float64) - 1e4                       # the offset taken off exactly
+    y = (0.7 * true1 + rng.normal(size=n)).astype(np.float32)
+    got = _one(x, y, None, None, "ols")
+    _check(got, x, y, None, None, "ols")
+    truth = R.table(true1[:, None], y, kind="ols")[0]
+    err = abs(got[1, 1] - truth[1]) / max(abs(truth[1]), truth[3])
+    print("slope error against the offset-free fit:", err)
+    assert err <= 1e-9 and abs(got[1, 3] - truth[3]) <= 1e-9 * truth[3] and abs(got[1, 5] - truth[5]) <= 1e-9 * truth[5]
+    yl = (rng.random(n) < 1.0 / (1.0 + np.exp(-0.8 * true1))).astype(np.float32)
+    _check(_one(x, yl, None, None, "logit"), x, yl, None, None, "logit")
+
+
+@pytest.mark.parametrize("type", ["continuous", "categorical"])
+def test_latent_pvalues_is_the_reference_frame(type):
+    rng = np.random.default_rng(33)
+    kind = "ols" if type == "continuous" else "logit"
+    latent, target, _ = R.make_case(rng, 212, 10, 0, kind)
+    got = metrics.latent_pvalues(latent, target, type)
+    ref = R.latent_pvalues(latent, target, type)
+    assert list(got.columns) == list(ref.columns) == ["labels"] + [f"latent {i}" for i in range(10)]
+    assert list(got["labels"]) == ["const", "latent"] and got.shape == (2, 11)
+    g, r = got.iloc[:, 1:].to_numpy(dtype=np.float64), ref.iloc[:, 1:].to_numpy(dtype=np.float64)
+    assert np.all(np.isfinite(r)) and np.all(np.abs(g - r) <= 1e-9 * np.abs(r))
+    got_t = metrics.latent_pvalues(torch.from_numpy(latent), torch.from_numpy(target), type)
+    assert got_t.equals(got)
