@@ -90,8 +90,12 @@ enum {
   NM_F_TRACE    = 64,  /* workgroup (0,0): per-wave interval timers between in-kernel stamps */
   NM_F_BNSTATS  = 256, /* nm_head_classifier: update BatchNorm running statistics (once per train-mode forward) */
   NM_F_SPLIT    = 512, /* set by nm_launch_split: one workgroup per (job, modality) */
-  NM_F_FAULT_INJECT = 1024 /* diagnostic, nm_launch_split only: part 1 of every job leaves at once, so the others' hand-off
+  NM_F_FAULT_INJECT = 1024, /* diagnostic, nm_launch_split only: part 1 of every job leaves at once, so the others' hand-off
                               times out (test of the error path: nm_split_errors) */
+  NM_F_PLAIN    = 2048 /* nm_launch: every job of the launch passes nm_plain_ok -- a training launch (NM_F_BACKWARD | NM_F_ADAM,
+                          no NM_F_GRADS / EXPORT / ZGIVEN) then runs the step kernel's plain-training instantiation, which has
+                          the launch constants of such a job folded (same arithmetic, bit-identical results); ignored by
+                          every other launch form.  A job that does not pass is refused by the kernel: NM_SYNC_ERR_PLAIN */
 };
 
 /* One modality (expert) of a model: its ROI table and where its tensors live inside the
@@ -342,6 +346,14 @@ int nm_rowsplit_groups(const int* job_M_host, int n_jobs, int* table_out, int ca
 /* NM_OK: the job can run row-split; NM_E_ROWSPLIT: it uses a switch that needs the whole batch in one workgroup (total correlation,
  * learnable loss weights, private latents, sigmoid output, decoder-only modalities, head models, general-shape path) */
 int nm_rowsplit_ok(const nm_job_t* job_host);
+/* Can the job train on the step kernel's plain-training instantiation (NM_F_PLAIN)?  0: yes -- a cVAE / cVAE_multimodal trunk on
+ * the fused kernel with no head (regression head, classifier, dz_extra / dloc_extra / dloc_rowcoef), Gaussian output, no private
+ * latent columns, no total correlation, no learnable loss weights, an encoder for every decoder, shadow images, and no export
+ * pointer set (out_mu / out_logvar / out_z, mod[m].out_loc / out_sqerr / out_rowdev); 1: no -- it needs the generic kernel
+ * (leave NM_F_PLAIN off); NM_E_NULL.  Shapes, the combiner, single_bypass, injected or in-kernel eps, shared_cov, ragged last
+ * batches and the learning-rate table play no part.  The kernel evaluates the same predicate on the device descriptor when it
+ * starts: a job that fails it gets NM_SYNC_ERR_PLAIN in its error word (nm_split_errors) and is left untouched. */
+int nm_plain_ok(const nm_job_t* job_host);
 /* Zero the hand-off words of every job (first 256 bytes of workspace tile 0); the split launches call it themselves. */
 int nm_sync_reset(const nm_job_t* jobs_dev, int n_jobs, void* stream);
 /* The ROI-wise deviation pass as its own kernel (csrc/nm_devpass.hip; multimodal_kfold_train_cvae_supervised_regression.py:163-192,
@@ -388,6 +400,7 @@ int nm_trace_read_rs(unsigned long long* out512, int reset);
 /* values of out_dev[j]: a hand-off timed out / the row-split kernel refused the job's shape */
 #define NM_SYNC_ERR_TIMEOUT 1
 #define NM_SYNC_ERR_SHAPE   2
+#define NM_SYNC_ERR_PLAIN   3   /* an NM_F_PLAIN launch met a job that does not pass nm_plain_ok: nothing of it was touched */
 int nm_split_errors(const nm_job_t* jobs_dev, int n_jobs, int* out_dev, int clear, void* stream);
 
 /* Convenience wrappers over nm_launch (same status convention). */

@@ -46,9 +46,12 @@ NM_LOSS_CONTRAST = 14
 NM_F_BNSTATS = 256
 NM_F_SPLIT = 512
 NM_F_FAULT_INJECT = 1024
-# values of a job's hand-off error word (nm_split_errors): a hand-off timed out / the row-split kernel refused the shape
+NM_F_PLAIN = 2048
+# values of a job's hand-off error word (nm_split_errors): a hand-off timed out / the row-split kernel refused the shape /
+# the plain-training kernel refused a job that does not pass nm_plain_ok
 NM_SYNC_ERR_TIMEOUT = 1
 NM_SYNC_ERR_SHAPE = 2
+NM_SYNC_ERR_PLAIN = 3
 NM_METRICS_MAX_N = 8192
 NM_METRICS_STRIDE = 8
 # nm_roi_effect: the Y rows its kernel stages in LDS at a time (tests put group sizes around it)
@@ -196,6 +199,7 @@ def load():
     lib.nm_launch_rowsplit_mixed.argtypes = [vp, i32, C.POINTER(i32), i32, i32, i32, i32, i32, i32, vp]
     lib.nm_rowsplit_groups.argtypes = [C.POINTER(i32), i32, C.POINTER(i32), i32]
     lib.nm_rowsplit_ok.argtypes = [C.POINTER(NmJob)]
+    lib.nm_plain_ok.argtypes = [C.POINTER(NmJob)]
     lib.nm_sync_reset.argtypes = [vp, i32, vp]
     lib.nm_trace_read_rs.argtypes = [C.POINTER(C.c_ulonglong), i32]
     lib.nm_devpass.argtypes = [vp, i32, i32, i32, i32, vp]
@@ -262,6 +266,7 @@ EXPORTED_SYMBOLS = [
     "nm_roi_effect", "nm_roi_significance_workspace", "nm_roi_significance",
     "nm_auc_bootstrap_workspace", "nm_auc_bootstrap",
     "nm_column_regress", "nm_student_t_two_sided",
+    "nm_plain_ok",
 ]
 
 

@@ -156,6 +156,8 @@ constexpr int WS_SYNC_BYTES = 256;       // hand-off counters of the split mode:
 constexpr int WS_SYNC_ERR_WORD = 32;
 // values of the error word: a hand-off timed out / the row-split kernel refused the job's shape (nm_rowsplit.hip: rs_fits)
 constexpr unsigned WS_SYNC_ERR_TIMEOUT = NM_SYNC_ERR_TIMEOUT, WS_SYNC_ERR_SHAPE = NM_SYNC_ERR_SHAPE;   // (nmhip.h)
+// ... / an NM_F_PLAIN launch met a job that needs the generic step kernel (plain_job below)
+constexpr unsigned WS_SYNC_ERR_PLAIN = NM_SYNC_ERR_PLAIN;
 // row-split launch (words of tile 0 unless noted): A[q] at word q, B[q] at 16 + q (q < 4: arrivals of the M modality parts of
 // slice q), C at 33 (all M k workgroups of the job: partials complete), D[m] at 40 + m (the k slices of modality m: sweep
 // complete); words 48.. of EVERY tile: that slice's loss shares (kl, then ll_m)
@@ -1214,7 +1216,9 @@ constexpr int WG_LOADS = 6;      // vector-memory operations of one wg_issue
 // b_chunk > 0: B is not one tile but 64-column chunk tiles `b_chunk` elements apart (pitch ldb each): k-tile pair kp sits in
 // chunk kp / 2 at column (kp & 1) * 32 -- the row-split first-layer pass over all x chunks at once.  bgrad_buf: where the
 // ones column is parked (default c.bgrad, 128 rows; a pass over more rows brings its own).
-template <bool SCALAR_TR, int RTV = RT, bool PART = false>
+// PLAIN (the step kernel's plain-training instantiation): Adam on, no gradient export, a shadow image behind every pass --
+// a valid tile always issues its 4 stores.
+template <bool SCALAR_TR, int RTV = RT, bool PART = false, bool PLAIN = false>
 __device__ __forceinline__ int wgrad_adam(const Ctx& cc, const __bf16* A, int lda, int a_col0, const __bf16* B, int ldb,
                                           const WgGeom& G, int pending = -1, int b_chunk = 0, float* bgrad_buf = nullptr) {
   NM_GEOM(RTV);
@@ -1229,8 +1233,9 @@ __device__ __forceinline__ int wgrad_adam(const Ctx& cc, const __bf16* A, int ld
   const int nunits = wg_units(G);
   const int kb = K - k_base;                    // pass column of the ones column
   const int kb_pair = wg_bias_pair(G), kb_j = (kb >> 4) & 1, kb_col = kb & 15;
-  const bool do_adam = !PART && (c.flags & NM_F_ADAM) != 0;
-  const bool do_grads = !PART && (c.flags & NM_F_GRADS) != 0;
+  static_assert(!PLAIN || !PART, "the plain instantiation owns the whole batch");
+  const bool do_adam = PLAIN || (!PART && (c.flags & NM_F_ADAM) != 0);
+  const bool do_grads = !PLAIN && !PART && (c.flags & NM_F_GRADS) != 0;
   const AdamK ak = adam_consts(c);
   gf32 Pp = asg(J->params), Mp = asg(J->adam_m), Vp = asg(J->adam_v);
   float* patch = T.patch + c.wave * PATCH_FLOATS;
@@ -1367,7 +1372,7 @@ __device__ __forceinline__ int wgrad_adam(const Ctx& cc, const __bf16* A, int ld
           __builtin_nontemporal_store(m4, (GAS f32x4*)(Mp + idx));
           __builtin_nontemporal_store(v4, (GAS f32x4*)(Vp + idx));
           nst += 3;
-          if (T.sh) {
+          if (PLAIN || T.sh) {
             bf16x4 pk;
 #pragma unroll
             for (int i = 0; i < 4; ++i) pk[i] = (__bf16)p4[i];
@@ -1471,6 +1476,22 @@ __device__ __forceinline__ WgGeom geom_l0(const nm_job_t* J, const nm_modality_t
   GAS char* const img = (GAS char*)J->wsh + md.enc_s[0];
   return WgGeom{N0, K0, kc * XCH, min(XCH, Kx - kc * XCH),
                 WgT{md.enc_w[0], md.enc_b[0], img + (int64_t)kc * XCH * 2, Kx * 2, (GAS float*)(img + l0_img_bytes(N0, Kx)), patch}};
+}
+
+// Can the step kernel's plain-training instantiation (nm_step_kernel<false, 0, true>, NM_F_PLAIN) serve this job?  A cVAE /
+// cVAE_multimodal trunk on the fused path with none of the features that instantiation has folded away: heads and their extra
+// gradients, sigmoid output, private latent columns, total correlation, learnable loss weights, decoder-only modalities,
+// export targets.  ONE definition: nm_plain_ok (host descriptor) and the kernel's own guard (device descriptor) both ask it.
+__host__ __device__ inline bool plain_job(const nm_job_t* j) {
+  if (j->wide || j->reg_head || j->reg_resid || j->reg_dres || j->cls_layers > 0 || j->cls_classes > 0 || j->dz_extra) return false;
+  if (j->out_kind != 0 || j->n_private != 0 || j->tc_weight != 0.f || j->w_off >= 0) return false;
+  if (j->M < 1 || j->M > NM_MAX_MOD || (j->M_enc != 0 && j->M_enc != j->M)) return false;
+  if (!j->wsh || j->out_mu || j->out_logvar || j->out_z) return false;
+  for (int m = 0; m < j->M; ++m) {
+    const nm_modality_t& md = j->mod[m];
+    if (md.out_loc || md.out_sqerr || md.out_rowdev || md.dloc_extra || md.dloc_rowcoef) return false;
+  }
+  return true;
 }
 
 // ---- expert fusion (cVAE.py:1144-1164) on one (row, z) element --------------------------------
@@ -1598,6 +1619,18 @@ __device__ __forceinline__ FuseGrad fuse_bwd(const nm_job_t* J, const Lat& L, co
   }
   return G;
 }
+// d loss / d (joint mu, joint logvar) of one latent element in the plain-training instantiation (run_step<.., PLAIN = true>):
+// the generic instantiation's  dz + klw mj  and  0.5 dz es + klw 0.5 (e^lj - 1)  with the contraction spelled out.  The
+// compiler fuses one of the two products of the second sum into the addition and rounds the other, and which one depends on
+// the code around the expression: the generic instantiation rounds 0.5 dz es in its element loops (VEC4 = false) and
+// klw 0.5 (e^lj - 1) in its four-column loops.  d alpha sums these in fp32, so the choice shows in the last bit.
+template <bool VEC4>
+__device__ __forceinline__ void plain_latent_deltas(float dz, float es, float mj, float lj, float klw, float& dmu_j, float& dlv_j) {
+#pragma clang fp contract(off)
+  const float e1 = fx_exp(lj) - 1.0f, hdz = 0.5f * dz, hk = klw * 0.5f;
+  dmu_j = fmaf(klw, mj, dz);
+  dlv_j = VEC4 ? fmaf(hdz, es, hk * e1) : fmaf(hk, e1, hdz * es);
+}
 __device__ __forceinline__ float pick(const float (&a)[NM_MAX_EXP], int m) {
   // a select chain, kept opaque: left alone the compiler turns it back into a[m], i.e. a private array in
   // scratch memory (12 floats stored and one reloaded per element of the fusion backward loop)
@@ -1609,6 +1642,73 @@ __device__ __forceinline__ float pick(const float (&a)[NM_MAX_EXP], int m) {
     r = t;
   }
   return r;
+}
+
+// The output chunk's epilogue in the plain-training instantiation (run_step<.., PLAIN = true>): bias, residual, the chunk's
+// share of the NLL, d logvar_out's column sums, delta chunk -> Dq ([256][LDX]).  The generic epilogue (run_step's chunk loop)
+// with everything a plain launch does not have taken out of the element expression -- the sigmoid and its derivative, the
+// hinge's row coefficient, the extra gradients, the exports -- and a form without row / column masks for a full tile (every
+// chunk but a modality's last, every batch but a ragged one).  Bit for bit the generic result: fp contraction is off and each
+// operation is written the way the generic instantiation compiles it -- the delta is ONE fused multiply-add with a zero
+// addend (there: diff * (coef + rc) + ex, times 1; rc = 0, ex = 0, so the sum keeps its +0 for a zero product whichever way
+// it is contracted), hq and the NLL term are separate multiplies and adds (there a select sits between them).
+template <int RTV>
+__device__ __forceinline__ void out_epilogue_plain(const Ctx& c, f32x4 (&acc)[RTV], const f32x4 (&xin)[RTV], const float* vb, __bf16* Dq,
+                                                   int d0, int D, float llw_b, float (&colsum)[4], float& nll_part) {
+#pragma clang fp contract(off)
+  NM_GEOM(RTV);
+  const int dl0 = c.wn * 16 + 4 * c.g, dg0 = d0 + dl0;
+  const f32x4 bo = *reinterpret_cast<const f32x4*>(vb + dl0);
+  const f32x4 sv = *reinterpret_cast<const f32x4*>(vb + OCH + dl0);
+  float inv[4], colq[4], coef[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    inv[i] = expf(-sv[i]);
+    colq[i] = 0.f;
+    coef[i] = ((dg0 + i < D) ? llw_b * inv[i] : 0.f) + 0.0f;
+  }
+  int nvalid = 0;
+  if (c.nrows == ROWS && d0 + OCH <= D) {             // wave-uniform: a full tile, no masks
+    nvalid = RT;
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+      const int r = c.wm * WROWS + rt * 16 + c.c16;
+      acc[rt] += bo;
+      bf16x4 pk;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float diff = acc[rt][i] - xin[rt][i];
+        colq[i] = fmaf(diff, diff, colq[i]);
+        pk[i] = (__bf16)fmaf(diff, coef[i], 0.0f);
+      }
+      *reinterpret_cast<bf16x4*>(Dq + r * LDX + dl0) = pk;
+    }
+  } else {
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+      const int r = c.wm * WROWS + rt * 16 + c.c16;
+      const bool rv = r < c.nrows;
+      nvalid += rv ? 1 : 0;
+      acc[rt] += bo;
+      bf16x4 pk;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float diff = rv ? acc[rt][i] - xin[rt][i] : 0.f;
+        colq[i] = fmaf(diff, diff, colq[i]);
+        pk[i] = (__bf16)fmaf(diff, coef[i], 0.0f);
+      }
+      *reinterpret_cast<bf16x4*>(Dq + r * LDX + dl0) = pk;
+    }
+  }
+  const float nv = (float)nvalid;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const bool dv = dg0 + i < D;
+    const float hq = (0.5f * inv[i]) * colq[i];
+    const float t = nv * fmaf(0.5f, sv[i], LOG_SQRT_2PI);
+    nll_part += dv ? hq + t : 0.f;
+    colsum[i] = dv ? fmaf(nv, 0.5f, -hq) : 0.f;
+  }
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -1623,24 +1723,30 @@ __device__ __forceinline__ float pick(const float (&a)[NM_MAX_EXP], int m) {
 // row-split launch (MODE 0 only; nm_rowsplit.hip) -- the workgroup runs modality c.part on slice c.rsq of the batch rows:
 // forward and backward on its rows, weight-gradient PARTIALS to c.gpart; the caller (rs_step) follows with the hand-off,
 // the fixed-order sum of the partials and the Adam sweep.
-template <bool SCALAR_TR, int MODE = 0, int RTV = RT>
+// PLAIN: the one-pass train step of a launch whose jobs all pass plain_job, with backward + Adam and no export (NM_F_PLAIN,
+// launch_impl): everything such a launch fixes -- the mode flags, model kind, output kind, extra gradients, private latent
+// columns, learnable loss weights, split or not -- is a compile-time constant here.  The arithmetic is the generic
+// instantiation's, operation by operation (results agree bit for bit: tests/test_gpu_plain.py); shapes, the combiner, the
+// bypass, the source of eps, shared covariates, ragged batches and the learning-rate table stay run-time values.
+template <bool SCALAR_TR, int MODE = 0, int RTV = RT, bool PLAIN = false>
 __device__ __forceinline__ void run_step(Ctx& c, int step) {
   NM_GEOM(RTV);
   constexpr bool RS = RTV < 8;                  // row-split: gradients leave as partials
   static_assert(!RS || MODE == 0, "row-split instantiations run the one-pass train step only");
+  static_assert(!PLAIN || (MODE == 0 && !RS && !SCALAR_TR), "the plain instantiation is the whole-batch one-pass train step");
   const nm_job_t* J = c.job;
   const int M = J->M, L = J->L, Z = J->Z, C = J->C;
   const int Me = experts(J);                    // modalities that have an encoder
   const bool nl = J->non_linear != 0;
-  const bool bwd = MODE != 1 && MODE != 3 && (c.flags & NM_F_BACKWARD) != 0;
+  const bool bwd = PLAIN || (MODE != 1 && MODE != 3 && (c.flags & NM_F_BACKWARD) != 0);
   constexpr bool FWD_ONLY = MODE == 1 || MODE == 3;   // output chunks export only: see the chunk loop
   const bool save = bwd || MODE == 1;           // activations go to the workspace
-  const bool exportf = MODE != 2 && (c.flags & NM_F_EXPORT) != 0;
+  const bool exportf = !PLAIN && MODE != 2 && (c.flags & NM_F_EXPORT) != 0;
   const WsLayout wl = ws_layout(M, L, Z);
   const int Zs = wl.Zs;
-  const bool split = c.part >= 0;               // this workgroup runs one modality of the model (NM_F_SPLIT)
+  const bool split = !PLAIN && c.part >= 0;     // this workgroup runs one modality of the model (NM_F_SPLIT)
   const int part = split ? c.part : 0;
-  const int S = J->n_private, Zc = Z - S;       // DMVAE family: private / shared latent columns (S = 0: all shared)
+  const int S = PLAIN ? 0 : J->n_private, Zc = Z - S;       // DMVAE family: private / shared latent columns (S = 0: all shared)
   const float rZc = Zc > 0 ? 1.0f / (float)Zc : 0.f;
   // latent phases four columns at a time when the rows divide evenly (measured: with Z = 10 the 12-column groups
   // leave half the threads a second, mostly padded round -- slower than the element loop; Z = 64: 2.5x faster)
@@ -1652,7 +1758,7 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
                        !((c.flags & NM_F_EXPORT) && (J->out_mu || J->out_logvar || J->out_z));
   __bf16* const zlds = reinterpret_cast<__bf16*>(c.stage);      // [256][32] bf16 in S (free until the last decoder layer)
   float kl_fast = 0.f;
-  const bool sigm = J->out_kind == 1;           // sigmoid output, ll = -0.5 sum (x - x_hat)^2
+  const bool sigm = !PLAIN && J->out_kind == 1; // sigmoid output, ll = -0.5 sum (x - x_hat)^2
   gf32 ws_mu_m = (gf32)(c.ws + wl.mu_m + (int64_t)(step & 1) * M * wl.lat);
   gf32 ws_lv_m = (gf32)(c.ws + wl.lv_m + (int64_t)(step & 1) * M * wl.lat);
   gf32 ws_mu_j = (gf32)(c.ws + wl.mu_j + part * wl.lat);
@@ -1723,7 +1829,8 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
   // posterior's half of it is a scalar minus its own mean, identically zero.  One wave per (expert, latent column):
   // max and sum over the rows by shuffles (fixed order), kept in LDS for the backward pass.
   float tc = 0.f;
-  if (MODE != 2 && J->tc_weight != 0.f) {
+  if constexpr (PLAIN) asm volatile("" : "+v"(tc));   // (a value, not a literal: the loss row's sum keeps the generic form)
+  if (!PLAIN && MODE != 2 && J->tc_weight != 0.f) {
     relaunder(c);
     for (int col = c.wave; col < Me * Z; col += NWAVES) {
       const int m = col / Z, z = col - m * Z;
@@ -1754,7 +1861,7 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
   // (weights[m] is read at the start of decoder m and updated at its end, by that decoder only; their sum, the
   //  weight of the KL term, is formed here, before any of them moves)
   float kl_w = J->kl_weight;
-  if (J->w_off >= 0) {
+  if (!PLAIN && J->w_off >= 0) {
     kl_w = 0.f;
     for (int m = 0; m < M; ++m) kl_w += asg(J->params)[J->w_off + m];
   }
@@ -1798,6 +1905,9 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
 #pragma unroll
         for (int m = 0; m < NM_MAX_EXP; ++m) { Lt.mu[m] = mu4[m][i]; Lt.lv[m] = lv4[m][i]; }
         Fuse f = fuse_fwd(J, Lt, al);
+        // (plain instantiation: the KL term below sits in the block that forms f -- no export branch in between -- and must
+        //  not contract with the multiply that ends fx_log, which the generic instantiation cannot reach across its branch)
+        if constexpr (PLAIN) asm volatile("" : "+v"(f.mu), "+v"(f.lv));
         float es = ep[i] * fx_exp(0.5f * f.lv);
         if (c.flags & NM_F_ZGIVEN) { f.mu = ep[i]; es = 0.f; }     // decode(z, c, m): the draw buffer holds z itself
         omu[i] = f.mu; olv[i] = f.lv; oes[i] = es;
@@ -1823,6 +1933,7 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
     Lat Lt;
     load_lat(Lt, r, S + z);
     Fuse f = fuse_fwd(J, Lt, al);
+    if constexpr (PLAIN) asm volatile("" : "+v"(f.mu), "+v"(f.lv));   // (as in the four-column loop above)
     float ep = J->eps ? asg(J->eps)[((int64_t)(step % J->eps_cap) * TROWS + c.rloc0 + r) * Z + z]
                       : randn_ctr(J->seed, (uint32_t)step, (uint32_t)(c.row0 + r), (uint32_t)z);
     float es = ep * fx_exp(0.5f * f.lv);
@@ -1936,11 +2047,11 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
     // read once, outside the per-lane selects below: a descriptor load inside `cond ? load * x : 0` becomes a
     // lane-divergent branch, and register spills placed around such branches are not safe with this compiler
     // (tools/check_spill_exec.py)
-    const float ll_w = (J->w_off >= 0) ? asg(J->params)[J->w_off + m] : J->ll_weight;
+    const float ll_w = (!PLAIN && J->w_off >= 0) ? asg(J->params)[J->w_off + m] : J->ll_weight;
     const float llw_b = ll_w * c.inv_b;
     // regression head: residual chunk images out (export), d loss / d x_hat chunk images in (second pass)
-    const int hq_all = (J->reg_head && m < Me) ? head_chunk0(J, Me) : 0;
-    const int64_t hq_m = (J->reg_head && m < Me) ? head_chunk0(J, m) : 0;
+    const int hq_all = (!PLAIN && J->reg_head && m < Me) ? head_chunk0(J, Me) : 0;
+    const int64_t hq_m = (!PLAIN && J->reg_head && m < Me) ? head_chunk0(J, m) : 0;
     GAS char* const res_out = (exportf && hq_all > 0 && J->reg_resid)           // (one set of images per 256-row tile)
         ? (GAS char*)asg(J->reg_resid) + ((int64_t)(c.row0 / TROWS) * hq_all + hq_m) * XIMG_TILE_BYTES : (GAS char*)nullptr;
     const GAS char* const dres_in = (MODE == 2 && hq_all > 0 && J->reg_dres)    // (one set: the batch in flight)
@@ -1972,7 +2083,7 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
       // d logvar_out of this chunk is applied after the epilogue by one lane per column (wave 0): its p / m / v are
       // requested now (hand-issued: a plain load there would wait for every older store of this wave), and are complete
       // by then -- the epilogue consumes this chunk's fp32 inputs, which are requested after them (in-order return)
-      const bool lvo_adam = !RS && bwd && (c.flags & NM_F_ADAM) && !sigm && c.wave == 0;
+      const bool lvo_adam = !RS && bwd && (PLAIN || (c.flags & NM_F_ADAM)) && !sigm && c.wave == 0;
       float lvp, lvm, lvv;
       asm volatile("" : "=v"(lvp), "=v"(lvm), "=v"(lvv));
       if (lvo_adam) {
@@ -2029,6 +2140,10 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
       }
       // epilogue: residual, NLL, d logvar_out, delta chunk -> Dq.  Lane: 4 consecutive ROI of one row.
       {
+        float colsum[4];
+        if constexpr (PLAIN) {
+          out_epilogue_plain<RTV>(c, acc, xin, vb, Dq, d0, D, llw_b, colsum, nll_part);
+        } else {
         const f32x4 bo = *reinterpret_cast<const f32x4*>(vb + dl0);
         const f32x4 sv = *reinterpret_cast<const f32x4*>(vb + OCH + dl0);
         // per column: q = sum_r diff^2 (valid rows only).  Then  NLL = sum_d [0.5 e^{-s} q + n (0.5 s + log sqrt(2 pi))]
@@ -2084,7 +2199,6 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
             *(GAS bf16x4*)(res_out + (int64_t)ch * XIMG_TILE_BYTES + (r * LDX + dl0) * 2) = rk;
           }
         }
-        float colsum[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const bool dv = dg0 + i < D;
@@ -2129,6 +2243,7 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
         if (FWD_ONLY)
           young_prev = RT + (res_out ? RT : 0) +
                        ((exportf && wave_cols) ? RT * ((md.out_loc ? 1 : 0) + (md.out_sqerr ? 1 : 0)) : 0);
+        }
         if (bwd) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
@@ -2168,7 +2283,7 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
       tr(c, 8);
       prof(c, PH_OUT_DGRAD);
       // wgrad + Adam of this chunk of decoder_mean_layer: dWo[d][k] = sum_r Dq[r][d] P[r][k]
-      const int n_wg = deferred ? 0 : wgrad_adam<SCALAR_TR, RTV, RS>(c, Dq, LDX, 0, c.P, LDP, Go);
+      const int n_wg = deferred ? 0 : wgrad_adam<SCALAR_TR, RTV, RS, PLAIN>(c, Dq, LDX, 0, c.P, LDP, Go);
       young_prev = RT + n_wg;                     // all younger than the next chunk's blob request
       tr(c, 9);
       prof(c, PH_OUT_WGRAD);
@@ -2209,7 +2324,10 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
     }
     float nll = block_sum(c, nll_part);
     float ll_this = -nll * c.inv_b;                 // compute_ll: sum over ROI, mean over rows
-    if (J->w_off >= 0) {                            // WeightedDMVAE: ll_i * weights[i]; d total / d weights[i] = KL - ll_i
+    // (plain instantiation: a product on its own, as in the generic one, where the weights' branch below keeps it from
+    //  contracting with the sum over the modalities)
+    if constexpr (PLAIN) asm volatile("" : "+v"(ll_this));
+    if (!PLAIN && J->w_off >= 0) {                  // WeightedDMVAE: ll_i * weights[i]; d total / d weights[i] = KL - ll_i
       if (c.tid == 0 && bwd) apply_grad(c, J->w_off + m, kl - ll_this, nullptr);
       ll_this *= ll_w;
     }
@@ -2251,7 +2369,7 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
       const __bf16* const Qact = dgrad_hidden(c, acc, dimg, act_img, Nout, Kin);
       tr(c, 10);
       prof(c, PH_DEC_DGRAD);
-      wgrad_adam<SCALAR_TR, RTV, RS>(c, c.P, LDP, 0, Qact, LDP, Gd, 0);
+      wgrad_adam<SCALAR_TR, RTV, RS, PLAIN>(c, c.P, LDP, 0, Qact, LDP, Gd, 0);
       tr(c, 11);
       prof(c, PH_DEC_WGRAD);
       if (d > 0) {
@@ -2291,7 +2409,7 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
       ll_sum = 0.f;
       for (int m = 0; m < M; ++m) ll_sum += row[NM_LOSS_LL_M + m];
     }
-    const float llw_tot = (J->w_off >= 0) ? 1.0f : J->ll_weight;        // (weighted per modality already)
+    const float llw_tot = (!PLAIN && J->w_off >= 0) ? 1.0f : J->ll_weight;        // (weighted per modality already)
     row[NM_LOSS_KL] = kl_w * kl;
     row[NM_LOSS_LL] = ll_sum;
     row[NM_LOSS_TC] = tc;
@@ -2328,7 +2446,7 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
   // ================= fusion backward: alpha gradients (gPoE) =================
   const bool fused = !(Me == 1 && J->single_bypass);
   const float klw = kl_w * c.inv_b;
-  const float tcw = J->tc_weight / (float)Me;     // (the softmax over the rows is normalised: no 1 / B)
+  const float tcw = PLAIN ? 0.f : J->tc_weight / (float)Me;     // (the softmax over the rows is normalised: no 1 / B)
   gbf16 ws_fz = (gbf16)ws_zc0;                    // the (dead) z|c slot, legacy [256][PW] layout
   // With several experts the fusion backward (8 exponentials per element) is evaluated ONCE: the deltas of every
   // expert go side by side into Q (expert m in columns [m 2Zs, (m+1) 2Zs) = [d mu_m | d logvar_m]), from there into
@@ -2379,7 +2497,7 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
         const f32x4 mj4 = *(const GAS f32x4*)(ws_mu_j + r * Zs + z0), lj4 = *(const GAS f32x4*)(ws_lv_j + r * Zs + z0);
         const f32x4 es4 = *(const GAS f32x4*)(ws_es + r * Zs + z0);
         f32x4 dz4 = load_dz4(r, z0);
-        if (J->dz_extra) {
+        if (!PLAIN && J->dz_extra) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) dz4[i] += asg(J->dz_extra)[(int64_t)(c.row0 + r) * Z + min(z0 + i, Z - 1)];
         }
@@ -2390,8 +2508,9 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
           Lat Lt;
 #pragma unroll
           for (int m = 0; m < NM_MAX_EXP; ++m) { Lt.mu[m] = mu4[m][i]; Lt.lv[m] = lv4[m][i]; }
-          const float dmu_j = dz4[i] + klw * mj4[i];
-          const float dlv_j = 0.5f * dz4[i] * es4[i] + klw * 0.5f * (fx_exp(lj4[i]) - 1.0f);
+          float dmu_j = dz4[i] + klw * mj4[i];
+          float dlv_j = 0.5f * dz4[i] * es4[i] + klw * 0.5f * (fx_exp(lj4[i]) - 1.0f);
+          if constexpr (PLAIN) plain_latent_deltas<true>(dz4[i], es4[i], mj4[i], lj4[i], klw, dmu_j, dlv_j);
           FuseGrad G = fuse_bwd(J, Lt, al, dmu_j, dlv_j);
           const bool ok = rv && z0 + i < Z;
 #pragma unroll
@@ -2424,9 +2543,10 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
         Lat Lt;
         load_lat(Lt, r, S + z);
         float mj = ws_mu_j[r * Zs + z], lj = ws_lv_j[r * Zs + z], es = ws_es[r * Zs + z], dz = load_dz(r, z);
-        if (J->dz_extra) dz += asg(J->dz_extra)[(int64_t)(c.row0 + r) * Z + z];
+        if (!PLAIN && J->dz_extra) dz += asg(J->dz_extra)[(int64_t)(c.row0 + r) * Z + z];
         float dmu_j = dz + klw * mj;
         float dlv_j = 0.5f * dz * es + klw * 0.5f * (fx_exp(lj) - 1.0f);
+        if constexpr (PLAIN) plain_latent_deltas<false>(dz, es, mj, lj, klw, dmu_j, dlv_j);
         FuseGrad G = fuse_bwd(J, Lt, al, dmu_j, dlv_j);
         const bool rv = r < c.nrows;
   #pragma unroll
@@ -2525,7 +2645,7 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
           const f32x4 mj4 = *(const GAS f32x4*)(ws_mu_j + r * Zs + z0), lj4 = *(const GAS f32x4*)(ws_lv_j + r * Zs + z0);
           const f32x4 es4 = *(const GAS f32x4*)(ws_es + r * Zs + z0);
           f32x4 dz4 = load_dz4(r, z0);
-          if (J->dz_extra) {
+          if (!PLAIN && J->dz_extra) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) dz4[i] += asg(J->dz_extra)[(int64_t)(c.row0 + r) * Z + min(z0 + i, Z - 1)];
           }
@@ -2536,8 +2656,9 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
             Lat Lt;
 #pragma unroll
             for (int q = 0; q < NM_MAX_EXP; ++q) { Lt.mu[q] = mu4[q][i]; Lt.lv[q] = lv4[q][i]; }
-            const float dmu_j = dz4[i] + klw * mj4[i];
-            const float dlv_j = 0.5f * dz4[i] * es4[i] + klw * 0.5f * (fx_exp(lj4[i]) - 1.0f);
+            float dmu_j = dz4[i] + klw * mj4[i];
+            float dlv_j = 0.5f * dz4[i] * es4[i] + klw * 0.5f * (fx_exp(lj4[i]) - 1.0f);
+            if constexpr (PLAIN) plain_latent_deltas<true>(dz4[i], es4[i], mj4[i], lj4[i], klw, dmu_j, dlv_j);
             FuseGrad G = fuse_bwd(J, Lt, al, dmu_j, dlv_j);
             const bool ok = rv && z0 + i < Z;
             float dmu_m = pick(G.dmu, m);
@@ -2557,9 +2678,10 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
           Lat Lt;
           load_lat(Lt, r, S + z);
           float mj = ws_mu_j[r * Zs + z], lj = ws_lv_j[r * Zs + z], es = ws_es[r * Zs + z], dz = load_dz(r, z);
-          if (J->dz_extra) dz += asg(J->dz_extra)[(int64_t)(c.row0 + r) * Z + z];
+          if (!PLAIN && J->dz_extra) dz += asg(J->dz_extra)[(int64_t)(c.row0 + r) * Z + z];
           float dmu_j = dz + klw * mj;
           float dlv_j = 0.5f * dz * es + klw * 0.5f * (fx_exp(lj) - 1.0f);
+          if constexpr (PLAIN) plain_latent_deltas<false>(dz, es, mj, lj, klw, dmu_j, dlv_j);
           FuseGrad G = fuse_bwd(J, Lt, al, dmu_j, dlv_j);
           const bool rv = r < c.nrows;
           float dmu_m = pick(G.dmu, m);
@@ -2596,10 +2718,10 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
     tr(c, 13);
     {
       const WgGeom Gm = geom_head(J, md, 0, spatch);
-      wgrad_adam<SCALAR_TR, RTV, RS>(c, c.P, LDP, 0, Qact, LDP, Gm, 0);
+      wgrad_adam<SCALAR_TR, RTV, RS, PLAIN>(c, c.P, LDP, 0, Qact, LDP, Gm, 0);
       const WgGeom Gl = geom_head(J, md, 1, spatch);
       // (pending = 0: its barrier also separates this pass's bias hand-off through LDS from the previous pass's)
-      wgrad_adam<SCALAR_TR, RTV, RS>(c, c.P, LDP, Zs, Qact, LDP, Gl, 0);
+      wgrad_adam<SCALAR_TR, RTV, RS, PLAIN>(c, c.P, LDP, Zs, Qact, LDP, Gl, 0);
     }
     prof(c, PH_ENCB_HEADS_WGRAD);
     finish_delta(c, acc, Qact, Hh, nl);             // P = delta of h_{L-1}
@@ -2612,7 +2734,7 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
       const WgGeom Ge = geom_enc(J, md, e, spatch);
       Qact = dgrad_hidden(c, acc, eimg, ws_enc + (int64_t)(m * L + (e - 1)) * ACT_BYTES, Nout, Kin);
       prof(c, PH_ENCB_DGRAD);
-      wgrad_adam<SCALAR_TR, RTV, RS>(c, c.P, LDP, 0, Qact, LDP, Ge, 0);
+      wgrad_adam<SCALAR_TR, RTV, RS, PLAIN>(c, c.P, LDP, 0, Qact, LDP, Ge, 0);
       prof(c, PH_ENCB_WGRAD);
       finish_delta(c, acc, Qact, Kin, nl);
       lds_barrier();
@@ -2636,7 +2758,7 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
           for (int j = 0; j < nch; ++j) dma_lin<0>(c, xsrc + (int64_t)j * XIMG_TILE_BYTES, Qb + j * XIMG_BYTES, XIMG_BYTES >> 10);
           WgGeom Gall = geom_l0(J, md, 0, spatch);
           Gall.ncols = Kx;
-          wgrad_adam<SCALAR_TR, RTV, RS>(c, c.P, LDP, 0, c.Q, LDX, Gall, 0, ROWS * LDX);
+          wgrad_adam<SCALAR_TR, RTV, RS, PLAIN>(c, c.P, LDP, 0, c.Q, LDX, Gall, 0, ROWS * LDX);
           prof(c, PH_ENCB_L0_WGRAD);
         } else {
         int cnt[NS];                                           // this wave's pieces of the copies in flight, oldest first
@@ -2653,7 +2775,7 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
 #pragma unroll
           for (int j = 1; j < NS - 1; ++j) behind += cnt[j];
           const __bf16* Xc = reinterpret_cast<const __bf16*>(Qb + (kc % NS) * XIMG_BYTES);
-          wgrad_adam<SCALAR_TR, RTV, RS>(c, c.P, LDP, 0, Xc, LDX, geom(kc), behind);
+          wgrad_adam<SCALAR_TR, RTV, RS, PLAIN>(c, c.P, LDP, 0, Xc, LDX, geom(kc), behind);
 #pragma unroll
           for (int j = 0; j < NS - 2; ++j) cnt[j] = cnt[j + 1];
           cnt[NS - 2] = n_new;
@@ -2669,7 +2791,7 @@ __device__ __forceinline__ void run_step(Ctx& c, int step) {
         int n_next = 0;
         if (kc + 1 < nch) n_next = dma_lin<0>(c, xsrc + (int64_t)(kc + 1) * XIMG_TILE_BYTES, Qb + ((kc + 1) & 1) * XIMG_BYTES, XIMG_BYTES >> 10);
         const __bf16* Xc = reinterpret_cast<const __bf16*>(Qb + (kc & 1) * XIMG_BYTES);
-        wgrad_adam<SCALAR_TR, RTV, RS>(c, c.P, LDP, 0, Xc, LDX, geom(kc), n_next);
+        wgrad_adam<SCALAR_TR, RTV, RS, PLAIN>(c, c.P, LDP, 0, Xc, LDX, geom(kc), n_next);
       }
       prof(c, PH_ENCB_L0_WGRAD);
       }
@@ -2731,13 +2853,16 @@ __device__ __forceinline__ void wait_us(int us) {
   while (__builtin_amdgcn_s_memrealtime() - t0 < ticks) __builtin_amdgcn_s_sleep(16);
 }
 
-template <bool SCALAR_TR, int MODE = 0>
+// PLAIN: see run_step.  launch_impl picks <false, 0, true> for NM_F_PLAIN training launches; the host cannot read the device
+// descriptors, so the kernel asks plain_job itself, once, before it touches anything of the job: on a miss the job's sticky
+// error word is set (nm_split_errors: NM_SYNC_ERR_PLAIN) and the workgroup leaves -- parameters, moments, images untouched.
+template <bool SCALAR_TR, int MODE = 0, bool PLAIN = false>
 __global__ __launch_bounds__(WG) void nm_step_kernel(const nm_job_t* __restrict__ jobs, int step0, int steps_per_tile,
                                                      int flags, int n_jobs, int nparts) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   int job_idx = blockIdx.x, part = -1;
   if ((flags & 64) && blockIdx.y == 0 && blockIdx.x < 512 && threadIdx.x == 0) nm_wg_times[blockIdx.x][0] = __builtin_amdgcn_s_memrealtime();
-  if (flags & NM_F_SPLIT) {
+  if (!PLAIN && (flags & NM_F_SPLIT)) {
     // workgroups b and b + 8 share an XCD (observed placement; speed only): the parts of a job are consecutive
     // workgroups of ONE XCD, so that their hand-offs and shared expert statistics stay inside one L2
     const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
@@ -2748,6 +2873,12 @@ __global__ __launch_bounds__(WG) void nm_step_kernel(const nm_job_t* __restrict_
   }
   const int tile_idx = blockIdx.y;
   const nm_job_t* J = jobs + job_idx;
+  if constexpr (PLAIN) {
+    if (!plain_job(J)) {                               // wave-uniform; every lane stores the same word
+      ((unsigned*)((char*)J->workspace + ws_layout(J->M, J->L, J->Z).sync))[WS_SYNC_ERR_WORD] = WS_SYNC_ERR_PLAIN;
+      return;
+    }
+  }
   Ctx c;
   c.job = J;
   c.part = part;
@@ -2783,8 +2914,8 @@ __global__ __launch_bounds__(WG) void nm_step_kernel(const nm_job_t* __restrict_
     if (flags & 64) c.tlast[c.wave_s] = clock64();
     lds_barrier();
     relaunder(c);
-    run_step<SCALAR_TR, MODE>(c, s);
-    if ((flags & NM_F_SPLIT) && *c.abort != 0u) break;       // a hand-off timed out (wave-uniform: LDS word read by all)
+    run_step<SCALAR_TR, MODE, RT, PLAIN>(c, s);
+    if (!PLAIN && (flags & NM_F_SPLIT) && *c.abort != 0u) break;       // a hand-off timed out (wave-uniform: LDS word read by all)
     tr(c, 62);
     // the next step reads what this one stored (weights, shadow images, workspace): drain, then meet
     handoff_barrier();

@@ -1306,7 +1306,7 @@ __global__ __launch_bounds__(WG) void test_gemm_kernel(int mode, const float* A,
 // ================================= C ABI ========================================================
 extern "C" {
 
-int nm_version(void) { return 10; }
+int nm_version(void) { return 11; }
 
 /* phase profile (NM_F_PROFILE): read / reset the per-phase shader-clock accumulators */
 int nm_prof_read(unsigned long long* out32, int reset) {
@@ -1501,6 +1501,11 @@ int nm_rowsplit_ok(const nm_job_t* j) {
   return 0;
 }
 
+int nm_plain_ok(const nm_job_t* j) {
+  if (!j) return NM_E_NULL;
+  return plain_job(j) ? 0 : 1;
+}
+
 static int launch_impl(const nm_job_t* jobs_dev, int n_jobs, int step0, int steps_per_tile, int n_tiles, int flags,
                        void* stream, bool scalar_tr, int parts = 1) {
   if (int bad = check_launch_geometry(jobs_dev, n_jobs, n_tiles, steps_per_tile, step0, flags)) return bad;
@@ -1519,8 +1524,14 @@ static int launch_impl(const nm_job_t* jobs_dev, int n_jobs, int step0, int step
     flags |= NM_F_SPLIT;
     nm_sync_reset(jobs_dev, n_jobs, stream);
   }
+  // NM_F_PLAIN counts for a whole-batch training launch only (backward + Adam, no gradient export, no exports, no given z);
+  // tracing and the phase profile stay legal with it
+  const int mode_flags = NM_F_BACKWARD | NM_F_ADAM | NM_F_GRADS | NM_F_EXPORT | NM_F_ZGIVEN;
+  const bool plain = (flags & NM_F_PLAIN) && parts <= 1 && !scalar_tr && (flags & mode_flags) == (NM_F_BACKWARD | NM_F_ADAM);
+  flags &= ~NM_F_PLAIN;
   auto kernel = nm_step_kernel<false, 3>;                 // forward only: the instantiation without the backward pass
   if (scalar_tr) kernel = nm_step_kernel<true>;
+  else if (plain) kernel = nm_step_kernel<false, 0, true>;
   else if (flags & NM_F_BACKWARD) kernel = nm_step_kernel<false>;
   return launch_kernel(kernel, grid, dim3(WG), SMEM_BYTES, stream, jobs_dev, step0, steps_per_tile, flags, n_jobs, parts);
 }

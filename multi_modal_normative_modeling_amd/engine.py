@@ -287,6 +287,18 @@ class Job:
         return (not s.wide and s.kind in ("single", "multimodal") and len(self.kmods) == s.M and s.M <= _lib.NM_MAX_EXP
                 and self.tc_weight == 0.0 and self.rowsplit_limit() is None)
 
+    def plain_ok(self) -> bool:
+        """nm_plain_ok for this job, read off the job as devpass_ok is: a cVAE / cVAE_multimodal trunk on the fused kernel with
+        nothing the step kernel's plain-training instantiation has folded away -- no head and none of its extra gradients, no
+        export buffer.  (The kinds left out carry the rest: the DMVAE family's sigmoid output, private columns and learnable
+        weights, mvtCAE's total correlation, the end-to-end model's decoder-only modalities.)"""
+        s = self.spec
+        return (not s.wide and s.kind in ("single", "multimodal") and len(self.kmods) == s.M and self.tc_weight == 0.0
+                and self.dz_extra is None and all(t is None for t in self.dloc_extra) and all(t is None for t in self.dloc_rowcoef)
+                and self.out_mu is None and self.out_logvar is None and self.out_z is None
+                and all(t is None for t in self.out_loc) and all(t is None for t in self.out_sqerr)
+                and all(t is None for t in self.out_rowdev))
+
     def rowsplit_limit(self) -> Optional[str]:
         """The row-split sweep table limit a modality of this model exceeds (layout.rowsplit_limit), or None."""
         kxs = tuple(self.tables[m].Kx for m, _, _ in self.kmods)
@@ -529,6 +541,8 @@ class JobSet:
         self._err_kinds = set()          # the kinds behind the error words in flight
         self._err_inflight = None        # (event, pinned host copy) of the error words being fetched
         self._err_dev = self._err_host = None
+        self._plain_sig = self._plain_all = None   # plain_pick(): the jobs' descriptor versions it last judged, and the verdict
+        self.last_launch = None          # {"entry", "flags", "plain"} of the set's last launch (plain: the plain-training kernel)
 
     @functools.cached_property
     def _cus(self) -> int:
@@ -549,7 +563,13 @@ class JobSet:
                 kinds = self._err_kinds
                 vals = host.tolist()
                 shape = [i for i, v in enumerate(vals) if v == _lib.NM_SYNC_ERR_SHAPE]
-                bad = [i for i, v in enumerate(vals) if v != 0 and v != _lib.NM_SYNC_ERR_SHAPE]
+                plain = [i for i, v in enumerate(vals) if v == _lib.NM_SYNC_ERR_PLAIN]
+                bad = [i for i, v in enumerate(vals) if v not in (0, _lib.NM_SYNC_ERR_SHAPE, _lib.NM_SYNC_ERR_PLAIN)]
+                if plain:
+                    raise _lib.NmError(f"plain-training launch (NM_F_PLAIN): job(s) {plain[:8]} need the generic step kernel "
+                                       f"(nm_plain_ok: a head, extra gradients, exports, a model kind beyond the plain trunk) and "
+                                       f"were refused by the kernel; their parameters were not updated -- run them with "
+                                       f"plain=False or NMHIP_PLAIN=0")
                 if shape:
                     raise _lib.NmError(f"row-split launch: job(s) {shape[:8]} exceed the Adam sweep's tables (passes, vector "
                                        f"segments or vector elements; nm_rowsplit_ok) -- or the launch's group map lists them "
@@ -635,9 +655,35 @@ class JobSet:
             self._split_pending = True
             self._pending_kinds.add(kind)
 
-    def _launch(self, step0, steps_per_tile, n_tiles, flags, scalar_tr=False):
+    def plain_pick(self) -> bool:
+        """Does every job of the set pass Job.plain_ok (the plain-training kernel serves the set's whole-batch training
+        launches)?  Judged once per state of the jobs' descriptors; NMHIP_PLAIN=0 switches the kernel off."""
+        if self.wide or os.environ.get("NMHIP_PLAIN", "1") == "0":
+            return False
+        sig = tuple(j._version for j in self.jobs)
+        if sig != self._plain_sig:
+            self._plain_sig, self._plain_all = sig, all(j.plain_ok() for j in self.jobs)
+        return self._plain_all
+
+    def _launch(self, step0, steps_per_tile, n_tiles, flags, scalar_tr=False, plain: Optional[bool] = None):
+        """nm_launch (general-shape sets: nm_launch_wide).  A training launch -- backward + Adam, nothing else but the
+        diagnostic flags -- of a set that passes plain_pick() carries NM_F_PLAIN: the step kernel's plain-training
+        instantiation, bit-identical results.  plain=False keeps the generic kernel; plain=True insists (ValueError if the
+        launch or a job does not qualify)."""
         entry = "nm_launch_wide" if self.wide else ("nm_launch_scalar_tr" if scalar_tr else "nm_launch")
+        mode = flags & (_lib.NM_F_BACKWARD | _lib.NM_F_ADAM | _lib.NM_F_GRADS | _lib.NM_F_EXPORT | _lib.NM_F_ZGIVEN)
+        use_plain = (plain is not False and entry == "nm_launch" and n_tiles == 1
+                     and mode == (_lib.NM_F_BACKWARD | _lib.NM_F_ADAM) and self.plain_pick())
+        if plain and not use_plain:
+            raise ValueError("plain=True: the plain-training kernel serves whole-batch training launches of sets whose jobs all "
+                             "pass Job.plain_ok() (and NMHIP_PLAIN is not 0)")
+        if use_plain:
+            flags |= _lib.NM_F_PLAIN
         self._issue(entry, n_tiles, step0, steps_per_tile, n_tiles, flags)
+        self.last_launch = {"entry": entry, "flags": int(flags), "plain": bool(use_plain)}
+        if use_plain:                                # (the kernel's own guard reports through the jobs' error words)
+            self._split_pending = True
+            self._pending_kinds.add("plain")
 
     def _launch_split(self, step0, n_steps, flags):
         """nm_launch_split: every model as one workgroup per modality (small sets; see split_parts)."""
@@ -716,14 +762,17 @@ class JobSet:
         parts = self.split_parts() if split is None else (len(self.jobs[0].kmods) if split else 1)
         return ("split", parts) if parts > 1 else ("whole", 1)
 
-    def _launch_form(self, form, step0: int, n_steps: int, flags: int, helpers: Optional[int], scalar_tr: bool):
+    def _launch_form(self, form, step0: int, n_steps: int, flags: int, helpers: Optional[int], scalar_tr: bool,
+                     plain: Optional[bool] = None):
         kind, k = form
         if kind == "rowsplit":
             self._launch_rowsplit(k, step0, n_steps, flags, helpers)
         elif kind == "split":
             self._launch_split(step0, n_steps, flags)
         else:
-            self._launch(step0, n_steps, 1, flags, scalar_tr)
+            self._launch(step0, n_steps, 1, flags, scalar_tr, plain)
+            return
+        self.last_launch = {"entry": kind, "flags": int(flags), "plain": False}
 
     def _check_jobs(self, head: Optional[str] = None, caller: str = "", at_step: bool = True) -> int:
         """Preconditions of a launch: every job at the same step (at_step; returned) and, for a head model's step
@@ -746,15 +795,17 @@ class JobSet:
             j.t += n_steps
 
     def train(self, n_steps: int, scalar_tr: bool = False, profile: bool = False, split: Optional[bool] = None,
-              rowsplit: Optional[int] = None, helpers: Optional[int] = None):
+              rowsplit: Optional[int] = None, helpers: Optional[int] = None, plain: Optional[bool] = None):
         """n_steps fused train steps per job in ONE launch (forward + ELBO + backward + Adam).  Small sets put several
         workgroups behind a model: k row slices per (model, modality) (rowsplit=None: rowsplit_k(); results agree with the
         one-workgroup launch to fp32 summation order), else one workgroup per modality (split=None: automatically;
-        bit-identical to the one-workgroup launch).  scalar_tr: the whole-batch launch on the scalar-loader kernel."""
+        bit-identical to the one-workgroup launch).  scalar_tr: the whole-batch launch on the scalar-loader kernel.
+        plain: the one-workgroup launch on the plain-training kernel (None: when every job passes plain_ok(); False: never;
+        bit-identical either way), see _launch."""
         step0 = self._check_jobs()
         flags = _lib.NM_F_BACKWARD | _lib.NM_F_ADAM | (_lib.NM_F_PROFILE if profile else 0)
         form = ("whole", 1) if scalar_tr else self._training_form(split, rowsplit)
-        self._launch_form(form, step0, n_steps, flags, helpers, scalar_tr)
+        self._launch_form(form, step0, n_steps, flags, helpers, scalar_tr, plain)
         self._advance(n_steps)
 
     def grads(self, step: Optional[int] = None, export: bool = True, scalar_tr: bool = False, split: bool = False,

@@ -63,6 +63,9 @@ def resources(asm_text: str):
 # scalar pressure worse is seen at build time (round 2 built 458 / 512 without anyone looking).
 LIMITS = {
     "nm_step_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 540},
+    # (the plain-training instantiation <false, 0, true>: launch constants folded, the build shows 360 against the generic 493 --
+    #  plus the margin of 64; the family entry above holds for it as well)
+    "nm_step_kernelILb0ELi0ELb1E": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 424},
     "nm_devpass_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 64, "vgpr_count": 128},
     # (the build shows 49 SGPR spills -- the loops over experts and decoders keep more scalars alive -- plus the margin of 64 above)
     "nm_devpass_multi_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 112, "vgpr_count": 128},
