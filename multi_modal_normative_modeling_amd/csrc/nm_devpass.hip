@@ -13,7 +13,8 @@
 //                        [64][136] output-chunk slots (their bias / logvar_out pieces go to the two vector slots), or --
 //                        beside the 32-row heads image -- the sampled z as bf16 [128][32]
 // 16-row MFMA tiles at or beyond the tile's valid rows are skipped in every phase (a 1064-row table costs 1064 rows
-// rounded to 16, not 5 x 256), and the export epilogue makes one pass: residual, its square (stored), row sum.
+// rounded to 16, not 5 x 256; their export rows are zeroed, dv_zero_dead_rows), and the export epilogue makes one pass:
+// residual, its square (stored), row sum.
 // Arithmetic, draws (keyed by absolute row) and exports are those of the general kernel, row by row: the two agree bit for
 // bit on out_sqerr / out_rowdev / out_loc (tests/test_gpu_devpass.py).  No loss log, no latent exports: launches that want
 // those, a first hidden layer wider than 112 or a latent wider than 32 stay on nm_forward.  Models with several experts
@@ -51,6 +52,21 @@ __device__ __forceinline__ void dv_carve(Ctx& c, unsigned char* smem) {
   c.lse = nullptr; c.bgrad = nullptr;
   c.tlast = reinterpret_cast<unsigned long long*>(c.rowacc + 128);
   c.abort = reinterpret_cast<unsigned*>(c.tlast + 8);
+}
+
+// The export rows of a 128-row tile that the output phase leaves alone: the dead 16-row tiles of out_loc / out_sqerr (rows
+// [live rounded up to 16, 128); a live 16-row tile's own rows past the table's end are stored as zeros by its wave) and every
+// row of out_rowdev from `live` on.  They come back as zeros whatever the buffers held before the launch -- the export
+// buffers hold whole 256-row tiles, and the general kernel stores the whole tile.  live = 0: a tile without a table row.
+__device__ __forceinline__ void dv_zero_dead_rows(const nm_modality_t& md, int row0, int live) {
+  const int xp = md.x_pitch, r16 = rup(live, 16);
+  for (int e = threadIdx.x; e < (DV_ROWS - r16) * (xp >> 2); e += WG) {
+    const int64_t gi = (int64_t)(row0 + r16) * xp + (int64_t)e * 4;
+    if (md.out_loc) *(GAS f32x4*)(asg(md.out_loc) + gi) = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (md.out_sqerr) *(GAS f32x4*)(asg(md.out_sqerr) + gi) = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  if (md.out_rowdev)
+    for (int r = live + (int)threadIdx.x; r < DV_ROWS; r += WG) asg(md.out_rowdev)[row0 + r] = 0.f;
 }
 
 // One hidden layer, P -> P in place, image in W (requested by the phase before, its vector piece in slot `vs`): wait, GEMM
@@ -93,15 +109,7 @@ __global__ __launch_bounds__(WG, 4) void nm_devpass_kernel(const nm_job_t* __res
   const int row0 = t128 * ROWS;
   if (row0 >= J->n_rows) {
     // the second half of a ragged last 256-row tile: its export rows come back as zeros, as from the general kernel
-    const nm_modality_t& m0 = J->mod[0];
-    const int xp0 = m0.x_pitch;
-    if (row0 < (J->n_rows + TROWS - 1) / TROWS * TROWS) {
-      for (int e = threadIdx.x; e < ROWS * (xp0 >> 2); e += WG) {
-        const int64_t gi = (int64_t)row0 * xp0 + (int64_t)e * 4;
-        if (m0.out_loc) *(GAS f32x4*)(asg(m0.out_loc) + gi) = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (m0.out_sqerr) *(GAS f32x4*)(asg(m0.out_sqerr) + gi) = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-    }
+    if (row0 < (J->n_rows + TROWS - 1) / TROWS * TROWS) dv_zero_dead_rows(J->mod[0], row0, 0);
     return;
   }
   Ctx c;
@@ -271,6 +279,7 @@ __global__ __launch_bounds__(WG, 4) void nm_devpass_kernel(const nm_job_t* __res
     v += __shfl_xor(v, 32, 64);
     if (c.g == 0 && orow < c.nrows) asg(md.out_rowdev)[row0 + orow] = v / (float)D;
   }
+  if (live < ROWS) dv_zero_dead_rows(md, row0, live);   // (a ragged tile only: the rows no wave has stored)
   tr(c, 8);
 }
 
@@ -324,17 +333,8 @@ __global__ __launch_bounds__(WG, 4) void nm_devpass_multi_kernel(const nm_job_t*
   const int row0 = t128 * ROWS;
   if (row0 >= J->n_rows) {
     // the second half of a ragged last 256-row tile: every modality's export rows come back as zeros
-    if (row0 < (J->n_rows + TROWS - 1) / TROWS * TROWS) {
-      for (int m = 0; m < M; ++m) {
-        const nm_modality_t& mm = J->mod[m];
-        const int xpm = mm.x_pitch;
-        for (int e = threadIdx.x; e < ROWS * (xpm >> 2); e += WG) {
-          const int64_t gi = (int64_t)row0 * xpm + (int64_t)e * 4;
-          if (mm.out_loc) *(GAS f32x4*)(asg(mm.out_loc) + gi) = f32x4{0.f, 0.f, 0.f, 0.f};
-          if (mm.out_sqerr) *(GAS f32x4*)(asg(mm.out_sqerr) + gi) = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-      }
-    }
+    if (row0 < (J->n_rows + TROWS - 1) / TROWS * TROWS)
+      for (int m = 0; m < M; ++m) dv_zero_dead_rows(J->mod[m], row0, 0);
     return;
   }
   Ctx c;
@@ -571,6 +571,7 @@ __global__ __launch_bounds__(WG, 4) void nm_devpass_multi_kernel(const nm_job_t*
       v += __shfl_xor(v, 32, 64);
       if (c.g == 0 && orow < c.nrows) asg(md.out_rowdev)[row0 + orow] = v / (float)D;
     }
+    if (live < ROWS) dv_zero_dead_rows(md, row0, live);   // (a ragged tile only: the rows no wave has stored)
     tr(c, 8);
   }
 }

@@ -97,7 +97,8 @@ def test_devpass_multi_equals_general_forward_bit_for_bit(N, dims, hidden, Z, c_
 def test_empty_half_tile_is_zeroed_in_every_modality():
     """300 rows: the 128-row tile [384, 512) holds no row -- its export rows must come back as zeros in EVERY modality, also
     when the buffers held something else before the launch (the general kernel stores the whole 256-row batch).  (Dead
-    16-row tiles inside a live 128-row tile, rows 304..383 here, are skipped, stores included, as in nm_devpass.)"""
+    16-row tiles inside a live 128-row tile, rows 304..383 here, are skipped in every phase, as in nm_devpass; their export
+    rows are zeroed once the output phase is through -- tests/test_gpu_twins.py looks at every row past the table.)"""
     N, dims = 300, (61, 90, 47)
     xs, cs = _data(N, dims, 3, seed=2)
     job = _job(_tables(xs, cs), dims, (64, 48), 12, 3, "gpoe", seed=4)
