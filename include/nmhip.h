@@ -624,6 +624,67 @@ int nm_column_regress(const nm_reg_set_t* sets_dev, int n_sets, int D, int max_r
                       double* out /* [n_sets][D][NM_METRICS_STRIDE] */, void* stream);
 double nm_student_t_two_sided(double t, double df);
 
+/* Normative z-maps: a cohort's deviations scored against a reference cohort, ROI by ROI, and the full-covariance distance
+ * in latent space (the sigma-normalised extra of SURVEY.md; never the parity output).  Set s of the device array sets_dev is
+ * a matrix x[rows][pitch] (fp32, pitch >= the width, read where it lies) with an optional second matrix sub[rows][sub_pitch]:
+ * the value of an element is v = (double)x - (double)sub (the signed residual, a table against the out_loc export), or
+ * v = x when sub is NULL (the squared error of the out_sqerr export).  group[rows] (int32): 0 = the reference cohort (the
+ * controls), 1 = the patients, anything else neither.  All arithmetic is fp64 from the load on; there are no atomics, every
+ * sum has a fixed order (two runs give the same bytes), and a set's output does not depend on its place in the launch.
+ * A set with rows < 0, rows > max_rows, pitch (or sub_pitch with sub, z_pitch with z) below the width, or a null x (or a
+ * null group where the entry point reads the groups) with rows > 0 is refused: nothing of it is read, its per-set and
+ * per-column outputs are NaN / status -2, and its per-row outputs are status / NaN rows when 0 <= rows <= max_rows (a row
+ * count outside that range names no rows to write).  Per-row outputs of set s start at row row_off of the output arrays.
+ *
+ * nm_cohort_moments: per (set, column) over the rows with group 0, in row order.  out [n_sets][D][NM_METRICS_STRIDE] fp64 =
+ *   {mean, sd, var, n_ref, min, max, n_nonfinite, status}; var = sum (v - mean)^2 / (n_ref - ddof), ddof 0 or 1, by two passes
+ *   over the column (the second corrected by the sum of the centred values), so an offset of 1e4 on unit spread keeps its
+ *   variance; min / max over the finite reference values (NaN without one); status 0, or -2 with mean = sd = var = NaN when
+ *   n_ref <= ddof, a reference value is not finite, or the variance is zero (min == max).  One workgroup per (set, 64 columns), a lane
+ *   per column, the four waves take every fourth row and their partials are merged through LDS in wave order.
+ * nm_normative_z: every row of set s (any group) against row ref = ref_of[s] (ref_of NULL: s) of a moments table
+ *   moments [n_moments][D][NM_METRICS_STRIDE] as nm_cohort_moments writes it; z = (v - mean) / sd in fp64.
+ *   z (per set, may be NULL) [rows][z_pitch] fp32: z rounded once; NaN where v is not finite or the column's moments are not
+ *     valid (status != 0); pad columns D..z_pitch are not touched.
+ *   rows_out [sum rows][NM_METRICS_STRIDE] = {n_hi, n_lo, mean_z, mean_abs_z, max_z, argmax_z, n_valid, status} over the
+ *     columns with valid moments and finite v: n_hi counts z > thr, n_lo z < -thr (compared in fp64); argmax_z the first
+ *     column of the largest z; without a valid column the means and max_z are NaN, argmax_z = -1 and status = -2.  A wave
+ *     per row: a lane adds its columns lane, lane + 64, ... in that order, the lanes are merged by a butterfly of fixed shape.
+ *   cols_out [n_sets][D][NM_METRICS_STRIDE] = {n_hi_x, n_lo_x, n_hi_y, n_lo_y, n_x, n_y, mean_z_x, mean_z_y}: x = the rows
+ *     of group 1, y = of group 0, with a finite v (the extreme-deviation map); rows walked as nm_cohort_moments walks them.
+ *     A column with invalid moments: six zero counts and NaN means; a refused set or ref outside 0..n_moments-1: NaN.
+ *   D <= NM_NORM_MAX_D (the rows kernel holds mean and sd of every column in LDS, 16 D bytes).
+ * nm_cohort_cov: per set over the rows with group 0 of a table of width Z, 1 <= Z <= NM_WIDE_MAX_LATENT: mean_out [n_sets][Z]
+ *   the column means, chol_out [n_sets][Z][Z] the lower Cholesky factor L (row-major, zeros above the diagonal) of the sample
+ *   covariance (ddof 1, np.cov(rowvar=False)) of the mean-centred rows plus ridge on the diagonal, status_out [n_sets] int32:
+ *   0, or -2 with L = NaN when n_ref < 2, a reference value is not finite, n_ref <= Z with ridge == 0 (the sample covariance
+ *   of n_ref rows has rank <= n_ref - 1), or a pivot is <= Z * 2^-52 * the largest diagonal entry (NaN included).  One
+ *   workgroup per set; the matrix lives in LDS (8 Z^2 bytes); rows are added in row order, the factor column by column.
+ * nm_mahalanobis: per row (any group) of set s, d2 = |L^-1 (v - mean)|^2 by forward substitution against factor
+ *   ref = ref_of[s] (NULL: s) of n_factors; d2_out / d_out [sum rows] fp64 (d = sqrt d2); NaN for a row with a non-finite
+ *   entry, a factor whose status is not 0, or ref outside 0..n_factors-1.  A thread per row.
+ * Status, decided before the device is asked anything: NM_E_NULL a required pointer missing; NM_E_LATENT Z outside
+ * 1..NM_WIDE_MAX_LATENT; NM_E_METRICS n_sets < 1, D < 1 (nm_normative_z: D > NM_NORM_MAX_D), max_rows outside
+ * 1..NM_METRICS_MAX_N, ddof not 0 or 1, thr not finite or <= 0, ridge negative or not finite, n_moments / n_factors < 1. */
+#define NM_NORM_MAX_D        4096
+#define NM_NORM_ROWS_PER_WG  32       /* rows a workgroup of the rows pass of nm_normative_z scores against one staging */
+typedef struct nm_norm_set {
+  const float*   x;              /* [rows][pitch], read where it lies */
+  const float*   sub;            /* [rows][sub_pitch] or NULL: v = x - sub */
+  const int32_t* group;          /* [rows]: 0 the reference cohort, 1 the patients (nm_mahalanobis does not read it) */
+  float*         z;              /* nm_normative_z: [rows][z_pitch] or NULL */
+  int32_t rows, pitch, sub_pitch, z_pitch;
+  int32_t row_off, pad;          /* the set's first row in the per-row outputs */
+} nm_norm_set_t;
+int nm_cohort_moments(const nm_norm_set_t* sets_dev, int n_sets, int D, int max_rows, int ddof,
+                      double* out /* [n_sets][D][NM_METRICS_STRIDE] */, void* stream);
+int nm_normative_z(const nm_norm_set_t* sets_dev, int n_sets, int D, int max_rows, const double* moments, int n_moments,
+                   const int32_t* ref_of, double thr, double* rows_out, double* cols_out, void* stream);
+int nm_cohort_cov(const nm_norm_set_t* sets_dev, int n_sets, int Z, int max_rows, double ridge, double* mean_out,
+                  double* chol_out, int32_t* status_out, void* stream);
+int nm_mahalanobis(const nm_norm_set_t* sets_dev, int n_sets, int Z, int max_rows, const double* mean, const double* chol,
+                   const int32_t* status, int n_factors, const int32_t* ref_of, double* d2_out, double* d_out, void* stream);
+
 /* The expert-fusion operators the reference exposes as public methods, as forward-only launches (elementwise over
  * [M][n] fp32 device tensors; csrc/nm_fusion.hip):
  *   cVAE_multimodal.combine_latent(mus, variances, combine)                      cVAE.py:1144-1164   (also :2292-2307)

@@ -71,6 +71,10 @@ NM_REG_LOGIT = 1
 NM_REG_MAX_COV = 4
 NM_REG_MAX_ITER = 35
 NM_REG_TOL = 1e-8
+# nm_normative_z: the widest table (its rows pass holds mean and sd of every column in LDS), the rows a workgroup of that
+# pass scores (tests put the heights around it)
+NM_NORM_MAX_D = 4096
+NM_NORM_ROWS_PER_WG = 32
 
 # status codes (nmhip.h; nm_status_string gives the text)
 NM_OK = 0
@@ -158,6 +162,13 @@ class NmRegSet(C.Structure):
                 ("rows", C.c_int32), ("pitch", C.c_int32), ("cov_pitch", C.c_int32), ("pad", C.c_int32)]
 
 
+class NmNormSet(C.Structure):
+    """nm_norm_set_t: one table of the pointer table of nm_cohort_moments, nm_normative_z, nm_cohort_cov, nm_mahalanobis."""
+    _fields_ = [("x", C.c_void_p), ("sub", C.c_void_p), ("group", C.c_void_p), ("z", C.c_void_p),
+                ("rows", C.c_int32), ("pitch", C.c_int32), ("sub_pitch", C.c_int32), ("z_pitch", C.c_int32),
+                ("row_off", C.c_int32), ("pad", C.c_int32)]
+
+
 class NmError(RuntimeError):
     pass
 
@@ -234,6 +245,10 @@ def load():
     lib.nm_auc_bootstrap_workspace.argtypes = [i32, i32, i32, i32]
     lib.nm_auc_bootstrap.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, C.c_uint64, vp, i32, vp, C.c_size_t, vp, vp, vp, vp]
     lib.nm_column_regress.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]
+    lib.nm_cohort_moments.argtypes = [vp, i32, i32, i32, i32, vp, vp]
+    lib.nm_normative_z.argtypes = [vp, i32, i32, i32, vp, i32, vp, C.c_double, vp, vp, vp]
+    lib.nm_cohort_cov.argtypes = [vp, i32, i32, i32, C.c_double, vp, vp, vp, vp]
+    lib.nm_mahalanobis.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp]
     lib.nm_student_t_two_sided.restype = C.c_double
     lib.nm_student_t_two_sided.argtypes = [C.c_double, C.c_double]
     lib.nm_adam_step.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, i64, vp]
@@ -267,6 +282,7 @@ EXPORTED_SYMBOLS = [
     "nm_auc_bootstrap_workspace", "nm_auc_bootstrap",
     "nm_column_regress", "nm_student_t_two_sided",
     "nm_plain_ok",
+    "nm_cohort_moments", "nm_normative_z", "nm_cohort_cov", "nm_mahalanobis",
 ]
 
 

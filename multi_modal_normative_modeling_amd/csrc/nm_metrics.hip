@@ -18,6 +18,10 @@
 //   nm_column_regress     tables and a target per set -> per column the OLS or Logit fit target ~ const + column + covariates:
 //                         both reported parameters, their standard errors and p-values
 //                         (latent_pvalues, utils_vae.py:163-174, once per column; after the bootstrap)
+//   nm_cohort_moments, nm_normative_z, nm_cohort_cov, nm_mahalanobis
+//                         ROI tables -> z-scores against a reference cohort, the per-subject and per-ROI counts beyond a threshold;
+//                         latent tables -> a cohort's covariance factor and every row's Mahalanobis distance to it
+//                         (the sigma-normalised extra of SURVEY.md; nm_normative.inc, included at the end of this file)
 //
 // One workgroup per score set (a (fold, procedure) cell); sets are segments of one concatenated array.  The
 // whole set lives in LDS: order-preserving 64-bit keys (score, label) are bitonic-sorted descending, label
@@ -1590,3 +1594,5 @@ int nm_auc_bootstrap(const float* scores, const int32_t* labels, const int32_t* 
 }
 
 }  // extern "C"
+
+#include "nm_normative.inc"

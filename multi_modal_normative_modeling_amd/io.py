@@ -135,6 +135,44 @@ def write_roi_regress_csv(out_dir, dataset_name: str, roi_columns: Sequence[str]
     return path
 
 
+def write_normative_csvs(out_dir, dataset_name: str, covariates: pd.DataFrame, roi_columns: Sequence[str], z: np.ndarray,
+                         rows: np.ndarray, cols: np.ndarray) -> Dict[str, Path]:
+    """The normative z-map of one set of subjects (metrics.normative_z), with the metadata columns of write_test_csvs:
+      normative_z_{name}.csv        participant_id, DIA, AGE, PTGENDER, then one z per ROI
+      normative_subject_{name}.csv  participant_id, DIA, AGE, PTGENDER, then metrics.NORMATIVE_ROW_COLUMNS
+      normative_map_{name}.csv      ROI, then metrics.NORMATIVE_COL_COLUMNS (the extreme-deviation map)"""
+    from .metrics import NORMATIVE_COL_COLUMNS, NORMATIVE_ROW_COLUMNS
+    z, rows, cols = np.asarray(z), np.asarray(rows, dtype=np.float64), np.asarray(cols, dtype=np.float64)
+    if z.shape != (len(covariates), len(roi_columns)) or rows.shape != (len(covariates), len(NORMATIVE_ROW_COLUMNS)) or \
+            cols.shape != (len(roi_columns), len(NORMATIVE_COL_COLUMNS)):
+        raise ValueError(f"z [{len(covariates)}, {len(roi_columns)}], rows [{len(covariates)}, 8] and cols [{len(roi_columns)}, 8] "
+                         f"are needed, got {z.shape}, {rows.shape}, {cols.shape}")
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    cov = covariates[META_COLS].copy().reset_index(drop=True)
+    paths = {k: out_dir / f"normative_{k}_{dataset_name}.csv" for k in ("z", "subject", "map")}
+    pd.concat([cov, pd.DataFrame(z, columns=list(roi_columns))], axis=1).to_csv(paths["z"], index=False)
+    pd.concat([cov, pd.DataFrame(rows, columns=list(NORMATIVE_ROW_COLUMNS))], axis=1).to_csv(paths["subject"], index=False)
+    df = pd.DataFrame(cols, columns=list(NORMATIVE_COL_COLUMNS))
+    df.insert(0, "ROI", list(roi_columns))
+    df.to_csv(paths["map"], index=False)
+    return paths
+
+
+def write_latent_mahalanobis_csv(out_dir, name: str, covariates: pd.DataFrame, d: np.ndarray) -> Path:
+    """latent_mahalanobis_{name}.csv: participant_id, DIA, AGE, PTGENDER, d2, d -- the Mahalanobis distance of every test
+    subject's joint mu to the fold's train cohort (metrics.cohort_cov / metrics.mahalanobis), next to latent_deviation_{name}.csv."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    df = covariates[META_COLS].copy().reset_index(drop=True)
+    d = np.asarray(d, dtype=np.float64)
+    df["d2"] = d * d
+    df["d"] = d
+    path = out_dir / f"latent_mahalanobis_{name}.csv"
+    df.to_csv(path, index=False)
+    return path
+
+
 def latent_pvalues_frame(table: np.ndarray) -> pd.DataFrame:
     """The DataFrame latent_pvalues returns (utils_vae.py:163-174) from a [Z, 8] metrics.column_regress table: labels =
     ['const', 'latent'], one column 'latent i' per latent dimension with the two p-values."""

@@ -13,6 +13,9 @@ Benjamini-Hochberg q and the max-statistic label-permutation test; `mann_whitney
 comparison of sets that share subjects; `auc_compare` is the two-procedure convenience on top of it.
 `column_regress` = one OLS or Logit fit per column of many tables at once (target ~ const + column + covariates, the Wald
 p-values of both reported parameters); `latent_pvalues` is the reference's signature (utils_vae.py:163-174) on top of it.
+`cohort_moments` / `normative_z` = the normative z-map: per ROI column the reference cohort's mean and sd, every subject's
+z-score against them with the per-subject extreme-deviation counts and the per-ROI extreme-deviation map; `cohort_cov` /
+`mahalanobis` = the full-covariance counterpart in latent space (the sigma-normalised extra of SURVEY.md, never the parity output).
 """
 from __future__ import annotations
 
@@ -411,3 +414,192 @@ def latent_pvalues(latent, target, type, device=None):
     tab = column_regress([lat.to(dev)], [tgt], kind="ols" if type == "continuous" else "logit", device=dev)[0].cpu().numpy()
     from .io import latent_pvalues_frame
     return latent_pvalues_frame(tab)
+
+
+COHORT_MOMENTS_COLUMNS = ("mean", "sd", "var", "n_ref", "min", "max", "n_nonfinite", "status")
+NORMATIVE_ROW_COLUMNS = ("n_hi", "n_lo", "mean_z", "mean_abs_z", "max_z", "argmax_z", "n_valid", "status")
+NORMATIVE_COL_COLUMNS = ("n_hi_x", "n_lo_x", "n_hi_y", "n_lo_y", "n_x", "n_y", "mean_z_x", "mean_z_y")
+
+
+def _norm_table(mats, groups=None, subs=None, zs=None):
+    """The pointer table of the four normative entry points on the host: every matrix where it lies, as _roi_table; the
+    per-row outputs of set k start at the sum of the heights before it."""
+    table = (_lib.NmNormSet * len(mats))()
+    off = 0
+    for k, m in enumerate(mats):
+        rows, e = int(m.shape[0]), table[k]
+        e.rows, e.pitch = rows, (int(m.stride(0)) if rows > 1 else int(m.shape[1]))
+        e.sub_pitch = e.z_pitch = e.pad = 0
+        e.row_off = off
+        off += rows
+        if rows:
+            e.x = m.data_ptr()
+            e.group = groups[k].data_ptr() if groups is not None else None
+            if subs is not None:
+                e.sub, e.sub_pitch = subs[k].data_ptr(), (int(subs[k].stride(0)) if rows > 1 else int(subs[k].shape[1]))
+            if zs is not None:
+                e.z, e.z_pitch = zs[k].data_ptr(), int(zs[k].stride(0)) if rows > 1 else int(zs[k].shape[1])
+    return table
+
+
+def _norm_check(mats, groups, sub) -> int:
+    """_roi_check, and a `sub` matrix of the same shape and kind per set (no device is looked for); the width."""
+    D = _roi_check(mats, groups)
+    if sub is not None:
+        if len(sub) != len(mats):
+            raise ValueError("sub must have one entry per set")
+        for k, (m, b) in enumerate(zip(mats, sub)):
+            if not isinstance(b, torch.Tensor) or b.dtype != torch.float32 or b.shape != m.shape:
+                raise ValueError(f"set {k}: sub must be a float32 tensor of the table's shape {tuple(m.shape)}")
+            if b.shape[0] > 0 and b.stride(1) != 1:
+                raise ValueError(f"set {k}: the columns of sub must be contiguous")
+            if b.device != m.device:
+                raise ValueError(f"set {k}: sub is on {b.device}, the table on {m.device}")
+    return D
+
+
+def _norm_device(mats, device):
+    dev = require_gpu(device if device is not None else (mats[0].device if mats[0].is_cuda else None))
+    if dev.index is None:
+        dev = torch.device(dev.type, torch.cuda.current_device())
+    for k, m in enumerate(mats):
+        if m.device != dev:
+            raise ValueError(f"set {k} is on {m.device}, not on {dev}: the tables are read where they lie")
+    return dev
+
+
+def _norm_groups(mats, groups, device):
+    """The device and the group words on it: host words of all sets go up in one copy (a copy per set costs more than the
+    kernels at 256 sets), words already on the device are used where they lie."""
+    dev = _norm_device(mats, device)
+    grp = [torch.as_tensor(g).reshape(-1) for g in groups]
+    if all(not g.is_cuda for g in grp):
+        flat = torch.cat([g.to(torch.int32) for g in grp]).to(dev)
+        return dev, list(torch.split(flat, [int(g.numel()) for g in grp]))
+    return dev, [g.to(device=dev, dtype=torch.int32).contiguous() for g in grp]
+
+
+def _ref_check(ref_of, n_sets, n_ref):
+    """ref_of as a list of ints inside 0..n_ref-1 (None: set k takes row k, so n_sets <= n_ref)."""
+    if ref_of is None:
+        if n_sets > n_ref:
+            raise ValueError(f"{n_sets} sets but {n_ref} reference entries: ref_of is needed")
+        return None
+    ref = [int(v) for v in np.asarray(ref_of).reshape(-1)]
+    if len(ref) != n_sets:
+        raise ValueError("ref_of must have one entry per set")
+    if any(not 0 <= v < n_ref for v in ref):
+        raise ValueError(f"ref_of entries must lie in 0..{n_ref - 1}")
+    return ref
+
+
+def _to_dev(table, dev):
+    return torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+
+
+def _max_rows(mats):
+    return max(max(int(m.shape[0]) for m in mats), 1)
+
+
+def cohort_moments(mats: Sequence[torch.Tensor], groups: Sequence, sub: Optional[Sequence[torch.Tensor]] = None, ddof: int = 1,
+                   device=None) -> torch.Tensor:
+    """[n_sets, D, 8] fp64 on the device, per (set, column) over the rows whose group word is 0 (the reference cohort): mean,
+    sd, var, n_ref, min, max, n_nonfinite, status (COHORT_MOMENTS_COLUMNS; include/nmhip.h has the definitions).  mats /
+    groups as for roi_effect; sub[k] (optional, the shape of mats[k]): the value is mats[k] - sub[k] in fp64 (a table against
+    its out_loc export: the signed residual).  status -2 (mean, sd, var NaN): n_ref <= ddof, a non-finite reference value, a
+    constant column.  One launch for all sets."""
+    if ddof not in (0, 1) or isinstance(ddof, bool):
+        raise ValueError(f"ddof must be 0 or 1, got {ddof!r}")
+    D = _norm_check(mats, groups, sub)
+    dev, grp = _norm_groups(mats, groups, device)
+    sets = _to_dev(_norm_table(mats, grp, sub), dev)
+    out = torch.empty(len(mats), D, _lib.NM_METRICS_STRIDE, dtype=torch.float64, device=dev)
+    _lib.check(_lib.load().nm_cohort_moments(sets.data_ptr(), len(mats), D, _max_rows(mats), int(ddof), out.data_ptr(),
+                                              _stream_ptr(dev)), "nm_cohort_moments")
+    return out
+
+
+def normative_z(mats: Sequence[torch.Tensor], groups: Sequence, moments: torch.Tensor, ref_of=None, thr: float = 1.96,
+                sub: Optional[Sequence[torch.Tensor]] = None, return_z: bool = True, device=None):
+    """Every row of every set z-scored, column by column, against row ref_of[k] (default k) of a cohort_moments table:
+    (z, rows, cols).  z: a list of [n_k, D] fp32 device tensors (None without return_z), NaN where the value is not finite or
+    the column's moments are not valid; rows [sum n_k, 8] fp64 = n_hi, n_lo, mean_z, mean_abs_z, max_z, argmax_z, n_valid,
+    status per subject (NORMATIVE_ROW_COLUMNS; n_hi counts z > thr, n_lo z < -thr), the sets one after another; cols
+    [n_sets, D, 8] fp64 = n_hi_x, n_lo_x, n_hi_y, n_lo_y, n_x, n_y, mean_z_x, mean_z_y per column (NORMATIVE_COL_COLUMNS; x =
+    group 1, y = group 0: the extreme-deviation map).  A row of any group is scored.  One launch pair for all sets."""
+    thr = float(thr)
+    if not (np.isfinite(thr) and thr > 0.0):
+        raise ValueError(f"thr must be finite and > 0, got {thr}")
+    D = _norm_check(mats, groups, sub)
+    if D > _lib.NM_NORM_MAX_D:
+        raise ValueError(f"at most {_lib.NM_NORM_MAX_D} columns, got {D}")
+    if not isinstance(moments, torch.Tensor) or moments.dtype != torch.float64 or moments.dim() != 3 or \
+            tuple(moments.shape[1:]) != (D, _lib.NM_METRICS_STRIDE):
+        raise ValueError(f"moments must be a float64 [n, {D}, {_lib.NM_METRICS_STRIDE}] tensor as cohort_moments returns it")
+    ref = _ref_check(ref_of, len(mats), int(moments.shape[0]))
+    dev, grp = _norm_groups(mats, groups, device)
+    mom = moments.to(dev).contiguous()
+    zs = [torch.empty(int(m.shape[0]), D, dtype=torch.float32, device=dev) for m in mats] if return_z else None
+    sets = _to_dev(_norm_table(mats, grp, sub, zs), dev)
+    total = sum(int(m.shape[0]) for m in mats)
+    rows = torch.empty(total, _lib.NM_METRICS_STRIDE, dtype=torch.float64, device=dev)
+    cols = torch.empty(len(mats), D, _lib.NM_METRICS_STRIDE, dtype=torch.float64, device=dev)
+    rf = torch.tensor(ref, dtype=torch.int32, device=dev) if ref is not None else None
+    _lib.check(_lib.load().nm_normative_z(sets.data_ptr(), len(mats), D, _max_rows(mats), mom.data_ptr(), int(mom.shape[0]),
+                                           rf.data_ptr() if rf is not None else None, thr, rows.data_ptr(), cols.data_ptr(),
+                                           _stream_ptr(dev)), "nm_normative_z")
+    return zs, rows, cols
+
+
+def _latent_width(Z: int):
+    if not 1 <= Z <= _lib.NM_WIDE_MAX_LATENT:
+        raise ValueError(f"the width must lie in 1..{_lib.NM_WIDE_MAX_LATENT}, got {Z}")
+
+
+def cohort_cov(mats: Sequence[torch.Tensor], groups: Sequence, ridge: float = 0.0, device=None):
+    """(mean [n_sets, Z], chol [n_sets, Z, Z], status [n_sets] int32) on the device, per set over the rows whose group word is
+    0: the column means, and the lower Cholesky factor of their sample covariance (np.cov(rowvar=False)) plus `ridge` on the
+    diagonal.  status -2 (a NaN factor): fewer than two reference rows, a non-finite value, n_ref <= Z with ridge == 0, or a
+    covariance that is numerically singular.  1 <= Z <= NM_WIDE_MAX_LATENT.  One launch for all sets."""
+    ridge = float(ridge)
+    if not (np.isfinite(ridge) and ridge >= 0.0):
+        raise ValueError(f"ridge must be finite and >= 0, got {ridge}")
+    Z = _norm_check(mats, groups, None)
+    _latent_width(Z)
+    dev, grp = _norm_groups(mats, groups, device)
+    sets = _to_dev(_norm_table(mats, grp), dev)
+    mean = torch.empty(len(mats), Z, dtype=torch.float64, device=dev)
+    chol = torch.empty(len(mats), Z, Z, dtype=torch.float64, device=dev)
+    status = torch.empty(len(mats), dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().nm_cohort_cov(sets.data_ptr(), len(mats), Z, _max_rows(mats), ridge, mean.data_ptr(), chol.data_ptr(),
+                                          status.data_ptr(), _stream_ptr(dev)), "nm_cohort_cov")
+    return mean, chol, status
+
+
+def mahalanobis(mats: Sequence[torch.Tensor], mean: torch.Tensor, chol: torch.Tensor, status: torch.Tensor, ref_of=None,
+                device=None):
+    """A list of [n_k] fp64 device tensors: the Mahalanobis distance d = |L^-1 (row - mean)| of every row of set k to cohort
+    ref_of[k] (default k) of a cohort_cov result.  NaN for a row with a non-finite entry and for every row scored against a
+    factor whose status is not 0.  One launch for all sets."""
+    # (no group words here: the table rules are checked with one placeholder word per row)
+    Z = _norm_check(mats, [torch.zeros(int(m.shape[0]) if isinstance(m, torch.Tensor) and m.dim() == 2 else 0) for m in mats], None)
+    _latent_width(Z)
+    for name, v, dt in (("mean", mean, torch.float64), ("chol", chol, torch.float64), ("status", status, torch.int32)):
+        if not isinstance(v, torch.Tensor) or v.dtype != dt:
+            raise ValueError(f"{name} must be a {dt} tensor as cohort_cov returns it")
+    n = int(status.numel())
+    if n < 1 or tuple(mean.shape) != (n, Z) or tuple(chol.shape) != (n, Z, Z) or status.dim() != 1:
+        raise ValueError(f"mean [n, {Z}], chol [n, {Z}, {Z}] and status [n] are needed, got {tuple(mean.shape)}, "
+                         f"{tuple(chol.shape)}, {tuple(status.shape)}")
+    ref = _ref_check(ref_of, len(mats), n)
+    dev = _norm_device(mats, device)
+    sets = _to_dev(_norm_table(mats), dev)
+    total = sum(int(m.shape[0]) for m in mats)
+    d2 = torch.empty(max(total, 1), dtype=torch.float64, device=dev)
+    d = torch.empty(max(total, 1), dtype=torch.float64, device=dev)
+    rf = torch.tensor(ref, dtype=torch.int32, device=dev) if ref is not None else None
+    mean, chol, status = mean.to(dev).contiguous(), chol.to(dev).contiguous(), status.to(dev).contiguous()
+    _lib.check(_lib.load().nm_mahalanobis(sets.data_ptr(), len(mats), Z, _max_rows(mats), mean.data_ptr(), chol.data_ptr(),
+                                           status.data_ptr(), n, rf.data_ptr() if rf is not None else None, d2.data_ptr(),
+                                           d.data_ptr(), _stream_ptr(dev)), "nm_mahalanobis")
+    return list(torch.split(d[:total], [int(m.shape[0]) for m in mats]))

@@ -569,6 +569,28 @@ def _column_regress_sets(mats: Sequence[torch.Tensor], targets, kind: str, covs,
     return out
 
 
+def _normative_sets(mats: Sequence[torch.Tensor], groups: Sequence[np.ndarray], subs, thr: float, device) -> List[dict]:
+    """metrics.cohort_moments and metrics.normative_z for tables of any widths, as _roi_effect_sets: one moments launch and one z
+    launch per distinct width, every table scored against its own group-0 rows.  Returns per table {"z" [n, D] fp32, "rows"
+    [n, 8], "cols" [D, 8], "moments" [D, 8]} on the device, in the order given."""
+    by_width: Dict[int, List[int]] = {}
+    for j, x in enumerate(mats):
+        by_width.setdefault(int(x.shape[1]), []).append(j)
+    out: List[Optional[dict]] = [None] * len(mats)
+    for idxs in by_width.values():
+        ms, gs = [mats[j] for j in idxs], [groups[j] for j in idxs]
+        sb = None if subs is None else [subs[j] for j in idxs]
+        mom = metrics.cohort_moments(ms, gs, sub=sb, ddof=1, device=device)
+        z, rows, cols = metrics.normative_z(ms, gs, mom, thr=thr, sub=sb, device=device)
+        rows = torch.split(rows, [int(m.shape[0]) for m in ms])
+        for a, j in enumerate(idxs):
+            out[j] = {"z": z[a], "rows": rows[a], "cols": cols[a], "moments": mom[a]}
+    return out
+
+
+NORMATIVE_KINDS = ("squared", "signed")
+
+
 def _roi_columns(roi_columns, m: str, d: int):
     return list(roi_columns[m]) if roi_columns and m in roi_columns else [f"{m}_{k}" for k in range(d)]
 
@@ -578,7 +600,8 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
                roi_columns: Optional[Dict[str, Sequence[str]]] = None, roi_effect: bool = False,
                disease_label=None, roi_significance: bool = False, roi_perm: int = 0,
                roi_seed: int = 0, roi_regress: Optional[tuple] = None,
-               roi_adjust: Sequence[str] = ()) -> List[Dict[str, np.ndarray]]:
+               roi_adjust: Sequence[str] = (), normative: Optional[str] = None,
+               z_thr: float = 1.96) -> List[Dict[str, np.ndarray]]:
     """test_fold for ALL folds of a procedure as one launch: jobs[i] is the trained model of fold i, folds[i] its
     (train_rows, test_rows); one evaluation job per fold, each on its own test tables (seed, scaler and covariates per fold
     exactly as test_fold), all in ONE JobSet -- a fold's ~N / K test rows are a single workgroup, K of them in a row leave
@@ -605,7 +628,29 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
     pooled sets in ONE launch (one per table width) -- per ROI the fit target ~ const + the ROI's squared error, kind "logit"
     or "ols", target a cohort column (regress_target; a Logit on DIA is patients against controls as roi_groups picks them),
     adjusted for the cohort columns named in roi_adjust (at most NM_REG_MAX_COV).  Each fold's dict gains "roi_regress":
-    {modality: [D, 8]} (metrics.COLUMN_REGRESS_COLUMNS) and "roi_regress_pooled"; with out_dirs, roi_regress_<m>.csv."""
+    {modality: [D, 8]} (metrics.COLUMN_REGRESS_COLUMNS) and "roi_regress_pooled"; with out_dirs, roi_regress_<m>.csv.
+
+    normative = "squared" or "signed" (needs roi_effect): the normative z-map of the same tables -- the sigma-normalised extra,
+    never the parity output.  Per fold and modality the moments of every ROI over that fold's healthy test subjects (the
+    hold-out controls, group 0 of roi_groups), every test subject of any group z-scored against them, the per-subject counts
+    of ROIs beyond +-z_thr and the per-ROI shares of patients and controls beyond it; the same on the pooled rows per modality.
+    "squared" scores the ROI-wise squared error (out_sqerr), "signed" the residual table - out_loc, both read where they lie.
+    One metrics.cohort_moments launch and one metrics.normative_z launch per table width over all folds, modalities and pooled
+    sets.  The controls are scored against statistics they are themselves part of: their z-scores have mean 0 and sd 1 by
+    construction, so a control's count of extreme ROIs is slightly optimistic and the patients' excess over it is the
+    finding, not the controls' level.  Each fold's dict gains "normative": {modality: {"z" [n, D] fp32, "rows" [n, 8]
+    (metrics.NORMATIVE_ROW_COLUMNS), "cols" [D, 8] (metrics.NORMATIVE_COL_COLUMNS), "moments" [D, 8]
+    (metrics.COHORT_MOMENTS_COLUMNS), "x" and "sub": the fp32 tables that were scored (sub None for "squared")}} and
+    "normative_pooled" (the same dict in every fold's result, its rows in fold order); with out_dirs, normative_z_<m>.csv,
+    normative_subject_<m>.csv and normative_map_<m>.csv."""
+    if normative is not None:
+        if normative not in NORMATIVE_KINDS:
+            raise ValueError(f"normative must be None or one of {NORMATIVE_KINDS}, got {normative!r}")
+        if not roi_effect:
+            raise ValueError("normative needs roi_effect=True (the evaluation jobs export the ROI-wise squared errors for it)")
+        z_thr = float(z_thr)
+        if not (np.isfinite(z_thr) and z_thr > 0.0):
+            raise ValueError(f"z_thr must be finite and > 0, got {z_thr}")
     if roi_significance and not roi_effect:
         raise ValueError("roi_significance needs roi_effect=True (the evaluation jobs export the ROI-wise squared errors for it)")
     if roi_regress is not None:
@@ -646,6 +691,17 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
             rep = lambda seq: [v for v in seq[:-1] for _ in range(nm_)] + [seq[-1]] * nm_
             reg = _column_regress_sets(mats + pooled_mats, rep([t for t, _ in tg]), reg_kind,
                                        None if cv is None else rep(cv), rep([w for _, w in tg]), device)
+        if normative is not None:
+            # the folds' sets, then the pooled ones: one table list, one moments and one z launch per width
+            if normative == "signed":
+                n_mats = [ev.tables[i].x_f32[:len(te), :ev.tables[i].D] for (ev, _), (_, te) in zip(evs, folds) for i in range(nm_)]
+                n_subs = [ev.out_loc[i][:len(te)] for (ev, _), (_, te) in zip(evs, folds) for i in range(nm_)]
+                n_subs = n_subs + [torch.cat(n_subs[i::nm_]) for i in range(nm_)]
+                n_mats = n_mats + [torch.cat(n_mats[i::nm_]) for i in range(nm_)]
+            else:
+                n_mats, n_subs = mats + pooled_mats, None
+            n_grp = [g for g in grp for _ in range(nm_)] + [np.concatenate(grp)] * nm_
+            norm = _normative_sets(n_mats, n_grp, n_subs, z_thr, device)
     torch.cuda.synchronize(device)
     out = [_fold_results(ev, xs, cohort, te, modalities, d, roi_columns) for (ev, xs), (_, te), d in zip(evs, folds, dirs)]
     if roi_effect:
@@ -672,6 +728,23 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
             if d is not None:
                 for m, tab in res["roi_regress"].items():
                     io.write_roi_regress_csv(Path(d) / m, m, _roi_columns(roi_columns, m, tab.shape[0]), tab)
+    if normative is not None:
+        def host(j):
+            res = {k: v.cpu().numpy() for k, v in norm[j].items()}
+            res["x"] = n_mats[j].cpu().numpy()
+            res["sub"] = None if n_subs is None else n_subs[j].cpu().numpy()
+            return res
+        norm_pooled = {m: host(len(mats) + i) for i, m in enumerate(modalities)}
+        for f, (res, (_, te), d) in enumerate(zip(out, folds, dirs)):
+            res["normative"] = {m: host(f * nm_ + i) for i, m in enumerate(modalities)}
+            res["normative_pooled"] = norm_pooled
+            if d is not None:
+                import pandas as pd
+                meta = pd.DataFrame({"participant_id": cohort.iid[te], "DIA": cohort.dia[te], "AGE": cohort.age[te],
+                                     "PTGENDER": cohort.gender[te]})
+                for m, t in res["normative"].items():
+                    io.write_normative_csvs(Path(d) / m, m, meta, _roi_columns(roi_columns, m, t["z"].shape[1]), t["z"], t["rows"],
+                                            t["cols"])
     return out
 
 
@@ -695,7 +768,7 @@ def _fold_latent_jobs(job: Job, cohort: prep.SyntheticCohort, train_rows: np.nda
 def latent_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequence[tuple], modalities: Sequence[str],
                  combines, device, out_dirs: Optional[Sequence] = None, name: str = "joint",
                  pvalues: Optional[Sequence[tuple]] = None, disease_label=None,
-                 pooled_dir=None) -> List[Dict[str, np.ndarray]]:
+                 pooled_dir=None, mahalanobis: bool = False, ridge: float = 0.0) -> List[Dict[str, np.ndarray]]:
     """The latent-space deviation (latent_deviation / separate_latent_deviation, utils_vae.py:155-161, on what pred_latent
     returns) for ALL folds of a procedure: jobs[i] is the trained model of fold i, folds[i] its (train_rows, test_rows).
     One latent launch over the folds' train tables, one over their test tables (JobSet.latent: the encoder-only kernel where
@@ -709,8 +782,18 @@ def latent_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Seque
     pooled rows (regress_target picks the values; a Logit on DIA is disease_label -- default: every patient -- against the
     healthy controls, the other classes excluded).  Each fold's dict gains "pvalues": {target: [Z, 8]}
     (metrics.COLUMN_REGRESS_COLUMNS) and "pvalues_pooled" (the same dict in every fold's result); with out_dirs,
-    latent_pvalues_<name>_<target>.csv in the reference's layout per fold, and with pooled_dir the pooled one there."""
+    latent_pvalues_<name>_<target>.csv in the reference's layout per fold, and with pooled_dir the pooled one there.
+
+    mahalanobis: the full-covariance counterpart of the per-dimension z-score -- ONE metrics.cohort_cov launch (every fold's
+    train cohort's joint mu: means, sample covariance + ridge on the diagonal, Cholesky factor) and ONE metrics.mahalanobis
+    launch (every fold's test subjects against their own fold's factor).  Each fold's dict gains "mahalanobis" [N] fp64 (the
+    distance d); with out_dirs, latent_mahalanobis_<name>.csv next to latent_deviation_<name>.csv.  A fold whose factor is
+    not valid (a numerically singular covariance with ridge = 0, fewer than two train subjects, a non-finite mu) gets NaN
+    and a printed line."""
     from . import engine
+    ridge = float(ridge)
+    if mahalanobis and not (np.isfinite(ridge) and ridge >= 0.0):
+        raise ValueError(f"ridge must be finite and >= 0, got {ridge}")
     if len(jobs) != len(folds):
         raise ValueError(f"{len(jobs)} models for {len(folds)} folds")
     pvalues = [tuple(p) for p in (pvalues or [])]
@@ -736,7 +819,19 @@ def latent_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Seque
         for target, kind in pvalues:
             tg = [regress_target(cohort, r, target, kind, disease_label) for r in rows_of]
             pv[target] = metrics.column_regress(sets, [t for t, _ in tg], kind=kind, include=[w for _, w in tg], device=device)
+    maha = None
+    if mahalanobis and mus:
+        trn_mus = [trn.out_mu[:len(tr)] for (trn, _), (tr, _) in zip(pairs, folds)]
+        c_mean, c_chol, c_status = metrics.cohort_cov(trn_mus, [np.zeros(len(tr), dtype=np.int32) for tr, _ in folds], ridge=ridge,
+                                                      device=device)
+        maha = metrics.mahalanobis(mus, c_mean, c_chol, c_status, device=device)
     torch.cuda.synchronize(device)
+    if maha is not None:
+        for f, st in enumerate(c_status.cpu().tolist()):
+            if st != 0:
+                print(f"[latent] fold {f}: no Mahalanobis distance -- the train cohort's covariance ({len(folds[f][0])} subjects, "
+                      f"Z = {int(c_mean.shape[1])}, ridge {ridge:g}) has no valid Cholesky factor (status {st}: too few subjects, a "
+                      f"non-finite mu, or numerically singular)", flush=True)
     pv = {t: tab.cpu().numpy() for t, tab in pv.items()}
     pv_pooled = {t: tab[-1] for t, tab in pv.items()}
     if pv and pooled_dir is not None:
@@ -750,6 +845,10 @@ def latent_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Seque
             meta = pd.DataFrame({"participant_id": cohort.iid[te], "DIA": cohort.dia[te], "AGE": cohort.age[te],
                                  "PTGENDER": cohort.gender[te]})
             io.write_latent_csvs(d, name, meta, res["mu"], res["var"], res["score"], res["z"])
+            if maha is not None:
+                io.write_latent_mahalanobis_csv(d, name, meta, maha[len(out)].cpu().numpy())
+        if maha is not None:
+            res["mahalanobis"] = maha[len(out)].cpu().numpy()
         if pv:
             res["pvalues"] = {t: tab[len(out)] for t, tab in pv.items()}
             res["pvalues_pooled"] = pv_pooled
@@ -1046,8 +1145,26 @@ def main_test(argv=None):
                          "roi_regress_<m>.csv")
     ap.add_argument("--roi-adjust", dest="roi_adjust", nargs="+", type=str, default=[], metavar="COLUMN",
                     help="with --roi-regress: cohort columns the fit is adjusted for (AGE PTGENDER)")
+    ap.add_argument("--normative", choices=NORMATIVE_KINDS, default=None,
+                    help="with --roi-effect: the normative z-map -- every ROI z-scored against the fold's healthy test subjects, on "
+                         "its squared error (squared) or its signed residual (signed): per fold and pooled normative_z_<m>.csv, "
+                         "normative_subject_<m>.csv (per subject the ROIs beyond +-z-thr) and normative_map_<m>.csv (per ROI the "
+                         "patients and controls beyond it)")
+    ap.add_argument("--z-thr", dest="z_thr", type=float, default=1.96, help="the threshold of --normative (default 1.96)")
+    ap.add_argument("--mahalanobis", action="store_true",
+                    help="with --latent: also every test subject's Mahalanobis distance to the fold's train cohort in latent space: "
+                         "per fold and all folds latent_mahalanobis_<P>.csv")
+    ap.add_argument("--ridge", type=float, default=0.0, help="added to the diagonal of the covariance of --mahalanobis (default 0)")
     _driver_common(ap)
     args = ap.parse_args(argv)
+    if args.normative and not args.roi_effect:
+        ap.error("--normative needs --roi-effect")
+    if args.normative and not (np.isfinite(args.z_thr) and args.z_thr > 0):
+        ap.error("--z-thr must be finite and > 0")
+    if args.mahalanobis and not args.latent:
+        ap.error("--mahalanobis needs --latent")
+    if args.mahalanobis and not (np.isfinite(args.ridge) and args.ridge >= 0):
+        ap.error("--ridge must be finite and >= 0")
     if args.roi_significance and not args.roi_effect:
         ap.error("--roi-significance needs --roi-effect")
     if args.latent_pvalues and not args.latent:
@@ -1094,7 +1211,8 @@ def main_test(argv=None):
     results = test_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs,
                          roi_effect=args.roi_effect, disease_label=args.disease_label, roi_significance=args.roi_significance,
                          roi_perm=args.roi_perm, roi_seed=args.roi_seed, roi_regress=roi_regress,
-                         roi_adjust=args.roi_adjust) if my else []
+                         roi_adjust=args.roi_adjust, **({"normative": args.normative, "z_thr": args.z_thr} if args.normative else {})
+                         ) if my else []
     for err in results:
         for m in mods:
             errors[m].append(err[m])
@@ -1121,12 +1239,24 @@ def main_test(argv=None):
             io.write_roi_regress_csv(out_root / m, m, _roi_columns(None, m, tab.shape[0]), tab)
             print(f"[test] {args.procedure} {m}: pooled ROI regression {args.roi_regress}, {int(np.nansum(tab[:, 5] <= 0.05))} of "
                   f"{tab.shape[0]} ROIs with p_coef <= 0.05", flush=True)
+        if args.normative and results:               # the pooled z-map: this rank's folds' test subjects against their controls
+            t = results[0]["normative_pooled"][m]
+            te_all = np.concatenate([te for _, te in fold_rows])
+            meta = pd.DataFrame({"participant_id": cohort.iid[te_all], "DIA": cohort.dia[te_all], "AGE": cohort.age[te_all],
+                                 "PTGENDER": cohort.gender[te_all]})
+            io.write_normative_csvs(out_root / m, m, meta, _roi_columns(None, m, t["z"].shape[1]), t["z"], t["rows"], t["cols"])
+            g = roi_groups(cohort.dia[te_all], args.disease_label)
+            ext = t["rows"][:, 0] + t["rows"][:, 1]
+            print(f"[test] {args.procedure} {m}: pooled normative z-map ({args.normative}), ROIs beyond +-{args.z_thr:g} per subject: "
+                  f"patients {float(ext[g == 1].mean()) if (g == 1).any() else float('nan'):.2f}, controls "
+                  f"{float(ext[g == 0].mean()) if (g == 0).any() else float('nan'):.2f}", flush=True)
     if args.latent and my:
         # the folds' train cohorts and test subjects in one latent launch each, one statistics and one score launch
         lat = latent_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs, name=args.procedure,
-                           pvalues=lat_pvalues, disease_label=args.disease_label, pooled_dir=out_root if lat_pvalues else None)
+                           pvalues=lat_pvalues, disease_label=args.disease_label, pooled_dir=out_root if lat_pvalues else None,
+                           **({"mahalanobis": True, "ridge": args.ridge} if args.mahalanobis else {}))
         out_root.mkdir(parents=True, exist_ok=True)
-        for kind in ("latent", "latent_deviation"):
+        for kind in ("latent", "latent_deviation") + (("latent_mahalanobis",) if args.mahalanobis else ()):
             parts = [pd.read_csv(root / f"{k:03d}" / f"{kind}_{args.procedure}.csv") for k in my]
             pd.concat(parts, ignore_index=True).to_csv(out_root / f"{kind}_{args.procedure}.csv", index=False)
         sc = np.concatenate([r["score"] for r in lat])
@@ -1235,6 +1365,10 @@ def _analysis_scores(root: Path, mods: Sequence[str], procedure: str, score: str
     for k in range(n_splits):
         if score == "latent":
             files = [root / f"{k:03d}" / f"latent_deviation_{procedure}.csv"]
+        elif score == "mahalanobis":
+            files = [root / f"{k:03d}" / f"latent_mahalanobis_{procedure}.csv"]
+        elif score in ("extreme", "zmean"):
+            files = [root / f"{k:03d}" / m / f"normative_subject_{m}.csv" for m in mods]
         else:
             files = [root / f"{k:03d}" / m / f"reconstruction_error_{m}.csv" for m in mods]
         if not all(f.exists() for f in files):
@@ -1242,6 +1376,12 @@ def _analysis_scores(root: Path, mods: Sequence[str], procedure: str, score: str
         dfs = [pd.read_csv(f) for f in files]
         if score == "latent":
             err = dfs[0]["Latent deviation"].to_numpy(dtype=np.float64)
+        elif score == "mahalanobis":
+            err = dfs[0]["d"].to_numpy(dtype=np.float64)
+        elif score == "extreme":
+            err = sum((d["n_hi"] + d["n_lo"]).to_numpy(dtype=np.float64) for d in dfs) / len(dfs)
+        elif score == "zmean":
+            err = sum(d["mean_abs_z"].to_numpy(dtype=np.float64) for d in dfs) / len(dfs)
         else:
             err = sum(d["Reconstruction error"].to_numpy(dtype=np.float64) for d in dfs) / len(dfs)
         dia = dfs[0]["DIA"].to_numpy()
@@ -1253,6 +1393,12 @@ def _analysis_scores(root: Path, mods: Sequence[str], procedure: str, score: str
         ids.append(dfs[0]["participant_id"].to_numpy())
     if not folds and score == "latent":
         raise FileNotFoundError(f"no latent_deviation_{procedure}.csv under {root}/<fold>/ -- run the `test` subcommand with --latent first")
+    if not folds and score == "mahalanobis":
+        raise FileNotFoundError(f"no latent_mahalanobis_{procedure}.csv under {root}/<fold>/ -- run the `test` subcommand with --latent "
+                                f"--mahalanobis first")
+    if not folds and score in ("extreme", "zmean"):
+        raise FileNotFoundError(f"no normative_subject_*.csv of {mods} under {root}/<fold>/ -- run the `test` subcommand with "
+                                f"--roi-effect --normative first")
     if not folds:
         raise FileNotFoundError(f"no reconstruction_error_*.csv of {mods} under {root}/<fold>/ -- run the `test` subcommand first")
     return scores, positive, folds, ids
@@ -1296,7 +1442,7 @@ def _analysis_bootstrap(root: Path, args, hc: int, scores, positive, folds, ids)
                                 pairs=pairs if others else None)
     tab, cmp_tab = (res[0].cpu().numpy(), res[1].cpu().numpy()) if others else (res.cpu().numpy(), None)
     names = [str(k) for k in folds] + ["pooled"]
-    tag = "latent_" if args.score == "latent" else ""
+    tag = "" if args.score == "reconstruction" else f"{args.score}_"
     df = pd.DataFrame(tab[:per], columns=list(metrics.AUC_BOOTSTRAP_COLUMNS))
     df.insert(0, "fold", names)
     df.to_csv(root / f"group_analysis_{tag}bootstrap.csv", index=False)
@@ -1335,9 +1481,12 @@ def main_analysis(argv=None):
     ap.add_argument("-E", "--epochs", dest="epochs", type=int, default=None)
     ap.add_argument("-K", "--n_splits", dest="n_splits", type=int, default=10)
     ap.add_argument("--models-dir", type=str, required=True, help="where the `test` subcommand wrote its per-fold CSVs")
-    ap.add_argument("--score", choices=("reconstruction", "latent"), default="reconstruction",
+    ap.add_argument("--score", choices=("reconstruction", "latent", "extreme", "zmean", "mahalanobis"), default="reconstruction",
                     help="the per-subject score: the modality-averaged reconstruction error, or the `Latent deviation` column "
-                         "of latent_deviation_<P>.csv (`test --latent`); latent writes group_analysis_latent.csv")
+                         "of latent_deviation_<P>.csv (`test --latent`); latent writes group_analysis_latent.csv.  extreme: n_hi + "
+                         "n_lo of normative_subject_<m>.csv (`test --roi-effect --normative`), averaged over the modalities; zmean: "
+                         "its mean_abs_z likewise; mahalanobis: d of latent_mahalanobis_<P>.csv (`test --latent --mahalanobis`); "
+                         "these write group_analysis_<score>.csv")
     ap.add_argument("--roi", action="store_true",
                     help="instead: which ROIs separate patients from controls -- per fold and modality every ROI's Cliff's delta and "
                          "ROC-AUC on reconstruction_error_roi_<m>.csv, their mean and std over folds to group_analysis_roi_<m>.csv")
@@ -1381,7 +1530,7 @@ def main_analysis(argv=None):
     table = metrics.posthoc_metrics(scores, positive).cpu()
     df = pd.DataFrame(table.numpy(), columns=list(metrics.POSTHOC_COLUMNS))
     df.insert(0, "fold", folds)
-    df.to_csv(root / ("group_analysis_latent.csv" if args.score == "latent" else "group_analysis.csv"), index=False)
+    df.to_csv(root / ("group_analysis.csv" if args.score == "reconstruction" else f"group_analysis_{args.score}.csv"), index=False)
     for _, r in df.iterrows():
         print(f"[analysis] fold {int(r['fold'])}: AUC {r['roc_auc']:.4f}  accuracy {r['accuracy']:.4f}  sensitivity {r['recall']:.4f}  "
               f"specificity {r['specificity']:.4f}  significance ratio {r['significance_ratio']:.3f}", flush=True)
