@@ -84,20 +84,28 @@ def write_latent_csvs(out_dir, name: str, covariates: pd.DataFrame, mu: np.ndarr
     return paths
 
 
+def write_roi_table_csv(kind: str, out_dir, dataset_name: str, roi_columns: Sequence[str], table: np.ndarray) -> Path:
+    """{kind}_{name}.csv, kind one of roi_effect / roi_significance / roi_regress: one row per ROI -- its column name, then the
+    kind's eight metrics columns (ROI_EFFECT_COLUMNS / ROI_SIGNIFICANCE_COLUMNS / COLUMN_REGRESS_COLUMNS)."""
+    from . import metrics
+    columns = {"roi_effect": metrics.ROI_EFFECT_COLUMNS, "roi_significance": metrics.ROI_SIGNIFICANCE_COLUMNS,
+               "roi_regress": metrics.COLUMN_REGRESS_COLUMNS}[kind]
+    table = np.asarray(table, dtype=np.float64)
+    if table.shape != (len(roi_columns), len(columns)):
+        raise ValueError(f"a [{len(roi_columns)}, {len(columns)}] table is needed, got {table.shape}")
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    df = pd.DataFrame(table, columns=list(columns))
+    df.insert(0, "ROI", list(roi_columns))
+    path = out_dir / f"{kind}_{dataset_name}.csv"
+    df.to_csv(path, index=False)
+    return path
+
+
 def write_roi_effect_csv(out_dir, dataset_name: str, roi_columns: Sequence[str], table: np.ndarray) -> Path:
     """roi_effect_{name}.csv: one row per ROI -- its column name, then metrics.ROI_EFFECT_COLUMNS (Cliff's delta of patients
     against controls on the ROI's squared error, its ROC-AUC, the pair counts, group sizes and group means)."""
-    from .metrics import ROI_EFFECT_COLUMNS
-    table = np.asarray(table, dtype=np.float64)
-    if table.shape != (len(roi_columns), len(ROI_EFFECT_COLUMNS)):
-        raise ValueError(f"a [{len(roi_columns)}, {len(ROI_EFFECT_COLUMNS)}] table is needed, got {table.shape}")
-    out_dir = Path(out_dir)
-    out_dir.mkdir(parents=True, exist_ok=True)
-    df = pd.DataFrame(table, columns=list(ROI_EFFECT_COLUMNS))
-    df.insert(0, "ROI", list(roi_columns))
-    path = out_dir / f"roi_effect_{dataset_name}.csv"
-    df.to_csv(path, index=False)
-    return path
+    return write_roi_table_csv("roi_effect", out_dir, dataset_name, roi_columns, table)
 
 
 def write_roi_significance_csv(out_dir, dataset_name: str, roi_columns: Sequence[str], table: np.ndarray) -> Path:
@@ -105,34 +113,14 @@ def write_roi_significance_csv(out_dir, dataset_name: str, roi_columns: Sequence
     Mann-Whitney U of patients against controls on the ROI's squared error, its tie term, z and asymptotic p, the
     Benjamini-Hochberg q over the ROIs, the label-permutation p of the ROI and against the maximum over the ROIs, and the
     number of permutations).  The subjects are taken as independent."""
-    from .metrics import ROI_SIGNIFICANCE_COLUMNS
-    table = np.asarray(table, dtype=np.float64)
-    if table.shape != (len(roi_columns), len(ROI_SIGNIFICANCE_COLUMNS)):
-        raise ValueError(f"a [{len(roi_columns)}, {len(ROI_SIGNIFICANCE_COLUMNS)}] table is needed, got {table.shape}")
-    out_dir = Path(out_dir)
-    out_dir.mkdir(parents=True, exist_ok=True)
-    df = pd.DataFrame(table, columns=list(ROI_SIGNIFICANCE_COLUMNS))
-    df.insert(0, "ROI", list(roi_columns))
-    path = out_dir / f"roi_significance_{dataset_name}.csv"
-    df.to_csv(path, index=False)
-    return path
+    return write_roi_table_csv("roi_significance", out_dir, dataset_name, roi_columns, table)
 
 
 def write_roi_regress_csv(out_dir, dataset_name: str, roi_columns: Sequence[str], table: np.ndarray) -> Path:
     """roi_regress_{name}.csv: one row per ROI -- its column name, then metrics.COLUMN_REGRESS_COLUMNS (the fit
     target ~ const + the ROI's squared error + the adjustment covariates: both reported parameters, their standard errors
     and p-values, the subjects that took part and the Newton steps; n_iter < 0 is a status, see metrics.column_regress)."""
-    from .metrics import COLUMN_REGRESS_COLUMNS
-    table = np.asarray(table, dtype=np.float64)
-    if table.shape != (len(roi_columns), len(COLUMN_REGRESS_COLUMNS)):
-        raise ValueError(f"a [{len(roi_columns)}, {len(COLUMN_REGRESS_COLUMNS)}] table is needed, got {table.shape}")
-    out_dir = Path(out_dir)
-    out_dir.mkdir(parents=True, exist_ok=True)
-    df = pd.DataFrame(table, columns=list(COLUMN_REGRESS_COLUMNS))
-    df.insert(0, "ROI", list(roi_columns))
-    path = out_dir / f"roi_regress_{dataset_name}.csv"
-    df.to_csv(path, index=False)
-    return path
+    return write_roi_table_csv("roi_regress", out_dir, dataset_name, roi_columns, table)
 
 
 def write_normative_csvs(out_dir, dataset_name: str, covariates: pd.DataFrame, roi_columns: Sequence[str], z: np.ndarray,

@@ -86,51 +86,124 @@ def confusion_metrics(pred: Sequence[torch.Tensor], labels: Sequence[torch.Tenso
     return out
 
 
-def _roi_table(mats: Sequence[torch.Tensor], groups: Sequence[torch.Tensor]):
-    """nm_roi_effect's pointer table on the host: every matrix where it lies (data_ptr of the view, its row stride as pitch)."""
-    table = (_lib.NmRoiSet * len(mats))()
-    for k, (m, g) in enumerate(zip(mats, groups)):
-        rows = int(m.shape[0])
-        table[k].x, table[k].group = (m.data_ptr(), g.data_ptr()) if rows else (None, None)
-        table[k].rows, table[k].pitch = rows, (int(m.stride(0)) if rows > 1 else int(m.shape[1]))
+def _to_dev(table, dev):
+    return torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+
+
+def _max_rows(mats):
+    return max(max(int(m.shape[0]) for m in mats), 1)
+
+
+def _set_table(struct, mats: Sequence[torch.Tensor], **fields):
+    """The pointer table of any of the table entry points on the host, `struct` one of _lib.NmRoiSet / NmRegSet / NmNormSet:
+    every matrix where it lies (x = data_ptr of the view, its row stride as pitch), and where the struct has row_off the sum of
+    the heights before the set (where its per-row outputs start).  fields: the struct's other members by name -- a pointer
+    member takes one tensor (or None) per set, a *pitch member an int for all sets or one tensor per set (its row stride).  A
+    set without rows keeps null pointers and zero pitches of its own; a field given as None stays zero."""
+    table = (struct * len(mats))()
+    sets = list(table)                                            # (views of the entries, made once)
+    rows = [int(m.shape[0]) for m in mats]
+    for e, m, n in zip(sets, mats, rows):
+        e.rows, e.pitch = n, (int(m.stride(0)) if n > 1 else int(m.shape[1]))
+        if n:
+            e.x = m.data_ptr()
+    if hasattr(struct, "row_off"):
+        off = 0
+        for e, n in zip(sets, rows):
+            e.row_off = off
+            off += n
+    for name, v in fields.items():
+        if v is None:
+            continue
+        if isinstance(v, int):
+            for e in sets:
+                setattr(e, name, v)
+        elif name.endswith("pitch"):
+            for e, b, n in zip(sets, v, rows):
+                if n and b is not None:
+                    setattr(e, name, int(b.stride(0)) if n > 1 else int(b.shape[1]))
+        else:
+            for e, b, n in zip(sets, v, rows):
+                if n and b is not None:
+                    setattr(e, name, b.data_ptr())
     return table
 
 
-def _roi_check(mats: Sequence[torch.Tensor], groups: Sequence) -> int:
-    """The argument checks nm_roi_effect's and nm_roi_significance's host functions share (no device is looked for); D."""
+def _roi_table(mats, groups):
+    return _set_table(_lib.NmRoiSet, mats, group=groups)
+
+
+def _reg_table(mats, targets, covs, incs, n_cov: int):
+    return _set_table(_lib.NmRegSet, mats, target=targets, cov=covs if n_cov else None, include=incs, cov_pitch=n_cov)
+
+
+def _norm_table(mats, groups=None, subs=None, zs=None):
+    return _set_table(_lib.NmNormSet, mats, group=groups, sub=subs, sub_pitch=subs, z=zs, z_pitch=zs)
+
+
+def _table_check(mats: Sequence[torch.Tensor], per_row: Optional[Sequence] = None) -> int:
+    """The argument checks every table entry point's host function shares (no device is looked for): a list of [n_k, D] fp32
+    tables with unit column stride and, where given, one per-row sequence (group words, targets) per table; D."""
     if len(mats) == 0:
         raise ValueError("no ROI tables")
-    if len(mats) != len(groups):
+    if per_row is not None and len(mats) != len(per_row):
         raise ValueError("mats and groups must have the same number of sets")
     D = None
     for k, m in enumerate(mats):
         if not isinstance(m, torch.Tensor) or m.dim() != 2 or m.dtype != torch.float32:
             raise ValueError(f"set {k}: a 2-D float32 tensor is needed")
+        n, d = int(m.shape[0]), int(m.shape[1])
         if D is None:
-            D = int(m.shape[1])
-        if int(m.shape[1]) != D or D < 1:
-            raise ValueError(f"set {k}: {int(m.shape[1])} columns, every set needs the same number (>= 1; set 0 has {D})")
-        if m.shape[0] > _lib.NM_METRICS_MAX_N:
-            raise ValueError(f"set {k}: at most {_lib.NM_METRICS_MAX_N} rows per set, got {int(m.shape[0])}")
-        if m.shape[0] > 0 and m.stride(1) != 1:
+            D = d
+        if d != D or D < 1:
+            raise ValueError(f"set {k}: {d} columns, every set needs the same number (>= 1; set 0 has {D})")
+        if n > _lib.NM_METRICS_MAX_N:
+            raise ValueError(f"set {k}: at most {_lib.NM_METRICS_MAX_N} rows per set, got {n}")
+        if n > 0 and m.stride(1) != 1:
             raise ValueError(f"set {k}: columns must be contiguous (stride(1) == 1), got {m.stride(1)}")
-        if m.shape[0] > 1 and m.stride(0) < D:
+        if n > 1 and m.stride(0) < D:
             raise ValueError(f"set {k}: row stride {m.stride(0)} below the {D} columns")
-        if int(torch.as_tensor(groups[k]).numel()) != int(m.shape[0]):
+        if per_row is not None and int(torch.as_tensor(per_row[k]).numel()) != n:
             raise ValueError(f"set {k}: one group entry per row is needed")
     return D
 
 
-def _roi_upload(mats: Sequence[torch.Tensor], groups: Sequence, device):
-    """The device, the group words on it and the pointer table's bytes (host) of checked inputs."""
+def _table_device(mats: Sequence[torch.Tensor], device):
+    """The device of checked tables (`device`, else where the first one lies); every table must lie on it."""
     dev = require_gpu(device if device is not None else (mats[0].device if mats[0].is_cuda else None))
     if dev.index is None:
         dev = torch.device(dev.type, torch.cuda.current_device())
     for k, m in enumerate(mats):
         if m.device != dev:
             raise ValueError(f"set {k} is on {m.device}, not on {dev}: the tables are read where they lie")
-    grp = [torch.as_tensor(g).reshape(-1).to(device=dev, dtype=torch.int32).contiguous() for g in groups]
-    return dev, grp, bytes(_roi_table(mats, grp))
+    return dev
+
+
+def _row_words(seqs: Sequence, dev, dtype, nonzero: bool = False):
+    """Per-row sequences (int32 group / include words, fp32 targets) on the device, one 1-D tensor per set; a None entry stays
+    None.  Host entries of all sets go up in one copy and come back as views of it (a copy per set costs more than the kernels at
+    256 sets); a single entry, or any with one already on the device, is used or moved where it lies.  nonzero: the words
+    become 0 / 1 (entry != 0).  A pointer table holds their addresses only: the caller keeps the list until its launch is queued."""
+    parts = [None if s is None else torch.as_tensor(s).reshape(-1) for s in seqs]
+    if nonzero:
+        parts = [None if p is None else p.ne(0) for p in parts]
+    have = [p for p in parts if p is not None]
+    if len(have) < 2 or any(p.is_cuda for p in have):
+        return [None if p is None else p.to(device=dev, dtype=dtype).contiguous() for p in parts]
+    views = iter(torch.split(torch.cat([p.to(dtype) for p in have]).to(dev), [int(p.numel()) for p in have]))
+    return [None if p is None else next(views) for p in parts]
+
+
+def _seed_check(seed) -> int:
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must be an unsigned 64-bit integer, got {seed}")
+    return seed
+
+
+def _host_f32(v) -> torch.Tensor:
+    """A tensor or array-like as a host fp32 tensor."""
+    return torch.as_tensor(np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, dtype=np.float32))
 
 
 def roi_effect(mats: Sequence[torch.Tensor], groups: Sequence, device=None) -> torch.Tensor:
@@ -138,12 +211,13 @@ def roi_effect(mats: Sequence[torch.Tensor], groups: Sequence, device=None) -> t
     (ROI_EFFECT_COLUMNS; include/nmhip.h has the definitions).  mats[k]: a [n_k, D] fp32 device tensor of any row stride
     and unit column stride -- a view such as job.out_sqerr[m][:n] is read where it lies; groups[k]: n_k entries, 1 = X
     (the patients), 0 = Y (the controls), any other value leaves the row out.  One launch for all sets."""
-    D = _roi_check(mats, groups)
-    dev, grp, table = _roi_upload(mats, groups, device)
-    sets = torch.frombuffer(bytearray(table), dtype=torch.uint8).to(dev)
+    D = _table_check(mats, groups)
+    dev = _table_device(mats, device)
+    grp = _row_words(groups, dev, torch.int32)                  # (held until the launch is queued: the table holds pointers only)
+    sets = _to_dev(_roi_table(mats, grp), dev)
     out = torch.empty(len(mats), D, _lib.NM_METRICS_STRIDE, dtype=torch.float64, device=dev)
-    _lib.check(_lib.load().nm_roi_effect(sets.data_ptr(), len(mats), D, max(max(int(m.shape[0]) for m in mats), 1),
-                                          out.data_ptr(), _stream_ptr(dev)), "nm_roi_effect")
+    _lib.check(_lib.load().nm_roi_effect(sets.data_ptr(), len(mats), D, _max_rows(mats), out.data_ptr(), _stream_ptr(dev)),
+               "nm_roi_effect")
     return out
 
 
@@ -155,12 +229,10 @@ ROI_SIGNIFICANCE_MAX_D = 8192
 
 
 def _perm_args(n_perm, seed):
-    n_perm, seed = int(n_perm), int(seed)
+    n_perm = int(n_perm)
     if not 0 <= n_perm <= _lib.NM_ROI_MAX_PERM:
         raise ValueError(f"n_perm must lie in 0..{_lib.NM_ROI_MAX_PERM}, got {n_perm}")
-    if not 0 <= seed < 1 << 64:
-        raise ValueError(f"seed must be an unsigned 64-bit integer, got {seed}")
-    return n_perm, seed
+    return n_perm, _seed_check(seed)
 
 
 def roi_significance(mats: Sequence[torch.Tensor], groups: Sequence, n_perm: int = 0, seed: int = 0, device=None,
@@ -179,13 +251,14 @@ def roi_significance(mats: Sequence[torch.Tensor], groups: Sequence, n_perm: int
     The workspace comes from nm_roi_significance_workspace; above ROI_SIGNIFICANCE_WORKSPACE_CAP the sets run in
     consecutive groups of a power of two that fit, set k keeping its own index in the permutation hash (the group's
     offset goes into the seed, as include/nmhip.h describes).  The same seed gives the same bytes."""
-    D = _roi_check(mats, groups)
+    D = _table_check(mats, groups)
     n_perm, seed = _perm_args(n_perm, seed)
     if D > ROI_SIGNIFICANCE_MAX_D:
         raise ValueError(f"at most {ROI_SIGNIFICANCE_MAX_D} columns (the Benjamini-Hochberg sort's limit), got {D}")
-    dev, grp, table = _roi_upload(mats, groups, device)
-    lib, n_sets, entry = _lib.load(), len(mats), C.sizeof(_lib.NmRoiSet)
-    max_rows = max(max(int(m.shape[0]) for m in mats), 1)
+    dev = _table_device(mats, device)
+    grp = _row_words(groups, dev, torch.int32)
+    table = bytes(_roi_table(mats, grp))
+    lib, n_sets, entry, max_rows = _lib.load(), len(mats), C.sizeof(_lib.NmRoiSet), _max_rows(mats)
     per = 1 << (n_sets - 1).bit_length()                   # sets per launch: the largest power of two whose workspace fits
     while per > 1 and lib.nm_roi_significance_workspace(min(per, n_sets), D, max_rows, n_perm) > ROI_SIGNIFICANCE_WORKSPACE_CAP:
         per >>= 1
@@ -195,7 +268,7 @@ def roi_significance(mats: Sequence[torch.Tensor], groups: Sequence, n_perm: int
     maxstat = torch.empty(n_sets, n_perm, dtype=torch.int32, device=dev) if return_maxstat else None
     for k0 in range(0, n_sets, per):
         k1 = min(k0 + per, n_sets)
-        sets = torch.frombuffer(bytearray(table[k0 * entry:k1 * entry]), dtype=torch.uint8).to(dev)
+        sets = _to_dev(table[k0 * entry:k1 * entry], dev)
         _lib.check(lib.nm_roi_significance(sets.data_ptr(), k1 - k0, D, max_rows, n_perm, seed ^ ((k0 << 40) & ((1 << 64) - 1)),
                                            ws.data_ptr(), need, out[k0:k1].data_ptr(),
                                            maxstat[k0:k1].data_ptr() if maxstat is not None and n_perm else None,
@@ -205,8 +278,7 @@ def roi_significance(mats: Sequence[torch.Tensor], groups: Sequence, n_perm: int
 
 def _two_groups(X, Y):
     """X over Y as one fp32 [n, D] host matrix with its group words, and whether the inputs were 1-D."""
-    x = torch.as_tensor(np.asarray(X.detach().cpu() if isinstance(X, torch.Tensor) else X, dtype=np.float32))
-    y = torch.as_tensor(np.asarray(Y.detach().cpu() if isinstance(Y, torch.Tensor) else Y, dtype=np.float32))
+    x, y = _host_f32(X), _host_f32(Y)
     if x.dim() != y.dim() or x.dim() not in (1, 2) or (x.dim() == 2 and x.shape[1] != y.shape[1]):
         raise ValueError(f"X and Y must both be 1-D, or 2-D with the same columns; got {tuple(x.shape)} and {tuple(y.shape)}")
     both = torch.cat([x.reshape(len(x), -1), y.reshape(len(y), -1)])
@@ -261,13 +333,12 @@ def _boot_check(scores, positive, n_boot, ci, seed, streams, pairs):
         raise ValueError("every score set needs one label per score")
     if max(sizes) > _lib.NM_METRICS_MAX_N:
         raise ValueError(f"at most {_lib.NM_METRICS_MAX_N} scores per set, got {max(sizes)}")
-    n_boot, seed, ci = int(n_boot), int(seed), float(ci)
+    n_boot, ci = int(n_boot), float(ci)
     if not 1 <= n_boot <= _lib.NM_BOOT_MAX:
         raise ValueError(f"n_boot must lie in 1..{_lib.NM_BOOT_MAX}, got {n_boot}")
     if not 0.0 < ci < 1.0:
         raise ValueError(f"ci must lie in (0, 1), got {ci}")
-    if not 0 <= seed < 1 << 64:
-        raise ValueError(f"seed must be an unsigned 64-bit integer, got {seed}")
+    seed = _seed_check(seed)
     if streams is not None:
         streams = [int(v) for v in np.asarray(streams).reshape(-1)]
         if len(streams) != len(sizes):
@@ -331,26 +402,11 @@ def auc_compare(scores_a, scores_c, positive, n_boot: int = 2000, ci: float = 0.
     return {name: float(row[j]) for j, name in enumerate(AUC_COMPARE_COLUMNS)}
 
 
-def _reg_table(mats, targets, covs, incs, n_cov: int):
-    """nm_column_regress's pointer table on the host: every matrix where it lies, as _roi_table; covs / incs entries may be None."""
-    table = (_lib.NmRegSet * len(mats))()
-    for k, m in enumerate(mats):
-        rows = int(m.shape[0])
-        e = table[k]
-        e.rows, e.pitch = rows, (int(m.stride(0)) if rows > 1 else int(m.shape[1]))
-        e.cov_pitch, e.pad = n_cov, 0
-        if rows:
-            e.x, e.target = m.data_ptr(), targets[k].data_ptr()
-            e.cov = covs[k].data_ptr() if n_cov else None
-            e.include = incs[k].data_ptr() if incs[k] is not None else None
-    return table
-
-
 def _reg_check(mats, targets, kind, covariates, include):
     """nm_column_regress's argument checks on the host (no device is looked for): D, the kind's code, n_cov."""
     if kind not in COLUMN_REGRESS_KINDS:
         raise ValueError(f"kind must be one of {sorted(COLUMN_REGRESS_KINDS)}, got {kind!r}")
-    D = _roi_check(mats, targets)                           # (the same table rules; one target entry per row)
+    D = _table_check(mats, targets)                         # (one target entry per row)
     for name, seq in (("covariates", covariates), ("include", include)):
         if seq is not None and len(seq) != len(mats):
             raise ValueError(f"{name} must have one entry per set")
@@ -383,20 +439,14 @@ def column_regress(mats: Sequence[torch.Tensor], targets: Sequence, kind: str = 
     words (or None), a row with 0 is left out and never looked at.  n_iter < 0 is a status with NaN statistics: -1 a Logit
     that did not converge (perfect separation ends here), -2 invalid input.  One launch for all sets."""
     D, code, n_cov = _reg_check(mats, targets, kind, covariates, include)
-    dev = require_gpu(device if device is not None else (mats[0].device if mats[0].is_cuda else None))
-    if dev.index is None:
-        dev = torch.device(dev.type, torch.cuda.current_device())
-    for k, m in enumerate(mats):
-        if m.device != dev:
-            raise ValueError(f"set {k} is on {m.device}, not on {dev}: the tables are read where they lie")
-    tgt = [torch.as_tensor(v).reshape(-1).to(device=dev, dtype=torch.float32).contiguous() for v in targets]
+    dev = _table_device(mats, device)
+    tgt = _row_words(targets, dev, torch.float32)
     cov = [torch.as_tensor(c).to(device=dev, dtype=torch.float32).contiguous() for c in covariates] if n_cov else None
-    inc = [None if (include is None or w is None) else torch.as_tensor(w).reshape(-1).ne(0).to(device=dev, dtype=torch.int32)
-           for w in (include if include is not None else [None] * len(mats))]
-    sets = torch.frombuffer(bytearray(bytes(_reg_table(mats, tgt, cov, inc, n_cov))), dtype=torch.uint8).to(dev)
+    inc = _row_words(include, dev, torch.int32, nonzero=True) if include is not None else None
+    sets = _to_dev(_reg_table(mats, tgt, cov, inc, n_cov), dev)
     out = torch.empty(len(mats), D, _lib.NM_METRICS_STRIDE, dtype=torch.float64, device=dev)
-    _lib.check(_lib.load().nm_column_regress(sets.data_ptr(), len(mats), D, max(max(int(m.shape[0]) for m in mats), 1), n_cov,
-                                              code, out.data_ptr(), _stream_ptr(dev)), "nm_column_regress")
+    _lib.check(_lib.load().nm_column_regress(sets.data_ptr(), len(mats), D, _max_rows(mats), n_cov, code, out.data_ptr(),
+                                              _stream_ptr(dev)), "nm_column_regress")
     return out
 
 
@@ -405,8 +455,7 @@ def latent_pvalues(latent, target, type, device=None):
     'latent'] and one column 'latent i' per latent dimension holding the p-values of target ~ const + latent_i;
     type == 'continuous' is OLS, anything else Logit.  A fit that statsmodels would refuse (separation, a constant
     column) gives NaN."""
-    lat = torch.as_tensor(np.asarray(latent.detach().cpu() if isinstance(latent, torch.Tensor) else latent, dtype=np.float32))
-    tgt = torch.as_tensor(np.asarray(target.detach().cpu() if isinstance(target, torch.Tensor) else target, dtype=np.float32))
+    lat, tgt = _host_f32(latent), _host_f32(target)
     if lat.dim() != 2 or tgt.dim() != 1 or tgt.numel() != lat.shape[0]:
         raise ValueError(f"latent must be [n, Z] and target [n]; got {tuple(lat.shape)} and {tuple(tgt.shape)}")
     _reg_check([lat], [tgt], "ols", None, None)
@@ -421,30 +470,9 @@ NORMATIVE_ROW_COLUMNS = ("n_hi", "n_lo", "mean_z", "mean_abs_z", "max_z", "argma
 NORMATIVE_COL_COLUMNS = ("n_hi_x", "n_lo_x", "n_hi_y", "n_lo_y", "n_x", "n_y", "mean_z_x", "mean_z_y")
 
 
-def _norm_table(mats, groups=None, subs=None, zs=None):
-    """The pointer table of the four normative entry points on the host: every matrix where it lies, as _roi_table; the
-    per-row outputs of set k start at the sum of the heights before it."""
-    table = (_lib.NmNormSet * len(mats))()
-    off = 0
-    for k, m in enumerate(mats):
-        rows, e = int(m.shape[0]), table[k]
-        e.rows, e.pitch = rows, (int(m.stride(0)) if rows > 1 else int(m.shape[1]))
-        e.sub_pitch = e.z_pitch = e.pad = 0
-        e.row_off = off
-        off += rows
-        if rows:
-            e.x = m.data_ptr()
-            e.group = groups[k].data_ptr() if groups is not None else None
-            if subs is not None:
-                e.sub, e.sub_pitch = subs[k].data_ptr(), (int(subs[k].stride(0)) if rows > 1 else int(subs[k].shape[1]))
-            if zs is not None:
-                e.z, e.z_pitch = zs[k].data_ptr(), int(zs[k].stride(0)) if rows > 1 else int(zs[k].shape[1])
-    return table
-
-
 def _norm_check(mats, groups, sub) -> int:
-    """_roi_check, and a `sub` matrix of the same shape and kind per set (no device is looked for); the width."""
-    D = _roi_check(mats, groups)
+    """_table_check, and a `sub` matrix of the same shape and kind per set (no device is looked for); the width."""
+    D = _table_check(mats, groups)
     if sub is not None:
         if len(sub) != len(mats):
             raise ValueError("sub must have one entry per set")
@@ -456,27 +484,6 @@ def _norm_check(mats, groups, sub) -> int:
             if b.device != m.device:
                 raise ValueError(f"set {k}: sub is on {b.device}, the table on {m.device}")
     return D
-
-
-def _norm_device(mats, device):
-    dev = require_gpu(device if device is not None else (mats[0].device if mats[0].is_cuda else None))
-    if dev.index is None:
-        dev = torch.device(dev.type, torch.cuda.current_device())
-    for k, m in enumerate(mats):
-        if m.device != dev:
-            raise ValueError(f"set {k} is on {m.device}, not on {dev}: the tables are read where they lie")
-    return dev
-
-
-def _norm_groups(mats, groups, device):
-    """The device and the group words on it: host words of all sets go up in one copy (a copy per set costs more than the
-    kernels at 256 sets), words already on the device are used where they lie."""
-    dev = _norm_device(mats, device)
-    grp = [torch.as_tensor(g).reshape(-1) for g in groups]
-    if all(not g.is_cuda for g in grp):
-        flat = torch.cat([g.to(torch.int32) for g in grp]).to(dev)
-        return dev, list(torch.split(flat, [int(g.numel()) for g in grp]))
-    return dev, [g.to(device=dev, dtype=torch.int32).contiguous() for g in grp]
 
 
 def _ref_check(ref_of, n_sets, n_ref):
@@ -493,14 +500,6 @@ def _ref_check(ref_of, n_sets, n_ref):
     return ref
 
 
-def _to_dev(table, dev):
-    return torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
-
-
-def _max_rows(mats):
-    return max(max(int(m.shape[0]) for m in mats), 1)
-
-
 def cohort_moments(mats: Sequence[torch.Tensor], groups: Sequence, sub: Optional[Sequence[torch.Tensor]] = None, ddof: int = 1,
                    device=None) -> torch.Tensor:
     """[n_sets, D, 8] fp64 on the device, per (set, column) over the rows whose group word is 0 (the reference cohort): mean,
@@ -511,7 +510,8 @@ def cohort_moments(mats: Sequence[torch.Tensor], groups: Sequence, sub: Optional
     if ddof not in (0, 1) or isinstance(ddof, bool):
         raise ValueError(f"ddof must be 0 or 1, got {ddof!r}")
     D = _norm_check(mats, groups, sub)
-    dev, grp = _norm_groups(mats, groups, device)
+    dev = _table_device(mats, device)
+    grp = _row_words(groups, dev, torch.int32)
     sets = _to_dev(_norm_table(mats, grp, sub), dev)
     out = torch.empty(len(mats), D, _lib.NM_METRICS_STRIDE, dtype=torch.float64, device=dev)
     _lib.check(_lib.load().nm_cohort_moments(sets.data_ptr(), len(mats), D, _max_rows(mats), int(ddof), out.data_ptr(),
@@ -537,7 +537,8 @@ def normative_z(mats: Sequence[torch.Tensor], groups: Sequence, moments: torch.T
             tuple(moments.shape[1:]) != (D, _lib.NM_METRICS_STRIDE):
         raise ValueError(f"moments must be a float64 [n, {D}, {_lib.NM_METRICS_STRIDE}] tensor as cohort_moments returns it")
     ref = _ref_check(ref_of, len(mats), int(moments.shape[0]))
-    dev, grp = _norm_groups(mats, groups, device)
+    dev = _table_device(mats, device)
+    grp = _row_words(groups, dev, torch.int32)
     mom = moments.to(dev).contiguous()
     zs = [torch.empty(int(m.shape[0]), D, dtype=torch.float32, device=dev) for m in mats] if return_z else None
     sets = _to_dev(_norm_table(mats, grp, sub, zs), dev)
@@ -566,7 +567,8 @@ def cohort_cov(mats: Sequence[torch.Tensor], groups: Sequence, ridge: float = 0.
         raise ValueError(f"ridge must be finite and >= 0, got {ridge}")
     Z = _norm_check(mats, groups, None)
     _latent_width(Z)
-    dev, grp = _norm_groups(mats, groups, device)
+    dev = _table_device(mats, device)
+    grp = _row_words(groups, dev, torch.int32)
     sets = _to_dev(_norm_table(mats, grp), dev)
     mean = torch.empty(len(mats), Z, dtype=torch.float64, device=dev)
     chol = torch.empty(len(mats), Z, Z, dtype=torch.float64, device=dev)
@@ -581,8 +583,7 @@ def mahalanobis(mats: Sequence[torch.Tensor], mean: torch.Tensor, chol: torch.Te
     """A list of [n_k] fp64 device tensors: the Mahalanobis distance d = |L^-1 (row - mean)| of every row of set k to cohort
     ref_of[k] (default k) of a cohort_cov result.  NaN for a row with a non-finite entry and for every row scored against a
     factor whose status is not 0.  One launch for all sets."""
-    # (no group words here: the table rules are checked with one placeholder word per row)
-    Z = _norm_check(mats, [torch.zeros(int(m.shape[0]) if isinstance(m, torch.Tensor) and m.dim() == 2 else 0) for m in mats], None)
+    Z = _table_check(mats)
     _latent_width(Z)
     for name, v, dt in (("mean", mean, torch.float64), ("chol", chol, torch.float64), ("status", status, torch.int32)):
         if not isinstance(v, torch.Tensor) or v.dtype != dt:
@@ -592,7 +593,7 @@ def mahalanobis(mats: Sequence[torch.Tensor], mean: torch.Tensor, chol: torch.Te
         raise ValueError(f"mean [n, {Z}], chol [n, {Z}, {Z}] and status [n] are needed, got {tuple(mean.shape)}, "
                          f"{tuple(chol.shape)}, {tuple(status.shape)}")
     ref = _ref_check(ref_of, len(mats), n)
-    dev = _norm_device(mats, device)
+    dev = _table_device(mats, device)
     sets = _to_dev(_norm_table(mats), dev)
     total = sum(int(m.shape[0]) for m in mats)
     d2 = torch.empty(max(total, 1), dtype=torch.float64, device=dev)

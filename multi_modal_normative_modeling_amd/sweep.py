@@ -10,6 +10,7 @@ CPU tests) -- there is no data-path exchange.
 from __future__ import annotations
 
 import argparse
+import os
 import time
 from dataclasses import dataclass
 from pathlib import Path
@@ -457,6 +458,13 @@ def _fold_eval_job(job: Job, cohort: prep.SyntheticCohort, train_rows: np.ndarra
     return ev, xs
 
 
+def _meta_frame(cohort, rows):
+    """The four metadata columns (io.META_COLS) of the given cohort rows."""
+    import pandas as pd
+    return pd.DataFrame({"participant_id": cohort.iid[rows], "DIA": cohort.dia[rows], "AGE": cohort.age[rows],
+                         "PTGENDER": cohort.gender[rows]})
+
+
 def _fold_results(ev: Job, xs, cohort: prep.SyntheticCohort, test_rows: np.ndarray, modalities: Sequence[str], out_dir,
                   roi_columns: Optional[Dict[str, Sequence[str]]]):
     """{modality: per-subject reconstruction error} of an evaluation job whose forward pass has run, and -- out_dir given --
@@ -467,11 +475,8 @@ def _fold_results(ev: Job, xs, cohort: prep.SyntheticCohort, test_rows: np.ndarr
         x_hat = ev.out_loc[i][:n].cpu().numpy()
         errors[m] = ev.out_rowdev[i][:n].cpu().numpy()
         if out_dir is not None:
-            import pandas as pd
-            meta = pd.DataFrame({"participant_id": cohort.iid[test_rows], "DIA": cohort.dia[test_rows],
-                                 "AGE": cohort.age[test_rows], "PTGENDER": cohort.gender[test_rows]})
-            cols = _roi_columns(roi_columns, m, xs[i].shape[1])
-            io.write_test_csvs(Path(out_dir) / m, m, meta, cols, xs[i], x_hat)
+            io.write_test_csvs(Path(out_dir) / m, m, _meta_frame(cohort, test_rows), _roi_columns(roi_columns, m, xs[i].shape[1]),
+                               xs[i], x_hat)
     return errors
 
 
@@ -498,33 +503,20 @@ def roi_groups(dia: np.ndarray, disease_label=None) -> np.ndarray:
     return np.where(dia == 1, 0, np.where(patient, 1, -1)).astype(np.int32)
 
 
-def _roi_effect_sets(mats: Sequence[torch.Tensor], groups: Sequence[np.ndarray], device) -> List[torch.Tensor]:
-    """metrics.roi_effect for tables of any widths: one launch per distinct width (an SE procedure's modalities share one, a
-    UCA procedure adds the early-fusion table's), every table read where it lies.  Returns one [D_k, 8] device tensor per
-    table, in the order given."""
+def _per_width(call, mats: Sequence[torch.Tensor], *per_set) -> list:
+    """A metrics call for tables of any widths: call(tables, *their per-set arguments) once per distinct width (an SE
+    procedure's modalities share one, a UCA procedure adds the early-fusion table's), in the order the widths first appear,
+    every table read where it lies; a per_set argument given as None stays None.  call returns one result per table it got (a
+    tensor's first axis counts); a table's index within its call -- what metrics.roi_significance's permutation hash sees -- is
+    its place among the tables of its width.  Returns the results in the order of `mats`."""
     by_width: Dict[int, List[int]] = {}
     for j, x in enumerate(mats):
         by_width.setdefault(int(x.shape[1]), []).append(j)
-    out: List[Optional[torch.Tensor]] = [None] * len(mats)
+    out: list = [None] * len(mats)
     for idxs in by_width.values():
-        tab = metrics.roi_effect([mats[j] for j in idxs], [groups[j] for j in idxs], device=device)
-        for a, j in enumerate(idxs):
-            out[j] = tab[a]
-    return out
-
-
-def _roi_significance_sets(mats: Sequence[torch.Tensor], groups: Sequence[np.ndarray], n_perm: int, seed: int,
-                           device) -> List[torch.Tensor]:
-    """metrics.roi_significance for tables of any widths, as _roi_effect_sets: one call per distinct width; a table's index in
-    the permutation hash is its place among the tables of its width."""
-    by_width: Dict[int, List[int]] = {}
-    for j, x in enumerate(mats):
-        by_width.setdefault(int(x.shape[1]), []).append(j)
-    out: List[Optional[torch.Tensor]] = [None] * len(mats)
-    for idxs in by_width.values():
-        tab = metrics.roi_significance([mats[j] for j in idxs], [groups[j] for j in idxs], n_perm=n_perm, seed=seed, device=device)
-        for a, j in enumerate(idxs):
-            out[j] = tab[a]
+        res = call(*(None if seq is None else [seq[j] for j in idxs] for seq in (mats,) + per_set))
+        for j, r in zip(idxs, res):
+            out[j] = r
     return out
 
 
@@ -554,38 +546,16 @@ def parse_regress_spec(spec: str):
     return target, kind
 
 
-def _column_regress_sets(mats: Sequence[torch.Tensor], targets, kind: str, covs, incs, device) -> List[torch.Tensor]:
-    """metrics.column_regress for tables of any widths, as _roi_effect_sets: one launch per distinct width."""
-    by_width: Dict[int, List[int]] = {}
-    for j, x in enumerate(mats):
-        by_width.setdefault(int(x.shape[1]), []).append(j)
-    out: List[Optional[torch.Tensor]] = [None] * len(mats)
-    for idxs in by_width.values():
-        tab = metrics.column_regress([mats[j] for j in idxs], [targets[j] for j in idxs], kind=kind,
-                                     covariates=None if covs is None else [covs[j] for j in idxs],
-                                     include=[incs[j] for j in idxs], device=device)
-        for a, j in enumerate(idxs):
-            out[j] = tab[a]
-    return out
-
-
 def _normative_sets(mats: Sequence[torch.Tensor], groups: Sequence[np.ndarray], subs, thr: float, device) -> List[dict]:
-    """metrics.cohort_moments and metrics.normative_z for tables of any widths, as _roi_effect_sets: one moments launch and one z
+    """metrics.cohort_moments and metrics.normative_z for tables of any widths (_per_width): one moments launch and one z
     launch per distinct width, every table scored against its own group-0 rows.  Returns per table {"z" [n, D] fp32, "rows"
     [n, 8], "cols" [D, 8], "moments" [D, 8]} on the device, in the order given."""
-    by_width: Dict[int, List[int]] = {}
-    for j, x in enumerate(mats):
-        by_width.setdefault(int(x.shape[1]), []).append(j)
-    out: List[Optional[dict]] = [None] * len(mats)
-    for idxs in by_width.values():
-        ms, gs = [mats[j] for j in idxs], [groups[j] for j in idxs]
-        sb = None if subs is None else [subs[j] for j in idxs]
+    def one_width(ms, gs, sb):
         mom = metrics.cohort_moments(ms, gs, sub=sb, ddof=1, device=device)
         z, rows, cols = metrics.normative_z(ms, gs, mom, thr=thr, sub=sb, device=device)
         rows = torch.split(rows, [int(m.shape[0]) for m in ms])
-        for a, j in enumerate(idxs):
-            out[j] = {"z": z[a], "rows": rows[a], "cols": cols[a], "moments": mom[a]}
-    return out
+        return [{"z": z[a], "rows": rows[a], "cols": cols[a], "moments": mom[a]} for a in range(len(ms))]
+    return _per_width(one_width, mats, groups, subs)
 
 
 NORMATIVE_KINDS = ("squared", "signed")
@@ -672,79 +642,73 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
         by_tiles.setdefault((ev.tables[0].n_tiles, bool(ev.spec.wide)), []).append(i)
     for idxs in by_tiles.values():
         JobSet([evs[i][0] for i in idxs]).forward(loss=False)
+    stats = []                  # (result key, one [D, 8] device table per entry of `mats`, the writer of its CSV)
     if roi_effect:
+        # one table list for every statistic: every fold x modality (fold-major), then the pooled rows of every modality; a
+        # value per row list (the folds' test rows, then all of them) goes with it through `per_table`
         nm_ = len(modalities)
-        grp = [roi_groups(cohort.dia[te], disease_label) for _, te in folds]
-        mats = [ev.out_sqerr[i][:len(te)] for (ev, _), (_, te) in zip(evs, folds) for i in range(nm_)]
-        per_fold = _roi_effect_sets(mats, [g for g in grp for _ in range(nm_)], device)
-        pooled_mats = [torch.cat(mats[i::nm_]) for i in range(nm_)]
-        pooled = _roi_effect_sets(pooled_mats, [np.concatenate(grp)] * nm_, device)
+        tests = [te for _, te in folds]
+        rows_of = tests + [np.concatenate(tests)]
+        n_fold = len(folds) * nm_
+
+        def per_table(seq):
+            return [v for v in seq for _ in range(nm_)]
+
+        def tables(export):
+            t = [export(ev, i)[:len(te)] for (ev, _), te in zip(evs, tests) for i in range(nm_)]
+            return t + [torch.cat(t[i::nm_]) for i in range(nm_)]
+
+        def folds_then_pooled(call):                # (two calls: a set's index within its call enters the permutation hash)
+            return _per_width(call, mats[:n_fold], grp[:n_fold]) + _per_width(call, mats[n_fold:], grp[n_fold:])
+        grp = per_table([roi_groups(cohort.dia[r], disease_label) for r in rows_of])
+        mats = tables(lambda ev, i: ev.out_sqerr[i])
+        effect = folds_then_pooled(lambda ms, gs: metrics.roi_effect(ms, gs, device=device))
+        stats.append(("roi_effect", effect, io.write_roi_effect_csv))
         if roi_significance:
-            sig_fold = _roi_significance_sets(mats, [g for g in grp for _ in range(nm_)], roi_perm, roi_seed, device)
-            sig_pooled = _roi_significance_sets(pooled_mats, [np.concatenate(grp)] * nm_, roi_perm, roi_seed, device)
+            signif = folds_then_pooled(lambda ms, gs: metrics.roi_significance(ms, gs, n_perm=roi_perm, seed=roi_seed, device=device))
+            stats.append(("roi_significance", signif, io.write_roi_significance_csv))
         if roi_regress is not None:
-            # the folds' sets, then the pooled ones: one table list, one launch per width
-            rows_of = [te for _, te in folds] + [np.concatenate([te for _, te in folds])]
+            # the folds' sets and the pooled ones in one launch per width
             tg = [regress_target(cohort, r, reg_target, reg_kind, disease_label) for r in rows_of]
             cv = [np.stack([np.asarray(getattr(cohort, REGRESS_TARGETS[a])[r], dtype=np.float32) for a in roi_adjust], 1)
                   for r in rows_of] if roi_adjust else None
-            rep = lambda seq: [v for v in seq[:-1] for _ in range(nm_)] + [seq[-1]] * nm_
-            reg = _column_regress_sets(mats + pooled_mats, rep([t for t, _ in tg]), reg_kind,
-                                       None if cv is None else rep(cv), rep([w for _, w in tg]), device)
+
+            def regress(ms, ts, cs, ws):
+                return metrics.column_regress(ms, ts, kind=reg_kind, covariates=cs, include=ws, device=device)
+            fits = _per_width(regress, mats, per_table([t for t, _ in tg]), None if cv is None else per_table(cv),
+                              per_table([w for _, w in tg]))
+            stats.append(("roi_regress", fits, io.write_roi_regress_csv))
         if normative is not None:
-            # the folds' sets, then the pooled ones: one table list, one moments and one z launch per width
+            # likewise: one moments and one z launch per width
+            n_mats, n_subs = mats, None
             if normative == "signed":
-                n_mats = [ev.tables[i].x_f32[:len(te), :ev.tables[i].D] for (ev, _), (_, te) in zip(evs, folds) for i in range(nm_)]
-                n_subs = [ev.out_loc[i][:len(te)] for (ev, _), (_, te) in zip(evs, folds) for i in range(nm_)]
-                n_subs = n_subs + [torch.cat(n_subs[i::nm_]) for i in range(nm_)]
-                n_mats = n_mats + [torch.cat(n_mats[i::nm_]) for i in range(nm_)]
-            else:
-                n_mats, n_subs = mats + pooled_mats, None
-            n_grp = [g for g in grp for _ in range(nm_)] + [np.concatenate(grp)] * nm_
-            norm = _normative_sets(n_mats, n_grp, n_subs, z_thr, device)
+                n_mats, n_subs = tables(lambda ev, i: ev.tables[i].x_f32[:, :ev.tables[i].D]), tables(lambda ev, i: ev.out_loc[i])
+            norm = _normative_sets(n_mats, grp, n_subs, z_thr, device)
     torch.cuda.synchronize(device)
     out = [_fold_results(ev, xs, cohort, te, modalities, d, roi_columns) for (ev, xs), (_, te), d in zip(evs, folds, dirs)]
-    if roi_effect:
-        pooled = {m: pooled[i].cpu().numpy() for i, m in enumerate(modalities)}
+    for key, tabs, write in stats:
+        tabs = [t.cpu().numpy() for t in tabs]
+        pooled = {m: tabs[n_fold + i] for i, m in enumerate(modalities)}
         for f, (res, d) in enumerate(zip(out, dirs)):
-            res["roi_effect"] = {m: per_fold[f * nm_ + i].cpu().numpy() for i, m in enumerate(modalities)}
-            res["roi_effect_pooled"] = pooled
+            res[key] = {m: tabs[f * nm_ + i] for i, m in enumerate(modalities)}
+            res[key + "_pooled"] = pooled
             if d is not None:
-                for m, tab in res["roi_effect"].items():
-                    io.write_roi_effect_csv(Path(d) / m, m, _roi_columns(roi_columns, m, tab.shape[0]), tab)
-    if roi_significance:
-        sig_pooled = {m: sig_pooled[i].cpu().numpy() for i, m in enumerate(modalities)}
-        for f, (res, d) in enumerate(zip(out, dirs)):
-            res["roi_significance"] = {m: sig_fold[f * nm_ + i].cpu().numpy() for i, m in enumerate(modalities)}
-            res["roi_significance_pooled"] = sig_pooled
-            if d is not None:
-                for m, tab in res["roi_significance"].items():
-                    io.write_roi_significance_csv(Path(d) / m, m, _roi_columns(roi_columns, m, tab.shape[0]), tab)
-    if roi_regress is not None:
-        reg_pooled = {m: reg[len(mats) + i].cpu().numpy() for i, m in enumerate(modalities)}
-        for f, (res, d) in enumerate(zip(out, dirs)):
-            res["roi_regress"] = {m: reg[f * nm_ + i].cpu().numpy() for i, m in enumerate(modalities)}
-            res["roi_regress_pooled"] = reg_pooled
-            if d is not None:
-                for m, tab in res["roi_regress"].items():
-                    io.write_roi_regress_csv(Path(d) / m, m, _roi_columns(roi_columns, m, tab.shape[0]), tab)
+                for m, tab in res[key].items():
+                    write(Path(d) / m, m, _roi_columns(roi_columns, m, tab.shape[0]), tab)
     if normative is not None:
         def host(j):
             res = {k: v.cpu().numpy() for k, v in norm[j].items()}
             res["x"] = n_mats[j].cpu().numpy()
             res["sub"] = None if n_subs is None else n_subs[j].cpu().numpy()
             return res
-        norm_pooled = {m: host(len(mats) + i) for i, m in enumerate(modalities)}
-        for f, (res, (_, te), d) in enumerate(zip(out, folds, dirs)):
+        norm_pooled = {m: host(n_fold + i) for i, m in enumerate(modalities)}
+        for f, (res, d) in enumerate(zip(out, dirs)):
             res["normative"] = {m: host(f * nm_ + i) for i, m in enumerate(modalities)}
             res["normative_pooled"] = norm_pooled
             if d is not None:
-                import pandas as pd
-                meta = pd.DataFrame({"participant_id": cohort.iid[te], "DIA": cohort.dia[te], "AGE": cohort.age[te],
-                                     "PTGENDER": cohort.gender[te]})
                 for m, t in res["normative"].items():
-                    io.write_normative_csvs(Path(d) / m, m, meta, _roi_columns(roi_columns, m, t["z"].shape[1]), t["z"], t["rows"],
-                                            t["cols"])
+                    io.write_normative_csvs(Path(d) / m, m, _meta_frame(cohort, tests[f]), _roi_columns(roi_columns, m, t["z"].shape[1]),
+                                            t["z"], t["rows"], t["cols"])
     return out
 
 
@@ -841,9 +805,7 @@ def latent_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Seque
     for mu, lv, z, sc, (_, te), d in zip(mus, lvs, zsep, score, folds, dirs):
         res = {"mu": mu.cpu().numpy(), "var": lv.exp().cpu().numpy(), "z": z.cpu().numpy(), "score": sc.cpu().numpy()}
         if d is not None:
-            import pandas as pd
-            meta = pd.DataFrame({"participant_id": cohort.iid[te], "DIA": cohort.dia[te], "AGE": cohort.age[te],
-                                 "PTGENDER": cohort.gender[te]})
+            meta = _meta_frame(cohort, te)
             io.write_latent_csvs(d, name, meta, res["mu"], res["var"], res["score"], res["z"])
             if maha is not None:
                 io.write_latent_mahalanobis_csv(d, name, meta, maha[len(out)].cpu().numpy())
@@ -917,7 +879,6 @@ def build_parser():
 def main(argv=None, _run_cells=None) -> torch.Tensor:
     """The sharded sweep; returns the gathered metric table on rank 0 (an empty tensor elsewhere).  `_run_cells`
     replaces run_cells in the CPU rehearsal tests (the real one needs a GPU)."""
-    import os
     args = build_parser().parse_args(argv)
     if args.model not in MODEL_KINDS:                                         # multimodal_kfold_train_cvae_supervised.py:170-171
         raise ValueError(f"Model '{args.model}' is not recognized. Available models are: {', '.join(MODEL_KINDS)}")
@@ -1023,7 +984,6 @@ def _driver_common(ap: argparse.ArgumentParser):
 
 
 def _my_folds(args) -> List[int]:
-    import os
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     folds = list(range(args.n_splits)) if args.folds is None else list(args.folds)
     return folds[rank::world]
@@ -1033,7 +993,6 @@ def main_regression(argv=None, _runner=None):
     """Command line of multimodal_kfold_train_cvae_supervised_regression.py:196-206 (same flag names): FI regression model
     on the folds of a cohort, every fold training concurrently in one launch; under torch.distributed.run the folds are
     dealt round-robin to the ranks (no collective: each rank writes its folds' files).  Returns the per-fold results."""
-    import os
     ap = argparse.ArgumentParser(prog="python -m multi_modal_normative_modeling_amd.sweep regression", description=main_regression.__doc__)
     ap.add_argument("-R", "--dataset_resourse", dest="dataset_resourse", type=str, default="HCPimage",
                     help="(the reference defaults to ADNI, whose y.csv carries no FI column; HCPimage is the resource with FI)")
@@ -1051,7 +1010,7 @@ def main_regression(argv=None, _runner=None):
         raise ValueError("-H takes the hidden widths followed by the latent size (the script's hz_para_list)")
     cohort = _cohort_from_args(args)
     mods = prep.datasets_name(args.dataset_resourse, args.procedure)
-    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+    device = _local_device()
     out_dir = None if args.out_dir is None else Path(args.out_dir) / args.dataset_resourse / "regression_outputs"
     runner = _runner or run_regression_folds
     res = runner(cohort, _my_folds(args), args.n_splits, args.epochs, device, out_dir=out_dir, modalities=mods,
@@ -1068,7 +1027,6 @@ def main_endtoend(argv=None, _runner=None):
     every fold training concurrently in one launch, evaluate() on the held-out fold.  Flags the script parses but never
     uses (-C, -O, -Model, -Maxlearningrate, -Learningrateclassifier, -Weightkl, -Weightrec: its loss call passes margin and
     weightcontrastive only, :298) are accepted and ignored the same way."""
-    import os
     ap = argparse.ArgumentParser(prog="python -m multi_modal_normative_modeling_amd.sweep endtoend", description=main_endtoend.__doc__)
     ap.add_argument("-R", "--dataset_resourse", dest="dataset_resourse", type=str, default="HCPimage")
     ap.add_argument("-H", "--hz_para_list", dest="hz_para_list", nargs="+", type=int, default=[110, 110, 64])
@@ -1093,7 +1051,7 @@ def main_endtoend(argv=None, _runner=None):
     cohort = _cohort_from_args(args)
     proc = f"SM-{args.single_modality}" if args.single_modality else args.procedure
     mods = [m for m in prep.datasets_name(args.dataset_resourse, proc)]
-    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+    device = _local_device()
     runner = _runner or run_endtoend_folds
     res = runner(cohort, _my_folds(args), args.n_splits, args.epochs, device, modalities=mods, latent=int(args.hz_para_list[-1]),
                  classifier_layers=tuple(args.layers), dropout_rate=args.dropout, margin=args.margin,
@@ -1115,7 +1073,6 @@ def main_test(argv=None):
     the covariates on the test rows, reconstruct from the joint latent and write the five CSV kinds per modality under
     <models-dir>/<resource>/<procedure>/<fold:03d>/<modality>/, then the all-folds tables under
     <out-dir>/<resource>/<procedure>/<modality>/ (the script's deviation_dir, :147-175).  Returns {modality: [N] errors}."""
-    import os
     import pandas as pd
     ap = argparse.ArgumentParser(prog="python -m multi_modal_normative_modeling_amd.sweep test", description=main_test.__doc__)
     ap.add_argument("-R", "--dataset_resourse", dest="dataset_resourse", type=str, default="HCPimage")
@@ -1181,7 +1138,7 @@ def main_test(argv=None):
     cohort = _cohort_from_args(args)
     mods, combine = workload.procedure_modalities(args.procedure, args.dataset_resourse)
     combine = (args.combine or combine).lower()
-    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+    device = _local_device()
     folds = prep.kfold_indices(len(cohort.iid), args.n_splits, 42)
     root = Path(args.models_dir) / args.dataset_resourse / args.procedure
     out_root = Path(args.out_dir or args.models_dir) / args.dataset_resourse / args.procedure
@@ -1242,9 +1199,7 @@ def main_test(argv=None):
         if args.normative and results:               # the pooled z-map: this rank's folds' test subjects against their controls
             t = results[0]["normative_pooled"][m]
             te_all = np.concatenate([te for _, te in fold_rows])
-            meta = pd.DataFrame({"participant_id": cohort.iid[te_all], "DIA": cohort.dia[te_all], "AGE": cohort.age[te_all],
-                                 "PTGENDER": cohort.gender[te_all]})
-            io.write_normative_csvs(out_root / m, m, meta, _roi_columns(None, m, t["z"].shape[1]), t["z"], t["rows"], t["cols"])
+            io.write_normative_csvs(out_root / m, m, _meta_frame(cohort, te_all), _roi_columns(None, m, t["z"].shape[1]), t["z"], t["rows"], t["cols"])
             g = roi_groups(cohort.dia[te_all], args.disease_label)
             ext = t["rows"][:, 0] + t["rows"][:, 1]
             print(f"[test] {args.procedure} {m}: pooled normative z-map ({args.normative}), ROIs beyond +-{args.z_thr:g} per subject: "
@@ -1267,16 +1222,26 @@ def main_test(argv=None):
     return out
 
 
-def _analysis_roi(root: Path, mods: Sequence[str], n_splits: int, hc: int, procedure: str) -> Dict[str, np.ndarray]:
-    """`analysis --roi`: the per-fold reconstruction_error_roi_<m>.csv files (this package's or the reference's: the four
-    metadata columns, then one column per ROI) uploaded, ONE metrics.roi_effect launch over all folds and modalities (one per
-    table width), and
-    per modality group_analysis_roi_<m>.csv: per ROI the mean and population std over folds of cliff_delta and auc.
-    Prints the ten ROIs with the largest mean |delta|; returns {modality: [folds, D, 8]}."""
-    import os
+def _local_device() -> torch.device:
+    """This process's GPU under torch.distributed.run (LOCAL_RANK), cuda:0 otherwise."""
+    return torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+
+
+def healthy(dia, hc: int) -> np.ndarray:
+    """The healthy controls of a DIA column: files written from a prep.Cohort carry the cohort's convention 1 = healthy (only 0
+    and 1 occur), raw tables the resource's own label hc."""
+    dia = np.asarray(dia)
+    return (dia == 1) if set(np.unique(dia)) <= {0, 1} else (dia == hc)
+
+
+def _read_roi_errors(root: Path, mods: Sequence[str], n_splits: int, hc: int):
+    """The per-fold reconstruction_error_roi_<m>.csv files of `test` (this package's or the reference's: the four metadata
+    columns, then one column per ROI), for the folds that have one per modality: (folds, {m: ROI names}, {m: [per fold the
+    row-major fp32 matrix]}, {m: [per fold the int32 group words, 0 = healthy, 1 = patient]})."""
     import pandas as pd
-    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
-    mats, groups, cols, folds = [], [], {}, []
+    folds, cols = [], {}
+    rows: Dict[str, list] = {m: [] for m in mods}
+    grp: Dict[str, list] = {m: [] for m in mods}
     for k in range(n_splits):
         files = [root / f"{k:03d}" / m / f"reconstruction_error_roi_{m}.csv" for m in mods]
         if not all(f.exists() for f in files):
@@ -1284,17 +1249,27 @@ def _analysis_roi(root: Path, mods: Sequence[str], n_splits: int, hc: int, proce
         folds.append(k)
         for m, f in zip(mods, files):
             df = pd.read_csv(f, float_precision="round_trip")      # (the float32 values the file was written from, exactly)
-            dia = df["DIA"].to_numpy()
-            # (DIA as in the reconstruction analysis: the cohort's convention 1 = healthy, or the resource's raw label)
-            healthy = (dia == 1) if set(np.unique(dia)) <= {0, 1} else (dia == hc)
             roi = [c for c in df.columns if c not in io.META_COLS]
             if cols.setdefault(m, roi) != roi:
                 raise ValueError(f"{f}: ROI columns differ from the first fold's")
-            mats.append(torch.as_tensor(np.ascontiguousarray(df[roi].to_numpy(dtype=np.float32))).to(device))   # (row-major)
-            groups.append(np.where(healthy, 0, 1).astype(np.int32))
+            rows[m].append(np.ascontiguousarray(df[roi].to_numpy(dtype=np.float32)))
+            grp[m].append(np.where(healthy(df["DIA"].to_numpy(), hc), 0, 1).astype(np.int32))
     if not folds:
         raise FileNotFoundError(f"no reconstruction_error_roi_*.csv of {list(mods)} under {root}/<fold>/ -- run the `test` subcommand first")
-    tabs = _roi_effect_sets(mats, groups, device)
+    return folds, cols, rows, grp
+
+
+def _analysis_roi(root: Path, mods: Sequence[str], n_splits: int, hc: int, procedure: str) -> Dict[str, np.ndarray]:
+    """`analysis --roi`: the per-fold reconstruction_error_roi_<m>.csv files (this package's or the reference's: the four
+    metadata columns, then one column per ROI) uploaded, ONE metrics.roi_effect launch over all folds and modalities (one per
+    table width), and
+    per modality group_analysis_roi_<m>.csv: per ROI the mean and population std over folds of cliff_delta and auc.
+    Prints the ten ROIs with the largest mean |delta|; returns {modality: [folds, D, 8]}."""
+    import pandas as pd
+    device = _local_device()
+    folds, cols, rows, grp = _read_roi_errors(root, mods, n_splits, hc)
+    mats = [torch.as_tensor(rows[m][a]).to(device) for a in range(len(folds)) for m in mods]
+    tabs = _per_width(lambda ms, gs: metrics.roi_effect(ms, gs, device=device), mats, [grp[m][a] for a in range(len(folds)) for m in mods])
     out = {m: torch.stack(tabs[i::len(mods)]).cpu().numpy() for i, m in enumerate(mods)}
     for m in mods:
         delta, auc = out[m][:, :, 0], out[m][:, :, 1]
@@ -1316,30 +1291,13 @@ def _analysis_roi_significance(root: Path, mods: Sequence[str], n_splits: int, h
     group_analysis_roi_significance_<m>.csv: every ROI with metrics.ROI_SIGNIFICANCE_COLUMNS, sorted by p_maxt, then by q_bh,
     under a comment line with n_x, n_y, n_perm and seed.  The pooled rows are taken as independent: a cohort recipe that
     repeats a subject across folds makes these p-values too small.  Returns {modality: [D, 8]} in the files' ROI order."""
-    import os
     import pandas as pd
-    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
-    rows: Dict[str, list] = {m: [] for m in mods}
-    grp: Dict[str, list] = {m: [] for m in mods}
-    cols: Dict[str, list] = {}
-    for k in range(n_splits):
-        files = [root / f"{k:03d}" / m / f"reconstruction_error_roi_{m}.csv" for m in mods]
-        if not all(f.exists() for f in files):
-            continue
-        for m, f in zip(mods, files):
-            df = pd.read_csv(f, float_precision="round_trip")
-            dia = df["DIA"].to_numpy()
-            healthy = (dia == 1) if set(np.unique(dia)) <= {0, 1} else (dia == hc)
-            roi = [c for c in df.columns if c not in io.META_COLS]
-            if cols.setdefault(m, roi) != roi:
-                raise ValueError(f"{f}: ROI columns differ from the first fold's")
-            rows[m].append(np.ascontiguousarray(df[roi].to_numpy(dtype=np.float32)))
-            grp[m].append(np.where(healthy, 0, 1).astype(np.int32))
-    if not cols:
-        raise FileNotFoundError(f"no reconstruction_error_roi_*.csv of {list(mods)} under {root}/<fold>/ -- run the `test` subcommand first")
+    device = _local_device()
+    _, cols, rows, grp = _read_roi_errors(root, mods, n_splits, hc)
     mats = [torch.as_tensor(np.concatenate(rows[m])).to(device) for m in mods]
     groups = [np.concatenate(grp[m]) for m in mods]
-    tabs = _roi_significance_sets(mats, groups, n_perm, seed, device)      # (more than NM_METRICS_MAX_N rows: its ValueError)
+    tabs = _per_width(lambda ms, gs: metrics.roi_significance(ms, gs, n_perm=n_perm, seed=seed, device=device), mats,
+                      groups)                                              # (more than NM_METRICS_MAX_N rows: its ValueError)
     out = {}
     for m, tab, g in zip(mods, tabs, groups):
         out[m] = tab = tab.cpu().numpy()
@@ -1356,51 +1314,40 @@ def _analysis_roi_significance(root: Path, mods: Sequence[str], n_splits: int, h
     return out
 
 
+# --score -> (the per-fold file: {m} one per modality, averaged; {p} one of the procedure), the score of a file's frame, what
+# `test` has to be run with for the file to exist
+ANALYSIS_SCORES = {
+    "reconstruction": ("reconstruction_error_{m}.csv", lambda d: d["Reconstruction error"], ""),
+    "latent": ("latent_deviation_{p}.csv", lambda d: d["Latent deviation"], " with --latent"),
+    "mahalanobis": ("latent_mahalanobis_{p}.csv", lambda d: d["d"], " with --latent --mahalanobis"),
+    "extreme": ("normative_subject_{m}.csv", lambda d: d["n_hi"] + d["n_lo"], " with --roi-effect --normative"),
+    "zmean": ("normative_subject_{m}.csv", lambda d: d["mean_abs_z"], " with --roi-effect --normative"),
+}
+
+
 def _analysis_scores(root: Path, mods: Sequence[str], procedure: str, score: str, n_splits: int, hc: int):
-    """The per-subject scores `analysis` works on, read from the files of `test`: per fold present the fp32 score tensor (the
-    modality-averaged reconstruction error, or the latent deviation), the int32 patient flags, the fold number and the
-    participant ids."""
+    """The per-subject scores `analysis` works on, read from the files of `test` (ANALYSIS_SCORES): per fold present the fp32
+    score tensor (the modality-averaged reconstruction error, or the latent deviation, ...), the int32 patient flags, the fold
+    number and the participant ids."""
     import pandas as pd
+    pattern, column, hint = ANALYSIS_SCORES.get(score, ANALYSIS_SCORES["reconstruction"])   # (any other name: the error)
+    per_modality = "{m}" in pattern
     scores, positive, folds, ids = [], [], [], []
     for k in range(n_splits):
-        if score == "latent":
-            files = [root / f"{k:03d}" / f"latent_deviation_{procedure}.csv"]
-        elif score == "mahalanobis":
-            files = [root / f"{k:03d}" / f"latent_mahalanobis_{procedure}.csv"]
-        elif score in ("extreme", "zmean"):
-            files = [root / f"{k:03d}" / m / f"normative_subject_{m}.csv" for m in mods]
-        else:
-            files = [root / f"{k:03d}" / m / f"reconstruction_error_{m}.csv" for m in mods]
+        files = [root / f"{k:03d}" / m / pattern.format(m=m) for m in mods] if per_modality else \
+            [root / f"{k:03d}" / pattern.format(p=procedure)]
         if not all(f.exists() for f in files):
             continue
         dfs = [pd.read_csv(f) for f in files]
-        if score == "latent":
-            err = dfs[0]["Latent deviation"].to_numpy(dtype=np.float64)
-        elif score == "mahalanobis":
-            err = dfs[0]["d"].to_numpy(dtype=np.float64)
-        elif score == "extreme":
-            err = sum((d["n_hi"] + d["n_lo"]).to_numpy(dtype=np.float64) for d in dfs) / len(dfs)
-        elif score == "zmean":
-            err = sum(d["mean_abs_z"].to_numpy(dtype=np.float64) for d in dfs) / len(dfs)
-        else:
-            err = sum(d["Reconstruction error"].to_numpy(dtype=np.float64) for d in dfs) / len(dfs)
-        dia = dfs[0]["DIA"].to_numpy()
-        # (files written from a prep.Cohort carry DIA in the cohort's convention 1 = healthy; raw tables the resource's label)
-        healthy = (dia == 1) if set(np.unique(dia)) <= {0, 1} else (dia == hc)
+        vals = [column(d).to_numpy(dtype=np.float64) for d in dfs]
+        err = sum(vals) / len(vals) if per_modality else vals[0]
         scores.append(torch.as_tensor(err, dtype=torch.float32))
-        positive.append(torch.as_tensor(~healthy, dtype=torch.int32))
+        positive.append(torch.as_tensor(~healthy(dfs[0]["DIA"].to_numpy(), hc), dtype=torch.int32))
         folds.append(k)
         ids.append(dfs[0]["participant_id"].to_numpy())
-    if not folds and score == "latent":
-        raise FileNotFoundError(f"no latent_deviation_{procedure}.csv under {root}/<fold>/ -- run the `test` subcommand with --latent first")
-    if not folds and score == "mahalanobis":
-        raise FileNotFoundError(f"no latent_mahalanobis_{procedure}.csv under {root}/<fold>/ -- run the `test` subcommand with --latent "
-                                f"--mahalanobis first")
-    if not folds and score in ("extreme", "zmean"):
-        raise FileNotFoundError(f"no normative_subject_*.csv of {mods} under {root}/<fold>/ -- run the `test` subcommand with "
-                                f"--roi-effect --normative first")
     if not folds:
-        raise FileNotFoundError(f"no reconstruction_error_*.csv of {mods} under {root}/<fold>/ -- run the `test` subcommand first")
+        what = f"{pattern.format(m='*')} of {mods}" if per_modality else pattern.format(p=procedure)
+        raise FileNotFoundError(f"no {what} under {root}/<fold>/ -- run the `test` subcommand{hint} first")
     return scores, positive, folds, ids
 
 

@@ -11,6 +11,7 @@ import torch
 from multi_modal_normative_modeling_amd import _lib, metrics
 from multi_modal_normative_modeling_amd.engine import _stream_ptr
 from tests import auc_bootstrap_ref as R
+from tests.table_stats_util import same_bits as _same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -71,12 +72,6 @@ def _expect(sets, n_boot, ci=0.95, seed=SEED, streams=None, pairs=None, max_set=
     if pairs is not None and len(pairs):
         prs = np.stack([R.pair_row((*sets[a], streams[a]), (*sets[c], streams[c]), n_boot, lo, hi, seed, max_set=max_set) for a, c in pairs])
     return np.stack(rows), prs, np.stack(boots)
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    nan = np.isnan(a) & np.isnan(b)
-    return a.shape == b.shape and bool(np.all((a.view(np.int64) == b.view(np.int64)) | nan))
 
 
 def _compare(got, ref, n_boot, what):

@@ -10,22 +10,13 @@ import torch
 from multi_modal_normative_modeling_amd import _lib, metrics
 from multi_modal_normative_modeling_amd.engine import _stream_ptr
 from tests import column_regress_ref as R
+from tests.table_stats_util import upload as _upload
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 POISON = -1.2345e300
 KINDS = {"ols": _lib.NM_REG_OLS, "logit": _lib.NM_REG_LOGIT}
-
-
-def _upload(x, pitch):
-    """[rows, D] view of a [rows, pitch] device buffer whose pad columns hold NaN and +-inf."""
-    rows, D = x.shape
-    assert pitch >= D
-    buf = torch.empty(rows, pitch, dtype=torch.float32)
-    buf[:] = torch.tensor([float("nan"), float("inf"), float("-inf")]).repeat(pitch)[:pitch]
-    buf[:, :D] = torch.from_numpy(np.ascontiguousarray(x))
-    return buf.to(DEV)[:, :D]
 
 
 def _launch(views, targets, covs, incs, kind, max_rows=None, rows=None, pitches=None):

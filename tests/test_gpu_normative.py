@@ -13,6 +13,7 @@ import torch
 from multi_modal_normative_modeling_amd import _lib, metrics
 from multi_modal_normative_modeling_amd.engine import _stream_ptr
 from tests import normative_ref as R
+from tests.table_stats_util import upload as _upload
 
 pytestmark = pytest.mark.gpu
 
@@ -23,16 +24,6 @@ WIDTHS = [1, 63, 64, 65, 130]
 HEIGHTS = [1, 2, 127, 128, 129, 300]
 # seeds moved on the CPU, with the yardstick alone, until input_conditions holds in every case: (D, rows) -> added to the seed
 SEED_BUMP = {(65, 127): 100}
-
-
-def _upload(x, pitch):
-    """[rows, D] view of a [rows, pitch] device buffer whose pad columns hold NaN and +-inf."""
-    rows, D = x.shape
-    assert pitch >= D
-    buf = torch.empty(rows, pitch, dtype=torch.float32)
-    buf[:] = torch.tensor([float("nan"), float("inf"), float("-inf")]).repeat(pitch)[:pitch]
-    buf[:, :D] = torch.from_numpy(np.ascontiguousarray(x))
-    return buf.to(DEV)[:, :D]
 
 
 def make_case(D, rows, k=0):

@@ -9,6 +9,7 @@ import torch
 from multi_modal_normative_modeling_amd import _lib, metrics
 from multi_modal_normative_modeling_amd.engine import _stream_ptr
 from tests import roi_effect_ref as R
+from tests.table_stats_util import same_bits as _same_bits, upload as _upload
 
 pytestmark = pytest.mark.gpu
 
@@ -28,17 +29,6 @@ def _groups(rng, rows):
     return g
 
 
-def _upload(x, pitch):
-    """[rows, D] view of a [rows, pitch] device buffer whose pad columns hold NaN and +-inf."""
-    rows, D = x.shape
-    assert pitch >= D
-    buf = torch.empty(rows, pitch, dtype=torch.float32)
-    pad = torch.tensor([float("nan"), float("inf"), float("-inf")]).repeat(pitch)[:pitch]
-    buf[:] = pad
-    buf[:, :D] = torch.from_numpy(x)
-    return buf.to(DEV)[:, :D]
-
-
 def _launch(views, groups, max_rows=None, rows=None, pitches=None):
     """The C entry point on a poisoned output; rows / pitches override what the table declares (the refusal cases)."""
     D = int(views[0].shape[1])
@@ -56,12 +46,6 @@ def _launch(views, groups, max_rows=None, rows=None, pitches=None):
     _lib.check(_lib.load().nm_roi_effect(sets.data_ptr(), len(views), D, max_rows, out.data_ptr(), _stream_ptr(DEV)), "nm_roi_effect")
     torch.cuda.synchronize()
     return out.cpu().numpy()
-
-
-def _same_bits(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    nan = np.isnan(a)
-    return np.array_equal(nan, np.isnan(b)) and np.array_equal(a[~nan].view(np.int64), b[~nan].view(np.int64))
 
 
 def _check(got, x, group, counts=R.counts_broadcast):
