@@ -580,6 +580,66 @@ int nm_auc_bootstrap(const float* scores, const int32_t* labels, const int32_t* 
                      const int32_t* pairs, int n_pairs, void* workspace, size_t workspace_bytes,
                      double* out, double* pairs_out, int32_t* boot_out, void* stream);
 
+/* Operating points: every way compute_classification_performance (multimodal_kfold_cvae_group_analysis_1x1.py:105-157) can
+ * choose its threshold, selected on one score set and scored on another, with the curve-level summaries of every set.  Sets
+ * as for nm_posthoc_metrics.  rules (HOST memory, 1 <= n_rules <= NM_OP_MAX_RULES) is the rule table; it travels by value.
+ * With the set sorted by descending score (-0 = +0), point j = 0..K-1 of its curve is the j-th distinct score with the counts
+ * (tp_j, fp_j) of `score >= that score`; P = n_pos, N = n_neg; every rule predicts (double)score >= threshold (:144).
+ *   NM_OP_ROC    :129-132  argmax(tpr - fpr) over roc_curve's points (drop_intermediate corners, the +inf origin first): the
+ *                threshold nm_posthoc_metrics picks, bit for bit.  objective = J
+ *   NM_OP_F1     :63-75    thresholds v_i = a + i * ((b - a) / (n - 1)), v_(n-1) = b (np.linspace(a, b, n), no fused multiply-
+ *                add), value 2 tp / (P + tp + fp) (sklearn's f1_score), from (threshold 0, value 0) the first strict improvement
+ *   NM_OP_COST   :83-97    the same grid, fp * cost_fp + fn * cost_fn, from (0, +inf) the first strict minimum
+ *   NM_OP_PR     :77-81    every distinct score ascending (precision_recall_curve of sklearn 1.7), p = tp / (tp + fp),
+ *                r = tp / P, F = 2 * (p * r) / (p + r); np.argmax's first maximum.  Where some point has tp = 0 its F is 0 / 0
+ *                and argmax returns the first NaN: the threshold is then the lowest score with tp = 0, objective NaN, status 1
+ *   NM_OP_F1MAX  the same scan with F = 0 where tp = 0 (ties to the lowest threshold): the best F1 a user means
+ *   NM_OP_EER    :99-103   nanargmin |(1 - tpr) - fpr| over roc_curve's points, the origin (value 1) first, first minimum
+ *   NM_OP_SPEC   the lowest threshold with tn >= ceil(a * N), i.e. specificity >= a (+inf if only the origin has it);
+ *                objective = the specificity reached
+ * rules_out [n_eval][n_rules][NM_METRICS_STRIDE] fp64 = {threshold, accuracy, recall, specificity, tp, fp, objective, status}:
+ * entry e scores set eval_of[e] (NULL: e) with the thresholds selected on set select_of[e] (NULL: e); the counts are the
+ * evaluation set's, objective the rule's own value on the selection set.  status 0; 1 (NM_OP_PR's NaN branch); -2 with the
+ * rest of the row NaN: a selection set that is empty, longer than NM_METRICS_MAX_N, of one class or holds a NaN score, an
+ * empty evaluation set, an index outside 0..n_sets-1.  An evaluation set without positives has recall NaN, without negatives
+ * specificity NaN.
+ * summary_out (may be NULL) [n_sets][NM_METRICS_STRIDE] fp64 = {roc_auc, average_precision, pauc, sens_at_spec, spec_at_sens,
+ * n_thresholds, n_pos, n_neg}: roc_auc with nm_posthoc_metrics' bits; average_precision = sum_j (tp_j - tp_(j-1)) / P *
+ * tp_j / (tp_j + fp_j) (sklearn's step sum); pauc = roc_auc_score(max_fpr=): the area up to max_fpr, McClish-standardised
+ * (roc_auc itself at max_fpr = 1); sens_at_spec = the highest tp_j / P with tn_j >= ceil(at_spec * N) (0 at the origin);
+ * spec_at_sens = the highest tn_j / N with tp_j >= ceil(at_sens * P); n_thresholds = K.  A set without a curve: NaN, with
+ * n_pos and n_neg where the set could be read.
+ * grid_out (G = 0: none; G <= NM_OP_MAX_GRID) [n_sets][G] fp64 = np.interp(np.linspace(0, 1, G), fpr, tpr) on the full curve
+ * (every distinct score, the origin first; at a vertical segment its upper end).
+ * One workgroup per set / per entry, no atomics, every sum in a fixed order: two runs give the same bytes and a row depends
+ * on its own sets alone.  workspace: device memory of at least the query's bytes (0 for arguments no launch accepts).
+ * Status, decided before the device is asked anything: NM_E_NULL: scores, labels, offsets, rules, workspace or rules_out
+ * missing, grid_out missing with G > 0; NM_E_METRICS: n_sets < 1, max_set outside 1..NM_METRICS_MAX_N, n_rules outside
+ * 1..NM_OP_MAX_RULES, n_eval < 1, G outside 0..NM_OP_MAX_GRID, at_spec / at_sens outside [0, 1], max_fpr outside (0, 1], an
+ * unknown kind, a grid with n outside 2..NM_OP_MAX_LINSPACE or a non-finite end, a non-finite cost, NM_OP_SPEC's a outside
+ * [0, 1], workspace_bytes below the query's answer. */
+#define NM_OP_ROC   0
+#define NM_OP_F1    1
+#define NM_OP_PR    2
+#define NM_OP_COST  3
+#define NM_OP_EER   4
+#define NM_OP_F1MAX 5
+#define NM_OP_SPEC  6
+#define NM_OP_MAX_RULES    16
+#define NM_OP_MAX_GRID     1024
+#define NM_OP_MAX_LINSPACE 65536
+typedef struct nm_op_rule {
+  int32_t kind;                  /* NM_OP_* */
+  int32_t n;                     /* NM_OP_F1 / NM_OP_COST: the grid's length */
+  double  a, b;                  /* the grid's ends; NM_OP_SPEC: a = the specificity asked for */
+  double  cost_fn, cost_fp;      /* NM_OP_COST */
+} nm_op_rule_t;
+size_t nm_operating_points_workspace(int n_sets, int n_rules);
+int nm_operating_points(const float* scores, const int32_t* labels, const int32_t* offsets, int n_sets, int max_set,
+                        const nm_op_rule_t* rules, int n_rules, const int32_t* select_of, int n_eval, const int32_t* eval_of,
+                        double at_spec, double at_sens, double max_fpr, void* workspace, size_t workspace_bytes,
+                        double* rules_out, double* summary_out, double* grid_out, int G, void* stream);
+
 /* One regression per column of a table: latent_pvalues(latent, target, type) of utils_vae.py:163-174 (statsmodels OLS /
  * Logit of target ~ const + latent_i, the p-values of both parameters) for every column of many tables at once, with
  * optional nuisance covariates.  Set s of the device array sets_dev is a matrix x[rows][pitch] (fp32, pitch >= D, read

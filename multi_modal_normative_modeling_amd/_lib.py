@@ -75,6 +75,17 @@ NM_REG_TOL = 1e-8
 # pass scores (tests put the heights around it)
 NM_NORM_MAX_D = 4096
 NM_NORM_ROWS_PER_WG = 32
+# nm_operating_points: the rule kinds, the most rules of a call, the widest ROC grid, the longest threshold grid of a rule
+NM_OP_ROC = 0
+NM_OP_F1 = 1
+NM_OP_PR = 2
+NM_OP_COST = 3
+NM_OP_EER = 4
+NM_OP_F1MAX = 5
+NM_OP_SPEC = 6
+NM_OP_MAX_RULES = 16
+NM_OP_MAX_GRID = 1024
+NM_OP_MAX_LINSPACE = 65536
 
 # status codes (nmhip.h; nm_status_string gives the text)
 NM_OK = 0
@@ -169,6 +180,12 @@ class NmNormSet(C.Structure):
                 ("row_off", C.c_int32), ("pad", C.c_int32)]
 
 
+class NmOpRule(C.Structure):
+    """nm_op_rule_t: one row of nm_operating_points' rule table (host memory)."""
+    _fields_ = [("kind", C.c_int32), ("n", C.c_int32), ("a", C.c_double), ("b", C.c_double),
+                ("cost_fn", C.c_double), ("cost_fp", C.c_double)]
+
+
 class NmError(RuntimeError):
     pass
 
@@ -244,6 +261,10 @@ def load():
     lib.nm_auc_bootstrap_workspace.restype = C.c_size_t
     lib.nm_auc_bootstrap_workspace.argtypes = [i32, i32, i32, i32]
     lib.nm_auc_bootstrap.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, C.c_uint64, vp, i32, vp, C.c_size_t, vp, vp, vp, vp]
+    lib.nm_operating_points_workspace.restype = C.c_size_t
+    lib.nm_operating_points_workspace.argtypes = [i32, i32]
+    lib.nm_operating_points.argtypes = [vp, vp, vp, i32, i32, C.POINTER(NmOpRule), i32, vp, i32, vp, C.c_double, C.c_double,
+                                        C.c_double, vp, C.c_size_t, vp, vp, vp, i32, vp]
     lib.nm_column_regress.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]
     lib.nm_cohort_moments.argtypes = [vp, i32, i32, i32, i32, vp, vp]
     lib.nm_normative_z.argtypes = [vp, i32, i32, i32, vp, i32, vp, C.c_double, vp, vp, vp]
@@ -283,6 +304,7 @@ EXPORTED_SYMBOLS = [
     "nm_column_regress", "nm_student_t_two_sided",
     "nm_plain_ok",
     "nm_cohort_moments", "nm_normative_z", "nm_cohort_cov", "nm_mahalanobis",
+    "nm_operating_points_workspace", "nm_operating_points",
 ]
 
 

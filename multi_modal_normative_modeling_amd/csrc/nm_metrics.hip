@@ -22,6 +22,9 @@
 //                         ROI tables -> z-scores against a reference cohort, the per-subject and per-ROI counts beyond a threshold;
 //                         latent tables -> a cohort's covariance factor and every row's Mahalanobis distance to it
 //                         (the sigma-normalised extra of SURVEY.md; nm_normative.inc, included at the end of this file)
+//   nm_operating_points   score sets -> the threshold of every rule of compute_classification_performance (roc, f1, pr, cost,
+//                         eer) and two more, scored on the same or on another set; PR-AUC, partial AUC, ROC on a grid
+//                         (nm_curve.inc, included at the end of this file)
 //
 // One workgroup per score set (a (fold, procedure) cell); sets are segments of one concatenated array.  The
 // whole set lives in LDS: order-preserving 64-bit keys (score, label) are bitonic-sorted descending, label
@@ -72,30 +75,25 @@ __device__ __forceinline__ void block_scan(int32_t* v, int npad, int32_t* part) 
   __syncthreads();
 }
 
-__global__ __launch_bounds__(MT) void posthoc_kernel(const float* __restrict__ scores, const int32_t* __restrict__ labels,
-                                                     const int32_t* __restrict__ offsets, const double* __restrict__ thr_in,
-                                                     double* __restrict__ out) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  uint64_t* key = reinterpret_cast<uint64_t*>(smem);            // [MAXN]
-  int32_t* cum = reinterpret_cast<int32_t*>(key + MAXN);        // [MAXN] label prefix sums (tps)
-  int32_t* bnd = cum + MAXN;                                    // [MAXN] boundary flags -> compacted indices
-  __shared__ int32_t part[MT];
-  __shared__ double redJ[MT];
-  __shared__ int32_t redI[MT];
-  __shared__ long long redA[MT];
-
-  const int s = blockIdx.x, t = threadIdx.x;
-  const int base = offsets[s], n = offsets[s + 1] - base;
-  double* o = out + (int64_t)s * NM_METRICS_STRIDE;
-  const double qnan = __longlong_as_double(0x7FF8000000000000ll);
-  if (n <= 0 || n > MAXN) {
-    if (t < NM_METRICS_STRIDE) o[t] = qnan;
-    return;
-  }
+// The sorted set both curve kernels work on (posthoc_kernel here, select_kernel in nm_curve.inc), all threads call, 1 <= n <= MAXN:
+// key[0..n) = (desc_key(score) << 32 | label != 0) ascending = scores descending, cum[i] = positives among the first i + 1,
+// bnd[j] = sorted position of the j-th distinct score's last member (sklearn's distinct_value_indices + the last position).
+// Returns K, the number of distinct scores; nan != 0 in a thread that loaded a NaN score.
+__device__ __forceinline__ int build_curve(const float* __restrict__ scores, const int32_t* __restrict__ labels, int base, int n,
+                                           uint64_t* key, int32_t* cum, int32_t* bnd, int32_t* part, int& nan) {
+  const int t = threadIdx.x;
+  nan = 0;
   int npad = 2;
   while (npad < n) npad <<= 1;
-  for (int i = t; i < npad; i += MT)
-    key[i] = (i < n) ? (((uint64_t)desc_key(scores[base + i]) << 32) | (uint64_t)(labels[base + i] != 0)) : ~0ull;
+  for (int i = t; i < npad; i += MT) {
+    uint64_t k = ~0ull;
+    if (i < n) {
+      const float v = scores[base + i];
+      nan |= (v != v);
+      k = ((uint64_t)desc_key(v) << 32) | (uint64_t)(labels[base + i] != 0);
+    }
+    key[i] = k;
+  }
   __syncthreads();
   // bitonic sort, ascending in key = descending in score
   for (int k = 2; k <= npad; k <<= 1) {
@@ -136,6 +134,31 @@ __global__ __launch_bounds__(MT) void posthoc_kernel(const float* __restrict__ s
     for (int q = 0; q < cnt; ++q) bnd[mypos[q]] = myidx[q];
     __syncthreads();
   }
+  return K;
+}
+
+__global__ __launch_bounds__(MT) void posthoc_kernel(const float* __restrict__ scores, const int32_t* __restrict__ labels,
+                                                     const int32_t* __restrict__ offsets, const double* __restrict__ thr_in,
+                                                     double* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint64_t* key = reinterpret_cast<uint64_t*>(smem);            // [MAXN]
+  int32_t* cum = reinterpret_cast<int32_t*>(key + MAXN);        // [MAXN] label prefix sums (tps)
+  int32_t* bnd = cum + MAXN;                                    // [MAXN] boundary flags -> compacted indices
+  __shared__ int32_t part[MT];
+  __shared__ double redJ[MT];
+  __shared__ int32_t redI[MT];
+  __shared__ long long redA[MT];
+
+  const int s = blockIdx.x, t = threadIdx.x;
+  const int base = offsets[s], n = offsets[s + 1] - base;
+  double* o = out + (int64_t)s * NM_METRICS_STRIDE;
+  const double qnan = __longlong_as_double(0x7FF8000000000000ll);
+  if (n <= 0 || n > MAXN) {
+    if (t < NM_METRICS_STRIDE) o[t] = qnan;
+    return;
+  }
+  int nan;
+  const int K = build_curve(scores, labels, base, n, key, cum, bnd, part, nan);
   const int P = cum[n - 1], Nn = n - P;
   if (P == 0 || Nn == 0) {                 // roc_curve is undefined with one class
     if (t < NM_METRICS_STRIDE) o[t] = qnan;
@@ -1596,3 +1619,4 @@ int nm_auc_bootstrap(const float* scores, const int32_t* labels, const int32_t* 
 }  // extern "C"
 
 #include "nm_normative.inc"
+#include "nm_curve.inc"

@@ -13,6 +13,9 @@ Benjamini-Hochberg q and the max-statistic label-permutation test; `mann_whitney
 comparison of sets that share subjects; `auc_compare` is the two-procedure convenience on top of it.
 `column_regress` = one OLS or Logit fit per column of many tables at once (target ~ const + column + covariates, the Wald
 p-values of both reported parameters); `latent_pvalues` is the reference's signature (utils_vae.py:163-174) on top of it.
+`operating_points` = every threshold rule of compute_classification_performance (roc, f1, pr, cost, eer; f1max and spec besides)
+selected on one score set and scored on another, with PR-AUC, partial AUC and the ROC on a grid per set;
+`classification_performance` is the reference's signature (group_analysis_1x1.py:105-157) on top of it.
 `cohort_moments` / `normative_z` = the normative z-map: per ROI column the reference cohort's mean and sd, every subject's
 z-score against them with the per-subject extreme-deviation counts and the per-ROI extreme-deviation map; `cohort_cov` /
 `mahalanobis` = the full-covariance counterpart in latent space (the sigma-normalised extra of SURVEY.md, never the parity output).
@@ -400,6 +403,114 @@ def auc_compare(scores_a, scores_c, positive, n_boot: int = 2000, ci: float = 0.
     _, prs = auc_bootstrap([a, c], [p, p], n_boot=n_boot, ci=ci, seed=seed, streams=[0, 0], pairs=[(0, 1)], device=device)
     row = prs[0].cpu().numpy()
     return {name: float(row[j]) for j, name in enumerate(AUC_COMPARE_COLUMNS)}
+
+
+OPERATING_POINT_COLUMNS = ("threshold", "accuracy", "recall", "specificity", "tp", "fp", "objective", "status")
+ROC_SUMMARY_COLUMNS = ("roc_auc", "average_precision", "pauc", "sens_at_spec", "spec_at_sens", "n_thresholds", "n_pos", "n_neg")
+OPERATING_RULES = {"roc": _lib.NM_OP_ROC, "f1": _lib.NM_OP_F1, "pr": _lib.NM_OP_PR, "cost": _lib.NM_OP_COST,
+                   "eer": _lib.NM_OP_EER, "f1max": _lib.NM_OP_F1MAX, "spec": _lib.NM_OP_SPEC}
+
+
+def _op_check(scores, positive, rules, select_of, evaluate, grid, cost_fn, cost_fp, spec, sens, max_fpr, roc_grid):
+    """nm_operating_points' argument checks on the host (no device is looked for): the sizes, the rule names, the threshold
+    grid, the costs, the three rates, the ROC grid and the two index lists as host values."""
+    if len(scores) == 0:
+        raise ValueError("no score sets")
+    if len(scores) != len(positive):
+        raise ValueError("scores and positive must have the same number of sets")
+    sizes = [int(torch.as_tensor(s).numel()) for s in scores]
+    if sizes != [int(torch.as_tensor(p).numel()) for p in positive]:
+        raise ValueError("every score set needs one label per score")
+    if max(sizes) > _lib.NM_METRICS_MAX_N:
+        raise ValueError(f"at most {_lib.NM_METRICS_MAX_N} scores per set, got {max(sizes)}")
+    rules = [rules] if isinstance(rules, str) else list(rules)
+    if not 1 <= len(rules) <= _lib.NM_OP_MAX_RULES:
+        raise ValueError(f"between 1 and {_lib.NM_OP_MAX_RULES} rules, got {len(rules)}")
+    for r in rules:
+        if r not in OPERATING_RULES:
+            raise ValueError(f"rule must be one of {sorted(OPERATING_RULES)}, got {r!r}")
+    if len(grid) != 3:
+        raise ValueError("grid is (lo, hi, n)")
+    lo, hi, n = float(grid[0]), float(grid[1]), int(grid[2])
+    if n != grid[2] or not 2 <= n <= _lib.NM_OP_MAX_LINSPACE:
+        raise ValueError(f"the threshold grid needs 2..{_lib.NM_OP_MAX_LINSPACE} values, got {grid[2]!r}")
+    if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError(f"the threshold grid's ends must be finite, got {grid[0]!r}, {grid[1]!r}")
+    cost_fn, cost_fp, spec, sens, max_fpr = float(cost_fn), float(cost_fp), float(spec), float(sens), float(max_fpr)
+    if not (np.isfinite(cost_fn) and np.isfinite(cost_fp)):
+        raise ValueError("cost_fn and cost_fp must be finite")
+    if not (0.0 <= spec <= 1.0 and 0.0 <= sens <= 1.0):
+        raise ValueError(f"spec and sens must lie in [0, 1], got {spec}, {sens}")
+    if not 0.0 < max_fpr <= 1.0:
+        raise ValueError(f"max_fpr must lie in (0, 1], got {max_fpr}")
+    roc_grid = int(roc_grid)
+    if not 0 <= roc_grid <= _lib.NM_OP_MAX_GRID:
+        raise ValueError(f"roc_grid must lie in 0..{_lib.NM_OP_MAX_GRID}, got {roc_grid}")
+    n_sets = len(sizes)
+    evaluate = list(range(n_sets)) if evaluate is None else [int(v) for v in np.asarray(evaluate).reshape(-1)]
+    select_of = list(evaluate) if select_of is None else [int(v) for v in np.asarray(select_of).reshape(-1)]
+    if not evaluate:
+        raise ValueError("no evaluation entry")
+    if len(select_of) != len(evaluate):
+        raise ValueError("select_of needs one set index per evaluation entry")
+    if any(not 0 <= v < n_sets for v in evaluate + select_of):
+        raise ValueError(f"set indices must lie in 0..{n_sets - 1}")
+    table = (_lib.NmOpRule * len(rules))()
+    for k, r in enumerate(rules):
+        table[k].kind, table[k].n, table[k].a, table[k].b = OPERATING_RULES[r], n, lo, hi
+        table[k].cost_fn, table[k].cost_fp = cost_fn, cost_fp
+        if r == "spec":
+            table[k].a = spec
+    return sizes, table, select_of, evaluate, spec, sens, max_fpr, roc_grid
+
+
+def operating_points(scores: Sequence[torch.Tensor], positive: Sequence[torch.Tensor], rules=("roc",), select_of=None,
+                     evaluate=None, grid=(0.0, 1.0, 100), cost_fn: float = 1.0, cost_fp: float = 1.0, spec: float = 0.9,
+                     sens: float = 0.9, max_fpr: float = 0.1, roc_grid: int = 0, device="cuda:0"):
+    """(points [n_eval, n_rules, 8], summary [n_sets, 8]) fp64 on the device, and [n_sets, roc_grid] when roc_grid > 0
+    (OPERATING_POINT_COLUMNS, ROC_SUMMARY_COLUMNS; include/nmhip.h has the definitions).  scores / positive as for
+    posthoc_metrics.  rules: names out of OPERATING_RULES -- "roc", "f1", "pr", "cost", "eer" are the five methods of
+    compute_classification_performance (group_analysis_1x1.py:105-157), "f1max" the best F1 over every distinct score, "spec"
+    the lowest threshold whose specificity is at least `spec`.  Entry e scores set evaluate[e] (default: every set in order)
+    with the thresholds selected on set select_of[e] (default: evaluate[e]): the reference's `optimal_threshold=` mode, a
+    threshold fitted on one set of subjects and applied to another.  grid = (lo, hi, n): the np.linspace of "f1" and "cost";
+    cost_fn / cost_fp: the two costs of "cost"; spec / sens: the rates of sens_at_spec / spec_at_sens; max_fpr: the partial
+    AUC's limit.  status 1 marks the "pr" rule where the reference's argmax lands on a NaN (the top score is a control),
+    -2 a row without a curve (NaN).  One call, two launches, for all sets; the same input gives the same bytes."""
+    sizes, table, select_of, evaluate, spec, sens, max_fpr, G = _op_check(scores, positive, rules, select_of, evaluate, grid,
+                                                                           cost_fn, cost_fp, spec, sens, max_fpr, roc_grid)
+    dev = require_gpu(device)
+    s, off, _ = _segments([torch.as_tensor(p) for p in scores], dev, torch.float32)
+    l, _, _ = _segments([torch.as_tensor(p) for p in positive], dev, torch.int32)
+    n_sets, n_rules, n_eval = len(sizes), len(table), len(evaluate)
+    sel = torch.tensor(select_of, dtype=torch.int32, device=dev)
+    ev = torch.tensor(evaluate, dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    need = int(lib.nm_operating_points_workspace(n_sets, n_rules))
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    points = torch.empty(n_eval, n_rules, _lib.NM_METRICS_STRIDE, dtype=torch.float64, device=dev)
+    summary = torch.empty(n_sets, _lib.NM_METRICS_STRIDE, dtype=torch.float64, device=dev)
+    curve = torch.empty(n_sets, G, dtype=torch.float64, device=dev) if G else None
+    _lib.check(lib.nm_operating_points(s.data_ptr(), l.data_ptr(), off.data_ptr(), n_sets, max(max(sizes), 1), table, n_rules,
+                                       sel.data_ptr(), n_eval, ev.data_ptr(), spec, sens, max_fpr, ws.data_ptr(), need,
+                                       points.data_ptr(), summary.data_ptr(), curve.data_ptr() if G else None, G,
+                                       _stream_ptr(dev)), "nm_operating_points")
+    return (points, summary, curve) if G else (points, summary)
+
+
+def classification_performance(scores, positive, method: str = "roc", optimal_threshold=None, device="cuda:0"):
+    """compute_classification_performance of group_analysis_1x1.py:105-157 on one score set: (roc_auc, accuracy, recall,
+    specificity, significance_ratio) as floats.  method: "roc", "f1", "pr", "cost" (costs 1 and 1, :138) or "eer" chooses the
+    threshold on the set itself; optimal_threshold, where given, is used instead (:128)."""
+    if method not in ("roc", "f1", "pr", "cost", "eer"):
+        raise ValueError("Unknown method for finding optimal threshold")
+    sc, po = torch.as_tensor(scores).reshape(-1), torch.as_tensor(positive).reshape(-1)
+    if optimal_threshold is not None:
+        row = posthoc_metrics([sc], [po], thresholds=[float(optimal_threshold)], device=device)[0].cpu().numpy()
+        return tuple(float(row[j]) for j in (0, 2, 3, 4, 5))
+    points, summary = operating_points([sc], [po], rules=(method,), device=device)
+    row, auc = points[0, 0].cpu().numpy(), float(summary[0, 0])
+    return auc, float(row[1]), float(row[2]), float(row[3]), auc / (1.0 - auc)
 
 
 def _reg_check(mats, targets, kind, covariates, include):

@@ -1410,6 +1410,56 @@ def _analysis_bootstrap(root: Path, args, hc: int, scores, positive, folds, ids)
     return tab[:per], cmp_tab
 
 
+def _analysis_operating(root: Path, args, scores, positive, folds, ids):
+    """`analysis --threshold-rule R [--threshold-from others] [--roc-grid G]`: every fold's set, the pooled rows of all folds
+    and, under `others`, per fold the pooled rows of all other folds without the subjects that fold k holds too (a cohort
+    recipe that puts every patient into every test fold would otherwise select on the subjects it scores), in ONE
+    metrics.operating_points call.  Writes group_analysis_operating_<R>.csv (per fold; under `self` also `pooled`),
+    group_analysis_curve.csv (the summary row per fold and pooled) and, with --roc-grid, group_analysis_roc_curve.csv (fpr,
+    mean and sd of the folds' TPR, one column per fold); prints the operating point per row."""
+    import pandas as pd
+    F = len(folds)
+    total = sum(int(s.numel()) for s in scores)
+    if total > _lib.NM_METRICS_MAX_N:
+        raise ValueError(f"the pooled rows of all folds are {total} subjects, a set holds at most {_lib.NM_METRICS_MAX_N}")
+    sets, labs = list(scores) + [torch.cat(list(scores))], list(positive) + [torch.cat(list(positive))]
+    evaluate, select_of = list(range(F + 1)), list(range(F + 1))
+    others = args.threshold_from == "others"
+    if others:
+        evaluate, select_of = list(range(F)), list(range(F + 1, 2 * F + 1))
+        for k in range(F):
+            rest = [j for j in range(F) if j != k]
+            keep = [torch.as_tensor(~np.isin(ids[j], ids[k])) for j in rest]
+            sets.append(torch.cat([scores[j][m] for j, m in zip(rest, keep)]) if rest else scores[k][:0])
+            labs.append(torch.cat([positive[j][m] for j, m in zip(rest, keep)]) if rest else positive[k][:0])
+    rule = args.threshold_rule
+    lo, hi, n = args.threshold_grid
+    res = metrics.operating_points(sets, labs, rules=(rule or "roc",), select_of=select_of, evaluate=evaluate,
+                                   grid=(lo, hi, int(n)), cost_fn=args.cost_fn, cost_fp=args.cost_fp, spec=args.spec,
+                                   roc_grid=args.roc_grid)
+    points, summary = res[0].cpu().numpy()[:, 0], res[1].cpu().numpy()[:F + 1]
+    names = [str(k) for k in folds] + ["pooled"]
+    tag = "" if args.score == "reconstruction" else f"{args.score}_"
+    if rule:
+        df = pd.DataFrame(points, columns=list(metrics.OPERATING_POINT_COLUMNS))
+        df.insert(0, "fold", names[:len(evaluate)])
+        df.to_csv(root / f"group_analysis_{tag}operating_{rule}.csv", index=False)
+        for name, r in zip(names, points):
+            print(f"[analysis] {args.procedure} {'fold ' if name != 'pooled' else ''}{name}: {rule} threshold {r[0]:.6g} (from "
+                  f"{args.threshold_from})  accuracy {r[1]:.4f}  sensitivity {r[2]:.4f}  specificity {r[3]:.4f}", flush=True)
+    dc = pd.DataFrame(summary, columns=list(metrics.ROC_SUMMARY_COLUMNS))
+    dc.insert(0, "fold", names)
+    dc.to_csv(root / f"group_analysis_{tag}curve.csv", index=False)
+    curve = None
+    if args.roc_grid:
+        curve = res[2].cpu().numpy()[:F]
+        dr = pd.DataFrame({"fpr": np.linspace(0.0, 1.0, args.roc_grid), "mean_tpr": curve.mean(axis=0), "sd_tpr": curve.std(axis=0)})
+        for k, row in zip(folds, curve):
+            dr[f"tpr_fold_{k}"] = row
+        dr.to_csv(root / f"group_analysis_{tag}roc_curve.csv", index=False)
+    return points, summary, curve
+
+
 def main_analysis(argv=None):
     """multimodal_kfold_cvae_group_analysis_1x1.py:160-235 on the files the `test` subcommand wrote: per fold the subjects'
     reconstruction errors averaged over the procedure's modalities (:205-209), healthy vs disease ROC-AUC, Youden-J
@@ -1417,8 +1467,10 @@ def main_analysis(argv=None):
     nm_posthoc_metrics) and the significance ratio auc / (1 - auc) (:231); prints the per-fold rows and mean +- std,
     writes <models-dir>/<resource>/<procedure>/group_analysis.csv.  Returns the [folds, 8] metric table.
     --bootstrap B adds the stratified-bootstrap interval of every fold's AUC and of the pooled rows (nm_auc_bootstrap),
-    --against Q the paired comparison with other procedures evaluated on the same folds; neither changes what is
-    written and returned without them."""
+    --against Q the paired comparison with other procedures evaluated on the same folds; --threshold-rule R the
+    operating point of any of the reference's five rules (and f1max, spec), selected on the fold itself or on the other
+    folds (nm_operating_points), with PR-AUC, partial AUC and, with --roc-grid, the mean ROC over folds; none of them
+    changes what is written and returned without them."""
     import pandas as pd
     ap = argparse.ArgumentParser(prog="python -m multi_modal_normative_modeling_amd.sweep analysis", description=main_analysis.__doc__)
     ap.add_argument("-R", "--dataset_resourse", dest="dataset_resourse", type=str, default="HCPimage")
@@ -1455,7 +1507,36 @@ def main_analysis(argv=None):
                          "call (fold k draws from stream k, the pooled rows from stream n_splits, on both sides): delta AUC, its "
                          "interval and the two-sided bootstrap p to group_analysis_compare_<P>_vs_<Q>.csv.  Q's files are read from "
                          "the same --models-dir and must hold the same folds with the same subjects and DIA in the same order")
+    ap.add_argument("--threshold-rule", dest="threshold_rule", choices=tuple(metrics.OPERATING_RULES), default=None,
+                    help="besides everything above: the operating point by this rule -- roc, f1, pr, cost, eer as "
+                         "compute_classification_performance's `method` has them, f1max (the best F1 over every distinct score), "
+                         "spec (the lowest threshold with specificity >= --spec) -- to group_analysis_operating_<rule>.csv, and every "
+                         "fold's PR-AUC, partial AUC, sensitivity at --spec to group_analysis_curve.csv")
+    ap.add_argument("--threshold-from", dest="threshold_from", choices=("self", "others"), default="self",
+                    help="self: the threshold is selected on the rows it is scored on (as the reference does; optimistic).  others: "
+                         "fold k is scored with the threshold selected on the pooled rows of all other folds, without the subjects "
+                         "whose participant_id fold k holds too")
+    ap.add_argument("--cost-fn", dest="cost_fn", type=float, default=1.0, help="--threshold-rule cost: the cost of a missed patient")
+    ap.add_argument("--cost-fp", dest="cost_fp", type=float, default=1.0, help="--threshold-rule cost: the cost of a false alarm")
+    ap.add_argument("--spec", type=float, default=0.9, help="the specificity of --threshold-rule spec and of sens_at_spec (default 0.9)")
+    ap.add_argument("--threshold-grid", dest="threshold_grid", nargs=3, type=float, default=[0.0, 1.0, 100], metavar=("LO", "HI", "N"),
+                    help="--threshold-rule f1 / cost: their thresholds are np.linspace(LO, HI, N) (default 0 1 100, the reference's)")
+    ap.add_argument("--roc-grid", dest="roc_grid", type=int, default=0, metavar="G",
+                    help="every fold's ROC at fpr = linspace(0, 1, G) (2..%d), their mean and sd over folds, to "
+                         "group_analysis_roc_curve.csv" % _lib.NM_OP_MAX_GRID)
     args = ap.parse_args(argv)
+    if args.threshold_from == "others" and not args.threshold_rule:
+        ap.error("--threshold-from others needs --threshold-rule")
+    if (args.threshold_rule or args.roc_grid) and args.roi:
+        ap.error("--threshold-rule / --roc-grid work on the per-subject score: they do not go with --roi")
+    if args.roc_grid and not 2 <= args.roc_grid <= _lib.NM_OP_MAX_GRID:
+        ap.error(f"--roc-grid must lie in 2..{_lib.NM_OP_MAX_GRID}")
+    if not 0.0 <= args.spec <= 1.0:
+        ap.error("--spec must lie in [0, 1]")
+    if not np.isfinite(args.threshold_grid).all():
+        ap.error("--threshold-grid: LO, HI and N must be finite")
+    if args.threshold_grid[2] != int(args.threshold_grid[2]) or not 2 <= args.threshold_grid[2] <= _lib.NM_OP_MAX_LINSPACE:
+        ap.error(f"--threshold-grid: N must be a whole number in 2..{_lib.NM_OP_MAX_LINSPACE}")
     if args.roi_significance and not args.roi:
         ap.error("--roi-significance needs --roi")
     if args.against and not args.bootstrap:
@@ -1485,6 +1566,8 @@ def main_analysis(argv=None):
           f"sensitivity {df['recall'].mean():.4f}  specificity {df['specificity'].mean():.4f}", flush=True)
     if args.bootstrap:
         _analysis_bootstrap(root, args, hc, scores, positive, folds, ids)
+    if args.threshold_rule or args.roc_grid:
+        _analysis_operating(root, args, scores, positive, folds, ids)
     return table
 
 
