@@ -745,6 +745,49 @@ int nm_cohort_cov(const nm_norm_set_t* sets_dev, int n_sets, int Z, int max_rows
 int nm_mahalanobis(const nm_norm_set_t* sets_dev, int n_sets, int Z, int max_rows, const double* mean, const double* chol,
                    const int32_t* status, int n_factors, const int32_t* ref_of, double* d2_out, double* d_out, void* stream);
 
+/* Normative centiles: where a subject falls in the empirical distribution of a reference cohort, ROI by ROI (no distributional
+ * assumption, and an exact leave-one-out form).  The table entry, the value of an element (v = x - sub or x), the groups and
+ * the refusal of an entry are those of the normative z-maps above; fp64 from the load on, contraction off, no atomics, every
+ * output element written on every call, two runs give the same bytes, a set's output does not depend on its place.
+ *
+ * nm_cohort_quantiles: per (set, column) over the n rows with group 0, sorted (a[0..n-1], -0 == +0).
+ *   q_out [n_sets][D][n_q] (NULL allowed with n_q == 0): the quantile at probs_host[q] in [0, 1] (host memory, read before the
+ *     launch), numpy's method="linear" operation by operation: h = (double)(n - 1) * p, j = floor(h), g = h - j; the neighbours
+ *     are a[j], a[j + 1], both a[n - 1] when h >= n - 1; d = b - a, r = a + d * g, and r = b - d * (1 - g) where g >= 0.5.
+ *   stats_out [n_sets][D][NM_METRICS_STRIDE] = {median, mad, q1, q3, iqr, n_ref, n_nonfinite, status}: np.median (the middle
+ *     value or (a[n/2-1] + a[n/2]) / 2), the same median of |v - median| (a second sort), the quantiles at 0.25 and 0.75 and
+ *     their difference.  A column is valid with n >= 1 and every reference value finite; otherwise quantiles and statistics
+ *     are NaN, status -2, n_ref and n_nonfinite still reported (0 and 0 for a refused set).
+ *   One workgroup per (set, column), the 64-bit keys of the column in dynamic LDS (8 bytes x max_rows rounded up to a power of two).
+ * nm_normative_centile: every row of every scored set s against the reference column of set ref = ref_of[s] (ref_of NULL: s).
+ *   ref_of[s] == -1: set s is a reference only -- its cols_out are NaN and it owns no rows.  Any other value outside
+ *   0..n_sets-1, or a refused reference set, is the scored set's own refusal of every element: NaN, status -2 rows.  A scored
+ *   set whose rows row_off..row_off+rows do not lie inside 0..total_rows is refused and has no rows written.
+ *   For a finite v in a valid column: left = #{a < v}, right = #{a <= v} (IEEE comparisons), k2 = left + right,
+ *   pct = (double)k2 * (50.0 / (double)n) = scipy.stats.percentileofscore(kind="mean").  loo = 1: a row of group 0 of a set
+ *   that is its own reference is ranked against the other n - 1 reference rows (right - 1, n - 1; n - 1 == 0: invalid).
+ *   workspace: nm_normative_centile_workspace(total_rows, D) bytes (0 for arguments no launch accepts), uint16 k2
+ *     [total_rows][D], 0xFFFF = invalid; written by the rank pass (one workgroup per scored set and column).
+ *   z (per set, may be NULL) [rows][z_pitch] fp32: pct rounded once, NaN where invalid; pad columns are not touched.
+ *   rows_out [total_rows][NM_METRICS_STRIDE] = {n_hi, n_lo, mean_pct, mean_abs_dev, max_pct, argmax_pct, n_valid, status}:
+ *     n_hi counts pct > 100 - tail, n_lo pct < tail (fp64); mean_pct = (double)sum k2 * (50 / n) / n_valid and mean_abs_dev =
+ *     (double)sum |k2 - n| * (50 / n) / n_valid from exact int64 sums, n the row's own divisor; argmax_pct the first column of
+ *     the largest pct; without a valid column the means and max_pct are NaN, argmax_pct = -1, status = -2.
+ *   cols_out [n_sets][D][NM_METRICS_STRIDE] = {n_hi_x, n_lo_x, n_hi_y, n_lo_y, n_x, n_y, mean_pct_x, mean_pct_y}: x = the rows of
+ *     group 1, y = of group 0, with a valid element; the k2 sums per group, multiplied once per group.  An invalid column: six
+ *     zero counts and NaN means; a refused set: NaN.
+ * Status, decided before the device is asked anything: NM_E_NULL a required pointer missing (probs_host and q_out with n_q > 0);
+ * NM_E_METRICS n_sets < 1, D < 1, max_rows outside 1..NM_METRICS_MAX_N, total_rows < 0, tail not finite or outside (0, 50), loo
+ * not 0 or 1, n_q outside 0..NM_CENT_MAX_Q, a probability outside [0, 1] or NaN, workspace_bytes below the query's answer, more
+ * than 2^31 - 1 workgroups. */
+#define NM_CENT_MAX_Q 32
+int    nm_cohort_quantiles(const nm_norm_set_t* sets_dev, int n_sets, int D, int max_rows, const double* probs_host, int n_q,
+                           double* q_out /* [n_sets][D][n_q] */, double* stats_out /* [n_sets][D][NM_METRICS_STRIDE] */, void* stream);
+size_t nm_normative_centile_workspace(int total_rows, int D);
+int    nm_normative_centile(const nm_norm_set_t* sets_dev, int n_sets, int D, int max_rows, int total_rows, const int32_t* ref_of,
+                            double tail, int loo, void* workspace, size_t workspace_bytes,
+                            double* rows_out /* [total_rows][8] */, double* cols_out /* [n_sets][D][8] */, void* stream);
+
 /* The expert-fusion operators the reference exposes as public methods, as forward-only launches (elementwise over
  * [M][n] fp32 device tensors; csrc/nm_fusion.hip):
  *   cVAE_multimodal.combine_latent(mus, variances, combine)                      cVAE.py:1144-1164   (also :2292-2307)

@@ -75,6 +75,8 @@ NM_REG_TOL = 1e-8
 # pass scores (tests put the heights around it)
 NM_NORM_MAX_D = 4096
 NM_NORM_ROWS_PER_WG = 32
+# nm_cohort_quantiles: the most probabilities of a call (they travel as a kernel argument)
+NM_CENT_MAX_Q = 32
 # nm_operating_points: the rule kinds, the most rules of a call, the widest ROC grid, the longest threshold grid of a rule
 NM_OP_ROC = 0
 NM_OP_F1 = 1
@@ -270,6 +272,10 @@ def load():
     lib.nm_normative_z.argtypes = [vp, i32, i32, i32, vp, i32, vp, C.c_double, vp, vp, vp]
     lib.nm_cohort_cov.argtypes = [vp, i32, i32, i32, C.c_double, vp, vp, vp, vp]
     lib.nm_mahalanobis.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp]
+    lib.nm_cohort_quantiles.argtypes = [vp, i32, i32, i32, C.POINTER(C.c_double), i32, vp, vp, vp]
+    lib.nm_normative_centile_workspace.restype = C.c_size_t
+    lib.nm_normative_centile_workspace.argtypes = [i32, i32]
+    lib.nm_normative_centile.argtypes = [vp, i32, i32, i32, i32, vp, C.c_double, i32, vp, C.c_size_t, vp, vp, vp]
     lib.nm_student_t_two_sided.restype = C.c_double
     lib.nm_student_t_two_sided.argtypes = [C.c_double, C.c_double]
     lib.nm_adam_step.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, i64, vp]
@@ -305,6 +311,7 @@ EXPORTED_SYMBOLS = [
     "nm_plain_ok",
     "nm_cohort_moments", "nm_normative_z", "nm_cohort_cov", "nm_mahalanobis",
     "nm_operating_points_workspace", "nm_operating_points",
+    "nm_cohort_quantiles", "nm_normative_centile_workspace", "nm_normative_centile",
 ]
 
 

@@ -25,6 +25,9 @@
 //   nm_operating_points   score sets -> the threshold of every rule of compute_classification_performance (roc, f1, pr, cost,
 //                         eer) and two more, scored on the same or on another set; PR-AUC, partial AUC, ROC on a grid
 //                         (nm_curve.inc, included at the end of this file)
+//   nm_cohort_quantiles, nm_normative_centile
+//                         ROI tables -> a reference cohort's quantiles, median and MAD per ROI; every subject's percentile rank
+//                         in it, the per-subject and per-ROI counts in the tails (nm_centile.inc, included at the end of this file)
 //
 // One workgroup per score set (a (fold, procedure) cell); sets are segments of one concatenated array.  The
 // whole set lives in LDS: order-preserving 64-bit keys (score, label) are bitonic-sorted descending, label
@@ -1620,3 +1623,4 @@ int nm_auc_bootstrap(const float* scores, const int32_t* labels, const int32_t* 
 
 #include "nm_normative.inc"
 #include "nm_curve.inc"
+#include "nm_centile.inc"

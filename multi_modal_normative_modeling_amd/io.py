@@ -84,12 +84,15 @@ def write_latent_csvs(out_dir, name: str, covariates: pd.DataFrame, mu: np.ndarr
     return paths
 
 
-def write_roi_table_csv(kind: str, out_dir, dataset_name: str, roi_columns: Sequence[str], table: np.ndarray) -> Path:
-    """{kind}_{name}.csv, kind one of roi_effect / roi_significance / roi_regress: one row per ROI -- its column name, then the
-    kind's eight metrics columns (ROI_EFFECT_COLUMNS / ROI_SIGNIFICANCE_COLUMNS / COLUMN_REGRESS_COLUMNS)."""
+def write_roi_table_csv(kind: str, out_dir, dataset_name: str, roi_columns: Sequence[str], table: np.ndarray,
+                        columns: Optional[Sequence[str]] = None) -> Path:
+    """{kind}_{name}.csv, kind one of roi_effect / roi_significance / roi_regress / centile_map: one row per ROI -- its column
+    name, then the kind's eight metrics columns (ROI_EFFECT_COLUMNS / ROI_SIGNIFICANCE_COLUMNS / COLUMN_REGRESS_COLUMNS /
+    CENTILE_COL_COLUMNS); any other kind names its `columns` itself (centile_curve: the quantiles it was asked for)."""
     from . import metrics
-    columns = {"roi_effect": metrics.ROI_EFFECT_COLUMNS, "roi_significance": metrics.ROI_SIGNIFICANCE_COLUMNS,
-               "roi_regress": metrics.COLUMN_REGRESS_COLUMNS}[kind]
+    if columns is None:
+        columns = {"roi_effect": metrics.ROI_EFFECT_COLUMNS, "roi_significance": metrics.ROI_SIGNIFICANCE_COLUMNS,
+                   "roi_regress": metrics.COLUMN_REGRESS_COLUMNS, "centile_map": metrics.CENTILE_COL_COLUMNS}[kind]
     table = np.asarray(table, dtype=np.float64)
     if table.shape != (len(roi_columns), len(columns)):
         raise ValueError(f"a [{len(roi_columns)}, {len(columns)}] table is needed, got {table.shape}")
@@ -144,6 +147,41 @@ def write_normative_csvs(out_dir, dataset_name: str, covariates: pd.DataFrame, r
     df = pd.DataFrame(cols, columns=list(NORMATIVE_COL_COLUMNS))
     df.insert(0, "ROI", list(roi_columns))
     df.to_csv(paths["map"], index=False)
+    return paths
+
+
+def quantile_column(p: float) -> str:
+    """The column name of the quantile at probability p in centile_curve_{name}.csv: q_0.05, q_0.5, ..."""
+    return f"q_{float(p):g}"
+
+
+def write_centile_csvs(out_dir, dataset_name: str, covariates: pd.DataFrame, roi_columns: Sequence[str], pct: np.ndarray,
+                       rows: np.ndarray, cols: np.ndarray, probs: Sequence[float], q: np.ndarray, stats: np.ndarray) -> Dict[str, Path]:
+    """The normative centiles of one set of subjects (metrics.normative_centile / cohort_quantiles), with the metadata
+    columns of write_test_csvs; the two per-ROI files go through write_roi_table_csv:
+      centile_pct_{name}.csv      participant_id, DIA, AGE, PTGENDER, then one percentile rank per ROI
+      centile_subject_{name}.csv  participant_id, DIA, AGE, PTGENDER, then metrics.CENTILE_ROW_COLUMNS
+      centile_map_{name}.csv      ROI, then metrics.CENTILE_COL_COLUMNS (the extreme-centile map)
+      centile_curve_{name}.csv    ROI, then the quantiles asked for (q_<p>) and metrics.COHORT_QUANTILE_COLUMNS of the
+                                  reference cohort: the normative range"""
+    from .metrics import CENTILE_ROW_COLUMNS, COHORT_QUANTILE_COLUMNS
+    pct, rows = np.asarray(pct), np.asarray(rows, dtype=np.float64)
+    q, stats = np.asarray(q, dtype=np.float64), np.asarray(stats, dtype=np.float64)
+    probs = [float(p) for p in probs]
+    n, D = len(covariates), len(roi_columns)
+    if pct.shape != (n, D) or rows.shape != (n, len(CENTILE_ROW_COLUMNS)) or q.shape != (D, len(probs)) or \
+            stats.shape != (D, len(COHORT_QUANTILE_COLUMNS)):
+        raise ValueError(f"pct [{n}, {D}], rows [{n}, 8], q [{D}, {len(probs)}] and stats [{D}, 8] are needed, got {pct.shape}, "
+                         f"{rows.shape}, {q.shape}, {stats.shape}")
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    cov = covariates[META_COLS].copy().reset_index(drop=True)
+    paths = {k: out_dir / f"centile_{k}_{dataset_name}.csv" for k in ("pct", "subject")}
+    pd.concat([cov, pd.DataFrame(pct, columns=list(roi_columns))], axis=1).to_csv(paths["pct"], index=False)
+    pd.concat([cov, pd.DataFrame(rows, columns=list(CENTILE_ROW_COLUMNS))], axis=1).to_csv(paths["subject"], index=False)
+    paths["map"] = write_roi_table_csv("centile_map", out_dir, dataset_name, roi_columns, cols)
+    paths["curve"] = write_roi_table_csv("centile_curve", out_dir, dataset_name, roi_columns, np.concatenate([q, stats], axis=1),
+                                         columns=[quantile_column(p) for p in probs] + list(COHORT_QUANTILE_COLUMNS))
     return paths
 
 

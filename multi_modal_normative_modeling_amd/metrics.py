@@ -19,6 +19,9 @@ selected on one score set and scored on another, with PR-AUC, partial AUC and th
 `cohort_moments` / `normative_z` = the normative z-map: per ROI column the reference cohort's mean and sd, every subject's
 z-score against them with the per-subject extreme-deviation counts and the per-ROI extreme-deviation map; `cohort_cov` /
 `mahalanobis` = the full-covariance counterpart in latent space (the sigma-normalised extra of SURVEY.md, never the parity output).
+`cohort_quantiles` / `normative_centile` = the normative centiles: per ROI column the reference cohort's quantiles, median and MAD,
+and every subject's percentile rank in that cohort (with an exact leave-one-out form), the per-subject counts in the tails and the
+per-ROI extreme-centile map; `robust_moments` turns median and MAD into a moments table for `normative_z`.
 """
 from __future__ import annotations
 
@@ -715,3 +718,159 @@ def mahalanobis(mats: Sequence[torch.Tensor], mean: torch.Tensor, chol: torch.Te
                                            status.data_ptr(), n, rf.data_ptr() if rf is not None else None, d2.data_ptr(),
                                            d.data_ptr(), _stream_ptr(dev)), "nm_mahalanobis")
     return list(torch.split(d[:total], [int(m.shape[0]) for m in mats]))
+
+
+COHORT_QUANTILE_COLUMNS = ("median", "mad", "q1", "q3", "iqr", "n_ref", "n_nonfinite", "status")
+CENTILE_ROW_COLUMNS = ("n_hi", "n_lo", "mean_pct", "mean_abs_dev", "max_pct", "argmax_pct", "n_valid", "status")
+CENTILE_COL_COLUMNS = ("n_hi_x", "n_lo_x", "n_hi_y", "n_lo_y", "n_x", "n_y", "mean_pct_x", "mean_pct_y")
+# nm_normative_centile's workspace above this many bytes: the scored sets run in consecutive groups that fit
+NORMATIVE_CENTILE_WORKSPACE_CAP = 1 << 30
+
+
+def _probs_check(probs):
+    """The probabilities of cohort_quantiles as a list of floats: at most NM_CENT_MAX_Q, each inside [0, 1]."""
+    p = [float(v) for v in np.asarray(probs, dtype=np.float64).reshape(-1)]
+    if len(p) > _lib.NM_CENT_MAX_Q:
+        raise ValueError(f"at most {_lib.NM_CENT_MAX_Q} probabilities, got {len(p)}")
+    if any(not 0.0 <= v <= 1.0 for v in p):
+        raise ValueError(f"every probability must lie in [0, 1], got {p}")
+    return p
+
+
+def _tail_check(tail) -> float:
+    tail = float(tail)
+    if not (np.isfinite(tail) and 0.0 < tail < 50.0):
+        raise ValueError(f"tail must lie inside (0, 50) percent, got {tail}")
+    return tail
+
+
+def _centile_ref_check(ref_of, n_sets):
+    """ref_of of normative_centile as a list of ints inside -1..n_sets-1 (None: every set is its own reference)."""
+    if ref_of is None:
+        return list(range(n_sets))
+    ref = [int(v) for v in np.asarray(ref_of).reshape(-1)]
+    if len(ref) != n_sets:
+        raise ValueError("ref_of must have one entry per set")
+    if any(not -1 <= v < n_sets for v in ref):
+        raise ValueError(f"ref_of entries must lie in -1..{n_sets - 1}")
+    return ref
+
+
+def cohort_quantiles(mats: Sequence[torch.Tensor], groups: Sequence, probs=(0.05, 0.25, 0.5, 0.75, 0.95),
+                     sub: Optional[Sequence[torch.Tensor]] = None, device=None):
+    """(q [n_sets, D, n_q], stats [n_sets, D, 8]) fp64 on the device, per (set, column) over the rows whose group word is 0 (the
+    reference cohort): the quantiles at `probs` (np.quantile, method="linear": the normative range, the centile curve) and
+    median, mad, q1, q3, iqr, n_ref, n_nonfinite, status (COHORT_QUANTILE_COLUMNS; include/nmhip.h has the definitions; mad is
+    scipy's median_abs_deviation with scale 1).  mats / groups / sub as for cohort_moments.  status -2 (everything else NaN):
+    no reference row, or a non-finite reference value.  One launch for all sets."""
+    p = _probs_check(probs)
+    D = _norm_check(mats, groups, sub)
+    dev = _table_device(mats, device)
+    grp = _row_words(groups, dev, torch.int32)
+    sets = _to_dev(_norm_table(mats, grp, sub), dev)
+    q = torch.empty(len(mats), D, len(p), dtype=torch.float64, device=dev)
+    stats = torch.empty(len(mats), D, _lib.NM_METRICS_STRIDE, dtype=torch.float64, device=dev)
+    _lib.check(_lib.load().nm_cohort_quantiles(sets.data_ptr(), len(mats), D, _max_rows(mats), (C.c_double * max(len(p), 1))(*p),
+                                                len(p), q.data_ptr() if p else None, stats.data_ptr(), _stream_ptr(dev)),
+               "nm_cohort_quantiles")
+    return q, stats
+
+
+def _centile_groups(lib, rows, scored, D):
+    """The scored sets in consecutive groups whose workspace stays below NORMATIVE_CENTILE_WORKSPACE_CAP (a set alone always runs)."""
+    out, cur, n = [], [], 0
+    for k in scored:
+        if cur and lib.nm_normative_centile_workspace(n + rows[k], D) > NORMATIVE_CENTILE_WORKSPACE_CAP:
+            out.append(cur)
+            cur, n = [], 0
+        cur.append(k)
+        n += rows[k]
+    if cur:
+        out.append(cur)
+    return out
+
+
+def normative_centile(mats: Sequence[torch.Tensor], groups: Sequence, ref_of=None, tail: float = 2.5, loo: bool = False,
+                      sub: Optional[Sequence[torch.Tensor]] = None, return_table: bool = True, device=None):
+    """Every row of every scored set ranked, column by column, among the reference rows (group 0) of set ref_of[k] (default k):
+    (pct, rows, cols).  ref_of[k] = -1: set k is a reference only (its pct entry is None, it owns no rows, its cols are NaN).
+    pct: a list of [n_k, D] fp32 device tensors (None without return_table), the percentile rank of the value in the reference
+    column (scipy's percentileofscore, kind="mean"), NaN where the value is not finite or the column has no valid reference;
+    rows [sum n_k over the scored sets, 8] fp64 = n_hi, n_lo, mean_pct, mean_abs_dev, max_pct, argmax_pct, n_valid, status per
+    subject (CENTILE_ROW_COLUMNS; n_hi counts pct > 100 - tail, n_lo pct < tail); cols [n_sets, D, 8] fp64 = n_hi_x, n_lo_x,
+    n_hi_y, n_lo_y, n_x, n_y, mean_pct_x, mean_pct_y per column (CENTILE_COL_COLUMNS; x = group 1, y = group 0: the
+    extreme-centile map).  loo: a reference row of a set that is its own reference is ranked among the other reference rows.
+
+    The workspace comes from nm_normative_centile_workspace; above NORMATIVE_CENTILE_WORKSPACE_CAP the scored sets run in
+    consecutive groups, each with the reference sets it names (as references only); the result is byte-identical."""
+    tail = _tail_check(tail)
+    if loo not in (False, True, 0, 1):
+        raise ValueError(f"loo must be a bool, got {loo!r}")
+    D = _norm_check(mats, groups, sub)
+    n_sets = len(mats)
+    ref = _centile_ref_check(ref_of, n_sets)
+    dev = _table_device(mats, device)
+    lib = _lib.load()
+    grp = _row_words(groups, dev, torch.int32)
+    heights = [int(m.shape[0]) for m in mats]
+    scored = [k for k in range(n_sets) if ref[k] != -1]
+    zs = [torch.empty(heights[k], D, dtype=torch.float32, device=dev) if ref[k] != -1 else None for k in range(n_sets)] \
+        if return_table else None
+    full = _norm_table(mats, grp, sub, zs)
+    starts, total = {}, 0
+    for k in scored:
+        starts[k] = total
+        total += heights[k]
+    rows = torch.empty(max(total, 1), _lib.NM_METRICS_STRIDE, dtype=torch.float64, device=dev)
+    plan = _centile_groups(lib, heights, scored, D)
+    need = max([int(lib.nm_normative_centile_workspace(sum(heights[k] for k in g), D)) for g in plan] or
+               [int(lib.nm_normative_centile_workspace(0, D))])
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    max_rows = _max_rows(mats)
+    if len(plan) <= 1:                                            # one call: the table as it stands, the kernel writes every column row
+        for k in range(n_sets):
+            full[k].row_off = starts.get(k, 0)
+        rf = torch.tensor(ref, dtype=torch.int32, device=dev) if ref_of is not None else None
+        sets = _to_dev(full, dev)
+        cols = torch.empty(n_sets, D, _lib.NM_METRICS_STRIDE, dtype=torch.float64, device=dev)
+        _lib.check(lib.nm_normative_centile(sets.data_ptr(), n_sets, D, max_rows, total, rf.data_ptr() if rf is not None else None,
+                                            tail, int(bool(loo)), ws.data_ptr(), need, rows.data_ptr(), cols.data_ptr(),
+                                            _stream_ptr(dev)), "nm_normative_centile")
+        return zs, rows[:total], cols
+    cols = torch.full((n_sets, D, _lib.NM_METRICS_STRIDE), float("nan"), dtype=torch.float64, device=dev)
+    for g in plan:
+        members = list(g) + sorted({ref[k] for k in g} - set(g))          # the group's scored sets, then references only
+        local = {k: i for i, k in enumerate(members)}
+        table = (_lib.NmNormSet * len(members))()
+        g_rows = 0
+        for i, k in enumerate(members):
+            C.memmove(C.byref(table, i * C.sizeof(_lib.NmNormSet)), C.byref(full, k * C.sizeof(_lib.NmNormSet)),
+                      C.sizeof(_lib.NmNormSet))
+            table[i].row_off = g_rows if i < len(g) else 0
+            g_rows += heights[k] if i < len(g) else 0
+        rf = torch.tensor([local[ref[k]] for k in g] + [-1] * (len(members) - len(g)), dtype=torch.int32, device=dev)
+        sets = _to_dev(table, dev)
+        cg = torch.empty(len(members), D, _lib.NM_METRICS_STRIDE, dtype=torch.float64, device=dev)
+        _lib.check(lib.nm_normative_centile(sets.data_ptr(), len(members), D, max_rows, g_rows, rf.data_ptr(), tail, int(bool(loo)),
+                                            ws.data_ptr(), int(ws.numel()), rows[starts[g[0]]:].data_ptr(), cg.data_ptr(),
+                                            _stream_ptr(dev)), "nm_normative_centile")
+        cols[torch.tensor(g, device=dev)] = cg[:len(g)]
+    return zs, rows[:total], cols
+
+
+def robust_moments(stats: torch.Tensor, scale: float = 1.4826) -> torch.Tensor:
+    """A cohort_quantiles `stats` table as a moments table for normative_z (COHORT_MOMENTS_COLUMNS): mean := median, sd :=
+    scale x mad (1.4826 makes the MAD of a normal sample estimate its sd), var := sd^2, n_ref, min and max NaN, n_nonfinite,
+    status -2 where the statistics' status is -2 or mad == 0.  A torch expression where `stats` lies; no kernel."""
+    scale = float(scale)
+    if not (np.isfinite(scale) and scale > 0.0):
+        raise ValueError(f"scale must be finite and > 0, got {scale}")
+    if not isinstance(stats, torch.Tensor) or stats.dtype != torch.float64 or stats.dim() != 3 or \
+            int(stats.shape[2]) != _lib.NM_METRICS_STRIDE:
+        raise ValueError(f"stats must be a float64 [n, D, {_lib.NM_METRICS_STRIDE}] tensor as cohort_quantiles returns it")
+    med, mad = stats[..., 0], stats[..., 1]
+    sd = scale * mad
+    nan = torch.full_like(med, float("nan"))
+    bad = (stats[..., 7] == -2.0) | (mad == 0.0)
+    status = torch.where(bad, torch.full_like(med, -2.0), torch.zeros_like(med))
+    return torch.stack([med, sd, sd * sd, stats[..., 5], nan, nan, stats[..., 6], status], dim=-1)

@@ -546,12 +546,17 @@ def parse_regress_spec(spec: str):
     return target, kind
 
 
-def _normative_sets(mats: Sequence[torch.Tensor], groups: Sequence[np.ndarray], subs, thr: float, device) -> List[dict]:
+def _normative_sets(mats: Sequence[torch.Tensor], groups: Sequence[np.ndarray], subs, thr: float, device,
+                    robust: bool = False) -> List[dict]:
     """metrics.cohort_moments and metrics.normative_z for tables of any widths (_per_width): one moments launch and one z
-    launch per distinct width, every table scored against its own group-0 rows.  Returns per table {"z" [n, D] fp32, "rows"
+    launch per distinct width, every table scored against its own group-0 rows.  robust: median and 1.4826 x MAD stand in for
+    mean and sd (metrics.cohort_quantiles and metrics.robust_moments).  Returns per table {"z" [n, D] fp32, "rows"
     [n, 8], "cols" [D, 8], "moments" [D, 8]} on the device, in the order given."""
     def one_width(ms, gs, sb):
-        mom = metrics.cohort_moments(ms, gs, sub=sb, ddof=1, device=device)
+        if robust:
+            mom = metrics.robust_moments(metrics.cohort_quantiles(ms, gs, (), sub=sb, device=device)[1])
+        else:
+            mom = metrics.cohort_moments(ms, gs, sub=sb, ddof=1, device=device)
         z, rows, cols = metrics.normative_z(ms, gs, mom, thr=thr, sub=sb, device=device)
         rows = torch.split(rows, [int(m.shape[0]) for m in ms])
         return [{"z": z[a], "rows": rows[a], "cols": cols[a], "moments": mom[a]} for a in range(len(ms))]
@@ -559,6 +564,19 @@ def _normative_sets(mats: Sequence[torch.Tensor], groups: Sequence[np.ndarray], 
 
 
 NORMATIVE_KINDS = ("squared", "signed")
+CENTILE_QUANTILES = (0.05, 0.25, 0.5, 0.75, 0.95)
+
+
+def _centile_sets(mats: Sequence[torch.Tensor], groups: Sequence[np.ndarray], subs, tail: float, probs, loo: bool, device) -> List[dict]:
+    """metrics.cohort_quantiles and metrics.normative_centile for tables of any widths (_per_width): one launch of each per
+    distinct width, every table ranked among its own group-0 rows.  Returns per table {"pct" [n, D] fp32, "rows" [n, 8],
+    "cols" [D, 8], "q" [D, n_q], "stats" [D, 8]} on the device, in the order given."""
+    def one_width(ms, gs, sb):
+        q, st = metrics.cohort_quantiles(ms, gs, probs, sub=sb, device=device)
+        pct, rows, cols = metrics.normative_centile(ms, gs, tail=tail, loo=loo, sub=sb, device=device)
+        rows = torch.split(rows, [int(m.shape[0]) for m in ms])
+        return [{"pct": pct[a], "rows": rows[a], "cols": cols[a], "q": q[a], "stats": st[a]} for a in range(len(ms))]
+    return _per_width(one_width, mats, groups, subs)
 
 
 def _roi_columns(roi_columns, m: str, d: int):
@@ -571,7 +589,9 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
                disease_label=None, roi_significance: bool = False, roi_perm: int = 0,
                roi_seed: int = 0, roi_regress: Optional[tuple] = None,
                roi_adjust: Sequence[str] = (), normative: Optional[str] = None,
-               z_thr: float = 1.96) -> List[Dict[str, np.ndarray]]:
+               z_thr: float = 1.96, centile: Optional[str] = None, tail: float = 2.5,
+               quantiles: Sequence[float] = CENTILE_QUANTILES, centile_loo: bool = False,
+               robust: bool = False) -> List[Dict[str, np.ndarray]]:
     """test_fold for ALL folds of a procedure as one launch: jobs[i] is the trained model of fold i, folds[i] its
     (train_rows, test_rows); one evaluation job per fold, each on its own test tables (seed, scaler and covariates per fold
     exactly as test_fold), all in ONE JobSet -- a fold's ~N / K test rows are a single workgroup, K of them in a row leave
@@ -612,7 +632,30 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
     (metrics.NORMATIVE_ROW_COLUMNS), "cols" [D, 8] (metrics.NORMATIVE_COL_COLUMNS), "moments" [D, 8]
     (metrics.COHORT_MOMENTS_COLUMNS), "x" and "sub": the fp32 tables that were scored (sub None for "squared")}} and
     "normative_pooled" (the same dict in every fold's result, its rows in fold order); with out_dirs, normative_z_<m>.csv,
-    normative_subject_<m>.csv and normative_map_<m>.csv."""
+    normative_subject_<m>.csv and normative_map_<m>.csv.  robust (needs normative): the z-map is scored against the controls'
+    median and 1.4826 x MAD (metrics.robust_moments of metrics.cohort_quantiles) instead of their mean and sd; only the
+    normative results and files change.
+
+    centile = "squared" or "signed" (needs roi_effect): the normative centiles of the same tables -- where every test subject
+    falls in the empirical distribution of that fold's healthy test subjects, ROI by ROI, with no distributional assumption
+    (a squared error is right-skewed: its z beyond 1.96 is not "outside the central 95 % of the controls", its percentile rank
+    beyond 100 - tail is).  Per subject the ROIs above 100 - tail and below tail percent, per ROI the shares of patients and
+    controls there, and per ROI the controls' quantiles at `quantiles`, median, MAD and quartiles (the normative range); the same
+    on the pooled rows.  centile_loo: a control is ranked among the OTHER controls (exact leave-one-out), so it is no
+    longer scored against a distribution it is part of.  One metrics.cohort_quantiles and one metrics.normative_centile call
+    per table width.  Each fold's dict gains "centile": {modality: {"pct" [n, D] fp32, "rows" [n, 8]
+    (metrics.CENTILE_ROW_COLUMNS), "cols" [D, 8] (metrics.CENTILE_COL_COLUMNS), "q" [D, n_q], "stats" [D, 8]
+    (metrics.COHORT_QUANTILE_COLUMNS), "x" and "sub"}} and "centile_pooled"; with out_dirs, centile_pct_<m>.csv,
+    centile_subject_<m>.csv, centile_map_<m>.csv and centile_curve_<m>.csv."""
+    if robust and normative is None:
+        raise ValueError("robust needs normative (it replaces the moments the z-map is scored against)")
+    if centile is not None:
+        if centile not in NORMATIVE_KINDS:
+            raise ValueError(f"centile must be None or one of {NORMATIVE_KINDS}, got {centile!r}")
+        if not roi_effect:
+            raise ValueError("centile needs roi_effect=True (the evaluation jobs export the ROI-wise squared errors for it)")
+        tail = metrics._tail_check(tail)
+        quantiles = metrics._probs_check(quantiles)
     if normative is not None:
         if normative not in NORMATIVE_KINDS:
             raise ValueError(f"normative must be None or one of {NORMATIVE_KINDS}, got {normative!r}")
@@ -683,7 +726,13 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
             n_mats, n_subs = mats, None
             if normative == "signed":
                 n_mats, n_subs = tables(lambda ev, i: ev.tables[i].x_f32[:, :ev.tables[i].D]), tables(lambda ev, i: ev.out_loc[i])
-            norm = _normative_sets(n_mats, grp, n_subs, z_thr, device)
+            norm = _normative_sets(n_mats, grp, n_subs, z_thr, device, robust=robust)
+        if centile is not None:
+            # likewise: one quantile and one centile call per width
+            c_mats, c_subs = mats, None
+            if centile == "signed":
+                c_mats, c_subs = tables(lambda ev, i: ev.tables[i].x_f32[:, :ev.tables[i].D]), tables(lambda ev, i: ev.out_loc[i])
+            cent = _centile_sets(c_mats, grp, c_subs, tail, quantiles, bool(centile_loo), device)
     torch.cuda.synchronize(device)
     out = [_fold_results(ev, xs, cohort, te, modalities, d, roi_columns) for (ev, xs), (_, te), d in zip(evs, folds, dirs)]
     for key, tabs, write in stats:
@@ -709,6 +758,20 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
                 for m, t in res["normative"].items():
                     io.write_normative_csvs(Path(d) / m, m, _meta_frame(cohort, tests[f]), _roi_columns(roi_columns, m, t["z"].shape[1]),
                                             t["z"], t["rows"], t["cols"])
+    if centile is not None:
+        def chost(j):
+            res = {k: v.cpu().numpy() for k, v in cent[j].items()}
+            res["x"] = c_mats[j].cpu().numpy()
+            res["sub"] = None if c_subs is None else c_subs[j].cpu().numpy()
+            return res
+        cent_pooled = {m: chost(n_fold + i) for i, m in enumerate(modalities)}
+        for f, (res, d) in enumerate(zip(out, dirs)):
+            res["centile"] = {m: chost(f * nm_ + i) for i, m in enumerate(modalities)}
+            res["centile_pooled"] = cent_pooled
+            if d is not None:
+                for m, t in res["centile"].items():
+                    io.write_centile_csvs(Path(d) / m, m, _meta_frame(cohort, tests[f]), _roi_columns(roi_columns, m, t["pct"].shape[1]),
+                                          t["pct"], t["rows"], t["cols"], quantiles, t["q"], t["stats"])
     return out
 
 
@@ -1112,8 +1175,30 @@ def main_test(argv=None):
                     help="with --latent: also every test subject's Mahalanobis distance to the fold's train cohort in latent space: "
                          "per fold and all folds latent_mahalanobis_<P>.csv")
     ap.add_argument("--ridge", type=float, default=0.0, help="added to the diagonal of the covariance of --mahalanobis (default 0)")
+    ap.add_argument("--centile", choices=NORMATIVE_KINDS, default=None,
+                    help="with --roi-effect: the normative centiles -- every ROI's percentile rank among the fold's healthy test "
+                         "subjects, on its squared error (squared) or its signed residual (signed): per fold and pooled "
+                         "centile_pct_<m>.csv, centile_subject_<m>.csv (per subject the ROIs in the tails), centile_map_<m>.csv (per "
+                         "ROI the patients and controls there) and centile_curve_<m>.csv (per ROI the controls' quantiles, median, MAD)")
+    ap.add_argument("--tail", type=float, default=2.5, help="the tail of --centile in percent: below it and above 100 - it (default 2.5)")
+    ap.add_argument("--quantiles", nargs="+", type=float, default=list(CENTILE_QUANTILES), metavar="P",
+                    help="the probabilities of centile_curve_<m>.csv (default 0.05 0.25 0.5 0.75 0.95)")
+    ap.add_argument("--centile-loo", dest="centile_loo", action="store_true",
+                    help="with --centile: a healthy subject is ranked among the OTHER healthy subjects (exact leave-one-out)")
+    ap.add_argument("--robust", action="store_true",
+                    help="with --normative: z-scores against the controls' median and 1.4826 x MAD instead of mean and sd")
     _driver_common(ap)
     args = ap.parse_args(argv)
+    if args.centile and not args.roi_effect:
+        ap.error("--centile needs --roi-effect")
+    if args.centile and not (np.isfinite(args.tail) and 0 < args.tail < 50):
+        ap.error("--tail must lie inside (0, 50)")
+    if args.centile and (len(args.quantiles) > _lib.NM_CENT_MAX_Q or not all(0 <= p <= 1 for p in args.quantiles)):
+        ap.error(f"--quantiles: at most {_lib.NM_CENT_MAX_Q} probabilities inside [0, 1]")
+    if args.centile_loo and not args.centile:
+        ap.error("--centile-loo needs --centile")
+    if args.robust and not args.normative:
+        ap.error("--robust needs --normative")
     if args.normative and not args.roi_effect:
         ap.error("--normative needs --roi-effect")
     if args.normative and not (np.isfinite(args.z_thr) and args.z_thr > 0):
@@ -1168,8 +1253,10 @@ def main_test(argv=None):
     results = test_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs,
                          roi_effect=args.roi_effect, disease_label=args.disease_label, roi_significance=args.roi_significance,
                          roi_perm=args.roi_perm, roi_seed=args.roi_seed, roi_regress=roi_regress,
-                         roi_adjust=args.roi_adjust, **({"normative": args.normative, "z_thr": args.z_thr} if args.normative else {})
-                         ) if my else []
+                         roi_adjust=args.roi_adjust, **({"normative": args.normative, "z_thr": args.z_thr} if args.normative else {}),
+                         **({"robust": True} if args.robust else {}),
+                         **({"centile": args.centile, "tail": args.tail, "quantiles": args.quantiles, "centile_loo": args.centile_loo}
+                            if args.centile else {})) if my else []
     for err in results:
         for m in mods:
             errors[m].append(err[m])
@@ -1204,6 +1291,16 @@ def main_test(argv=None):
             ext = t["rows"][:, 0] + t["rows"][:, 1]
             print(f"[test] {args.procedure} {m}: pooled normative z-map ({args.normative}), ROIs beyond +-{args.z_thr:g} per subject: "
                   f"patients {float(ext[g == 1].mean()) if (g == 1).any() else float('nan'):.2f}, controls "
+                  f"{float(ext[g == 0].mean()) if (g == 0).any() else float('nan'):.2f}", flush=True)
+        if args.centile and results:                 # the pooled centiles: this rank's folds' test subjects among their controls
+            t = results[0]["centile_pooled"][m]
+            te_all = np.concatenate([te for _, te in fold_rows])
+            io.write_centile_csvs(out_root / m, m, _meta_frame(cohort, te_all), _roi_columns(None, m, t["pct"].shape[1]), t["pct"],
+                                  t["rows"], t["cols"], args.quantiles, t["q"], t["stats"])
+            g = roi_groups(cohort.dia[te_all], args.disease_label)
+            ext = t["rows"][:, 0] + t["rows"][:, 1]
+            print(f"[test] {args.procedure} {m}: pooled normative centiles ({args.centile}), ROIs in the {args.tail:g} % tails per "
+                  f"subject: patients {float(ext[g == 1].mean()) if (g == 1).any() else float('nan'):.2f}, controls "
                   f"{float(ext[g == 0].mean()) if (g == 0).any() else float('nan'):.2f}", flush=True)
     if args.latent and my:
         # the folds' train cohorts and test subjects in one latent launch each, one statistics and one score launch
@@ -1322,7 +1419,11 @@ ANALYSIS_SCORES = {
     "mahalanobis": ("latent_mahalanobis_{p}.csv", lambda d: d["d"], " with --latent --mahalanobis"),
     "extreme": ("normative_subject_{m}.csv", lambda d: d["n_hi"] + d["n_lo"], " with --roi-effect --normative"),
     "zmean": ("normative_subject_{m}.csv", lambda d: d["mean_abs_z"], " with --roi-effect --normative"),
+    # (--centile-score tails / depth: a flag of its own, the --score choice list is pinned)
+    "centile_tails": ("centile_subject_{m}.csv", lambda d: d["n_hi"] + d["n_lo"], " with --roi-effect --centile"),
+    "centile_depth": ("centile_subject_{m}.csv", lambda d: d["mean_abs_dev"], " with --roi-effect --centile"),
 }
+CENTILE_SCORES = ("tails", "depth")
 
 
 def _analysis_scores(root: Path, mods: Sequence[str], procedure: str, score: str, n_splits: int, hc: int):
@@ -1486,6 +1587,10 @@ def main_analysis(argv=None):
                          "n_lo of normative_subject_<m>.csv (`test --roi-effect --normative`), averaged over the modalities; zmean: "
                          "its mean_abs_z likewise; mahalanobis: d of latent_mahalanobis_<P>.csv (`test --latent --mahalanobis`); "
                          "these write group_analysis_<score>.csv")
+    ap.add_argument("--centile-score", dest="centile_score", choices=CENTILE_SCORES, default=None,
+                    help="instead of --score: the per-subject score from centile_subject_<m>.csv (`test --roi-effect --centile`), "
+                         "averaged over the modalities -- tails: n_hi + n_lo, the ROIs in the tails; depth: mean_abs_dev, the mean "
+                         "distance of the percentile ranks from 50; writes group_analysis_centile_<kind>.csv")
     ap.add_argument("--roi", action="store_true",
                     help="instead: which ROIs separate patients from controls -- per fold and modality every ROI's Cliff's delta and "
                          "ROC-AUC on reconstruction_error_roi_<m>.csv, their mean and std over folds to group_analysis_roi_<m>.csv")
@@ -1525,6 +1630,12 @@ def main_analysis(argv=None):
                     help="every fold's ROC at fpr = linspace(0, 1, G) (2..%d), their mean and sd over folds, to "
                          "group_analysis_roc_curve.csv" % _lib.NM_OP_MAX_GRID)
     args = ap.parse_args(argv)
+    if args.centile_score:
+        if args.score != "reconstruction":
+            ap.error("--centile-score is a score of its own: it does not go with --score")
+        if args.roi:
+            ap.error("--centile-score is a per-subject score: it does not go with --roi")
+        args.score = f"centile_{args.centile_score}"
     if args.threshold_from == "others" and not args.threshold_rule:
         ap.error("--threshold-from others needs --threshold-rule")
     if (args.threshold_rule or args.roc_grid) and args.roi:
