@@ -14,7 +14,8 @@ import os
 import time
 from dataclasses import dataclass
 from pathlib import Path
-from typing import Dict, List, Optional, Sequence
+from types import SimpleNamespace
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -546,41 +547,186 @@ def parse_regress_spec(spec: str):
     return target, kind
 
 
-def _normative_sets(mats: Sequence[torch.Tensor], groups: Sequence[np.ndarray], subs, thr: float, device,
-                    robust: bool = False) -> List[dict]:
-    """metrics.cohort_moments and metrics.normative_z for tables of any widths (_per_width): one moments launch and one z
-    launch per distinct width, every table scored against its own group-0 rows.  robust: median and 1.4826 x MAD stand in for
-    mean and sd (metrics.cohort_quantiles and metrics.robust_moments).  Returns per table {"z" [n, D] fp32, "rows"
-    [n, 8], "cols" [D, 8], "moments" [D, 8]} on the device, in the order given."""
-    def one_width(ms, gs, sb):
-        if robust:
-            mom = metrics.robust_moments(metrics.cohort_quantiles(ms, gs, (), sub=sb, device=device)[1])
-        else:
-            mom = metrics.cohort_moments(ms, gs, sub=sb, ddof=1, device=device)
-        z, rows, cols = metrics.normative_z(ms, gs, mom, thr=thr, sub=sb, device=device)
-        rows = torch.split(rows, [int(m.shape[0]) for m in ms])
-        return [{"z": z[a], "rows": rows[a], "cols": cols[a], "moments": mom[a]} for a in range(len(ms))]
-    return _per_width(one_width, mats, groups, subs)
-
-
 NORMATIVE_KINDS = ("squared", "signed")
 CENTILE_QUANTILES = (0.05, 0.25, 0.5, 0.75, 0.95)
 
 
-def _centile_sets(mats: Sequence[torch.Tensor], groups: Sequence[np.ndarray], subs, tail: float, probs, loo: bool, device) -> List[dict]:
-    """metrics.cohort_quantiles and metrics.normative_centile for tables of any widths (_per_width): one launch of each per
-    distinct width, every table ranked among its own group-0 rows.  Returns per table {"pct" [n, D] fp32, "rows" [n, 8],
-    "cols" [D, 8], "q" [D, n_q], "stats" [D, 8]} on the device, in the order given."""
-    def one_width(ms, gs, sb):
-        q, st = metrics.cohort_quantiles(ms, gs, probs, sub=sb, device=device)
-        pct, rows, cols = metrics.normative_centile(ms, gs, tail=tail, loo=loo, sub=sb, device=device)
-        rows = torch.split(rows, [int(m.shape[0]) for m in ms])
-        return [{"pct": pct[a], "rows": rows[a], "cols": cols[a], "q": q[a], "stats": st[a]} for a in range(len(ms))]
-    return _per_width(one_width, mats, groups, subs)
-
-
 def _roi_columns(roi_columns, m: str, d: int):
     return list(roi_columns[m]) if roi_columns and m in roi_columns else [f"{m}_{k}" for k in range(d)]
+
+
+def _by_height(jobs: Sequence[Job]) -> List[List[Job]]:
+    """The jobs of one pass as one launch per table height: grouped by their number of 256-row tiles (the folds of a K-fold
+    split differ by at most one row) and by whether their shape takes the wide kernels, in the order first seen."""
+    groups: Dict[tuple, List[Job]] = {}
+    for j in jobs:
+        groups.setdefault((j.tables[0].n_tiles, bool(j.spec.wide)), []).append(j)
+    return list(groups.values())
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The ROI statistics of the test path, each described once by a RoiStat of ROI_STATS: test_folds queues, attaches and writes the
+# ones whose keyword (the key) is on, main_test writes and prints their pooled entries.  `o`: the keywords of test_folds as
+# attributes (main_test builds the same from its flags).  `t`: the tables every statistic starts from -- t.mats, the ROI-wise
+# squared errors of every fold x modality (fold-major), then of the pooled rows per modality (all folds' test rows, concatenated
+# on the device: the all-folds tables of the test script, :157-178; at most NM_METRICS_MAX_N subjects in all); t.grp, their
+# roi_groups words (cohort.dia; disease_label picks one diagnosis as the patients); t.tables(export), the same list of another
+# export; t.rows_of, the cohort rows of every fold and then of all of them, t.per_table(seq), a value per entry of t.rows_of
+# repeated for its tables; t.n_fold, where the pooled tables begin; t.cohort, t.device.
+# ---------------------------------------------------------------------------------------------------------------
+class RoiStat(NamedTuple):
+    key: str                # of a fold's result dict: {modality: entry}; key + "_pooled" holds the pooled entries
+    queue: Callable         # (t, o) -> one entry per table of t.mats, still on the device: a [D, 8] tensor or a dict of tensors
+    write: Callable         # (directory, modality, ROI names, the subjects' _meta_frame, host entry, o): a fold's files and the pooled ones
+    summary: Callable       # (pooled host entry, the pooled subjects' roi_groups, o) -> what `test` prints of it
+
+
+def _host(entry):
+    """A queued entry as the result dict holds it: numpy, a dict key by key, None where there is no table."""
+    if isinstance(entry, dict):
+        return {k: _host(v) for k, v in entry.items()}
+    return None if entry is None else entry.cpu().numpy()
+
+
+def _n_roi(entry) -> int:
+    return (entry["cols"] if isinstance(entry, dict) else entry).shape[0]
+
+
+def _folds_then_pooled(call, t) -> list:
+    """_per_width as two calls per width, the folds' sets and then the pooled ones (roi_effect and roi_significance stay two
+    calls: a set's index within its call enters the permutation hash)."""
+    return _per_width(call, t.mats[:t.n_fold], t.grp[:t.n_fold]) + _per_width(call, t.mats[t.n_fold:], t.grp[t.n_fold:])
+
+
+def _queue_effect(t, o):
+    """roi_effect: ONE metrics.roi_effect launch over all folds x modalities (one per table width, where the modalities' widths
+    differ) gives every ROI's Cliff's delta / ROC-AUC of patients against controls, one more the same on the pooled set per
+    modality.  Entries [D, 8] (metrics.ROI_EFFECT_COLUMNS); with out_dirs, roi_effect_<m>.csv next to the five kinds."""
+    return _folds_then_pooled(lambda ms, gs: metrics.roi_effect(ms, gs, device=t.device), t)
+
+
+def _queue_significance(t, o):
+    """roi_significance: metrics.roi_significance on the same tables with roi_perm label permutations and the seed roi_seed --
+    per ROI the Mann-Whitney U, z and asymptotic p, the Benjamini-Hochberg q over the ROIs and the permutation p-values of the
+    ROI and against the maximum over the ROIs.  Entries [D, 8] (metrics.ROI_SIGNIFICANCE_COLUMNS); with out_dirs,
+    roi_significance_<m>.csv.  The subjects are taken as independent: a cohort recipe that repeats a subject across folds
+    makes the pooled p-values too small."""
+    return _folds_then_pooled(lambda ms, gs: metrics.roi_significance(ms, gs, n_perm=o.roi_perm, seed=o.roi_seed, device=t.device), t)
+
+
+def _queue_regress(t, o):
+    """roi_regress = (kind, target): metrics.column_regress on the same tables, every fold x modality and the pooled sets in
+    ONE launch (one per table width) -- per ROI the fit target ~ const + the ROI's squared error, kind "logit" or "ols", target
+    a cohort column (regress_target; a Logit on DIA is patients against controls as roi_groups picks them), adjusted for the
+    cohort columns named in roi_adjust (at most NM_REG_MAX_COV).  Entries [D, 8] (metrics.COLUMN_REGRESS_COLUMNS); with
+    out_dirs, roi_regress_<m>.csv."""
+    kind, target = o.roi_regress
+    tg = [regress_target(t.cohort, r, target, kind, o.disease_label) for r in t.rows_of]
+    cv = [np.stack([np.asarray(getattr(t.cohort, REGRESS_TARGETS[a])[r], dtype=np.float32) for a in o.roi_adjust], 1)
+          for r in t.rows_of] if o.roi_adjust else None
+
+    def regress(ms, ts, cs, ws):
+        return metrics.column_regress(ms, ts, kind=kind, covariates=cs, include=ws, device=t.device)
+    return _per_width(regress, t.mats, t.per_table([v for v, _ in tg]), None if cv is None else t.per_table(cv),
+                      t.per_table([w for _, w in tg]))
+
+
+def _scored(t, kind: str, one_width) -> List[dict]:
+    """The entries of a map (normative, centile): one_width(tables, groups, subs) -> a dict of device tensors per table, once per
+    distinct width (_per_width), on the tables the kind scores -- "squared" the ROI-wise squared error (out_sqerr), "signed" the
+    residual table - out_loc, both read where they lie, every table against its own group-0 rows -- and with each entry the
+    fp32 tables that were scored, "x" and "sub" (sub None for "squared")."""
+    xs, subs = t.mats, None
+    if kind == "signed":
+        xs, subs = t.tables(lambda ev, i: ev.tables[i].x_f32[:, :ev.tables[i].D]), t.tables(lambda ev, i: ev.out_loc[i])
+    return [dict(e, x=xs[j], sub=None if subs is None else subs[j]) for j, e in enumerate(_per_width(one_width, xs, t.grp, subs))]
+
+
+def _queue_normative(t, o):
+    """normative = "squared" or "signed": the normative z-map of the same tables -- the sigma-normalised extra, never the parity
+    output.  Per fold and modality the moments of every ROI over that fold's healthy test subjects (the hold-out controls,
+    group 0 of roi_groups), every test subject of any group z-scored against them, the per-subject counts of ROIs beyond
+    +-z_thr and the per-ROI shares of patients and controls beyond it; the same on the pooled rows per modality.  One
+    metrics.cohort_moments launch and one metrics.normative_z launch per table width over all folds, modalities and pooled
+    sets.  The controls are scored against statistics they are themselves part of: their z-scores have mean 0 and sd 1 by
+    construction, so a control's count of extreme ROIs is slightly optimistic and the patients' excess over it is the
+    finding, not the controls' level.  Entries {"z" [n, D] fp32, "rows" [n, 8] (metrics.NORMATIVE_ROW_COLUMNS), "cols" [D, 8]
+    (metrics.NORMATIVE_COL_COLUMNS), "moments" [D, 8] (metrics.COHORT_MOMENTS_COLUMNS), "x" and "sub" (_scored)}, the pooled
+    ones with their rows in fold order; with out_dirs, normative_z_<m>.csv, normative_subject_<m>.csv and
+    normative_map_<m>.csv.  robust: the z-map is scored against the controls' median and 1.4826 x MAD (metrics.robust_moments
+    of metrics.cohort_quantiles) instead of their mean and sd; only the normative results and files change."""
+    def one_width(ms, gs, sb):
+        if o.robust:
+            mom = metrics.robust_moments(metrics.cohort_quantiles(ms, gs, (), sub=sb, device=t.device)[1])
+        else:
+            mom = metrics.cohort_moments(ms, gs, sub=sb, ddof=1, device=t.device)
+        z, rows, cols = metrics.normative_z(ms, gs, mom, thr=o.z_thr, sub=sb, device=t.device)
+        rows = torch.split(rows, [int(m.shape[0]) for m in ms])
+        return [{"z": z[a], "rows": rows[a], "cols": cols[a], "moments": mom[a]} for a in range(len(ms))]
+    return _scored(t, o.normative, one_width)
+
+
+def _queue_centile(t, o):
+    """centile = "squared" or "signed": the normative centiles of the same tables -- where every test subject falls in the
+    empirical distribution of that fold's healthy test subjects, ROI by ROI, with no distributional assumption (a squared error
+    is right-skewed: its z beyond 1.96 is not "outside the central 95 % of the controls", its percentile rank beyond 100 - tail
+    is).  Per subject the ROIs above 100 - tail and below tail percent, per ROI the shares of patients and controls there, and
+    per ROI the controls' quantiles at `quantiles`, median, MAD and quartiles (the normative range); the same on the pooled
+    rows.  centile_loo: a control is ranked among the OTHER controls (exact leave-one-out), so it is no longer scored against
+    a distribution it is part of.  One metrics.cohort_quantiles and one metrics.normative_centile call per table width.
+    Entries {"pct" [n, D] fp32, "rows" [n, 8] (metrics.CENTILE_ROW_COLUMNS), "cols" [D, 8] (metrics.CENTILE_COL_COLUMNS), "q"
+    [D, n_q], "stats" [D, 8] (metrics.COHORT_QUANTILE_COLUMNS), "x" and "sub" (_scored)}; with out_dirs, centile_pct_<m>.csv,
+    centile_subject_<m>.csv, centile_map_<m>.csv and centile_curve_<m>.csv."""
+    def one_width(ms, gs, sb):
+        q, st = metrics.cohort_quantiles(ms, gs, o.quantiles, sub=sb, device=t.device)
+        pct, rows, cols = metrics.normative_centile(ms, gs, tail=o.tail, loo=bool(o.centile_loo), sub=sb, device=t.device)
+        rows = torch.split(rows, [int(m.shape[0]) for m in ms])
+        return [{"pct": pct[a], "rows": rows[a], "cols": cols[a], "q": q[a], "stats": st[a]} for a in range(len(ms))]
+    return _scored(t, o.centile, one_width)
+
+
+def _effect_summary(tab, g, o) -> str:
+    top = int(np.nanargmax(np.abs(tab[:, 0]))) if np.isfinite(tab[:, 0]).any() else 0
+    return f"pooled ROI effect, largest |delta| {tab[top, 0]:+.4f} (AUC {tab[top, 1]:.4f}) at ROI {top}"
+
+
+def _significance_summary(tab, g, o) -> str:
+    col = 6 if o.roi_perm else 4
+    return (f"pooled ROI significance, {int(np.nansum(tab[:, col] <= 0.05))} of {tab.shape[0]} ROIs with "
+            f"{metrics.ROI_SIGNIFICANCE_COLUMNS[col]} <= 0.05")
+
+
+def _regress_summary(tab, g, o) -> str:
+    kind, target = o.roi_regress
+    return f"pooled ROI regression {target}:{kind}, {int(np.nansum(tab[:, 5] <= 0.05))} of {tab.shape[0]} ROIs with p_coef <= 0.05"
+
+
+def _beyond(e, g) -> str:
+    """The mean per-subject count of ROIs beyond a map's threshold on either side, patients and then controls."""
+    ext = e["rows"][:, 0] + e["rows"][:, 1]
+    return (f"patients {float(ext[g == 1].mean()) if (g == 1).any() else float('nan'):.2f}, controls "
+            f"{float(ext[g == 0].mean()) if (g == 0).any() else float('nan'):.2f}")
+
+
+def _normative_summary(e, g, o) -> str:
+    return f"pooled normative z-map ({o.normative}), ROIs beyond +-{o.z_thr:g} per subject: {_beyond(e, g)}"
+
+
+def _centile_summary(e, g, o) -> str:
+    return f"pooled normative centiles ({o.centile}), ROIs in the {o.tail:g} % tails per subject: {_beyond(e, g)}"
+
+
+# (in the order of the device calls, of the keys in a fold's dict and of the lines `test` prints)
+ROI_STATS = (
+    RoiStat("roi_effect", _queue_effect, lambda d, m, rois, meta, e, o: io.write_roi_effect_csv(d, m, rois, e), _effect_summary),
+    RoiStat("roi_significance", _queue_significance, lambda d, m, rois, meta, e, o: io.write_roi_significance_csv(d, m, rois, e),
+            _significance_summary),
+    RoiStat("roi_regress", _queue_regress, lambda d, m, rois, meta, e, o: io.write_roi_regress_csv(d, m, rois, e), _regress_summary),
+    RoiStat("normative", _queue_normative,
+            lambda d, m, rois, meta, e, o: io.write_normative_csvs(d, m, meta, rois, e["z"], e["rows"], e["cols"]), _normative_summary),
+    RoiStat("centile", _queue_centile,
+            lambda d, m, rois, meta, e, o: io.write_centile_csvs(d, m, meta, rois, e["pct"], e["rows"], e["cols"], o.quantiles, e["q"],
+                                                                 e["stats"]), _centile_summary))
 
 
 def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequence[tuple], modalities: Sequence[str],
@@ -599,179 +745,68 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
     Folds whose test tables differ in their number of 256-row tiles run as one launch per height (the folds of a K-fold
     split differ by at most one row).  Returns test_fold's result per fold; bit-identical to the fold-by-fold form.
 
-    roi_effect: the evaluation jobs also export their ROI-wise squared errors, and after the forward launches ONE
-    metrics.roi_effect launch over all folds x modalities (one per table width, where the modalities' widths differ) gives
-    every ROI's Cliff's delta / ROC-AUC of patients against controls (roi_groups on cohort.dia; disease_label picks one
-    diagnosis as the patients), one more the same on the pooled set per modality (all folds' test rows, concatenated on the
-    device: the all-folds tables of the test script, :157-178; at most NM_METRICS_MAX_N subjects in all).
-    Each fold's dict gains "roi_effect": {modality: [D, 8]} (metrics.ROI_EFFECT_COLUMNS) and "roi_effect_pooled": the pooled
-    tables (the same dict in every fold's result); with out_dirs, roi_effect_<m>.csv next to the five kinds.
-
-    roi_significance (needs roi_effect): metrics.roi_significance on the same tables with roi_perm label permutations and the
-    seed roi_seed -- per ROI the Mann-Whitney U, z and asymptotic p, the Benjamini-Hochberg q over the ROIs and the
-    permutation p-values of the ROI and against the maximum over the ROIs.  Each fold's dict gains "roi_significance":
-    {modality: [D, 8]} (metrics.ROI_SIGNIFICANCE_COLUMNS) and "roi_significance_pooled"; with out_dirs,
-    roi_significance_<m>.csv.  The subjects are taken as independent: a cohort recipe that repeats a subject across folds
-    makes the pooled p-values too small.
-
-    roi_regress = (kind, target) (needs roi_effect): metrics.column_regress on the same tables, every fold x modality and the
-    pooled sets in ONE launch (one per table width) -- per ROI the fit target ~ const + the ROI's squared error, kind "logit"
-    or "ols", target a cohort column (regress_target; a Logit on DIA is patients against controls as roi_groups picks them),
-    adjusted for the cohort columns named in roi_adjust (at most NM_REG_MAX_COV).  Each fold's dict gains "roi_regress":
-    {modality: [D, 8]} (metrics.COLUMN_REGRESS_COLUMNS) and "roi_regress_pooled"; with out_dirs, roi_regress_<m>.csv.
-
-    normative = "squared" or "signed" (needs roi_effect): the normative z-map of the same tables -- the sigma-normalised extra,
-    never the parity output.  Per fold and modality the moments of every ROI over that fold's healthy test subjects (the
-    hold-out controls, group 0 of roi_groups), every test subject of any group z-scored against them, the per-subject counts
-    of ROIs beyond +-z_thr and the per-ROI shares of patients and controls beyond it; the same on the pooled rows per modality.
-    "squared" scores the ROI-wise squared error (out_sqerr), "signed" the residual table - out_loc, both read where they lie.
-    One metrics.cohort_moments launch and one metrics.normative_z launch per table width over all folds, modalities and pooled
-    sets.  The controls are scored against statistics they are themselves part of: their z-scores have mean 0 and sd 1 by
-    construction, so a control's count of extreme ROIs is slightly optimistic and the patients' excess over it is the
-    finding, not the controls' level.  Each fold's dict gains "normative": {modality: {"z" [n, D] fp32, "rows" [n, 8]
-    (metrics.NORMATIVE_ROW_COLUMNS), "cols" [D, 8] (metrics.NORMATIVE_COL_COLUMNS), "moments" [D, 8]
-    (metrics.COHORT_MOMENTS_COLUMNS), "x" and "sub": the fp32 tables that were scored (sub None for "squared")}} and
-    "normative_pooled" (the same dict in every fold's result, its rows in fold order); with out_dirs, normative_z_<m>.csv,
-    normative_subject_<m>.csv and normative_map_<m>.csv.  robust (needs normative): the z-map is scored against the controls'
-    median and 1.4826 x MAD (metrics.robust_moments of metrics.cohort_quantiles) instead of their mean and sd; only the
-    normative results and files change.
-
-    centile = "squared" or "signed" (needs roi_effect): the normative centiles of the same tables -- where every test subject
-    falls in the empirical distribution of that fold's healthy test subjects, ROI by ROI, with no distributional assumption
-    (a squared error is right-skewed: its z beyond 1.96 is not "outside the central 95 % of the controls", its percentile rank
-    beyond 100 - tail is).  Per subject the ROIs above 100 - tail and below tail percent, per ROI the shares of patients and
-    controls there, and per ROI the controls' quantiles at `quantiles`, median, MAD and quartiles (the normative range); the same
-    on the pooled rows.  centile_loo: a control is ranked among the OTHER controls (exact leave-one-out), so it is no
-    longer scored against a distribution it is part of.  One metrics.cohort_quantiles and one metrics.normative_centile call
-    per table width.  Each fold's dict gains "centile": {modality: {"pct" [n, D] fp32, "rows" [n, 8]
-    (metrics.CENTILE_ROW_COLUMNS), "cols" [D, 8] (metrics.CENTILE_COL_COLUMNS), "q" [D, n_q], "stats" [D, 8]
-    (metrics.COHORT_QUANTILE_COLUMNS), "x" and "sub"}} and "centile_pooled"; with out_dirs, centile_pct_<m>.csv,
-    centile_subject_<m>.csv, centile_map_<m>.csv and centile_curve_<m>.csv."""
+    roi_effect: the evaluation jobs also export their ROI-wise squared errors, and after the forward launches the ROI
+    statistics that are switched on are queued on them (ROI_STATS; each one's docstring, _queue_effect ... _queue_centile, says
+    what it computes, what its entries hold and which files it writes).  roi_significance, roi_regress, normative and centile
+    need roi_effect; robust needs normative.  Each fold's dict gains, per statistic, "<key>": {modality: entry} and
+    "<key>_pooled": the entries of the pooled rows (the same dict in every fold's result), in the order of ROI_STATS; with
+    out_dirs, the statistic's files next to the five kinds."""
+    for name, on in (("centile", centile is not None), ("normative", normative is not None), ("roi_significance", roi_significance),
+                     ("roi_regress", roi_regress is not None)):
+        if on and not roi_effect:
+            raise ValueError(f"{name} needs roi_effect=True (the evaluation jobs export the ROI-wise squared errors for it)")
     if robust and normative is None:
         raise ValueError("robust needs normative (it replaces the moments the z-map is scored against)")
+    for name, kind in (("centile", centile), ("normative", normative)):
+        if kind is not None and kind not in NORMATIVE_KINDS:
+            raise ValueError(f"{name} must be None or one of {NORMATIVE_KINDS}, got {kind!r}")
     if centile is not None:
-        if centile not in NORMATIVE_KINDS:
-            raise ValueError(f"centile must be None or one of {NORMATIVE_KINDS}, got {centile!r}")
-        if not roi_effect:
-            raise ValueError("centile needs roi_effect=True (the evaluation jobs export the ROI-wise squared errors for it)")
-        tail = metrics._tail_check(tail)
-        quantiles = metrics._probs_check(quantiles)
+        tail, quantiles = metrics._tail_check(tail), metrics._probs_check(quantiles)
     if normative is not None:
-        if normative not in NORMATIVE_KINDS:
-            raise ValueError(f"normative must be None or one of {NORMATIVE_KINDS}, got {normative!r}")
-        if not roi_effect:
-            raise ValueError("normative needs roi_effect=True (the evaluation jobs export the ROI-wise squared errors for it)")
         z_thr = float(z_thr)
         if not (np.isfinite(z_thr) and z_thr > 0.0):
             raise ValueError(f"z_thr must be finite and > 0, got {z_thr}")
-    if roi_significance and not roi_effect:
-        raise ValueError("roi_significance needs roi_effect=True (the evaluation jobs export the ROI-wise squared errors for it)")
     if roi_regress is not None:
-        if not roi_effect:
-            raise ValueError("roi_regress needs roi_effect=True (the evaluation jobs export the ROI-wise squared errors for it)")
-        reg_kind, reg_target = roi_regress
-        regress_target(cohort, np.zeros(0, dtype=np.int64), reg_target, reg_kind)
+        regress_target(cohort, np.zeros(0, dtype=np.int64), roi_regress[1], roi_regress[0])
         roi_adjust = list(roi_adjust)
         if any(a not in REGRESS_TARGETS for a in roi_adjust) or len(roi_adjust) > _lib.NM_REG_MAX_COV:
             raise ValueError(f"roi_adjust: at most {_lib.NM_REG_MAX_COV} of {sorted(REGRESS_TARGETS)}, got {roi_adjust}")
     if len(jobs) != len(folds):
         raise ValueError(f"{len(jobs)} models for {len(folds)} folds")
+    o = SimpleNamespace(roi_effect=roi_effect, disease_label=disease_label, roi_significance=roi_significance, roi_perm=roi_perm,
+                        roi_seed=roi_seed, roi_regress=roi_regress, roi_adjust=roi_adjust, normative=normative, z_thr=z_thr,
+                        robust=robust, centile=centile, tail=tail, quantiles=quantiles, centile_loo=centile_loo)
     combs = [combines] * len(jobs) if isinstance(combines, str) else list(combines)
     dirs = [None] * len(jobs) if out_dirs is None else list(out_dirs)
     evs = [_fold_eval_job(j, cohort, tr, te, modalities, cb, device, sqerr=roi_effect)
            for j, (tr, te), cb in zip(jobs, folds, combs)]
-    by_tiles: Dict[tuple, List[int]] = {}
-    for i, (ev, _) in enumerate(evs):
-        by_tiles.setdefault((ev.tables[0].n_tiles, bool(ev.spec.wide)), []).append(i)
-    for idxs in by_tiles.values():
-        JobSet([evs[i][0] for i in idxs]).forward(loss=False)
-    stats = []                  # (result key, one [D, 8] device table per entry of `mats`, the writer of its CSV)
+    for group in _by_height([ev for ev, _ in evs]):
+        JobSet(group).forward(loss=False)
+    queued = []                 # (statistic, its device entry per table of t.mats): everything is queued before the one synchronise
     if roi_effect:
-        # one table list for every statistic: every fold x modality (fold-major), then the pooled rows of every modality; a
-        # value per row list (the folds' test rows, then all of them) goes with it through `per_table`
         nm_ = len(modalities)
         tests = [te for _, te in folds]
-        rows_of = tests + [np.concatenate(tests)]
-        n_fold = len(folds) * nm_
-
-        def per_table(seq):
-            return [v for v in seq for _ in range(nm_)]
 
         def tables(export):
-            t = [export(ev, i)[:len(te)] for (ev, _), te in zip(evs, tests) for i in range(nm_)]
-            return t + [torch.cat(t[i::nm_]) for i in range(nm_)]
-
-        def folds_then_pooled(call):                # (two calls: a set's index within its call enters the permutation hash)
-            return _per_width(call, mats[:n_fold], grp[:n_fold]) + _per_width(call, mats[n_fold:], grp[n_fold:])
-        grp = per_table([roi_groups(cohort.dia[r], disease_label) for r in rows_of])
-        mats = tables(lambda ev, i: ev.out_sqerr[i])
-        effect = folds_then_pooled(lambda ms, gs: metrics.roi_effect(ms, gs, device=device))
-        stats.append(("roi_effect", effect, io.write_roi_effect_csv))
-        if roi_significance:
-            signif = folds_then_pooled(lambda ms, gs: metrics.roi_significance(ms, gs, n_perm=roi_perm, seed=roi_seed, device=device))
-            stats.append(("roi_significance", signif, io.write_roi_significance_csv))
-        if roi_regress is not None:
-            # the folds' sets and the pooled ones in one launch per width
-            tg = [regress_target(cohort, r, reg_target, reg_kind, disease_label) for r in rows_of]
-            cv = [np.stack([np.asarray(getattr(cohort, REGRESS_TARGETS[a])[r], dtype=np.float32) for a in roi_adjust], 1)
-                  for r in rows_of] if roi_adjust else None
-
-            def regress(ms, ts, cs, ws):
-                return metrics.column_regress(ms, ts, kind=reg_kind, covariates=cs, include=ws, device=device)
-            fits = _per_width(regress, mats, per_table([t for t, _ in tg]), None if cv is None else per_table(cv),
-                              per_table([w for _, w in tg]))
-            stats.append(("roi_regress", fits, io.write_roi_regress_csv))
-        if normative is not None:
-            # likewise: one moments and one z launch per width
-            n_mats, n_subs = mats, None
-            if normative == "signed":
-                n_mats, n_subs = tables(lambda ev, i: ev.tables[i].x_f32[:, :ev.tables[i].D]), tables(lambda ev, i: ev.out_loc[i])
-            norm = _normative_sets(n_mats, grp, n_subs, z_thr, device, robust=robust)
-        if centile is not None:
-            # likewise: one quantile and one centile call per width
-            c_mats, c_subs = mats, None
-            if centile == "signed":
-                c_mats, c_subs = tables(lambda ev, i: ev.tables[i].x_f32[:, :ev.tables[i].D]), tables(lambda ev, i: ev.out_loc[i])
-            cent = _centile_sets(c_mats, grp, c_subs, tail, quantiles, bool(centile_loo), device)
+            tabs = [export(ev, i)[:len(te)] for (ev, _), te in zip(evs, tests) for i in range(nm_)]
+            return tabs + [torch.cat(tabs[i::nm_]) for i in range(nm_)]
+        t = SimpleNamespace(cohort=cohort, device=device, tables=tables, rows_of=tests + [np.concatenate(tests)],
+                            n_fold=len(folds) * nm_, per_table=lambda seq: [v for v in seq for _ in range(nm_)])
+        t.grp = t.per_table([roi_groups(cohort.dia[r], disease_label) for r in t.rows_of])
+        t.mats = tables(lambda ev, i: ev.out_sqerr[i])
+        queued = [(st, st.queue(t, o)) for st in ROI_STATS if getattr(o, st.key)]
     torch.cuda.synchronize(device)
     out = [_fold_results(ev, xs, cohort, te, modalities, d, roi_columns) for (ev, xs), (_, te), d in zip(evs, folds, dirs)]
-    for key, tabs, write in stats:
-        tabs = [t.cpu().numpy() for t in tabs]
-        pooled = {m: tabs[n_fold + i] for i, m in enumerate(modalities)}
+    for st, entries in queued:
+        entries = [_host(e) for e in entries]
+        pooled = {m: entries[t.n_fold + i] for i, m in enumerate(modalities)}
         for f, (res, d) in enumerate(zip(out, dirs)):
-            res[key] = {m: tabs[f * nm_ + i] for i, m in enumerate(modalities)}
-            res[key + "_pooled"] = pooled
+            res[st.key] = {m: entries[f * nm_ + i] for i, m in enumerate(modalities)}
+            res[st.key + "_pooled"] = pooled
             if d is not None:
-                for m, tab in res[key].items():
-                    write(Path(d) / m, m, _roi_columns(roi_columns, m, tab.shape[0]), tab)
-    if normative is not None:
-        def host(j):
-            res = {k: v.cpu().numpy() for k, v in norm[j].items()}
-            res["x"] = n_mats[j].cpu().numpy()
-            res["sub"] = None if n_subs is None else n_subs[j].cpu().numpy()
-            return res
-        norm_pooled = {m: host(n_fold + i) for i, m in enumerate(modalities)}
-        for f, (res, d) in enumerate(zip(out, dirs)):
-            res["normative"] = {m: host(f * nm_ + i) for i, m in enumerate(modalities)}
-            res["normative_pooled"] = norm_pooled
-            if d is not None:
-                for m, t in res["normative"].items():
-                    io.write_normative_csvs(Path(d) / m, m, _meta_frame(cohort, tests[f]), _roi_columns(roi_columns, m, t["z"].shape[1]),
-                                            t["z"], t["rows"], t["cols"])
-    if centile is not None:
-        def chost(j):
-            res = {k: v.cpu().numpy() for k, v in cent[j].items()}
-            res["x"] = c_mats[j].cpu().numpy()
-            res["sub"] = None if c_subs is None else c_subs[j].cpu().numpy()
-            return res
-        cent_pooled = {m: chost(n_fold + i) for i, m in enumerate(modalities)}
-        for f, (res, d) in enumerate(zip(out, dirs)):
-            res["centile"] = {m: chost(f * nm_ + i) for i, m in enumerate(modalities)}
-            res["centile_pooled"] = cent_pooled
-            if d is not None:
-                for m, t in res["centile"].items():
-                    io.write_centile_csvs(Path(d) / m, m, _meta_frame(cohort, tests[f]), _roi_columns(roi_columns, m, t["pct"].shape[1]),
-                                          t["pct"], t["rows"], t["cols"], quantiles, t["q"], t["stats"])
+                meta = _meta_frame(cohort, tests[f])
+                for m, e in res[st.key].items():
+                    st.write(Path(d) / m, m, _roi_columns(roi_columns, m, _n_roi(e)), meta, e, o)
     return out
 
 
@@ -830,12 +865,10 @@ def latent_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Seque
     dirs = [None] * len(jobs) if out_dirs is None else list(out_dirs)
     pairs = [_fold_latent_jobs(j, cohort, tr, te, modalities, cb, device) for j, (tr, te), cb in zip(jobs, folds, combs)]
     for side in (0, 1):
-        by_tiles: Dict[tuple, List[int]] = {}
-        for i, pr in enumerate(pairs):
-            by_tiles.setdefault((pr[side].tables[0].n_tiles, bool(pr[side].spec.wide)), []).append(i)
-        for idxs in by_tiles.values():
-            JobSet([pairs[i][side] for i in idxs]).latent()
-    mean, var = engine.latent_stats([trn.out_mu[:len(tr)] for (trn, _), (tr, _) in zip(pairs, folds)])
+        for group in _by_height([pr[side] for pr in pairs]):
+            JobSet(group).latent()
+    trn_mus = [trn.out_mu[:len(tr)] for (trn, _), (tr, _) in zip(pairs, folds)]
+    mean, var = engine.latent_stats(trn_mus)
     mus = [ev.out_mu[:len(te)] for (_, ev), (_, te) in zip(pairs, folds)]
     lvs = [ev.out_logvar[:len(te)] for (_, ev), (_, te) in zip(pairs, folds)]
     zsep, score = engine.latent_scores(mus, lvs, mean, var)
@@ -848,7 +881,6 @@ def latent_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Seque
             pv[target] = metrics.column_regress(sets, [t for t, _ in tg], kind=kind, include=[w for _, w in tg], device=device)
     maha = None
     if mahalanobis and mus:
-        trn_mus = [trn.out_mu[:len(tr)] for (trn, _), (tr, _) in zip(pairs, folds)]
         c_mean, c_chol, c_status = metrics.cohort_cov(trn_mus, [np.zeros(len(tr), dtype=np.int32) for tr, _ in folds], ridge=ridge,
                                                       device=device)
         maha = metrics.mahalanobis(mus, c_mean, c_chol, c_status, device=device)
@@ -865,21 +897,20 @@ def latent_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Seque
         for target, tab in pv_pooled.items():
             io.write_latent_pvalues_csv(pooled_dir, name, target, tab)
     out = []
-    for mu, lv, z, sc, (_, te), d in zip(mus, lvs, zsep, score, folds, dirs):
+    for f, (mu, lv, z, sc, (_, te), d) in enumerate(zip(mus, lvs, zsep, score, folds, dirs)):
         res = {"mu": mu.cpu().numpy(), "var": lv.exp().cpu().numpy(), "z": z.cpu().numpy(), "score": sc.cpu().numpy()}
+        if maha is not None:
+            res["mahalanobis"] = maha[f].cpu().numpy()
+        if pv:
+            res["pvalues"] = {t: tab[f] for t, tab in pv.items()}
+            res["pvalues_pooled"] = pv_pooled
         if d is not None:
             meta = _meta_frame(cohort, te)
             io.write_latent_csvs(d, name, meta, res["mu"], res["var"], res["score"], res["z"])
             if maha is not None:
-                io.write_latent_mahalanobis_csv(d, name, meta, maha[len(out)].cpu().numpy())
-        if maha is not None:
-            res["mahalanobis"] = maha[len(out)].cpu().numpy()
-        if pv:
-            res["pvalues"] = {t: tab[len(out)] for t, tab in pv.items()}
-            res["pvalues_pooled"] = pv_pooled
-            if d is not None:
-                for target, tab in res["pvalues"].items():
-                    io.write_latent_pvalues_csv(d, name, target, tab)
+                io.write_latent_mahalanobis_csv(d, name, meta, res["mahalanobis"])
+            for target, tab in res.get("pvalues", {}).items():
+                io.write_latent_pvalues_csv(d, name, target, tab)
         out.append(res)
     return out
 
@@ -1189,32 +1220,24 @@ def main_test(argv=None):
                     help="with --normative: z-scores against the controls' median and 1.4826 x MAD instead of mean and sd")
     _driver_common(ap)
     args = ap.parse_args(argv)
-    if args.centile and not args.roi_effect:
-        ap.error("--centile needs --roi-effect")
-    if args.centile and not (np.isfinite(args.tail) and 0 < args.tail < 50):
-        ap.error("--tail must lie inside (0, 50)")
-    if args.centile and (len(args.quantiles) > _lib.NM_CENT_MAX_Q or not all(0 <= p <= 1 for p in args.quantiles)):
-        ap.error(f"--quantiles: at most {_lib.NM_CENT_MAX_Q} probabilities inside [0, 1]")
-    if args.centile_loo and not args.centile:
-        ap.error("--centile-loo needs --centile")
-    if args.robust and not args.normative:
-        ap.error("--robust needs --normative")
-    if args.normative and not args.roi_effect:
-        ap.error("--normative needs --roi-effect")
-    if args.normative and not (np.isfinite(args.z_thr) and args.z_thr > 0):
-        ap.error("--z-thr must be finite and > 0")
-    if args.mahalanobis and not args.latent:
-        ap.error("--mahalanobis needs --latent")
-    if args.mahalanobis and not (np.isfinite(args.ridge) and args.ridge >= 0):
-        ap.error("--ridge must be finite and >= 0")
-    if args.roi_significance and not args.roi_effect:
-        ap.error("--roi-significance needs --roi-effect")
-    if args.latent_pvalues and not args.latent:
-        ap.error("--latent-pvalues needs --latent")
-    if args.roi_regress and not args.roi_effect:
-        ap.error("--roi-regress needs --roi-effect")
-    if args.roi_adjust and not args.roi_regress:
-        ap.error("--roi-adjust needs --roi-regress")
+    # (what is refused, first match first; a value is judged only where its switch is on -- test_folds and latent_folds do the same)
+    refusals = ((args.centile and not args.roi_effect, "--centile needs --roi-effect"),
+                (args.centile and not (np.isfinite(args.tail) and 0 < args.tail < 50), "--tail must lie inside (0, 50)"),
+                (args.centile and (len(args.quantiles) > _lib.NM_CENT_MAX_Q or not all(0 <= p <= 1 for p in args.quantiles)),
+                 f"--quantiles: at most {_lib.NM_CENT_MAX_Q} probabilities inside [0, 1]"),
+                (args.centile_loo and not args.centile, "--centile-loo needs --centile"),
+                (args.robust and not args.normative, "--robust needs --normative"),
+                (args.normative and not args.roi_effect, "--normative needs --roi-effect"),
+                (args.normative and not (np.isfinite(args.z_thr) and args.z_thr > 0), "--z-thr must be finite and > 0"),
+                (args.mahalanobis and not args.latent, "--mahalanobis needs --latent"),
+                (args.mahalanobis and not (np.isfinite(args.ridge) and args.ridge >= 0), "--ridge must be finite and >= 0"),
+                (args.roi_significance and not args.roi_effect, "--roi-significance needs --roi-effect"),
+                (args.latent_pvalues and not args.latent, "--latent-pvalues needs --latent"),
+                (args.roi_regress and not args.roi_effect, "--roi-regress needs --roi-effect"),
+                (args.roi_adjust and not args.roi_regress, "--roi-adjust needs --roi-regress"))
+    for refused, message in refusals:
+        if refused:
+            ap.error(message)
     try:
         lat_pvalues = [parse_regress_spec(v) for v in (args.latent_pvalues or [])]
         roi_regress = tuple(reversed(parse_regress_spec(args.roi_regress))) if args.roi_regress else None
@@ -1229,7 +1252,6 @@ def main_test(argv=None):
     out_root = Path(args.out_dir or args.models_dir) / args.dataset_resourse / args.procedure
     from .prep_device import DeviceCohort
     dc = DeviceCohort(cohort, device)
-    errors: Dict[str, list] = {m: [] for m in mods}
     my = _my_folds(args)
     fold_jobs, fold_rows, fold_combines, fold_dirs = [], [], [], []
     for k in my:
@@ -1250,70 +1272,38 @@ def main_test(argv=None):
         fold_rows.append((tr, te))
         fold_dirs.append(fold_dir)
     # all folds of this rank in one launch (one job per fold on its own test tables)
-    results = test_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs,
-                         roi_effect=args.roi_effect, disease_label=args.disease_label, roi_significance=args.roi_significance,
-                         roi_perm=args.roi_perm, roi_seed=args.roi_seed, roi_regress=roi_regress,
-                         roi_adjust=args.roi_adjust, **({"normative": args.normative, "z_thr": args.z_thr} if args.normative else {}),
-                         **({"robust": True} if args.robust else {}),
-                         **({"centile": args.centile, "tail": args.tail, "quantiles": args.quantiles, "centile_loo": args.centile_loo}
-                            if args.centile else {})) if my else []
-    for err in results:
-        for m in mods:
-            errors[m].append(err[m])
+    o = SimpleNamespace(roi_effect=args.roi_effect, disease_label=args.disease_label, roi_significance=args.roi_significance,
+                        roi_perm=args.roi_perm, roi_seed=args.roi_seed, roi_regress=roi_regress, roi_adjust=args.roi_adjust,
+                        normative=args.normative, z_thr=args.z_thr, robust=args.robust, centile=args.centile, tail=args.tail,
+                        quantiles=args.quantiles, centile_loo=args.centile_loo)
+    results = test_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs, **vars(o)) if my else []
+    # the pooled entries of every statistic that is on: this rank's folds' test subjects as one set (the maps: against their controls)
+    pooled_stats = [st for st in ROI_STATS if getattr(o, st.key)] if results else []
+    if pooled_stats:
+        te_all = np.concatenate([te for _, te in fold_rows])
+        meta_all, g_all = _meta_frame(cohort, te_all), roi_groups(cohort.dia[te_all], args.disease_label)
     for m in mods:                                   # all folds of this rank, one table per CSV kind (:147-175)
         (out_root / m).mkdir(parents=True, exist_ok=True)
         for kind in ("normalized", "reconstruction", "reconstruction_error", "reconstruction_error_roi", "deviation_as_feature_importance"):
             parts = [pd.read_csv(root / f"{k:03d}" / m / f"{kind}_{m}.csv") for k in my]
             if parts:
                 pd.concat(parts, ignore_index=True).to_csv(out_root / m / f"{kind}_{m}.csv", index=False)
-        if args.roi_effect and results:              # the pooled table: this rank's folds' test subjects as one set
-            tab = results[0]["roi_effect_pooled"][m]
-            io.write_roi_effect_csv(out_root / m, m, _roi_columns(None, m, tab.shape[0]), tab)
-            top = int(np.nanargmax(np.abs(tab[:, 0]))) if np.isfinite(tab[:, 0]).any() else 0
-            print(f"[test] {args.procedure} {m}: pooled ROI effect, largest |delta| {tab[top, 0]:+.4f} (AUC {tab[top, 1]:.4f}) at ROI {top}",
-                  flush=True)
-        if args.roi_significance and results:
-            tab = results[0]["roi_significance_pooled"][m]
-            io.write_roi_significance_csv(out_root / m, m, _roi_columns(None, m, tab.shape[0]), tab)
-            col = 6 if args.roi_perm else 4
-            print(f"[test] {args.procedure} {m}: pooled ROI significance, {int(np.nansum(tab[:, col] <= 0.05))} of {tab.shape[0]} ROIs with "
-                  f"{metrics.ROI_SIGNIFICANCE_COLUMNS[col]} <= 0.05", flush=True)
-        if roi_regress and results:
-            tab = results[0]["roi_regress_pooled"][m]
-            io.write_roi_regress_csv(out_root / m, m, _roi_columns(None, m, tab.shape[0]), tab)
-            print(f"[test] {args.procedure} {m}: pooled ROI regression {args.roi_regress}, {int(np.nansum(tab[:, 5] <= 0.05))} of "
-                  f"{tab.shape[0]} ROIs with p_coef <= 0.05", flush=True)
-        if args.normative and results:               # the pooled z-map: this rank's folds' test subjects against their controls
-            t = results[0]["normative_pooled"][m]
-            te_all = np.concatenate([te for _, te in fold_rows])
-            io.write_normative_csvs(out_root / m, m, _meta_frame(cohort, te_all), _roi_columns(None, m, t["z"].shape[1]), t["z"], t["rows"], t["cols"])
-            g = roi_groups(cohort.dia[te_all], args.disease_label)
-            ext = t["rows"][:, 0] + t["rows"][:, 1]
-            print(f"[test] {args.procedure} {m}: pooled normative z-map ({args.normative}), ROIs beyond +-{args.z_thr:g} per subject: "
-                  f"patients {float(ext[g == 1].mean()) if (g == 1).any() else float('nan'):.2f}, controls "
-                  f"{float(ext[g == 0].mean()) if (g == 0).any() else float('nan'):.2f}", flush=True)
-        if args.centile and results:                 # the pooled centiles: this rank's folds' test subjects among their controls
-            t = results[0]["centile_pooled"][m]
-            te_all = np.concatenate([te for _, te in fold_rows])
-            io.write_centile_csvs(out_root / m, m, _meta_frame(cohort, te_all), _roi_columns(None, m, t["pct"].shape[1]), t["pct"],
-                                  t["rows"], t["cols"], args.quantiles, t["q"], t["stats"])
-            g = roi_groups(cohort.dia[te_all], args.disease_label)
-            ext = t["rows"][:, 0] + t["rows"][:, 1]
-            print(f"[test] {args.procedure} {m}: pooled normative centiles ({args.centile}), ROIs in the {args.tail:g} % tails per "
-                  f"subject: patients {float(ext[g == 1].mean()) if (g == 1).any() else float('nan'):.2f}, controls "
-                  f"{float(ext[g == 0].mean()) if (g == 0).any() else float('nan'):.2f}", flush=True)
+        for st in pooled_stats:
+            e = results[0][st.key + "_pooled"][m]
+            st.write(out_root / m, m, _roi_columns(None, m, _n_roi(e)), meta_all, e, o)
+            print(f"[test] {args.procedure} {m}: {st.summary(e, g_all, o)}", flush=True)
     if args.latent and my:
         # the folds' train cohorts and test subjects in one latent launch each, one statistics and one score launch
         lat = latent_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs, name=args.procedure,
                            pvalues=lat_pvalues, disease_label=args.disease_label, pooled_dir=out_root if lat_pvalues else None,
-                           **({"mahalanobis": True, "ridge": args.ridge} if args.mahalanobis else {}))
+                           mahalanobis=args.mahalanobis, ridge=args.ridge)
         out_root.mkdir(parents=True, exist_ok=True)
         for kind in ("latent", "latent_deviation") + (("latent_mahalanobis",) if args.mahalanobis else ()):
             parts = [pd.read_csv(root / f"{k:03d}" / f"{kind}_{args.procedure}.csv") for k in my]
             pd.concat(parts, ignore_index=True).to_csv(out_root / f"{kind}_{args.procedure}.csv", index=False)
         sc = np.concatenate([r["score"] for r in lat])
         print(f"[test] {args.procedure} latent: {len(sc)} subjects, mean latent deviation {float(sc.mean()):.5f}", flush=True)
-    out = {m: np.concatenate(v) if v else np.empty(0) for m, v in errors.items()}
+    out = {m: np.concatenate([r[m] for r in results]) if results else np.empty(0) for m in mods}
     for m, v in out.items():
         print(f"[test] {args.procedure} {m}: {len(v)} subjects, mean reconstruction error {float(v.mean()) if len(v) else float('nan'):.5f}", flush=True)
     return out
@@ -1452,6 +1442,19 @@ def _analysis_scores(root: Path, mods: Sequence[str], procedure: str, score: str
     return scores, positive, folds, ids
 
 
+def _with_pooled(scores, positive, flag: str = ""):
+    """(scores, labels) of every fold's set, then of the pooled rows of all folds -- which have to fit one set."""
+    total = sum(int(s.numel()) for s in scores)
+    if total > _lib.NM_METRICS_MAX_N:
+        raise ValueError(f"{flag}the pooled rows of all folds are {total} subjects, a set holds at most {_lib.NM_METRICS_MAX_N}")
+    return list(scores) + [torch.cat(list(scores))], list(positive) + [torch.cat(list(positive))]
+
+
+def _score_tag(args) -> str:
+    """What the file names of `analysis --bootstrap` / `--threshold-rule` carry for any score but the reconstruction error."""
+    return "" if args.score == "reconstruction" else f"{args.score}_"
+
+
 def _analysis_bootstrap(root: Path, args, hc: int, scores, positive, folds, ids):
     """`analysis --bootstrap B [--against Q ...]`: every fold's set and the pooled rows of all folds, of the procedure and of
     every procedure it is compared against, in ONE metrics.auc_bootstrap call.  Fold k draws from stream k, the pooled rows
@@ -1459,14 +1462,7 @@ def _analysis_bootstrap(root: Path, args, hc: int, scores, positive, folds, ids)
     group_analysis_bootstrap.csv (`fold` column, `pooled` as the last row) and per Q
     group_analysis_compare_<P>_vs_<Q>.csv; prints AUC [lo, hi] per row."""
     import pandas as pd
-
-    def with_pooled(sc, po):
-        return list(sc) + [torch.cat(list(sc))], list(po) + [torch.cat(list(po))]
-
-    total = sum(int(s.numel()) for s in scores)
-    if total > _lib.NM_METRICS_MAX_N:
-        raise ValueError(f"--bootstrap: the pooled rows of all folds are {total} subjects, a set holds at most {_lib.NM_METRICS_MAX_N}")
-    sets, labs = with_pooled(scores, positive)
+    sets, labs = _with_pooled(scores, positive, "--bootstrap: ")
     per = len(folds) + 1
     streams = list(folds) + [args.n_splits]
     pairs, others = [], list(args.against or [])
@@ -1481,7 +1477,7 @@ def _analysis_bootstrap(root: Path, args, hc: int, scores, positive, folds, ids)
                 raise ValueError(f"--against {q}: fold {k} does not hold {args.procedure}'s subjects with their DIA in the same order "
                                  f"({qroot / f'{k:03d}'}): the comparison is paired subject by subject -- evaluate both procedures "
                                  f"on the same folds of the same cohort")
-        qs, qp = with_pooled(qs, qp)
+        qs, qp = _with_pooled(qs, qp, f"--against {q}: ")
         sets += qs
         labs += qp
         pairs += [(i, (qi + 1) * per + i) for i in range(per)]
@@ -1490,7 +1486,7 @@ def _analysis_bootstrap(root: Path, args, hc: int, scores, positive, folds, ids)
                                 pairs=pairs if others else None)
     tab, cmp_tab = (res[0].cpu().numpy(), res[1].cpu().numpy()) if others else (res.cpu().numpy(), None)
     names = [str(k) for k in folds] + ["pooled"]
-    tag = "" if args.score == "reconstruction" else f"{args.score}_"
+    tag = _score_tag(args)
     df = pd.DataFrame(tab[:per], columns=list(metrics.AUC_BOOTSTRAP_COLUMNS))
     df.insert(0, "fold", names)
     df.to_csv(root / f"group_analysis_{tag}bootstrap.csv", index=False)
@@ -1520,10 +1516,7 @@ def _analysis_operating(root: Path, args, scores, positive, folds, ids):
     mean and sd of the folds' TPR, one column per fold); prints the operating point per row."""
     import pandas as pd
     F = len(folds)
-    total = sum(int(s.numel()) for s in scores)
-    if total > _lib.NM_METRICS_MAX_N:
-        raise ValueError(f"the pooled rows of all folds are {total} subjects, a set holds at most {_lib.NM_METRICS_MAX_N}")
-    sets, labs = list(scores) + [torch.cat(list(scores))], list(positive) + [torch.cat(list(positive))]
+    sets, labs = _with_pooled(scores, positive)
     evaluate, select_of = list(range(F + 1)), list(range(F + 1))
     others = args.threshold_from == "others"
     if others:
@@ -1540,7 +1533,7 @@ def _analysis_operating(root: Path, args, scores, positive, folds, ids):
                                    roc_grid=args.roc_grid)
     points, summary = res[0].cpu().numpy()[:, 0], res[1].cpu().numpy()[:F + 1]
     names = [str(k) for k in folds] + ["pooled"]
-    tag = "" if args.score == "reconstruction" else f"{args.score}_"
+    tag = _score_tag(args)
     if rule:
         df = pd.DataFrame(points, columns=list(metrics.OPERATING_POINT_COLUMNS))
         df.insert(0, "fold", names[:len(evaluate)])

@@ -1,8 +1,9 @@
-"""The shared host path of the table statistics on the device.  test_folds with every statistic switched on at once against four
+"""The shared host path of the table statistics on the device.  test_folds with every statistic switched on at once against five
 calls that switch on one each: key by key and file by file the same bytes -- what a crossed key or writer in the loop the
-statistics share would break, and no per-feature test sees.  And the one per-row uploader: host words (one copy for all sets) and
-the same words already on the device give the same tables.  The cohort of tests/table_stats_util.py: 120 subjects, three
-diagnoses, two folds, widths 40 and 23, one epoch."""
+statistics share (sweep.ROI_STATS: the three [D, 8] tables and the two maps alike, the z-map on its robust branch) would break,
+and no per-feature test sees.  And the one per-row uploader: host words (one copy for all sets) and the same words already on
+the device give the same tables.  The cohort of tests/table_stats_util.py: 120 subjects, three diagnoses, two folds, widths 40
+and 23, one epoch."""
 import filecmp
 import tempfile
 from pathlib import Path
@@ -21,7 +22,8 @@ PERM = _lib.NM_ROI_PERM_CHUNK + 1
 OPTIONS = {"roi_effect": {},
            "roi_significance": dict(roi_significance=True, roi_perm=PERM, roi_seed=31),
            "roi_regress": dict(roi_regress=("logit", "DIA"), roi_adjust=["AGE"]),
-           "normative": dict(normative="signed")}
+           "normative": dict(normative="signed", robust=True),
+           "centile": dict(centile="signed", tail=5.0, quantiles=(0.1, 0.9), centile_loo=True)}
 
 
 @pytest.fixture(scope="module")
@@ -42,7 +44,7 @@ def _same(a, b):
     return a.dtype == b.dtype and np.array_equal(a, b, equal_nan=True)
 
 
-def test_everything_on_is_the_four_single_options(trained):
+def test_everything_on_is_the_single_options(trained):
     cohort, folds, mods, jobs = trained
     assert PERM == 65
     with tempfile.TemporaryDirectory() as d:
@@ -68,7 +70,8 @@ def test_everything_on_is_the_four_single_options(trained):
                 assert filecmp.cmp(Path(d) / "all" / p, Path(d) / name / p, shallow=False), (name, p)
             seen |= set(fs)
         assert seen == set(fa)
-        stems = ("roi_effect", "roi_significance", "roi_regress", "normative_z", "normative_subject", "normative_map")
+        stems = ("roi_effect", "roi_significance", "roi_regress", "normative_z", "normative_subject", "normative_map",
+                 "centile_pct", "centile_subject", "centile_map", "centile_curve")
         assert {Path(f"{k:03d}") / m / f"{s}_{m}.csv" for k in range(len(folds)) for m in mods for s in stems} <= seen
 
 
