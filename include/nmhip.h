@@ -380,6 +380,34 @@ int nm_devpass_ok(const nm_job_t* job_host);
  * NM_E_DEVPASS otherwise (such a job runs on nm_forward); NM_E_NULL for a null pointer. */
 int nm_devpass_multi(const nm_job_t* jobs_dev, int n_jobs, int tile0, int n_tiles, int flags, void* stream);   /* flags: 0 or NM_F_TRACE */
 int nm_devpass_multi_ok(const nm_job_t* job_host);
+/* The modality-subset pass (csrc/nm_devpass.hip: nm_devpass_subsets_kernel): every expert's encoder ONCE per 128-row tile,
+ * then for each of n_subsets entries the fusion of the experts in that entry's mask, the latent draw and the decoders the
+ * entry exports -- "the same model with less evidence": the AUC from T1w alone, modality m predicted from the others, rows
+ * with a missing modality.  Per row r and entry s: E = mask_s & present_s[r] (present NULL: every expert); the job's
+ * combiner over E with M replaced by |E| (gpoe: the softmax over the logits of E alone; no single-expert bypass);
+ * z = mu_E + eps[r] exp(logvar_E / 2) with the draw the full pass uses for that row (injected eps or the counter draw), so
+ * every subset of a row sees the same noise.  Exports per decoder as from the several-expert pass above: pad columns 0,
+ * rows from the table's end to the end of its last 256-row tile 0; a row with E empty is NaN (columns < D) in every export
+ * of the entry; a row whose present byte lacks bit m is NaN in out_sqerr[m] / out_rowdev[m] (its x is a placeholder) while
+ * out_loc[m] holds the prediction, the imputation.  A decoder whose three pointers are NULL in an entry is skipped.  The
+ * entry with the full mask and no present bytes writes what the several-expert pass writes, bit for bit.  The table holds
+ * n_jobs x n_subsets entries in device memory, job-major.  Geometry, LDS plan, workspace tiles and the admitted jobs are
+ * those of the several-expert pass (the _ok predicate below is the same predicate); status is decided on the host before
+ * the device is asked anything: NM_E_NULL for a missing array or table, NM_E_GEOMETRY for n_subsets outside
+ * 1..NM_MAX_SUBSETS and the geometry rules of every launch.  The per-entry rules (mask != 0, no bit >= M) are the
+ * caller's, who builds the table. */
+#define NM_MAX_SUBSETS 15
+typedef struct nm_subset_t {
+  uint32_t mask;                     /* bit m: expert m takes part in the fusion */
+  uint32_t reserved;
+  const unsigned char* present;      /* one byte per absolute table row, bit m: expert m was observed; NULL: all were */
+  float* out_loc[NM_MAX_EXP];        /* [rows_alloc][x_pitch of modality m], or NULL */
+  float* out_sqerr[NM_MAX_EXP];
+  float* out_rowdev[NM_MAX_EXP];     /* [rows_alloc] */
+} nm_subset_t;
+int nm_devpass_subsets(const nm_job_t* jobs_dev, int n_jobs, const nm_subset_t* subsets_dev, int n_subsets, int tile0, int n_tiles,
+                       int flags, void* stream);   /* flags: 0 or NM_F_TRACE */
+int nm_devpass_subsets_ok(const nm_job_t* job_host);
 /* The encoder half alone (csrc/nm_devpass.hip: nm_latent_kernel): the joint posterior of every row, what cVAE.pred_latent
  * returns (cVAE.py:539-545), over table rows [tile0 * 128, (tile0 + n_tiles) * 128).  Every expert's encoder and the fusion
  * of nm_forward, no latent draw and no decoder; writes out_mu / out_logvar and nothing else -- bit for bit nm_forward's

@@ -88,6 +88,8 @@ NM_OP_SPEC = 6
 NM_OP_MAX_RULES = 16
 NM_OP_MAX_GRID = 1024
 NM_OP_MAX_LINSPACE = 65536
+# nm_devpass_subsets: the most entries per job (every non-empty set of NM_MAX_EXP experts)
+NM_MAX_SUBSETS = 15
 
 # status codes (nmhip.h; nm_status_string gives the text)
 NM_OK = 0
@@ -164,6 +166,13 @@ class NmJob(C.Structure):
     ]
 
 
+class NmSubset(C.Structure):
+    """nm_subset_t: one entry of nm_devpass_subsets' [n_jobs][n_subsets] table (device memory)."""
+    _fields_ = [("mask", C.c_uint32), ("reserved", C.c_uint32), ("present", C.c_void_p),
+                ("out_loc", C.c_void_p * NM_MAX_EXP), ("out_sqerr", C.c_void_p * NM_MAX_EXP),
+                ("out_rowdev", C.c_void_p * NM_MAX_EXP)]
+
+
 class NmRoiSet(C.Structure):
     """nm_roi_set_t: one matrix of nm_roi_effect's pointer table."""
     _fields_ = [("x", C.c_void_p), ("group", C.c_void_p), ("rows", C.c_int32), ("pitch", C.c_int32)]
@@ -237,6 +246,8 @@ def load():
     lib.nm_devpass_ok.argtypes = [C.POINTER(NmJob)]
     lib.nm_devpass_multi.argtypes = [vp, i32, i32, i32, i32, vp]
     lib.nm_devpass_multi_ok.argtypes = [C.POINTER(NmJob)]
+    lib.nm_devpass_subsets.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp]
+    lib.nm_devpass_subsets_ok.argtypes = [C.POINTER(NmJob)]
     lib.nm_latent_pass.argtypes = [vp, i32, i32, i32, i32, vp]
     lib.nm_latent_pass_ok.argtypes = [C.POINTER(NmJob)]
     lib.nm_latent_stats.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
@@ -312,6 +323,7 @@ EXPORTED_SYMBOLS = [
     "nm_cohort_moments", "nm_normative_z", "nm_cohort_cov", "nm_mahalanobis",
     "nm_operating_points_workspace", "nm_operating_points",
     "nm_cohort_quantiles", "nm_normative_centile_workspace", "nm_normative_centile",
+    "nm_devpass_subsets", "nm_devpass_subsets_ok",
 ]
 
 

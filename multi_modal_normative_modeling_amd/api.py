@@ -215,8 +215,10 @@ class _Base(nn.Module):
         return self._device
 
     def _run(self, xes: Sequence[torch.Tensor], cs: Sequence[torch.Tensor], combine: str, flags: int, eps=None,
-             kl_w=None, ll_w=1.0, recon_only: bool = False, latent_only: bool = False):
-        """latent_only (forward-only calls that read the joint posterior alone -- pred_latent of the multimodal classes): the
+             kl_w=None, ll_w=1.0, recon_only: bool = False, latent_only: bool = False, subsets=None, present=None):
+        """subsets (pred_recon_given: a list of tuples of modality indices): the launch is the modality-subset pass
+        (JobSet.forward_subsets: encoders once, every subset fused and decoded), its reconstructions in job.sub_loc.
+        latent_only (forward-only calls that read the joint posterior alone -- pred_latent of the multimodal classes): the
         launch goes through JobSet.latent(), i.e. on the encoder-only kernel where the model's shape allows (same out_mu /
         out_logvar, bit for bit).
         recon_only (forward-only calls that read the reconstruction alone -- pred_recon): the job's latent exports are
@@ -273,6 +275,11 @@ class _Base(nn.Module):
             # through _publish_grads, every gradient -- then carries; the NmError itself is raised by the next call's upload.
             j.loss_log[0].fill_(float("nan"))
             self._js._launch_split(0, 1, flags | getattr(self, "_fault_inject", 0))
+        elif subsets is not None:
+            subsets = [tuple(int(m) for m in g) for g in subsets]
+            if j.subsets != subsets or j.sub_loc[0][0].shape[0] != j.tables[0].rows_alloc:
+                j.enable_subset_exports(subsets, loc=True, sqerr=False, rowdev=False)
+            self._js.forward_subsets(present, 0, nt)
         elif recon_only and flags == _lib.NM_F_EXPORT:
             self._js.forward(0, nt, loss=False)
         elif latent_only and flags == _lib.NM_F_EXPORT:
@@ -521,6 +528,21 @@ class cVAE_multimodal(_ExpertOps, _Base):
         j, B = self._run(xs, [ct] * self.modalities, combine, _lib.NM_F_EXPORT, recon_only=True)
         return [j.out_loc[m][:B].cpu().numpy() for m in range(self.modalities)]
 
+    def pred_recon_given(self, xes, c, DEVICE, combine, given, present=None):
+        """pred_recon with the joint latent inferred from a SUBSET of the modalities, for every subset of `given` (a list of
+        tuples of modality indices) in one launch: the encoders run once, each subset is fused with the model's combiner
+        over its own experts (gPoE: the softmax over their logits alone), drawn with the same noise, and decoded.  Returns,
+        per subset, pred_recon's list per modality -- the same model with less evidence: `given=[(0,)]` reconstructs every
+        modality from the first alone, `given=[(1, 2)]`'s first element predicts modality 0 from the others.  present: one
+        integer per subject, bit m set where modality m was observed (a missing modality's x is a placeholder); a subject
+        with none of a subset's modalities observed comes back as NaN."""
+        xs = [torch.tensor(np.asarray(x.values if hasattr(x, "values") else x), dtype=torch.float32) for x in xes]
+        ct = torch.tensor(np.asarray(c), dtype=torch.long)
+        self._dev()
+        given = [tuple(g) for g in given]
+        j, B = self._run(xs, [ct] * self.modalities, combine, _lib.NM_F_EXPORT, recon_only=True, subsets=given, present=present)
+        return [[j.sub_loc[s][m][:B].cpu().numpy() for m in range(self.modalities)] for s in range(len(given))]
+
     def pred_latent(self, xes, c, DEVICE, combine):
         """The joint counterpart of cVAE.pred_latent (cVAE.py:539-545): DataFrames in, (mu_joint, var_joint) as numpy out."""
         mu, logvar = self._latent_joint(list(xes), c, combine)
@@ -703,6 +725,9 @@ class mmJSD(cVAE_multimodal):
     def pred_recon(self, xes, c, DEVICE, combine):
         return super().pred_recon(xes, c, DEVICE, "poe")
 
+    def pred_recon_given(self, xes, c, DEVICE, combine, given, present=None):
+        return super().pred_recon_given(xes, c, DEVICE, "poe", given, present)
+
     def pred_latent(self, xes, c, DEVICE, combine="poe"):
         return super().pred_latent(xes, c, DEVICE, "poe")
 
@@ -848,6 +873,9 @@ class cVAE_multimodal_regression(_ExpertOps, _HeadBase):
 
     def pred_latent(self, xes, c, DEVICE, combine):
         return cVAE_multimodal.pred_latent(self, xes, c, DEVICE, combine)
+
+    def pred_recon_given(self, xes, c, DEVICE, combine, given, present=None):
+        return cVAE_multimodal.pred_recon_given(self, xes, c, DEVICE, combine, given, present)
 
     def encode(self, x, c, m):
         return cVAE_multimodal.encode(self, x, c, m)

@@ -577,6 +577,371 @@ __global__ __launch_bounds__(WG, 4) void nm_devpass_multi_kernel(const nm_job_t*
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// nm_devpass_subsets_kernel -- the pass above with the experts of every row fused n_subsets times, each time over another
+// subset of them: encoders once per tile, then per entry of the job's nm_subset_t row the fusion under that entry's mask,
+// the latent draw, and the decoders the entry exports (nm_devpass_multi_kernel's source stays as it is: its decoder loop is
+// repeated here with the export pointers taken from the entry).
+//
+// Per row r and entry s: E = mask_s & present_s[r] (no present bytes: every expert).  The combiner is fuse_fwd's with the
+// sums over E and |E| in the place of M (dvs_fuse / dvs_softmax below keep its operations in its order, fp contraction
+// off: under the full mask they ARE fuse_fwd / softmax_alpha, which is what makes the full-mask entry equal
+// nm_devpass_multi_kernel bit for bit); never the single-expert bypass.  The draw is the full pass's draw of that row.
+// A row with E empty gets z = 0 and NaN exports; a row whose present byte lacks bit m gets NaN in out_sqerr[m] /
+// out_rowdev[m] (x is a placeholder there), out_loc[m] stays the prediction.
+//
+// Geometry, LDS plan (P, W, vector slots, scalars, Z [128][32] bf16), workspace tile and dvm_refused domain are those of
+// nm_devpass_multi_kernel; the LDS plan grows by the gPoE weights of every expert set, [16][4] fp32 (256 bytes), computed
+// once per workgroup: with present bytes the set differs from row to row.
+constexpr int DVS_AL_BYTES = (1 << NM_MAX_EXP) * NM_MAX_EXP * 4;      // 256
+constexpr int DVS_SMEM = DVM_SMEM + DVS_AL_BYTES;
+static_assert(2 * DVS_SMEM <= 160 * 1024, "two workgroups per CU");
+static_assert((DVM_SMEM & 15) == 0, "alpha table alignment");
+static_assert(NM_MAX_SUBSETS == (1 << NM_MAX_EXP) - 1, "every non-empty expert set");
+
+// softmax_alpha over the experts of E alone (E = every expert: softmax_alpha itself, operation by operation)
+__device__ __forceinline__ void dvs_softmax(const nm_job_t* J, unsigned E, float (&al)[NM_MAX_EXP]) {
+#pragma clang fp contract(off)
+  float mx = -INFINITY;
+#pragma unroll
+  for (int m = 0; m < NM_MAX_EXP; ++m)
+    if ((E >> m) & 1u) mx = fmaxf(mx, asg(J->params)[J->mod[m].alpha]);
+  float s = 0.f;
+#pragma unroll
+  for (int m = 0; m < NM_MAX_EXP; ++m) {
+    al[m] = ((E >> m) & 1u) ? fx_exp(asg(J->params)[J->mod[m].alpha] - mx) : 0.f;
+    s += al[m];
+  }
+  const float rs_ = fx_rcp(s);
+#pragma unroll
+  for (int m = 0; m < NM_MAX_EXP; ++m) al[m] *= rs_;
+}
+// fuse_fwd over the experts of E (non-empty) with nE = |E| in the place of M, without the single-expert bypass
+__device__ __forceinline__ Fuse dvs_fuse(const nm_job_t* J, const Lat& L, const float (&al)[NM_MAX_EXP], unsigned E, float nE) {
+#pragma clang fp contract(off)
+  Fuse f;
+  const int cb = J->combine;
+  float S = 0.f, Smu = 0.f, sm = 0.f, sv = 0.f;
+#pragma unroll
+  for (int m = 0; m < NM_MAX_EXP; ++m) {
+    if ((E >> m) & 1u) {
+      float var = fx_exp(L.lv[m]);
+      float w = (cb == NM_COMBINE_POE2V) ? fx_exp(-var) : ((cb == NM_COMBINE_GPOE) ? al[m] * fx_rcp(var) : fx_rcp(var));
+      S += w; Smu += L.mu[m] * w;
+      sm += L.mu[m]; sv += var;
+    }
+  }
+  if (cb == NM_COMBINE_MOE) { f.mu = sm * fx_rcp(nE); f.var = sv * fx_rcp(nE); }
+  else {
+    f.var = fx_rcp(S); f.mu = Smu * f.var;
+    if (cb == NM_COMBINE_MOPOE) { f.mu = (sm + f.mu) * fx_rcp(nE + 1.0f); f.var = (sv + f.var) * fx_rcp(nE + 1.0f); }
+    if (cb == NM_COMBINE_POE2V) f.var = fx_log(fx_rcp(S));
+  }
+  if (J->var_floor > 0.f) f.var = fmaxf(f.var, J->var_floor);
+  f.lv = fx_log(f.var);
+  return f;
+}
+
+// dv_zero_dead_rows with the export pointers of one (entry, decoder)
+__device__ __forceinline__ void dvs_zero_dead_rows(int tid, int xp, gf32 oloc, gf32 osq, gf32 ordv, int row0, int live) {
+  const int r16 = rup(live, 16);
+  for (int e = tid; e < (DV_ROWS - r16) * (xp >> 2); e += WG) {
+    const int64_t gi = (int64_t)(row0 + r16) * xp + (int64_t)e * 4;
+    if (oloc) *(GAS f32x4*)(oloc + gi) = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (osq) *(GAS f32x4*)(osq + gi) = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  if (ordv)
+    for (int r = live + tid; r < DV_ROWS; r += WG) ordv[row0 + r] = 0.f;
+}
+
+__global__ __launch_bounds__(WG, 4) void nm_devpass_subsets_kernel(const nm_job_t* __restrict__ jobs, const nm_subset_t* __restrict__ subsets,
+                                                                     int n_subsets, int tile0, int flags) {
+  constexpr int RT = DV_RT, ROWS = DV_ROWS;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const nm_job_t* J = jobs + blockIdx.x;
+  if (dvm_refused(J) || !J->workspace || n_subsets < 1 || n_subsets > NM_MAX_SUBSETS) return;
+  const nm_subset_t* const subs = subsets + (int64_t)blockIdx.x * n_subsets;
+  const int M = J->M;
+  const int t128 = tile0 + (int)blockIdx.y;
+  const int row0 = t128 * ROWS;
+  if (row0 >= J->n_rows) {
+    // the second half of a ragged last 256-row tile: every entry's export rows come back as zeros
+    if (row0 < (J->n_rows + TROWS - 1) / TROWS * TROWS)
+      for (int s = 0; s < n_subsets; ++s)
+        for (int m = 0; m < M; ++m)
+          dvs_zero_dead_rows((int)threadIdx.x, J->mod[m].x_pitch, asg(subs[s].out_loc[m]), asg(subs[s].out_sqerr[m]), asg(subs[s].out_rowdev[m]), row0, 0);
+    return;
+  }
+  Ctx c;
+  c.job = J;
+  c.part = -1; c.nparts = 1; c.lstep = 0;
+  c.slope = J->act_slope;
+  dv_carve(c, smem);
+  relaunder(c);
+  c.flags = NM_F_EXPORT | (flags & NM_F_TRACE);
+  c.t_last = 0;
+  c.ws = (GAS char*)J->workspace + (int64_t)(t128 / 2 - tile0 / 2) * J->workspace_stride;
+  for (int i = c.tid; i < DVS_SMEM / 4; i += WG) reinterpret_cast<uint32_t*>(smem)[i] = 0u;
+  __syncthreads();
+  if (c.flags & 64) c.tlast[c.wave_s] = clock64();
+  c.row0 = row0;
+  c.rloc0 = row0 % TROWS;
+  c.nrows = min(ROWS, J->n_rows - row0);
+  c.inv_b = 1.0f / (float)c.nrows;
+  const int live = c.nrows;
+  const int step = row0 / TROWS;
+  const int L = J->L, Z = J->Z, C = J->C;
+  const int Zs = rup(Z, 16);
+  const bool nl = J->non_linear != 0;
+  const bool vec4 = (Z & 3) == 0;
+  const unsigned all_m = (1u << M) - 1u;
+  GAS char* const wsh = (GAS char*)J->wsh;
+  char* const Wb = reinterpret_cast<char*>(c.Q);
+  __bf16* const zlds = reinterpret_cast<__bf16*>(smem + DV_SMEM);
+  float* const altab = reinterpret_cast<float*>(smem + DVM_SMEM);    // [16 expert sets][4]: gPoE weights (zeros otherwise)
+  const WsLayout wl = ws_layout(M, L, Z);
+  gf32 ws_mu_m = (gf32)(c.ws + wl.mu_m) + c.rloc0 * Zs;
+  gf32 ws_lv_m = (gf32)(c.ws + wl.lv_m) + c.rloc0 * Zs;
+  auto to_W = [&](const GAS char* blob, int vs, int rows, int K) {
+    return Next{blob, Wb, IMG_BYTES >> 10, blob + cimg_bytes(rows, K), reinterpret_cast<char*>(c.vec) + vs * VEC_BYTES, rows, blob_kp(K)};
+  };
+
+  // ---- encoders: every expert's chain ONCE, statistics to the workspace ----
+  for (int m = 0; m < M; ++m) {
+    relaunder(c);
+    const nm_modality_t& md = J->mod[m];
+    const int nch = (md.Kx + XCH - 1) / XCH;
+    const GAS char* after0 = wsh + (L > 1 ? md.enc_s[1] : md.heads_s);
+    fwd_first_layer<RT>(c, (const GAS char*)asg(md.xb) + (int64_t)(row0 / TROWS) * nch * XIMG_TILE_BYTES + (int64_t)c.rloc0 * (LDX * 2),
+                        md.Kx, wsh + md.enc_s[0], to_W(after0, 0, L > 1 ? J->H[1] : 2 * Zs, J->H[0]), J->H[0], nl, (gbf16)nullptr, true,
+                        DV_W0_PIECES, live);
+    int vs = 0;
+    for (int e = 1; e < L; ++e) {
+      const GAS char* nxt = wsh + (e + 1 < L ? md.enc_s[e + 1] : md.heads_s);
+      dv_layer(c, vs, to_W(nxt, vs ^ 1, e + 1 < L ? J->H[e + 1] : 2 * Zs, J->H[e]), J->H[e], J->H[e - 1], nl, live);
+      vs ^= 1;
+    }
+    tr(c, 1);
+    wait_vm(0);
+    fwd_heads<RT>(c, 0, no_next(), Z, J->H[L - 1], ws_mu_m + (int64_t)m * TROWS * Zs, ws_lv_m + (int64_t)m * TROWS * Zs, Zs, 0,
+                  (__bf16*)nullptr, step, vec4, (float*)nullptr, c.vec + vs * (VEC_BYTES / 4));
+  }
+  // the gPoE weights of every expert set (thread t: set t; set 0 stays zeros), published by the barrier below
+  if (J->combine == NM_COMBINE_GPOE && c.tid > 0 && c.tid <= (int)all_m) {
+    float a4[NM_MAX_EXP];
+    dvs_softmax(J, (unsigned)c.tid, a4);
+#pragma unroll
+    for (int m = 0; m < NM_MAX_EXP; ++m) altab[c.tid * NM_MAX_EXP + m] = a4[m];
+  }
+  handoff_barrier();                               // the heads' stores are complete for every thread of the workgroup
+
+  // ---- the entries: fusion under the mask + the latent draw -> LDS, then the decoders the entry exports ----
+  const int Hl = J->H[0];
+  const int ob = L & 1;                            // (see nm_devpass_kernel: chunk 0's vectors avoid the last hidden layer's bias)
+  for (int s = 0; s < n_subsets; ++s) {
+    relaunder(c);
+    const nm_subset_t& en = subs[s];
+    const unsigned mask = en.mask & all_m;
+    const GAS unsigned char* const pres = asg(en.present);
+    int mf = -1;                                   // the first decoder this entry exports
+    for (int m = M - 1; m >= 0; --m)
+      if (en.out_loc[m] || en.out_sqerr[m] || en.out_rowdev[m]) mf = m;
+    if (mf < 0) continue;                          // (workgroup-uniform)
+    if (s > 0) lds_barrier();                      // the previous entry's last chunk is finished everywhere: P, W, vectors, Z free
+    // W and P are free: the first decoder's image lands during the latent arithmetic
+    issue_next(c, to_W(wsh + J->mod[mf].dec_s[0], 0, J->H[L - 1], Z + C));
+    if (vec4) {
+      const int nq4 = (Z + 3) >> 2;
+      const float rq4 = 1.0f / (float)nq4;
+#pragma unroll 1
+      for (int e = c.tid; e < ROWS * nq4; e += WG) {
+        const int r = idiv(e, nq4, rq4), z0 = 4 * (e - r * nq4);
+        const unsigned E = (pres && r < live) ? (mask & (unsigned)pres[row0 + r]) : mask;
+        const float nE = (float)__popc(E);
+        float al[NM_MAX_EXP];
+#pragma unroll
+        for (int m = 0; m < NM_MAX_EXP; ++m) al[m] = altab[E * NM_MAX_EXP + m];
+        f32x4 mu4[NM_MAX_EXP], lv4[NM_MAX_EXP];
+#pragma unroll
+        for (int m = 0; m < NM_MAX_EXP; ++m) {
+          mu4[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+          lv4[m] = mu4[m];
+          if (m < M) {
+            mu4[m] = *(const GAS f32x4*)(ws_mu_m + ((int64_t)m * TROWS + r) * Zs + z0);
+            lv4[m] = *(const GAS f32x4*)(ws_lv_m + ((int64_t)m * TROWS + r) * Zs + z0);
+          }
+        }
+        float ep[4];
+        if (J->eps) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) ep[i] = asg(J->eps)[((int64_t)(step % J->eps_cap) * TROWS + c.rloc0 + r) * Z + min(z0 + i, Z - 1)];
+        } else {
+          randn2_ctr(J->seed, (uint32_t)step, (uint32_t)(c.row0 + r), (uint32_t)(z0 >> 1), ep[0], ep[1]);
+          randn2_ctr(J->seed, (uint32_t)step, (uint32_t)(c.row0 + r), (uint32_t)(z0 >> 1) + 1u, ep[2], ep[3]);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ep[i] = (z0 + i < Z) ? ep[i] : 0.f;
+        bf16x4 zk;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          Lat Lt;
+#pragma unroll
+          for (int m = 0; m < NM_MAX_EXP; ++m) { Lt.mu[m] = mu4[m][i]; Lt.lv[m] = lv4[m][i]; }
+          const Fuse f = dvs_fuse(J, Lt, al, E, nE);
+          const float es = ep[i] * fx_exp(0.5f * f.lv);
+          zk[i] = (__bf16)(E ? dvm_add(f.mu, es) : 0.f);
+        }
+        *reinterpret_cast<bf16x4*>(zlds + r * 32 + z0) = zk;
+      }
+    } else {
+      const float rZ = 1.0f / (float)Z;
+#pragma unroll 1
+      for (int e = c.tid; e < ROWS * Z; e += WG) {
+        const int r = idiv(e, Z, rZ), z = e - r * Z;
+        const unsigned E = (pres && r < live) ? (mask & (unsigned)pres[row0 + r]) : mask;
+        const float nE = (float)__popc(E);
+        float al[NM_MAX_EXP];
+#pragma unroll
+        for (int m = 0; m < NM_MAX_EXP; ++m) al[m] = altab[E * NM_MAX_EXP + m];
+        Lat Lt;
+#pragma unroll
+        for (int m = 0; m < NM_MAX_EXP; ++m) {
+          Lt.mu[m] = (m < M) ? ws_mu_m[((int64_t)m * TROWS + r) * Zs + z] : 0.f;
+          Lt.lv[m] = (m < M) ? ws_lv_m[((int64_t)m * TROWS + r) * Zs + z] : 0.f;
+        }
+        const Fuse f = dvs_fuse(J, Lt, al, E, nE);
+        const float ep = J->eps ? asg(J->eps)[((int64_t)(step % J->eps_cap) * TROWS + c.rloc0 + r) * Z + z]
+                                : randn_ctr(J->seed, (uint32_t)step, (uint32_t)(c.row0 + r), (uint32_t)z);
+        const float es = ep * fx_exp(0.5f * f.lv);
+        zlds[r * 32 + z] = (__bf16)(E ? dvm_add(f.mu, es) : 0.f);
+      }
+    }
+    lds_barrier();                                 // z is complete (the decoder image requested above stays in flight)
+    tr(c, 3);
+
+    for (int m = mf; m < M; ++m) {
+      relaunder(c);
+      const gf32 oloc = asg(en.out_loc[m]), osq = asg(en.out_sqerr[m]), ordv = asg(en.out_rowdev[m]);
+      if (!oloc && !osq && !ordv) continue;        // (workgroup-uniform) nothing of this decoder is wanted: skipped entirely
+      const nm_modality_t& md = J->mod[m];
+      const int D = md.D;
+      if (m != mf) {
+        lds_barrier();                             // the previous decoder's last chunk is finished everywhere: P, W, vectors free
+        issue_next(c, to_W(wsh + md.dec_s[0], 0, J->H[L - 1], Z + C));
+      }
+      build_zc<RT>(c, c.P, md, (gcf32)nullptr, (gcf32)nullptr, Z, C, Zs, 0, (gcf32)nullptr, zlds);
+      tr(c, 4);
+      int vs = 0;
+      const GAS char* oblob = wsh + md.out_s;
+      const int nck = (D + OCH - 1) / OCH;
+      auto out_blob = [&](int ch) {
+        return Next{oblob + (int64_t)ch * OBLOB_BYTES, Wb + (ch & 1) * OIMG_BYTES, OIMG_BYTES >> 10,
+                    oblob + (int64_t)ch * OBLOB_BYTES + OIMG_BYTES, reinterpret_cast<char*>(c.vec) + ((ch + ob) & 1) * VEC_BYTES, 0, 0};
+      };
+      for (int d = 0; d < L; ++d) {
+        const int Kin = (d == 0) ? Z + C : J->H[L - d], Nout = J->H[L - 1 - d];
+        const Next nx = (d + 1 < L) ? to_W(wsh + md.dec_s[d + 1], vs ^ 1, J->H[L - 2 - d], Nout) : out_blob(0);
+        dv_layer(c, vs, nx, Nout, Kin, nl, live);    // (its first barrier also publishes z | c | 1)
+        vs ^= 1;
+      }
+      tr(c, 5);
+      // output layer in 64-ROI chunks, wave w owns rows [16 w, 16 w + 16) and all 64 columns: see nm_devpass_kernel
+      gcf32 xf = asg(md.x_f32);
+      const int xp = md.x_pitch;
+      float rdev = 0.f;
+      const int orow = c.wave * 16 + c.c16;
+      const bool wave_live = c.wave * 16 < live;
+      const bool rv = orow < c.nrows;
+      // this lane's row: its observed experts (read once), whether anything was fused, whether x of this modality is real
+      const unsigned prow = (pres && rv) ? (unsigned)pres[row0 + orow] : all_m;
+      const bool none = (mask & prow) == 0u;
+      const bool xmiss = none || ((prow >> m) & 1u) == 0u;
+      const float qnan = __builtin_nanf("");
+      auto load_xin = [&](int chx, f32x4 (&xv)[4]) {
+#pragma unroll
+        for (int ft = 0; ft < 4; ++ft) {
+          const int dcl = min(chx * OCH + ft * 16 + 4 * c.g, xp - 4);
+          xv[ft] = *(const GAS f32x4*)(xf + (int64_t)(row0 + orow) * xp + dcl);
+        }
+      };
+      int stores_prev = 0;
+      auto chunk = [&](const int ch, f32x4 (&xin)[4], f32x4 (&xnx)[4]) {
+        relaunder(c);
+        const int d0 = ch * OCH;
+        const __bf16* Wc = reinterpret_cast<const __bf16*>(Wb + (ch & 1) * OIMG_BYTES);
+        const float* vb = c.vec + ((ch + ob) & 1) * (VEC_BYTES / 4);
+        wait_vm(ch > 0 ? stores_prev : 0);
+        lds_barrier();
+        if (ch + 1 < nck) { issue_next(c, out_blob(ch + 1)); if (wave_live) load_xin(ch + 1, xnx); }
+        stores_prev = 0;
+        if (!wave_live) return;
+        f32x4 acc[4];
+#pragma unroll
+        for (int ft = 0; ft < 4; ++ft) acc[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
+        const int ksteps = wpad(Hl) / 32;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+          if (ks < ksteps) {
+            const bf16x8 a = lds_frag(c.P, LDP, orow, ks * 32 + 8 * c.g);
+#pragma unroll
+            for (int ft = 0; ft < 4; ++ft) acc[ft] = mfma(lds_frag(Wc, LDP, ft * 16 + c.c16, ks * 32 + 8 * c.g), a, acc[ft]);
+          }
+        }
+        tr(c, 6);
+        const bool full = live == ROWS && d0 + OCH <= D && !pres;         // no row / column / presence masks needed (wave-uniform)
+#pragma unroll
+        for (int ft = 0; ft < 4; ++ft) {
+          const int dg0 = d0 + ft * 16 + 4 * c.g;
+          const f32x4 bo = *reinterpret_cast<const f32x4*>(vb + ft * 16 + 4 * c.g);
+          f32x4 lo, sq;
+          if (full) {
+            lo = acc[ft] + bo;
+            const f32x4 diff = lo - xin[ft];
+            sq = diff * diff;
+          } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const float xh = acc[ft][i] + bo[i];
+              const bool dv = rv && dg0 + i < D;
+              const float diff = xh - xin[ft][i];
+              lo[i] = dv ? (none ? qnan : xh) : 0.f;
+              sq[i] = dv ? (xmiss ? qnan : diff * diff) : 0.f;
+            }
+          }
+          rdev += ((sq[0] + sq[1]) + sq[2]) + sq[3];
+          if (d0 + ft * 16 < xp) {                      // wave-uniform
+            if (dg0 < xp) {
+              const int64_t gi = (int64_t)(row0 + orow) * xp + dg0;
+              if (oloc) *(GAS f32x4*)(oloc + gi) = lo;
+              if (osq) *(GAS f32x4*)(osq + gi) = sq;
+            }
+            stores_prev += (oloc ? 1 : 0) + (osq ? 1 : 0);
+          }
+        }
+        tr(c, 7);
+      };
+      {
+        f32x4 xa[4], xb[4];
+        if (wave_live) load_xin(0, xa);
+        for (int ch = 0; ch < nck; ch += 2) {
+          chunk(ch, xa, xb);
+          if (ch + 1 < nck) chunk(ch + 1, xb, xa);
+        }
+      }
+      if (ordv && wave_live) {
+        float v = rdev;
+        v += __shfl_xor(v, 16, 64);
+        v += __shfl_xor(v, 32, 64);
+        if (c.g == 0 && orow < c.nrows) ordv[row0 + orow] = v / (float)D;
+      }
+      // (a ragged tile only: the rows no wave has stored; the laundered thread index keeps the loop's addresses from being
+      //  hoisted out of the entry loop and held in registers across it)
+      if (live < ROWS) { relaunder(c); dvs_zero_dead_rows(c.tid, xp, oloc, osq, ordv, row0, live); }
+      tr(c, 8);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // nm_latent_kernel -- the encoder half of the pass above and nothing else: the joint posterior (mu, logvar) of every row,
 // what cVAE.pred_latent returns (cVAE.py:539-545) and latent_deviation / separate_latent_deviation score against the
 // training cohort (utils_vae.py:155-161).  No latent draw, no z | c | 1, no decoder, no output chunks.
@@ -833,6 +1198,25 @@ int nm_devpass_multi_ok(const nm_job_t* j) {
 int nm_devpass_multi(const nm_job_t* jobs_dev, int n_jobs, int tile0, int n_tiles, int flags, void* stream) {
   if (int bad = check_launch_geometry(jobs_dev, n_jobs, n_tiles, 1, tile0, 0)) return bad;
   return launch_kernel(nm_devpass_multi_kernel, dim3(n_jobs, n_tiles), dim3(WG), DVM_SMEM, stream, jobs_dev, tile0, flags & NM_F_TRACE);
+}
+
+/* The predicate of nm_devpass_multi_ok: the subset pass runs the same encoders and decoders in the same LDS plan. */
+int nm_devpass_subsets_ok(const nm_job_t* j) {
+  if (!j) return NM_E_NULL;
+  return dvm_refused(j);
+}
+
+/* The modality-subset pass over table rows [tile0 * 128, (tile0 + n_tiles) * 128): encoders once per tile, then per entry of
+ * subsets_dev[job][0 .. n_subsets) the fusion under the entry's mask, the draw and the decoders the entry exports (nmhip.h).
+ * Status is decided here, on the host, before the device is asked anything -- the table and the descriptors live in device
+ * memory: the per-entry rules (mask != 0, no bit >= M) are the caller's.  Workspace tiles as for nm_devpass_multi. */
+int nm_devpass_subsets(const nm_job_t* jobs_dev, int n_jobs, const nm_subset_t* subsets_dev, int n_subsets, int tile0, int n_tiles,
+                       int flags, void* stream) {
+  if (!jobs_dev || !subsets_dev) return NM_E_NULL;
+  if (n_subsets < 1 || n_subsets > NM_MAX_SUBSETS) return NM_E_GEOMETRY;
+  if (int bad = check_launch_geometry(jobs_dev, n_jobs, n_tiles, 1, tile0, 0)) return bad;
+  return launch_kernel(nm_devpass_subsets_kernel, dim3(n_jobs, n_tiles), dim3(WG), DVS_SMEM, stream, jobs_dev, subsets_dev, n_subsets,
+                       tile0, flags & NM_F_TRACE);
 }
 
 /* 0: the job's joint latent statistics can come from the encoder-only kernel (not wide; 1..NM_MAX_EXP modalities, every one

@@ -212,6 +212,9 @@ class Job:
         self.out_loc: List[Optional[torch.Tensor]] = [None] * nk
         self.out_sqerr: List[Optional[torch.Tensor]] = [None] * nk
         self.out_rowdev: List[Optional[torch.Tensor]] = [None] * nk
+        # the modality-subset pass (enable_subset_exports): the subsets, their expert masks, exports per (subset, modality)
+        self.subsets = self.sub_masks = self.sub_decoders = None
+        self.sub_loc = self.sub_sqerr = self.sub_rowdev = None
 
     # -- buffers -------------------------------------------------------------------------------
     def _ensure_workspace(self, n_tiles: int):
@@ -397,6 +400,64 @@ class Job:
             self.out_loc[j] = torch.zeros(ra, t.x_pitch, device=self.device)[:, :t.D] if loc else None
             self.out_sqerr[j] = torch.zeros(ra, t.x_pitch, device=self.device)[:, :t.D] if sqerr else None
             self.out_rowdev[j] = torch.zeros(ra, device=self.device) if rowdev else None
+
+    def enable_subset_exports(self, subsets, loc=True, sqerr=True, rowdev=True, decoders=None):
+        """Buffers of the modality-subset pass (JobSet.forward_subsets, nm_devpass_subsets).  subsets: a list of 1 to 15
+        tuples of expert indices, each the experts one entry fuses; decoders: per subset the modalities to decode (None:
+        every one) -- a decoder left out of an entry is skipped by the kernel.  Afterwards sub_loc[s][m], sub_sqerr[s][m]
+        ([rows_alloc, D] views) and sub_rowdev[s][m] ([rows_alloc]) hold entry s's exports of modality m, None where the
+        decoder or the kind of export was not asked for.  Refused (ValueError): an empty subset, an index beyond the
+        model's experts, the same subset twice, no subset or more than 15."""
+        M = len(self.kmods)
+        subsets = [tuple(int(i) for i in s) for s in subsets]
+        if not 1 <= len(subsets) <= _lib.NM_MAX_SUBSETS:
+            raise ValueError(f"need 1 to {_lib.NM_MAX_SUBSETS} subsets, got {len(subsets)}")
+        masks = []
+        for s in subsets:
+            if not s:
+                raise ValueError("an empty subset has no joint posterior (mask 0)")
+            if any(i < 0 or i >= M or i >= _lib.NM_MAX_EXP for i in s):
+                raise ValueError(f"subset {s}: the model has experts 0..{min(M, _lib.NM_MAX_EXP) - 1}")
+            mask = 0
+            for i in s:
+                mask |= 1 << i
+            if mask in masks:
+                raise ValueError(f"subset {s} is listed twice")
+            masks.append(mask)
+        if decoders is None:
+            decoders = [tuple(range(M))] * len(subsets)
+        decoders = [tuple(int(m) for m in d) for d in decoders]
+        if len(decoders) != len(subsets) or any(m < 0 or m >= M for d in decoders for m in d):
+            raise ValueError(f"decoders: one list of modalities 0..{M - 1} per subset")
+        ra = self.tables[0].rows_alloc
+        self.subsets, self.sub_masks, self.sub_decoders = subsets, masks, decoders
+        self.sub_loc, self.sub_sqerr, self.sub_rowdev = [], [], []
+        for d in decoders:
+            pitch = [self.tables[m].x_pitch for m, _, _ in self.kmods]
+            width = [self.tables[m].D for m, _, _ in self.kmods]
+            self.sub_loc.append([torch.zeros(ra, pitch[m], device=self.device)[:, :width[m]] if loc and m in d else None
+                                 for m in range(M)])
+            self.sub_sqerr.append([torch.zeros(ra, pitch[m], device=self.device)[:, :width[m]] if sqerr and m in d else None
+                                   for m in range(M)])
+            self.sub_rowdev.append([torch.zeros(ra, device=self.device) if rowdev and m in d else None for m in range(M)])
+        self._version += 1
+
+    def subset_structs(self, present=None):
+        """This job's row of nm_devpass_subsets' table: one NmSubset per entry.  present: per entry a uint8 device tensor
+        [rows_alloc] or None."""
+        if getattr(self, "sub_masks", None) is None:
+            raise ValueError("enable_subset_exports() first")
+        out = []
+        for s, mask in enumerate(self.sub_masks):
+            e = _lib.NmSubset()
+            e.mask = mask
+            p = present[s] if present is not None else None
+            e.present = p.data_ptr() if p is not None else None
+            for m in range(len(self.kmods)):
+                for field, bufs in (("out_loc", self.sub_loc), ("out_sqerr", self.sub_sqerr), ("out_rowdev", self.sub_rowdev)):
+                    getattr(e, field)[m] = bufs[s][m].data_ptr() if bufs[s][m] is not None else None
+            out.append(e)
+        return out
 
     def set_latent_exports(self, on: bool):
         """Switch the joint-latent exports (out_mu / out_logvar / out_z) of a job that has them off and back on; the
@@ -861,6 +922,88 @@ class JobSet:
             self._issue("nm_devpass_multi", nt, tile0 * 2, nt * 2, _lib.NM_F_TRACE if trace else 0)
             return
         self._launch(tile0, 1, nt, _lib.NM_F_EXPORT)
+
+    def _subsets_refusal(self) -> Optional[str]:
+        """Why the set cannot run the modality-subset pass (nm_devpass_subsets_ok asked of every job's descriptor, once per
+        state of the descriptor); None: it can."""
+        if self.wide:
+            return "general-shape path (a hidden width or latent beyond the fused kernel's tile)"
+        for i, j in enumerate(self.jobs):
+            if getattr(j, "_sub_ok_version", None) == j._version:
+                continue
+            st = self.lib.nm_devpass_subsets_ok(C.byref(j.struct()))
+            if st != 0:
+                s = j.spec
+                return (f"job {i}: nm_devpass_subsets_ok refuses it with status {st} "
+                        f"({self.lib.nm_status_string(st).decode()}): kind {s.kind!r}, {s.M} modalities of which "
+                        f"{len(j.kmods)} in the kernel, hidden {list(s.hidden)}, latent {s.latent}, private {s.n_private}, "
+                        f"tc_weight {j.tc_weight} -- the pass takes 2..{_lib.NM_MAX_EXP} experts, first hidden width <= 112, "
+                        f"latent rounded to 16 <= 32, no end-to-end trunk")
+            j._sub_ok_version = j._version
+        return None
+
+    def _present_rows(self, present):
+        """present of forward_subsets -> per job a list of per-entry uint8 device tensors [rows_alloc] (or None)."""
+        if present is None:
+            return [None] * len(self.jobs)
+        per_job = list(present) if isinstance(present, (list, tuple)) else [present] * len(self.jobs)
+        if len(per_job) != len(self.jobs):
+            raise ValueError(f"present: one entry per job ({len(self.jobs)}), got {len(per_job)}")
+        out = []
+        for j, p in zip(self.jobs, per_job):
+            ns, N, ra = len(j.sub_masks), j.tables[0].N, j.tables[0].rows_alloc
+            per_sub = list(p) if isinstance(p, (list, tuple)) else [p] * ns
+            if len(per_sub) != ns:
+                raise ValueError(f"present: one entry per subset ({ns}), got {len(per_sub)}")
+            row, cache = [], {}
+            for q in per_sub:
+                if q is None:
+                    row.append(None)
+                    continue
+                if id(q) not in cache:
+                    t = torch.as_tensor(np.asarray(q) if not torch.is_tensor(q) else q).reshape(-1)
+                    if t.numel() != N:
+                        raise ValueError(f"present has {t.numel()} values for {N} table rows")
+                    if t.dtype == torch.bool or t.is_floating_point() or int(t.min()) < 0 or int(t.max()) >= (1 << len(j.kmods)):
+                        raise ValueError(f"present: one integer per row, bit m set where expert m was observed "
+                                         f"(0..{(1 << len(j.kmods)) - 1})")
+                    buf = torch.zeros(ra, dtype=torch.uint8, device=self.device)
+                    buf[:N] = t.to(device=self.device, dtype=torch.uint8)
+                    cache[id(q)] = buf
+                row.append(cache[id(q)])
+            out.append(row)
+        return out
+
+    def forward_subsets(self, present=None, tile0: int = 0, n_tiles: Optional[int] = None, trace: bool = False):
+        """The modality-subset pass (nm_devpass_subsets): every expert's encoder once per 128-row tile, then per subset of
+        Job.enable_subset_exports the fusion of that subset's experts, the latent draw -- the full pass's draw of the row,
+        the same for every subset -- and the decoders the subset exports, into job.sub_loc / sub_sqerr / sub_rowdev.  All
+        jobs of the set in one launch; they must list the same number of subsets.  present: which experts each row has
+        observed -- one integer per table row, bit m for expert m -- as one array (every job and subset), a list per job, or
+        per job a list per subset (None entries: all observed); row r of a subset then fuses the subset's experts that r
+        has observed, a row with none of them comes back as NaN, and so do out_sqerr / out_rowdev of a modality the row has
+        not observed (its reconstruction is the imputation).  A set holding a job the kernel does not take (general-shape
+        path, first hidden width > 112, latent rounded to 16 > 32, an end-to-end trunk, one expert) raises ValueError
+        naming the refusal.  trace: the kernel records its phase cycles (nm_trace_read_dv)."""
+        if any(j.sub_masks is None for j in self.jobs):
+            raise ValueError("forward_subsets: Job.enable_subset_exports() first, on every job of the set")
+        ns = len(self.jobs[0].sub_masks)
+        if any(len(j.sub_masks) != ns for j in self.jobs):
+            raise ValueError("forward_subsets: the jobs of one set must list the same number of subsets")
+        why = self._subsets_refusal()
+        if why is not None:
+            raise ValueError("forward_subsets: the set cannot run on nm_devpass_subsets: " + why)
+        # the table on the device: rebuilt when a job's descriptor (and with it, maybe, its subset buffers) changed or presence
+        # bytes are handed in; kept until then -- the launch reads it, and the presence bytes, in stream order
+        sig = tuple(j._version for j in self.jobs) if present is None else None
+        if sig is None or getattr(self, "_sub_sig", None) != sig:
+            rows = self._present_rows(present)
+            table = [e for j, p in zip(self.jobs, rows) for e in j.subset_structs(p)]
+            arr = (_lib.NmSubset * len(table))(*table)
+            self._sub_keep = (torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device), rows)
+            self._sub_sig = sig
+        nt = self.jobs[0].tables[0].n_tiles if n_tiles is None else n_tiles
+        self._issue("nm_devpass_subsets", nt, self._sub_keep[0].data_ptr(), ns, tile0 * 2, nt * 2, _lib.NM_F_TRACE if trace else 0)
 
     def latent_ok(self) -> bool:
         """Can the set's joint latent statistics come from the encoder-only kernel (nm_latent_pass)?  The conditions of

@@ -64,6 +64,24 @@ def write_test_csvs(out_dir, dataset_name: str, covariates: pd.DataFrame, roi_co
     return paths
 
 
+def given_filename(dataset_name: str, tag: str) -> str:
+    """The per-subject error of modality `dataset_name` reconstructed from the modalities of `tag` (their names joined by +)."""
+    return f"reconstruction_error_{dataset_name}_given_{tag}.csv"
+
+
+def write_given_csv(out_dir, dataset_name: str, tag: str, covariates: pd.DataFrame, x: np.ndarray, x_hat: np.ndarray) -> Path:
+    """reconstruction_error_<name>_given_<tag>.csv in the layout of reconstruction_error_<name>.csv (write_test_csvs): the
+    metadata columns and `Reconstruction error`, the row mean of (x - x_hat)^2 formed the same way -- x_hat here the
+    reconstruction from the joint latent of the modalities in `tag` alone (sweep.test_folds(given=...))."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    err = covariates[META_COLS].copy().reset_index(drop=True)
+    err["Reconstruction error"] = np.sum((x - x_hat) ** 2, axis=1) / x.shape[1]
+    path = out_dir / given_filename(dataset_name, tag)
+    err.to_csv(path, index=False)
+    return path
+
+
 def write_latent_csvs(out_dir, name: str, covariates: pd.DataFrame, mu: np.ndarray, var: np.ndarray, score: np.ndarray,
                       zsep: np.ndarray) -> Dict[str, Path]:
     """The latent-space deviation of one fold's test subjects (pred_latent + latent_deviation / separate_latent_deviation,

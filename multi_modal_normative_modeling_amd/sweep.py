@@ -729,6 +729,40 @@ ROI_STATS = (
                                                                  e["stats"]), _centile_summary))
 
 
+GIVEN_KINDS = ("all", "loo", "single")
+
+
+def given_subsets(given, modalities: Sequence[str]) -> List[tuple]:
+    """The modality subsets `given` names, as (tag, indices into `modalities`) in the order asked, each once.  given: one
+    entry or a list of them -- "all" (every non-empty subset), "loo" (every set that leaves one modality out), "single"
+    (every one-modality set), or a set of its own: the modality names joined by + ("T1w+T2w") or a tuple of them.  The tag
+    is the set's names joined by + in the procedure's order.  A procedure with one modality has no subsets: ValueError."""
+    mods, M = list(modalities), len(modalities)
+    if M < 2:
+        raise ValueError(f"given: the modalities {mods} are one expert -- a modality subset needs a procedure with several "
+                         f"(SE-*, UCA-*); an SM-* model is its own single-modality answer")
+    out, seen = [], set()
+    for g in ([given] if isinstance(given, str) else list(given)):
+        if g == "all":
+            sets = [tuple(i for i in range(M) if (mask >> i) & 1) for mask in range(1, 1 << M)]
+        elif g == "loo":
+            sets = [tuple(i for i in range(M) if i != left) for left in range(M)]
+        elif g == "single":
+            sets = [(i,) for i in range(M)]
+        else:
+            names = g.split("+") if isinstance(g, str) else list(g)
+            bad = [n for n in names if n not in mods]
+            if bad or not names:
+                raise ValueError(f"given: {g!r} names {bad or 'nothing'}; the procedure's modalities are {mods} "
+                                 f"(or one of {GIVEN_KINDS})")
+            sets = [tuple(sorted({mods.index(n) for n in names}))]
+        for s in sets:
+            if s not in seen:
+                seen.add(s)
+                out.append(("+".join(mods[i] for i in s), s))
+    return out
+
+
 def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequence[tuple], modalities: Sequence[str],
                combines, device, out_dirs: Optional[Sequence] = None,
                roi_columns: Optional[Dict[str, Sequence[str]]] = None, roi_effect: bool = False,
@@ -737,7 +771,7 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
                roi_adjust: Sequence[str] = (), normative: Optional[str] = None,
                z_thr: float = 1.96, centile: Optional[str] = None, tail: float = 2.5,
                quantiles: Sequence[float] = CENTILE_QUANTILES, centile_loo: bool = False,
-               robust: bool = False) -> List[Dict[str, np.ndarray]]:
+               robust: bool = False, given=None) -> List[Dict[str, np.ndarray]]:
     """test_fold for ALL folds of a procedure as one launch: jobs[i] is the trained model of fold i, folds[i] its
     (train_rows, test_rows); one evaluation job per fold, each on its own test tables (seed, scaler and covariates per fold
     exactly as test_fold), all in ONE JobSet -- a fold's ~N / K test rows are a single workgroup, K of them in a row leave
@@ -750,7 +784,15 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
     what it computes, what its entries hold and which files it writes).  roi_significance, roi_regress, normative and centile
     need roi_effect; robust needs normative.  Each fold's dict gains, per statistic, "<key>": {modality: entry} and
     "<key>_pooled": the entries of the pooled rows (the same dict in every fold's result), in the order of ROI_STATS; with
-    out_dirs, the statistic's files next to the five kinds."""
+    out_dirs, the statistic's files next to the five kinds.
+
+    given (given_subsets: "all", "loo", "single", "T1w+T2w", or a list of those): after the pass above the evaluation jobs run
+    the modality-subset pass (JobSet.forward_subsets: the encoders once, every subset fused with the model's combiner over its
+    own experts, the same draw, every decoder) -- all folds in one launch per table height -- and each fold's dict gains
+    "given": {tag: {modality: per-subject reconstruction error from the modalities of `tag` alone}}; with out_dirs, per target
+    modality reconstruction_error_<m>_given_<tag>.csv next to reconstruction_error_<m>.csv, in its layout.  A set holding a
+    model the subset kernel does not take (JobSet.forward_subsets) raises ValueError.  Without `given` nothing changes."""
+    subsets = given_subsets(given, modalities) if given is not None else []
     for name, on in (("centile", centile is not None), ("normative", normative is not None), ("roi_significance", roi_significance),
                      ("roi_regress", roi_regress is not None)):
         if on and not roi_effect:
@@ -782,6 +824,11 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
            for j, (tr, te), cb in zip(jobs, folds, combs)]
     for group in _by_height([ev for ev, _ in evs]):
         JobSet(group).forward(loss=False)
+    if subsets:
+        for ev, _ in evs:
+            ev.enable_subset_exports([idx for _, idx in subsets], loc=True, sqerr=False, rowdev=False)
+        for group in _by_height([ev for ev, _ in evs]):
+            JobSet(group).forward_subsets()
     queued = []                 # (statistic, its device entry per table of t.mats): everything is queued before the one synchronise
     if roi_effect:
         nm_ = len(modalities)
@@ -797,6 +844,16 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
         queued = [(st, st.queue(t, o)) for st in ROI_STATS if getattr(o, st.key)]
     torch.cuda.synchronize(device)
     out = [_fold_results(ev, xs, cohort, te, modalities, d, roi_columns) for (ev, xs), (_, te), d in zip(evs, folds, dirs)]
+    if subsets:
+        for res, (ev, xs), (_, te), d in zip(out, evs, folds, dirs):
+            res["given"] = {}
+            for s, (tag, _) in enumerate(subsets):
+                x_hats = [ev.sub_loc[s][i][:len(te)].cpu().numpy() for i in range(len(modalities))]
+                # (the row mean formed as io.write_test_csvs forms it: the full set's file equals reconstruction_error_<m>.csv)
+                res["given"][tag] = {m: np.sum((xs[i] - x_hats[i]) ** 2, axis=1) / xs[i].shape[1] for i, m in enumerate(modalities)}
+                if d is not None:
+                    for i, m in enumerate(modalities):
+                        io.write_given_csv(Path(d) / m, m, tag, _meta_frame(cohort, te), xs[i], x_hats[i])
     for st, entries in queued:
         entries = [_host(e) for e in entries]
         pooled = {m: entries[t.n_fold + i] for i, m in enumerate(modalities)}
@@ -1218,8 +1275,18 @@ def main_test(argv=None):
                     help="with --centile: a healthy subject is ranked among the OTHER healthy subjects (exact leave-one-out)")
     ap.add_argument("--robust", action="store_true",
                     help="with --normative: z-scores against the controls' median and 1.4826 x MAD instead of mean and sd")
+    ap.add_argument("--given", nargs="+", type=str, default=None, metavar="SET",
+                    help="also every modality reconstructed from a SUBSET of the modalities -- the same model with less evidence: "
+                         "all (every non-empty subset), loo (every set that leaves one modality out), single (every one-modality "
+                         "set), or sets of their own as names joined by + (T1w+T2w): per fold and all folds "
+                         "reconstruction_error_<m>_given_<SET>.csv per target modality m; procedures with several modalities only")
     _driver_common(ap)
     args = ap.parse_args(argv)
+    if args.given:
+        try:
+            given_subsets(args.given, workload.procedure_modalities(args.procedure, args.dataset_resourse)[0])
+        except ValueError as e:
+            ap.error(f"--given: {e}")
     # (what is refused, first match first; a value is judged only where its switch is on -- test_folds and latent_folds do the same)
     refusals = ((args.centile and not args.roi_effect, "--centile needs --roi-effect"),
                 (args.centile and not (np.isfinite(args.tail) and 0 < args.tail < 50), "--tail must lie inside (0, 50)"),
@@ -1276,7 +1343,9 @@ def main_test(argv=None):
                         roi_perm=args.roi_perm, roi_seed=args.roi_seed, roi_regress=roi_regress, roi_adjust=args.roi_adjust,
                         normative=args.normative, z_thr=args.z_thr, robust=args.robust, centile=args.centile, tail=args.tail,
                         quantiles=args.quantiles, centile_loo=args.centile_loo)
-    results = test_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs, **vars(o)) if my else []
+    results = test_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs, given=args.given,
+                         **vars(o)) if my else []
+    given_tags = [tag for tag, _ in given_subsets(args.given, mods)] if args.given else []
     # the pooled entries of every statistic that is on: this rank's folds' test subjects as one set (the maps: against their controls)
     pooled_stats = [st for st in ROI_STATS if getattr(o, st.key)] if results else []
     if pooled_stats:
@@ -1288,6 +1357,9 @@ def main_test(argv=None):
             parts = [pd.read_csv(root / f"{k:03d}" / m / f"{kind}_{m}.csv") for k in my]
             if parts:
                 pd.concat(parts, ignore_index=True).to_csv(out_root / m / f"{kind}_{m}.csv", index=False)
+        for tag in given_tags if my else []:
+            parts = [pd.read_csv(root / f"{k:03d}" / m / io.given_filename(m, tag)) for k in my]
+            pd.concat(parts, ignore_index=True).to_csv(out_root / m / io.given_filename(m, tag), index=False)
         for st in pooled_stats:
             e = results[0][st.key + "_pooled"][m]
             st.write(out_root / m, m, _roi_columns(None, m, _n_roi(e)), meta_all, e, o)
@@ -1554,6 +1626,81 @@ def _analysis_operating(root: Path, args, scores, positive, folds, ids):
     return points, summary, curve
 
 
+def _analysis_given(root: Path, args, mods: Sequence[str], hc: int):
+    """`analysis --given SET ... [--bootstrap B]`: which modalities carry the signal.  Per subset of --given and target
+    modality m the subjects' reconstruction_error_<m>_given_<tag>.csv of `test --given` (and, as target `mean`, their average
+    over the modalities -- the score of the plain analysis), healthy against disease: every fold's set and the pooled rows of
+    all folds through metrics.posthoc_metrics in one call, to group_analysis_given_<P>.csv (columns given, target, fold --
+    `pooled` last -- and the metric columns).  --bootstrap B: the pooled `mean` score of every subset and of the full set in
+    one metrics.auc_bootstrap call on one stream -- the subsets of one model score the same subjects, the paired case -- to
+    group_analysis_given_<P>_bootstrap.csv: the interval of each pooled AUC and its paired difference against the full set.
+    Returns the first table as a DataFrame."""
+    import pandas as pd
+    subsets = given_subsets(args.given, mods)
+    full_tag = "+".join(mods)
+    cells, sets, labs = [], [], []                    # (tag, target) per block of len(folds) + 1 sets
+    folds = ids = None
+    pooled_mean = {}
+    for tag, _ in subsets:
+        per_target, first = {}, None
+        for m in mods:
+            files = {k: root / f"{k:03d}" / m / io.given_filename(m, tag) for k in range(args.n_splits)}
+            have = [k for k, f in files.items() if f.exists()]
+            if not have:
+                raise FileNotFoundError(f"no {io.given_filename(m, tag)} under {root}/<fold>/{m}/ -- run the `test` subcommand "
+                                        f"with --given {tag} (or --given all) first")
+            dfs = [pd.read_csv(files[k]) for k in have]
+            if folds is None:
+                folds, ids = have, [d["participant_id"].to_numpy() for d in dfs]
+                positive = [torch.as_tensor(~healthy(d["DIA"].to_numpy(), hc), dtype=torch.int32) for d in dfs]
+            elif have != folds or any(not np.array_equal(d["participant_id"].to_numpy(), i) for d, i in zip(dfs, ids)):
+                raise ValueError(f"{io.given_filename(m, tag)}: folds {have} / their subjects are not those of the first file read "
+                                 f"({folds}) -- run `test --given` for every subset on the same folds")
+            per_target[m] = [d["Reconstruction error"].to_numpy(dtype=np.float64) for d in dfs]
+        per_target["mean"] = [sum(per_target[m][f] for m in mods) / len(mods) for f in range(len(folds))]
+        for target, vals in per_target.items():
+            sc, po = _with_pooled([torch.as_tensor(v, dtype=torch.float32) for v in vals], positive, "--given: ")
+            cells.append((tag, target))
+            sets += sc
+            labs += po
+            if target == "mean":
+                pooled_mean[tag] = sc[-1]
+    table = metrics.posthoc_metrics(sets, labs).cpu().numpy()
+    per = len(folds) + 1
+    df = pd.DataFrame(table, columns=list(metrics.POSTHOC_COLUMNS))
+    df.insert(0, "given", [tag for tag, _ in cells for _ in range(per)])
+    df.insert(1, "target", [target for _, target in cells for _ in range(per)])
+    df.insert(2, "fold", ([str(k) for k in folds] + ["pooled"]) * len(cells))
+    df.to_csv(root / f"group_analysis_given_{args.procedure}.csv", index=False)
+    for (tag, target), r in zip(cells, table[per - 1::per]):
+        print(f"[analysis] {args.procedure} {target} given {tag}: pooled AUC {r[0]:.4f}", flush=True)
+    if args.bootstrap:
+        if full_tag not in pooled_mean:               # the full set's score: the plain analysis's, from reconstruction_error_<m>.csv
+            fs, fp, ff, _ = _analysis_scores(root, mods, args.procedure, "reconstruction", args.n_splits, hc)
+            if ff != folds:
+                raise ValueError(f"--given --bootstrap: reconstruction_error_<m>.csv holds folds {ff}, the subset files {folds}")
+            pooled_mean[full_tag] = torch.cat(fs)
+        tags = list(pooled_mean)
+        lab = torch.cat(positive)
+        i_full = tags.index(full_tag)
+        pairs = [(i, i_full) for i in range(len(tags)) if i != i_full]
+        res = metrics.auc_bootstrap([pooled_mean[t] for t in tags], [lab] * len(tags), n_boot=args.bootstrap, ci=args.ci,
+                                    seed=args.boot_seed, streams=[args.n_splits] * len(tags), pairs=pairs or None)
+        tab, cmp_tab = (res[0].cpu().numpy(), res[1].cpu().numpy()) if pairs else (res.cpu().numpy(), np.zeros((0, 8)))
+        db = pd.DataFrame(tab, columns=list(metrics.AUC_BOOTSTRAP_COLUMNS))
+        db.insert(0, "given", tags)
+        cmp_rows = np.full((len(tags), len(metrics.AUC_COMPARE_COLUMNS)), np.nan)
+        for (i, _), row in zip(pairs, cmp_tab):
+            cmp_rows[i] = row
+        for j, name in enumerate(metrics.AUC_COMPARE_COLUMNS):
+            db[f"vs_full_{name}"] = cmp_rows[:, j]
+        db.to_csv(root / f"group_analysis_given_{args.procedure}_bootstrap.csv", index=False)
+        for t, r, c in zip(tags, tab, cmp_rows):
+            tail = "" if t == full_tag else f"  against {full_tag}: delta AUC {c[0]:+.4f} [{c[1]:+.4f}, {c[2]:+.4f}]  p {c[5]:.3g}"
+            print(f"[analysis] {args.procedure} given {t}: pooled AUC {r[0]:.4f} [{r[1]:.4f}, {r[2]:.4f}]{tail}", flush=True)
+    return df
+
+
 def main_analysis(argv=None):
     """multimodal_kfold_cvae_group_analysis_1x1.py:160-235 on the files the `test` subcommand wrote: per fold the subjects'
     reconstruction errors averaged over the procedure's modalities (:205-209), healthy vs disease ROC-AUC, Youden-J
@@ -1622,7 +1769,21 @@ def main_analysis(argv=None):
     ap.add_argument("--roc-grid", dest="roc_grid", type=int, default=0, metavar="G",
                     help="every fold's ROC at fpr = linspace(0, 1, G) (2..%d), their mean and sd over folds, to "
                          "group_analysis_roc_curve.csv" % _lib.NM_OP_MAX_GRID)
+    ap.add_argument("--given", nargs="+", type=str, default=None, metavar="SET",
+                    help="instead: which modalities carry the signal -- per subset (all, loo, single, or names joined by +: "
+                         "T1w+T2w) and target modality, and for their mean, the ROC-AUC per fold and pooled on "
+                         "reconstruction_error_<m>_given_<SET>.csv (`test --given`), to group_analysis_given_<P>.csv; with "
+                         "--bootstrap B also every subset's pooled interval and its paired difference against the full set, to "
+                         "group_analysis_given_<P>_bootstrap.csv")
     args = ap.parse_args(argv)
+    if args.given:
+        if args.score != "reconstruction" or args.centile_score or args.roi or args.against or args.threshold_rule or args.roc_grid:
+            ap.error("--given scores the reconstruction error of modality subsets: it does not go with --score, --centile-score, "
+                     "--roi, --against, --threshold-rule or --roc-grid")
+        try:
+            given_subsets(args.given, workload.procedure_modalities(args.procedure, args.dataset_resourse)[0])
+        except ValueError as e:
+            ap.error(f"--given: {e}")
     if args.centile_score:
         if args.score != "reconstruction":
             ap.error("--centile-score is a score of its own: it does not go with --score")
@@ -1654,6 +1815,11 @@ def main_analysis(argv=None):
     mods, _ = workload.procedure_modalities(args.procedure, args.dataset_resourse)
     root = Path(args.models_dir) / args.dataset_resourse / args.procedure
     hc = prep.HC_LABEL.get(args.dataset_resourse, 1)
+    if args.given:
+        try:
+            return _analysis_given(root, args, mods, hc)
+        except FileNotFoundError as e:
+            ap.error(str(e))
     if args.roi and args.roi_significance:
         return _analysis_roi_significance(root, mods, args.n_splits, hc, args.procedure, args.roi_perm, args.roi_seed)
     if args.roi:
