@@ -408,6 +408,55 @@ typedef struct nm_subset_t {
 int nm_devpass_subsets(const nm_job_t* jobs_dev, int n_jobs, const nm_subset_t* subsets_dev, int n_subsets, int tile0, int n_tiles,
                        int flags, void* stream);   /* flags: 0 or NM_F_TRACE */
 int nm_devpass_subsets_ok(const nm_job_t* job_host);
+/* The posterior-predictive pass (csrc/nm_devpass.hip: nm_devpass_draws_kernel): every expert's encoder ONCE per 128-row tile,
+ * then S = n_draws times the fusion, a latent draw and every decoder, the S reconstructions of an element folded in the
+ * kernel into their mean, their sample variance and the scores below.  The parity output -- (x - x_hat)^2 for ONE draw --
+ * stays what nm_devpass / nm_devpass_multi write; this is the sigma-normalised extra next to it.
+ *   Draw s of job j (entry draws[j * n_draws + s]): the row's noise keyed on (seed_s, step, row, z) exactly as the
+ *   several-expert pass keys job.seed -- or, where the entry's eps is not NULL, that array in the layout and indexing of
+ *   job.eps ([eps_cap][NM_BATCH][Z], block step % eps_cap).  x_hat_s is the value nm_devpass (one expert with the bypass) /
+ *   nm_devpass_multi / nm_forward would store to out_loc for that element if launched with that seed or eps: the joint
+ *   posterior goes through the same fusion code and the same z = mu + eps exp(logvar / 2) operation order as that pass.
+ *   Fold, per (row, ROI), fp32, no fused multiply-add, in draw order:
+ *     s = 0: mean = x_hat_0, M2 = 0;  s >= 1: d = x_hat_s - mean; mean += d * (1.0f / (float)(s + 1)); M2 += d * (x_hat_s - mean)
+ *   Exports per decoder m (pad columns 0; rows from the table's end to the end of its last 256-row tile 0):
+ *     pred_mean   [rows_alloc][x_pitch]  mean
+ *     pred_var    M2 * v, v = 1.0f / (float)(S - 1) (S = 1: 0) -- the sample variance
+ *     pred_msq    e * e + pred_var * c, e = x - mean, c = (float)(S - 1) / (float)S: the Monte-Carlo mean of (x - x_hat_s)^2
+ *                 through E[(x - x_hat_s)^2] = (x - mean)^2 + Var_pop(x_hat_s); S = 1: (x - x_hat_0)^2 exactly
+ *     pred_z      e / sqrt(noise_var[d] + pred_var); noise_var: fp32 [x_pitch] per decoder, the host's exp(logvar_out)
+ *     pred_rowdev [rows_alloc]  row mean of pred_msq over D     (summation order of out_rowdev in the several-expert pass)
+ *     pred_rowz2  [rows_alloc]  row mean of pred_z^2 over D
+ *   pred_mean and pred_var are required for every decoder that is wanted (both NULL: the decoder is skipped): they hold mean
+ *   and M2 between the draws.  The output phase's ownership (wave w: rows 16 w .. 16 w + 15, a lane: four columns) is the
+ *   same in every draw, so each element is read and written by one lane alone with plain loads and stores -- no atomics,
+ *   the same bytes on every run.  Draw 0 writes without reading (stale buffer contents never enter a result); the last
+ *   draw finalises in registers and writes every export.  Each of the other exports may be NULL; pred_z / pred_rowz2 need
+ *   noise_var (the caller refuses pred_z with noise_var NULL; the kernel then writes neither).
+ * Admitted (nm_devpass_draws_ok): what nm_devpass_multi_ok admits AND one-expert jobs with the bypass on or off -- not wide,
+ * 1..NM_MAX_EXP modalities, each with an encoder, n_private == 0, tc_weight == 0, w_off < 0, out_kind == 0, H[0] <= 112, Z
+ * rounded to 16 <= 32; NM_E_DEVPASS otherwise (no general-kernel counterpart).  Geometry, LDS plan and workspace tiles (one
+ * per 256-row batch the launch touches, one-expert jobs included) are those of nm_devpass_multi.  Status is decided on the
+ * host before the device is asked anything: NM_E_NULL for a missing array, NM_E_GEOMETRY for n_draws outside
+ * 1..NM_MAX_DRAWS and the geometry rules of every launch.  The tables hold n_jobs x n_draws entries (job-major) and n_jobs
+ * entries, in device memory. */
+#define NM_MAX_DRAWS 64
+typedef struct nm_draw_t {
+  uint64_t seed;                     /* generator key of this draw when eps == NULL */
+  const float* eps;                  /* [eps_cap][NM_BATCH][Z] injected draws, or NULL */
+} nm_draw_t;
+typedef struct nm_pred_t {
+  float* pred_mean[NM_MAX_EXP];      /* [rows_alloc][x_pitch of modality m]; required with pred_var, both NULL: decoder skipped */
+  float* pred_var[NM_MAX_EXP];
+  float* pred_msq[NM_MAX_EXP];       /* ... or NULL */
+  float* pred_z[NM_MAX_EXP];         /* ... or NULL; needs noise_var */
+  float* pred_rowdev[NM_MAX_EXP];    /* [rows_alloc], or NULL */
+  float* pred_rowz2[NM_MAX_EXP];     /* [rows_alloc], or NULL; needs noise_var */
+  const float* noise_var[NM_MAX_EXP];/* [x_pitch of modality m], or NULL */
+} nm_pred_t;
+int nm_devpass_draws(const nm_job_t* jobs_dev, int n_jobs, const nm_draw_t* draws_dev, int n_draws, const nm_pred_t* pred_dev,
+                     int tile0, int n_tiles, int flags, void* stream);   /* flags: 0 or NM_F_TRACE */
+int nm_devpass_draws_ok(const nm_job_t* job_host);
 /* The encoder half alone (csrc/nm_devpass.hip: nm_latent_kernel): the joint posterior of every row, what cVAE.pred_latent
  * returns (cVAE.py:539-545), over table rows [tile0 * 128, (tile0 + n_tiles) * 128).  Every expert's encoder and the fusion
  * of nm_forward, no latent draw and no decoder; writes out_mu / out_logvar and nothing else -- bit for bit nm_forward's

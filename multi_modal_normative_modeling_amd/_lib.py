@@ -90,6 +90,8 @@ NM_OP_MAX_GRID = 1024
 NM_OP_MAX_LINSPACE = 65536
 # nm_devpass_subsets: the most entries per job (every non-empty set of NM_MAX_EXP experts)
 NM_MAX_SUBSETS = 15
+# nm_devpass_draws: the most latent draws per row
+NM_MAX_DRAWS = 64
 
 # status codes (nmhip.h; nm_status_string gives the text)
 NM_OK = 0
@@ -173,6 +175,19 @@ class NmSubset(C.Structure):
                 ("out_rowdev", C.c_void_p * NM_MAX_EXP)]
 
 
+class NmDraw(C.Structure):
+    """nm_draw_t: one entry of nm_devpass_draws' [n_jobs][n_draws] table (device memory)."""
+    _fields_ = [("seed", C.c_uint64), ("eps", C.c_void_p)]
+
+
+class NmPred(C.Structure):
+    """nm_pred_t: one job's predictive exports, nm_devpass_draws' [n_jobs] table (device memory)."""
+    _fields_ = [("pred_mean", C.c_void_p * NM_MAX_EXP), ("pred_var", C.c_void_p * NM_MAX_EXP),
+                ("pred_msq", C.c_void_p * NM_MAX_EXP), ("pred_z", C.c_void_p * NM_MAX_EXP),
+                ("pred_rowdev", C.c_void_p * NM_MAX_EXP), ("pred_rowz2", C.c_void_p * NM_MAX_EXP),
+                ("noise_var", C.c_void_p * NM_MAX_EXP)]
+
+
 class NmRoiSet(C.Structure):
     """nm_roi_set_t: one matrix of nm_roi_effect's pointer table."""
     _fields_ = [("x", C.c_void_p), ("group", C.c_void_p), ("rows", C.c_int32), ("pitch", C.c_int32)]
@@ -248,6 +263,8 @@ def load():
     lib.nm_devpass_multi_ok.argtypes = [C.POINTER(NmJob)]
     lib.nm_devpass_subsets.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp]
     lib.nm_devpass_subsets_ok.argtypes = [C.POINTER(NmJob)]
+    lib.nm_devpass_draws.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, vp]
+    lib.nm_devpass_draws_ok.argtypes = [C.POINTER(NmJob)]
     lib.nm_latent_pass.argtypes = [vp, i32, i32, i32, i32, vp]
     lib.nm_latent_pass_ok.argtypes = [C.POINTER(NmJob)]
     lib.nm_latent_stats.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
@@ -324,6 +341,7 @@ EXPORTED_SYMBOLS = [
     "nm_operating_points_workspace", "nm_operating_points",
     "nm_cohort_quantiles", "nm_normative_centile_workspace", "nm_normative_centile",
     "nm_devpass_subsets", "nm_devpass_subsets_ok",
+    "nm_devpass_draws", "nm_devpass_draws_ok",
 ]
 
 

@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .engine import Job, JobSet, Table, adam_step, latent_scores, latent_stats, require_gpu
+from .engine import Job, JobSet, Table, adam_step, draw_seeds, latent_scores, latent_stats, require_gpu
 from .layout import ModelSpec, ParamLayout
 
 
@@ -215,8 +215,11 @@ class _Base(nn.Module):
         return self._device
 
     def _run(self, xes: Sequence[torch.Tensor], cs: Sequence[torch.Tensor], combine: str, flags: int, eps=None,
-             kl_w=None, ll_w=1.0, recon_only: bool = False, latent_only: bool = False, subsets=None, present=None):
-        """subsets (pred_recon_given: a list of tuples of modality indices): the launch is the modality-subset pass
+             kl_w=None, ll_w=1.0, recon_only: bool = False, latent_only: bool = False, subsets=None, present=None, draws=None):
+        """draws (pred_recon_draws: (S, the S generator keys)): the launch is the posterior-predictive pass
+        (JobSet.forward_draws: encoders once, S draws folded on the device), its statistics in job.pred_mean / pred_var /
+        pred_msq / pred_z.
+        subsets (pred_recon_given: a list of tuples of modality indices): the launch is the modality-subset pass
         (JobSet.forward_subsets: encoders once, every subset fused and decoded), its reconstructions in job.sub_loc.
         latent_only (forward-only calls that read the joint posterior alone -- pred_latent of the multimodal classes): the
         launch goes through JobSet.latent(), i.e. on the encoder-only kernel where the model's shape allows (same out_mu /
@@ -280,6 +283,11 @@ class _Base(nn.Module):
             if j.subsets != subsets or j.sub_loc[0][0].shape[0] != j.tables[0].rows_alloc:
                 j.enable_subset_exports(subsets, loc=True, sqerr=False, rowdev=False)
             self._js.forward_subsets(present, 0, nt)
+        elif draws is not None:
+            S, seeds = int(draws[0]), [int(v) for v in draws[1]]
+            if j.n_draws != S or j.pred_seeds != seeds or j.pred_mean[0].shape[0] != j.tables[0].rows_alloc:
+                j.enable_predictive_exports(S, seeds=seeds, rowdev=False, rowz2=False)
+            self._js.forward_draws(0, nt)
         elif recon_only and flags == _lib.NM_F_EXPORT:
             self._js.forward(0, nt, loss=False)
         elif latent_only and flags == _lib.NM_F_EXPORT:
@@ -287,6 +295,21 @@ class _Base(nn.Module):
         else:
             self._js._launch(0, 1, nt, flags)
         return j, B
+
+    def _pred_draws(self, xs, cs, combine: str, n_draws: int, seed):
+        """The posterior-predictive statistics of every modality over n_draws in-kernel latent draws: per modality a dict of
+        numpy arrays [subjects, ROIs] -- "mean" (the mean reconstruction), "var" (its sample variance over the draws), "msq"
+        (the Monte-Carlo mean of (x - x_hat_s)^2) and "z" ((x - mean) / sqrt(exp(logvar_out) + var)).  seed: the key of draw
+        0, draw s is keyed (seed + s * 0x9E3779B97F4A7C15) mod 2^64; None: taken from torch's generator, as pred_recon's
+        draw is.  n_draws = 1 with the seed of a Job gives that Job's single-draw reconstruction and (x - x_hat)^2."""
+        self._dev()
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        S = int(n_draws)
+        zeros = torch.zeros(int(xs[0].shape[0]), self.spec.latent)     # (the job's own draw buffer is not read by this pass)
+        j, B = self._run(xs, cs, combine, _lib.NM_F_EXPORT, eps=zeros, recon_only=True, draws=(S, draw_seeds(seed, S)))
+        return [{"mean": j.pred_mean[m][:B].cpu().numpy(), "var": j.pred_var[m][:B].cpu().numpy(),
+                 "msq": j.pred_msq[m][:B].cpu().numpy(), "z": j.pred_z[m][:B].cpu().numpy()} for m in range(len(j.kmods))]
 
     # -- the latent deviation (utils_vae.py:155-161) ----------------------------------------------------
     def _latent_joint(self, xes, c, combine: str = "poe"):
@@ -543,6 +566,14 @@ class cVAE_multimodal(_ExpertOps, _Base):
         j, B = self._run(xs, [ct] * self.modalities, combine, _lib.NM_F_EXPORT, recon_only=True, subsets=given, present=present)
         return [[j.sub_loc[s][m][:B].cpu().numpy() for m in range(self.modalities)] for s in range(len(given))]
 
+    def pred_recon_draws(self, xes, c, DEVICE, combine, n_draws, seed=None):
+        """pred_recon over n_draws latent draws in ONE launch, folded on the device (JobSet.forward_draws): DataFrames in; per
+        modality a dict of numpy arrays out -- "mean", "var", "msq", "z" (see _Base._pred_draws).  The encoders run once;
+        n_draws is 1 to 64."""
+        xs = [torch.tensor(np.asarray(x.values if hasattr(x, "values") else x), dtype=torch.float32) for x in xes]
+        ct = torch.tensor(np.asarray(c), dtype=torch.long)
+        return self._pred_draws(xs, [ct] * self.modalities, combine, n_draws, seed)
+
     def pred_latent(self, xes, c, DEVICE, combine):
         """The joint counterpart of cVAE.pred_latent (cVAE.py:539-545): DataFrames in, (mu_joint, var_joint) as numpy out."""
         mu, logvar = self._latent_joint(list(xes), c, combine)
@@ -728,6 +759,9 @@ class mmJSD(cVAE_multimodal):
     def pred_recon_given(self, xes, c, DEVICE, combine, given, present=None):
         return super().pred_recon_given(xes, c, DEVICE, "poe", given, present)
 
+    def pred_recon_draws(self, xes, c, DEVICE, combine, n_draws, seed=None):
+        return super().pred_recon_draws(xes, c, DEVICE, "poe", n_draws, seed)
+
     def pred_latent(self, xes, c, DEVICE, combine="poe"):
         return super().pred_latent(xes, c, DEVICE, "poe")
 
@@ -778,6 +812,13 @@ class cVAE(_Base):
         ct = torch.as_tensor(np.asarray(c), dtype=torch.long)
         mu, _ = self.encode(xt, ct)
         return self.decode(mu, ct).loc.cpu().numpy()
+
+    def pred_recon_draws(self, x, c, DEVICE, combine=None, n_draws=1, seed=None):
+        """The posterior-predictive statistics of x over n_draws latent draws in one launch (JobSet.forward_draws): a dict of
+        numpy arrays "mean", "var", "msq", "z" (see _Base._pred_draws).  combine plays no part in a one-expert model."""
+        xt = torch.as_tensor(np.asarray(x.to_numpy() if hasattr(x, "to_numpy") else x), dtype=torch.float32)
+        ct = torch.as_tensor(np.asarray(c), dtype=torch.long)
+        return self._pred_draws([xt], [ct], "poe", n_draws, seed)[0]
 
 
 # =========================================================================================================
@@ -876,6 +917,9 @@ class cVAE_multimodal_regression(_ExpertOps, _HeadBase):
 
     def pred_recon_given(self, xes, c, DEVICE, combine, given, present=None):
         return cVAE_multimodal.pred_recon_given(self, xes, c, DEVICE, combine, given, present)
+
+    def pred_recon_draws(self, xes, c, DEVICE, combine, n_draws, seed=None):
+        return cVAE_multimodal.pred_recon_draws(self, xes, c, DEVICE, combine, n_draws, seed)
 
     def encode(self, x, c, m):
         return cVAE_multimodal.encode(self, x, c, m)

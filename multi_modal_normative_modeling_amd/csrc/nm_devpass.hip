@@ -1160,6 +1160,392 @@ __global__ __launch_bounds__(WG, 4) void nm_latent_kernel(const nm_job_t* __rest
   tr(c, 3);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// nm_devpass_draws_kernel -- the posterior-predictive pass: nm_devpass_subsets_kernel's shape with the loop over DRAWS in
+// the place of the loop over subsets, and the statistics of the S reconstructions folded in the output epilogue (nmhip.h
+// states the definition).  Encoders once per tile, statistics to the workspace tile; then per draw s the fusion (the same
+// fuse_fwd / softmax_alpha every time: the posterior does not depend on s), the draw under (seed_s | eps_s) and every
+// decoder that is wanted.  The sources of the kernels above stay as they are: their decoder loop is repeated here with the
+// fold in the place of the export stores.
+//
+// One expert: the heads' statistics go through the workspace like several experts' and through fuse_fwd with the job's
+// single_bypass (as nm_latent_kernel does); with the bypass the draw is fwd_heads' expression (nm_devpass_kernel is the
+// pass such a job otherwise runs on), without it the general kernel's separate addition (dvm_add) as for several experts.
+//
+// Accumulators: mean and M2 of an element live in pred_mean / pred_var between the draws.  The output phase's ownership
+// (wave w: rows 16 w .. 16 w + 15, lane: four columns of a feature tile) does not depend on s, so an element is loaded and
+// stored by ONE lane, with plain loads and stores; draw 0 stores without loading, the last draw finalises in registers.
+// The chunk boundary takes a full wait (wait_vm(0)): the accumulator loads are vector-memory operations of their own, a
+// count of the previous chunk's stores would no longer mean what it means in the kernels above.
+//
+// Geometry, LDS plan (P, W, vector slots, scalars, Z [128][32] bf16) and workspace tile: nm_devpass_multi_kernel's.
+constexpr int DVD_SMEM = DVM_SMEM;
+static_assert(2 * DVD_SMEM <= 160 * 1024, "two workgroups per CU");
+
+__host__ __device__ inline int dvd_refused(const nm_job_t* j) { return lat_refused(j); }   // 1..NM_MAX_EXP experts, the compact shapes
+
+// fwd_heads' in-register draw of a one-expert job (zdst path), written as it is written there
+__device__ __forceinline__ float dvd_z_bypass(float mu, float ep, float lv) { return mu + ep * fx_exp(0.5f * lv); }
+
+// one step of the fold (s >= 1): rs = 1 / (s + 1)
+__device__ __forceinline__ void dvd_fold(float xh, float rs, float& mean, float& m2) {
+#pragma clang fp contract(off)
+  const float d = xh - mean;
+  mean = mean + d * rs;
+  m2 = m2 + d * (xh - mean);
+}
+// the exports of one element from its final (mean, M2): v = 1 / (S - 1) (S = 1: 0), cf = (S - 1) / S
+__device__ __forceinline__ void dvd_final(float x, float mean, float m2, float v, float cf, float nv, float& var, float& msq, float& z) {
+#pragma clang fp contract(off)
+  var = m2 * v;
+  const float e = x - mean;
+  msq = e * e + var * cf;
+  z = e / sqrtf(nv + var);
+}
+__device__ __forceinline__ float dvd_sum4(const f32x4& a) {
+#pragma clang fp contract(off)
+  return ((a[0] + a[1]) + a[2]) + a[3];
+}
+__device__ __forceinline__ float dvd_sumsq4(const f32x4& a) {
+#pragma clang fp contract(off)
+  return ((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]) + a[3] * a[3];
+}
+
+struct DvdOut { gf32 mean, var, msq, z, rdev, rz2; gcf32 nv; };
+__device__ __forceinline__ DvdOut dvd_out(const nm_pred_t& p, int m) {
+  DvdOut o;
+  o.mean = asg(p.pred_mean[m]); o.var = asg(p.pred_var[m]);
+  const bool on = o.mean && o.var;                  // (both accumulators, or the decoder is skipped)
+  o.nv = on ? asg(p.noise_var[m]) : nullptr;
+  o.msq = on ? asg(p.pred_msq[m]) : nullptr;
+  o.z = (on && o.nv) ? asg(p.pred_z[m]) : nullptr;
+  o.rdev = on ? asg(p.pred_rowdev[m]) : nullptr;
+  o.rz2 = (on && o.nv) ? asg(p.pred_rowz2[m]) : nullptr;
+  if (!on) { o.mean = nullptr; o.var = nullptr; }
+  return o;
+}
+// dv_zero_dead_rows with the export pointers of one decoder's predictive exports
+__device__ __forceinline__ void dvd_zero_dead_rows(int tid, int xp, const DvdOut& o, int row0, int live) {
+  if (!o.mean) return;
+  const int r16 = rup(live, 16);
+  for (int e = tid; e < (DV_ROWS - r16) * (xp >> 2); e += WG) {
+    const int64_t gi = (int64_t)(row0 + r16) * xp + (int64_t)e * 4;
+    *(GAS f32x4*)(o.mean + gi) = f32x4{0.f, 0.f, 0.f, 0.f};
+    *(GAS f32x4*)(o.var + gi) = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (o.msq) *(GAS f32x4*)(o.msq + gi) = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (o.z) *(GAS f32x4*)(o.z + gi) = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  for (int r = live + tid; r < DV_ROWS; r += WG) {
+    if (o.rdev) o.rdev[row0 + r] = 0.f;
+    if (o.rz2) o.rz2[row0 + r] = 0.f;
+  }
+}
+
+__global__ __launch_bounds__(WG, 4) void nm_devpass_draws_kernel(const nm_job_t* __restrict__ jobs, const nm_draw_t* __restrict__ draws,
+                                                                   int n_draws, const nm_pred_t* __restrict__ preds, int tile0, int flags) {
+  constexpr int RT = DV_RT, ROWS = DV_ROWS;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const nm_job_t* J = jobs + blockIdx.x;
+  if (dvd_refused(J) || !J->workspace || n_draws < 1 || n_draws > NM_MAX_DRAWS) return;
+  const nm_draw_t* const drs = draws + (int64_t)blockIdx.x * n_draws;
+  const nm_pred_t& pr = preds[blockIdx.x];
+  const int M = J->M;
+  const int t128 = tile0 + (int)blockIdx.y;
+  const int row0 = t128 * ROWS;
+  if (row0 >= J->n_rows) {
+    // the second half of a ragged last 256-row tile: every decoder's export rows come back as zeros
+    if (row0 < (J->n_rows + TROWS - 1) / TROWS * TROWS)
+      for (int m = 0; m < M; ++m) dvd_zero_dead_rows((int)threadIdx.x, J->mod[m].x_pitch, dvd_out(pr, m), row0, 0);
+    return;
+  }
+  int mf = -1;                                     // the first decoder that is wanted
+  for (int m = M - 1; m >= 0; --m)
+    if (pr.pred_mean[m] && pr.pred_var[m]) mf = m;
+  if (mf < 0) return;                              // (workgroup-uniform)
+  Ctx c;
+  c.job = J;
+  c.part = -1; c.nparts = 1; c.lstep = 0;
+  c.slope = J->act_slope;
+  dv_carve(c, smem);
+  relaunder(c);
+  c.flags = NM_F_EXPORT | (flags & NM_F_TRACE);
+  c.t_last = 0;
+  c.ws = (GAS char*)J->workspace + (int64_t)(t128 / 2 - tile0 / 2) * J->workspace_stride;
+  for (int i = c.tid; i < DVD_SMEM / 4; i += WG) reinterpret_cast<uint32_t*>(smem)[i] = 0u;
+  __syncthreads();
+  if (c.flags & 64) c.tlast[c.wave_s] = clock64();
+  c.row0 = row0;
+  c.rloc0 = row0 % TROWS;
+  c.nrows = min(ROWS, J->n_rows - row0);
+  c.inv_b = 1.0f / (float)c.nrows;
+  const int live = c.nrows;
+  const int step = row0 / TROWS;
+  const int L = J->L, Z = J->Z, C = J->C;
+  const int Zs = rup(Z, 16);
+  const bool nl = J->non_linear != 0;
+  const bool vec4 = (Z & 3) == 0;
+  const bool byp = M == 1 && J->single_bypass != 0;
+  GAS char* const wsh = (GAS char*)J->wsh;
+  char* const Wb = reinterpret_cast<char*>(c.Q);
+  __bf16* const zlds = reinterpret_cast<__bf16*>(smem + DV_SMEM);
+  const WsLayout wl = ws_layout(M, L, Z);
+  gf32 ws_mu_m = (gf32)(c.ws + wl.mu_m) + c.rloc0 * Zs;
+  gf32 ws_lv_m = (gf32)(c.ws + wl.lv_m) + c.rloc0 * Zs;
+  auto to_W = [&](const GAS char* blob, int vs, int rows, int K) {
+    return Next{blob, Wb, IMG_BYTES >> 10, blob + cimg_bytes(rows, K), reinterpret_cast<char*>(c.vec) + vs * VEC_BYTES, rows, blob_kp(K)};
+  };
+
+  // ---- encoders: every expert's chain ONCE, statistics to the workspace ----
+  for (int m = 0; m < M; ++m) {
+    relaunder(c);
+    const nm_modality_t& md = J->mod[m];
+    const int nch = (md.Kx + XCH - 1) / XCH;
+    const GAS char* after0 = wsh + (L > 1 ? md.enc_s[1] : md.heads_s);
+    fwd_first_layer<RT>(c, (const GAS char*)asg(md.xb) + (int64_t)(row0 / TROWS) * nch * XIMG_TILE_BYTES + (int64_t)c.rloc0 * (LDX * 2),
+                        md.Kx, wsh + md.enc_s[0], to_W(after0, 0, L > 1 ? J->H[1] : 2 * Zs, J->H[0]), J->H[0], nl, (gbf16)nullptr, true,
+                        DV_W0_PIECES, live);
+    int vs = 0;
+    for (int e = 1; e < L; ++e) {
+      const GAS char* nxt = wsh + (e + 1 < L ? md.enc_s[e + 1] : md.heads_s);
+      dv_layer(c, vs, to_W(nxt, vs ^ 1, e + 1 < L ? J->H[e + 1] : 2 * Zs, J->H[e]), J->H[e], J->H[e - 1], nl, live);
+      vs ^= 1;
+    }
+    tr(c, 1);
+    wait_vm(0);
+    fwd_heads<RT>(c, 0, no_next(), Z, J->H[L - 1], ws_mu_m + (int64_t)m * TROWS * Zs, ws_lv_m + (int64_t)m * TROWS * Zs, Zs, 0,
+                  (__bf16*)nullptr, step, vec4, (float*)nullptr, c.vec + vs * (VEC_BYTES / 4));
+  }
+  handoff_barrier();                               // the heads' stores are complete for every thread of the workgroup
+
+  // ---- the draws: fusion + draw s -> LDS, then every wanted decoder with the fold in its output epilogue ----
+  const int Hl = J->H[0];
+  const int ob = L & 1;                            // (see nm_devpass_kernel: chunk 0's vectors avoid the last hidden layer's bias)
+  const float vS = n_draws > 1 ? 1.0f / (float)(n_draws - 1) : 0.f;
+  const float cS = (float)(n_draws - 1) / (float)n_draws;
+  for (int s = 0; s < n_draws; ++s) {
+    relaunder(c);
+    const uint64_t seed = drs[s].seed;
+    const GAS float* const epsp = asg(drs[s].eps);
+    const bool first = s == 0, last = s == n_draws - 1;
+    const float rs = 1.0f / (float)(s + 1);
+    if (s > 0) lds_barrier();                      // the previous draw's last chunk is finished everywhere: P, W, vectors, Z free
+    // W and P are free: the first decoder's image lands during the latent arithmetic
+    issue_next(c, to_W(wsh + J->mod[mf].dec_s[0], 0, J->H[L - 1], Z + C));
+    {
+      float al[NM_MAX_EXP] = {0.f, 0.f, 0.f, 0.f};
+      if (J->combine == NM_COMBINE_GPOE && !byp) softmax_alpha(J, al);
+      relaunder(c);
+      if (vec4) {
+        const int nq4 = (Z + 3) >> 2;
+        const float rq4 = 1.0f / (float)nq4;
+#pragma unroll 1
+        for (int e = c.tid; e < ROWS * nq4; e += WG) {
+          const int r = idiv(e, nq4, rq4), z0 = 4 * (e - r * nq4);
+          f32x4 mu4[NM_MAX_EXP], lv4[NM_MAX_EXP];
+#pragma unroll
+          for (int m = 0; m < NM_MAX_EXP; ++m) {
+            mu4[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+            lv4[m] = mu4[m];
+            if (m < M) {
+              mu4[m] = *(const GAS f32x4*)(ws_mu_m + ((int64_t)m * TROWS + r) * Zs + z0);
+              lv4[m] = *(const GAS f32x4*)(ws_lv_m + ((int64_t)m * TROWS + r) * Zs + z0);
+            }
+          }
+          float ep[4];
+          if (epsp) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) ep[i] = epsp[((int64_t)(step % J->eps_cap) * TROWS + c.rloc0 + r) * Z + min(z0 + i, Z - 1)];
+          } else {
+            randn2_ctr(seed, (uint32_t)step, (uint32_t)(c.row0 + r), (uint32_t)(z0 >> 1), ep[0], ep[1]);
+            randn2_ctr(seed, (uint32_t)step, (uint32_t)(c.row0 + r), (uint32_t)(z0 >> 1) + 1u, ep[2], ep[3]);
+          }
+#pragma unroll
+          for (int i = 0; i < 4; ++i) ep[i] = (z0 + i < Z) ? ep[i] : 0.f;
+          bf16x4 zk;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            Lat Lt;
+#pragma unroll
+            for (int m = 0; m < NM_MAX_EXP; ++m) { Lt.mu[m] = mu4[m][i]; Lt.lv[m] = lv4[m][i]; }
+            const Fuse f = fuse_fwd(J, Lt, al);
+            if (byp) {
+              zk[i] = (__bf16)((z0 + i < Z) ? dvd_z_bypass(f.mu, ep[i], f.lv) : 0.f);
+            } else {
+              const float es = ep[i] * fx_exp(0.5f * f.lv);
+              zk[i] = (__bf16)dvm_add(f.mu, es);
+            }
+          }
+          *reinterpret_cast<bf16x4*>(zlds + r * 32 + z0) = zk;
+        }
+      } else {
+        const float rZ = 1.0f / (float)Z;
+#pragma unroll 1
+        for (int e = c.tid; e < ROWS * Z; e += WG) {
+          const int r = idiv(e, Z, rZ), z = e - r * Z;
+          Lat Lt;
+#pragma unroll
+          for (int m = 0; m < NM_MAX_EXP; ++m) {
+            Lt.mu[m] = (m < M) ? ws_mu_m[((int64_t)m * TROWS + r) * Zs + z] : 0.f;
+            Lt.lv[m] = (m < M) ? ws_lv_m[((int64_t)m * TROWS + r) * Zs + z] : 0.f;
+          }
+          const Fuse f = fuse_fwd(J, Lt, al);
+          const float ep = epsp ? epsp[((int64_t)(step % J->eps_cap) * TROWS + c.rloc0 + r) * Z + z]
+                                : randn_ctr(seed, (uint32_t)step, (uint32_t)(c.row0 + r), (uint32_t)z);
+          if (byp) {
+            zlds[r * 32 + z] = (__bf16)dvd_z_bypass(f.mu, ep, f.lv);
+          } else {
+            const float es = ep * fx_exp(0.5f * f.lv);
+            zlds[r * 32 + z] = (__bf16)dvm_add(f.mu, es);
+          }
+        }
+      }
+    }
+    lds_barrier();                                 // z is complete (the decoder image requested above stays in flight)
+    tr(c, 3);
+
+    for (int m = mf; m < M; ++m) {
+      relaunder(c);
+      const DvdOut o = dvd_out(pr, m);
+      if (!o.mean) continue;                       // (workgroup-uniform) this decoder is not wanted: skipped entirely
+      const nm_modality_t& md = J->mod[m];
+      const int D = md.D;
+      if (m != mf) {
+        lds_barrier();                             // the previous decoder's last chunk is finished everywhere: P, W, vectors free
+        issue_next(c, to_W(wsh + md.dec_s[0], 0, J->H[L - 1], Z + C));
+      }
+      build_zc<RT>(c, c.P, md, (gcf32)nullptr, (gcf32)nullptr, Z, C, Zs, 0, (gcf32)nullptr, zlds);
+      tr(c, 4);
+      int vs = 0;
+      const GAS char* oblob = wsh + md.out_s;
+      const int nck = (D + OCH - 1) / OCH;
+      auto out_blob = [&](int ch) {
+        return Next{oblob + (int64_t)ch * OBLOB_BYTES, Wb + (ch & 1) * OIMG_BYTES, OIMG_BYTES >> 10,
+                    oblob + (int64_t)ch * OBLOB_BYTES + OIMG_BYTES, reinterpret_cast<char*>(c.vec) + ((ch + ob) & 1) * VEC_BYTES, 0, 0};
+      };
+      for (int d = 0; d < L; ++d) {
+        const int Kin = (d == 0) ? Z + C : J->H[L - d], Nout = J->H[L - 1 - d];
+        const Next nx = (d + 1 < L) ? to_W(wsh + md.dec_s[d + 1], vs ^ 1, J->H[L - 2 - d], Nout) : out_blob(0);
+        dv_layer(c, vs, nx, Nout, Kin, nl, live);    // (its first barrier also publishes z | c | 1)
+        vs ^= 1;
+      }
+      tr(c, 5);
+      // output layer in 64-ROI chunks, wave w owns rows [16 w, 16 w + 16) and all 64 columns: see nm_devpass_kernel
+      gcf32 xf = asg(md.x_f32);
+      const int xp = md.x_pitch;
+      float rdev = 0.f, rz2 = 0.f;
+      const int orow = c.wave * 16 + c.c16;
+      const bool wave_live = c.wave * 16 < live;
+      const bool rv = orow < c.nrows;
+      auto load_xin = [&](int chx, f32x4 (&xv)[4]) {
+#pragma unroll
+        for (int ft = 0; ft < 4; ++ft) {
+          const int dcl = min(chx * OCH + ft * 16 + 4 * c.g, xp - 4);
+          xv[ft] = *(const GAS f32x4*)(xf + (int64_t)(row0 + orow) * xp + dcl);
+        }
+      };
+      auto chunk = [&](const int ch, f32x4 (&xin)[4], f32x4 (&xnx)[4]) {
+        relaunder(c);
+        const int d0 = ch * OCH;
+        const __bf16* Wc = reinterpret_cast<const __bf16*>(Wb + (ch & 1) * OIMG_BYTES);
+        const float* vb = c.vec + ((ch + ob) & 1) * (VEC_BYTES / 4);
+        // chunk ch's rows, vectors and inputs have landed, and everything else this wave has in flight with them: the
+        // accumulator loads and stores of the previous chunk are counted in the same queue (a full wait, not a count)
+        wait_vm(0);
+        lds_barrier();
+        if (ch + 1 < nck) { issue_next(c, out_blob(ch + 1)); if (wave_live && last) load_xin(ch + 1, xnx); }
+        if (!wave_live) return;
+        f32x4 acc[4];
+#pragma unroll
+        for (int ft = 0; ft < 4; ++ft) acc[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
+        const int ksteps = wpad(Hl) / 32;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+          if (ks < ksteps) {
+            const bf16x8 a = lds_frag(c.P, LDP, orow, ks * 32 + 8 * c.g);
+#pragma unroll
+            for (int ft = 0; ft < 4; ++ft) acc[ft] = mfma(lds_frag(Wc, LDP, ft * 16 + c.c16, ks * 32 + 8 * c.g), a, acc[ft]);
+          }
+        }
+        tr(c, 6);
+#pragma unroll
+        for (int ft = 0; ft < 4; ++ft) {
+          const int dg0 = d0 + ft * 16 + 4 * c.g;
+          const f32x4 bo = *reinterpret_cast<const f32x4*>(vb + ft * 16 + 4 * c.g);
+          if (d0 + ft * 16 < xp && dg0 < xp) {          // (the first: wave-uniform) whole tiles are stored, zeros past the table's end
+            const int64_t gi = (int64_t)(row0 + orow) * xp + dg0;
+            f32x4 mn, m2;
+            if (first) {
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                const float xh = acc[ft][i] + bo[i];
+                mn[i] = (rv && dg0 + i < D) ? xh : 0.f;
+                m2[i] = 0.f;
+              }
+            } else {
+              const f32x4 pm = *(const GAS f32x4*)(o.mean + gi), p2 = *(const GAS f32x4*)(o.var + gi);
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                const float xh = acc[ft][i] + bo[i];
+                float a = pm[i], b = p2[i];
+                dvd_fold(xh, rs, a, b);
+                const bool dv = rv && dg0 + i < D;
+                mn[i] = dv ? a : 0.f;
+                m2[i] = dv ? b : 0.f;
+              }
+            }
+            if (!last) {
+              *(GAS f32x4*)(o.mean + gi) = mn;
+              *(GAS f32x4*)(o.var + gi) = m2;
+            } else {
+              f32x4 nv4 = f32x4{1.f, 1.f, 1.f, 1.f};
+              if (o.nv) nv4 = *(const GAS f32x4*)(o.nv + min(dg0, xp - 4));
+              f32x4 va, sq, zz;
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                float v1, q1, z1;
+                dvd_final(xin[ft][i], mn[i], m2[i], vS, cS, nv4[i], v1, q1, z1);
+                const bool dv = rv && dg0 + i < D;
+                va[i] = dv ? v1 : 0.f;
+                sq[i] = dv ? q1 : 0.f;
+                zz[i] = (dv && o.nv) ? z1 : 0.f;
+              }
+              *(GAS f32x4*)(o.mean + gi) = mn;
+              *(GAS f32x4*)(o.var + gi) = va;
+              if (o.msq) *(GAS f32x4*)(o.msq + gi) = sq;
+              if (o.z) *(GAS f32x4*)(o.z + gi) = zz;
+              rdev += dvd_sum4(sq);
+              rz2 += dvd_sumsq4(zz);
+            }
+          }
+        }
+        tr(c, 7);
+      };
+      {
+        f32x4 xa[4], xb[4];
+        if (wave_live && last) load_xin(0, xa);
+        for (int ch = 0; ch < nck; ch += 2) {
+          chunk(ch, xa, xb);
+          if (ch + 1 < nck) chunk(ch + 1, xb, xa);
+        }
+      }
+      if (last && wave_live) {                      // the row's four column groups sit in the lanes c16, c16 + 16, + 32, + 48
+        float v = rdev, w = rz2;
+        v += __shfl_xor(v, 16, 64);
+        v += __shfl_xor(v, 32, 64);
+        w += __shfl_xor(w, 16, 64);
+        w += __shfl_xor(w, 32, 64);
+        if (c.g == 0 && orow < c.nrows) {
+          if (o.rdev) o.rdev[row0 + orow] = v / (float)D;
+          if (o.rz2) o.rz2[row0 + orow] = w / (float)D;
+        }
+      }
+      // (a ragged tile only, once: the rows no wave stores)
+      if (last && live < ROWS) { relaunder(c); dvd_zero_dead_rows(c.tid, xp, o, row0, live); }
+      tr(c, 8);
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1217,6 +1603,27 @@ int nm_devpass_subsets(const nm_job_t* jobs_dev, int n_jobs, const nm_subset_t* 
   if (int bad = check_launch_geometry(jobs_dev, n_jobs, n_tiles, 1, tile0, 0)) return bad;
   return launch_kernel(nm_devpass_subsets_kernel, dim3(n_jobs, n_tiles), dim3(WG), DVS_SMEM, stream, jobs_dev, subsets_dev, n_subsets,
                        tile0, flags & NM_F_TRACE);
+}
+
+/* 0: the job can run the posterior-predictive pass: what nm_devpass_multi_ok admits and one-expert jobs (bypass on or off)
+ * within the same shape limits; NM_E_DEVPASS otherwise. */
+int nm_devpass_draws_ok(const nm_job_t* j) {
+  if (!j) return NM_E_NULL;
+  return dvd_refused(j);
+}
+
+/* The posterior-predictive pass over table rows [tile0 * 128, (tile0 + n_tiles) * 128): encoders once per tile, then n_draws
+ * times the fusion, the draw of draws_dev[job][s] and every decoder pred_dev[job] wants, folded into mean / variance /
+ * mean squared error / z per ROI (nmhip.h).  Status is decided here, on the host, before the device is asked anything -- the
+ * tables and the descriptors live in device memory: the per-job rules (pred_mean with pred_var, pred_z only with noise_var)
+ * are the caller's.  Workspace tiles as for nm_devpass_multi, one-expert jobs included. */
+int nm_devpass_draws(const nm_job_t* jobs_dev, int n_jobs, const nm_draw_t* draws_dev, int n_draws, const nm_pred_t* pred_dev,
+                     int tile0, int n_tiles, int flags, void* stream) {
+  if (!jobs_dev || !draws_dev || !pred_dev) return NM_E_NULL;
+  if (n_draws < 1 || n_draws > NM_MAX_DRAWS) return NM_E_GEOMETRY;
+  if (int bad = check_launch_geometry(jobs_dev, n_jobs, n_tiles, 1, tile0, 0)) return bad;
+  return launch_kernel(nm_devpass_draws_kernel, dim3(n_jobs, n_tiles), dim3(WG), DVD_SMEM, stream, jobs_dev, draws_dev, n_draws,
+                       pred_dev, tile0, flags & NM_F_TRACE);
 }
 
 /* 0: the job's joint latent statistics can come from the encoder-only kernel (not wide; 1..NM_MAX_EXP modalities, every one

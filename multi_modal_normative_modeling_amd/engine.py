@@ -33,6 +33,14 @@ DEVPASS_MULTI_AUTO = {2: True, 3: True, 4: True}
 # stays on the general kernel until it does (JobSet.latent(compact=True) reaches nm_latent_pass all the same)
 LATENT_AUTO = {1: True, 2: False, 3: True, 4: True}
 
+_MASK64 = (1 << 64) - 1
+
+
+def draw_seeds(seed: int, n_draws: int) -> List[int]:
+    """The default generator keys of the posterior-predictive pass: draw 0 is the job's own seed (S = 1 is the parity pass),
+    draw s is (seed + s * 0x9E3779B97F4A7C15) mod 2^64 -- the golden-ratio stride keeps the keys of neighbouring seeds apart."""
+    return [(int(seed) + s * 0x9E3779B97F4A7C15) & _MASK64 for s in range(int(n_draws))]
+
 
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
@@ -215,6 +223,11 @@ class Job:
         # the modality-subset pass (enable_subset_exports): the subsets, their expert masks, exports per (subset, modality)
         self.subsets = self.sub_masks = self.sub_decoders = None
         self.sub_loc = self.sub_sqerr = self.sub_rowdev = None
+        # the posterior-predictive pass (enable_predictive_exports): draws per row, their keys / injected noise, exports per modality
+        self.n_draws = self.pred_seeds = self.pred_eps = self.noise_var = None
+        self.pred_mean = self.pred_var = self.pred_msq = self.pred_z = self.pred_rowdev = self.pred_rowz2 = None
+        self._params_epoch = 0           # bumped by every host-side write of the parameters (refresh_noise_var)
+        self._nv_state = None
 
     # -- buffers -------------------------------------------------------------------------------
     def _ensure_workspace(self, n_tiles: int):
@@ -459,6 +472,94 @@ class Job:
             out.append(e)
         return out
 
+    def draws_ok(self) -> bool:
+        """nm_devpass_draws_ok for this job, read off the job as latent_ok is: 1..NM_MAX_EXP experts (one expert with the
+        bypass on or off), every modality with an encoder, no private latent / learnable weights / total correlation,
+        Gaussian output, first hidden width <= 112, latent <= 32."""
+        return self.latent_ok()
+
+    def enable_predictive_exports(self, n_draws, seeds=None, eps=None, msq=True, z=True, rowdev=True, rowz2=True):
+        """Buffers of the posterior-predictive pass (JobSet.forward_draws, nm_devpass_draws): S = n_draws latent draws per row,
+        folded on the device.  seeds: one generator key per draw (default: draw_seeds(job.seed, S)); eps: a list of S tensors
+        in the layout set_eps takes, used in the place of the generator.  Afterwards pred_mean[m], pred_var[m], pred_msq[m],
+        pred_z[m] ([rows_alloc, D] views) and pred_rowdev[m], pred_rowz2[m] ([rows_alloc]) hold the exports of modality m,
+        None where the kind was not asked for.  With z or rowz2 the observation variance exp(logvar_out) of the current
+        parameters travels along (refreshed by forward_draws whenever the parameters have changed).  Refused (ValueError):
+        n_draws outside 1..64, seeds / eps of another length, both given, eps draws of differing step counts."""
+        S = int(n_draws)
+        if not 1 <= S <= _lib.NM_MAX_DRAWS:
+            raise ValueError(f"n_draws must be 1 to {_lib.NM_MAX_DRAWS}, got {n_draws}")
+        if seeds is not None and eps is not None:
+            raise ValueError("give seeds or eps, not both: an injected draw has no generator key")
+        if seeds is not None and len(seeds) != S:
+            raise ValueError(f"seeds: one per draw ({S}), got {len(seeds)}")
+        if eps is not None and len(eps) != S:
+            raise ValueError(f"eps: one tensor per draw ({S}), got {len(eps)}")
+        self.pred_seeds = [int(v) & _MASK64 for v in seeds] if seeds is not None else draw_seeds(self.seed, S)
+        self.pred_eps = None
+        if eps is not None:
+            Z, out = self.spec.latent, []
+            for e in eps:
+                e = torch.as_tensor(e, dtype=torch.float32)
+                if e.dim() == 2:
+                    e = e.unsqueeze(0)
+                if e.dim() != 3 or e.shape[2] != Z or e.shape[1] > BATCH:
+                    raise ValueError(f"eps: every draw is [steps, <= {BATCH}, {Z}], got {tuple(e.shape)}")
+                steps = self.eps_cap if self.eps is not None else (out[0].shape[0] if out else e.shape[0])
+                if e.shape[0] != steps:
+                    raise ValueError(f"eps: every draw holds the same number of steps (the job's eps_cap, {steps}), "
+                                     f"got {e.shape[0]}")
+                pad = torch.zeros(e.shape[0], BATCH, Z, dtype=torch.float32)
+                pad[:, :e.shape[1]] = e
+                out.append(pad.to(self.device).contiguous())
+            if self.eps is None:
+                self.eps_cap = int(out[0].shape[0])      # (the draws' step count indexes as the job's own eps would)
+            self.pred_eps = out
+        ra, M = self.tables[0].rows_alloc, len(self.kmods)
+        pitch = [self.tables[m].x_pitch for m, _, _ in self.kmods]
+        width = [self.tables[m].D for m, _, _ in self.kmods]
+        mat = lambda on: [torch.zeros(ra, pitch[m], device=self.device)[:, :width[m]] if on else None for m in range(M)]
+        row = lambda on: [torch.zeros(ra, device=self.device) if on else None for _ in range(M)]
+        self.n_draws = S
+        self.pred_mean, self.pred_var, self.pred_msq, self.pred_z = mat(True), mat(True), mat(msq), mat(z)
+        self.pred_rowdev, self.pred_rowz2 = row(rowdev), row(rowz2)
+        self.noise_var = [torch.ones(pitch[m], device=self.device) if (z or rowz2) else None for m in range(M)]
+        self._nv_state = None
+        self._version += 1
+
+    def refresh_noise_var(self):
+        """noise_var[m] = exp(logvar_out of decoder m) of the CURRENT parameters (in place: the table on the device keeps its
+        pointers); done again only after an optimizer step or a host-side write of the parameters."""
+        if getattr(self, "noise_var", None) is None or all(v is None for v in self.noise_var):
+            return
+        state = (self.t, self._params_epoch)
+        if self._nv_state == state:
+            return
+        for k, (m, _, dp) in enumerate(self.kmods):
+            if self.noise_var[k] is not None:
+                lv = self.layout.get(self.params, f"{dp}logvar_out").reshape(-1)
+                self.noise_var[k][: lv.numel()] = torch.exp(lv)
+        self._nv_state = state
+
+    def pred_structs(self):
+        """This job's rows of nm_devpass_draws' two tables: ([NmDraw] * n_draws, NmPred)."""
+        if getattr(self, "n_draws", None) is None:
+            raise ValueError("enable_predictive_exports() first")
+        draws = []
+        for s in range(self.n_draws):
+            d = _lib.NmDraw()
+            d.seed = self.pred_seeds[s]
+            d.eps = self.pred_eps[s].data_ptr() if self.pred_eps is not None else None
+            draws.append(d)
+        p = _lib.NmPred()
+        for m in range(len(self.kmods)):
+            for field in ("pred_mean", "pred_var", "pred_msq", "pred_z", "pred_rowdev", "pred_rowz2", "noise_var"):
+                buf = getattr(self, field)[m]
+                getattr(p, field)[m] = buf.data_ptr() if buf is not None else None
+            if p.pred_z[m] and not p.noise_var[m]:
+                raise ValueError("pred_z needs noise_var: the score is scaled by exp(logvar_out) + the draw variance")
+        return draws, p
+
     def set_latent_exports(self, on: bool):
         """Switch the joint-latent exports (out_mu / out_logvar / out_z) of a job that has them off and back on; the
         buffers are kept.  Off, a reconstruction-only forward (JobSet.forward(loss=False)) can run on the compact kernels."""
@@ -558,11 +659,13 @@ class Job:
     def load_state_dict(self, state: Dict[str, torch.Tensor]):
         self.params.copy_(self.layout.flatten(state, device=self.device))
         self.shadow_dirty = True
+        self._params_epoch += 1
 
     def params_changed(self):
         """Call after writing ``params`` from the host side (an external optimizer, a hand edit): the bf16 shadow
         images the kernels read are rebuilt before the next launch."""
         self.shadow_dirty = True
+        self._params_epoch += 1
 
     def grads_dict(self) -> Dict[str, torch.Tensor]:
         return {k: v.detach().cpu().clone() for k, v in self.layout.unflatten(self.grads).items()}
@@ -1004,6 +1107,57 @@ class JobSet:
             self._sub_sig = sig
         nt = self.jobs[0].tables[0].n_tiles if n_tiles is None else n_tiles
         self._issue("nm_devpass_subsets", nt, self._sub_keep[0].data_ptr(), ns, tile0 * 2, nt * 2, _lib.NM_F_TRACE if trace else 0)
+
+    def _draws_refusal(self) -> Optional[str]:
+        """Why the set cannot run the posterior-predictive pass (nm_devpass_draws_ok asked of every job's descriptor, once per
+        state of the descriptor); None: it can."""
+        if self.wide:
+            return "general-shape path (a hidden width or latent beyond the fused kernel's tile)"
+        for i, j in enumerate(self.jobs):
+            if getattr(j, "_draws_ok_version", None) == j._version:
+                continue
+            st = self.lib.nm_devpass_draws_ok(C.byref(j.struct()))
+            if st != 0:
+                s = j.spec
+                return (f"job {i}: nm_devpass_draws_ok refuses it with status {st} "
+                        f"({self.lib.nm_status_string(st).decode()}): kind {s.kind!r}, {s.M} modalities of which "
+                        f"{len(j.kmods)} in the kernel, hidden {list(s.hidden)}, latent {s.latent}, private {s.n_private}, "
+                        f"tc_weight {j.tc_weight} -- the pass takes 1..{_lib.NM_MAX_EXP} experts, first hidden width <= 112, "
+                        f"latent rounded to 16 <= 32, Gaussian output, no end-to-end trunk")
+            j._draws_ok_version = j._version
+        return None
+
+    def forward_draws(self, tile0: int = 0, n_tiles: Optional[int] = None, trace: bool = False):
+        """The posterior-predictive pass (nm_devpass_draws): every expert's encoder once per 128-row tile, then per draw of
+        Job.enable_predictive_exports the fusion, the latent draw and every decoder, the S reconstructions of an element
+        folded on the device into job.pred_mean / pred_var / pred_msq / pred_z and the row means pred_rowdev / pred_rowz2.
+        All jobs of the set in one launch; they must ask for the same number of draws.  A set holding a job the kernel does
+        not take (general-shape path, first hidden width > 112, latent rounded to 16 > 32, an end-to-end trunk, a
+        non-Gaussian output) raises ValueError naming the refusal.  trace: the kernel records its phase cycles
+        (nm_trace_read_dv)."""
+        if any(getattr(j, "n_draws", None) is None for j in self.jobs):
+            raise ValueError("forward_draws: Job.enable_predictive_exports() first, on every job of the set")
+        S = self.jobs[0].n_draws
+        if any(j.n_draws != S for j in self.jobs):
+            raise ValueError("forward_draws: the jobs of one set must ask for the same number of draws")
+        why = self._draws_refusal()
+        if why is not None:
+            raise ValueError("forward_draws: the set cannot run on nm_devpass_draws: " + why)
+        # the two tables on the device: rebuilt when a job's descriptor (and with it, maybe, its predictive buffers) changed; kept
+        # until then -- the launch reads them in stream order
+        sig = tuple(j._version for j in self.jobs)
+        if getattr(self, "_draw_sig", None) != sig:
+            rows = [j.pred_structs() for j in self.jobs]
+            draws = (_lib.NmDraw * (S * len(rows)))(*[d for dr, _ in rows for d in dr])
+            preds = (_lib.NmPred * len(rows))(*[p for _, p in rows])
+            self._draw_keep = (torch.frombuffer(bytearray(bytes(draws)), dtype=torch.uint8).to(self.device),
+                               torch.frombuffer(bytearray(bytes(preds)), dtype=torch.uint8).to(self.device))
+            self._draw_sig = sig
+        for j in self.jobs:
+            j.refresh_noise_var()
+        nt = self.jobs[0].tables[0].n_tiles if n_tiles is None else n_tiles
+        self._issue("nm_devpass_draws", nt, self._draw_keep[0].data_ptr(), S, self._draw_keep[1].data_ptr(), tile0 * 2, nt * 2,
+                    _lib.NM_F_TRACE if trace else 0)
 
     def latent_ok(self) -> bool:
         """Can the set's joint latent statistics come from the encoder-only kernel (nm_latent_pass)?  The conditions of

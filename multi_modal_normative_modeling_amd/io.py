@@ -82,6 +82,39 @@ def write_given_csv(out_dir, dataset_name: str, tag: str, covariates: pd.DataFra
     return path
 
 
+PREDICTIVE_KINDS = ("reconstruction_mc", "reconstruction_error_roi_mc", "reconstruction_error_mc", "predictive_z", "predictive_subject")
+
+
+def write_predictive_csvs(out_dir, dataset_name: str, covariates: pd.DataFrame, roi_columns: Sequence[str], mean: np.ndarray,
+                          msq: np.ndarray, z: np.ndarray) -> Dict[str, Path]:
+    """The files of the posterior-predictive pass (sweep.test_folds(draws=S)), next to the five kinds of write_test_csvs and in
+    their layouts: reconstruction_mc_ (the mean reconstruction over the draws), reconstruction_error_roi_mc_ (per ROI the
+    Monte-Carlo mean of (x - x_hat_s)^2), reconstruction_error_mc_ (its row mean, formed as reconstruction_error_ forms its
+    own: one draw gives that file byte for byte), predictive_z_ (per ROI (x - mean) / sqrt(exp(logvar_out) + the draw
+    variance)) and predictive_subject_ (per subject the mean squared error, the mean z^2, the largest |z| and its ROI)."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    cov = covariates[META_COLS].copy().reset_index(drop=True)
+    frames = {}
+    for kind, values in (("reconstruction_mc", mean), ("reconstruction_error_roi_mc", msq), ("predictive_z", z)):
+        frames[kind] = pd.concat([cov, pd.DataFrame(np.asarray(values), columns=list(roi_columns))], axis=1)
+    err = cov.copy()
+    err["Reconstruction error"] = np.sum(msq, axis=1) / msq.shape[1]
+    frames["reconstruction_error_mc"] = err
+    sub = cov.copy()
+    worst = np.argmax(np.abs(z), axis=1)
+    sub["Mean squared error"] = err["Reconstruction error"]
+    sub["Mean z2"] = np.sum(z * z, axis=1) / z.shape[1]
+    sub["Max abs z"] = np.abs(z)[np.arange(len(z)), worst]
+    sub["Max abs z ROI"] = [roi_columns[i] for i in worst]
+    frames["predictive_subject"] = sub
+    paths = {}
+    for kind in PREDICTIVE_KINDS:
+        paths[kind] = out_dir / f"{kind}_{dataset_name}.csv"
+        frames[kind].to_csv(paths[kind], index=False)
+    return paths
+
+
 def write_latent_csvs(out_dir, name: str, covariates: pd.DataFrame, mu: np.ndarray, var: np.ndarray, score: np.ndarray,
                       zsep: np.ndarray) -> Dict[str, Path]:
     """The latent-space deviation of one fold's test subjects (pred_latent + latent_deviation / separate_latent_deviation,

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, io, metrics, prep, workload
-from .engine import Job, JobSet, Table
+from .engine import Job, JobSet, Table, draw_seeds
 from .layout import ModelSpec
 
 # one row per cell in the table the final all_gather carries
@@ -763,6 +763,20 @@ def given_subsets(given, modalities: Sequence[str]) -> List[tuple]:
     return out
 
 
+def check_draws(draws, draw_seed=None):
+    """(draws, draw_seed) of test_folds / `test --draws S [--draw-seed N]` as integers, or (None, None) where the pass is off.
+    Refused (ValueError): draws outside 1..NM_MAX_DRAWS, a draw_seed without draws, a draw_seed outside [0, 2^64)."""
+    if draws is None:
+        if draw_seed is not None:
+            raise ValueError("draw_seed needs draws (it keys the latent draws of the posterior-predictive pass)")
+        return None, None
+    if int(draws) != draws or not 1 <= int(draws) <= _lib.NM_MAX_DRAWS:
+        raise ValueError(f"draws must be an integer from 1 to {_lib.NM_MAX_DRAWS}, got {draws}")
+    if draw_seed is not None and (int(draw_seed) != draw_seed or not 0 <= int(draw_seed) < 1 << 64):
+        raise ValueError(f"draw_seed must be an integer inside [0, 2^64), got {draw_seed}")
+    return int(draws), (None if draw_seed is None else int(draw_seed))
+
+
 def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequence[tuple], modalities: Sequence[str],
                combines, device, out_dirs: Optional[Sequence] = None,
                roi_columns: Optional[Dict[str, Sequence[str]]] = None, roi_effect: bool = False,
@@ -771,7 +785,8 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
                roi_adjust: Sequence[str] = (), normative: Optional[str] = None,
                z_thr: float = 1.96, centile: Optional[str] = None, tail: float = 2.5,
                quantiles: Sequence[float] = CENTILE_QUANTILES, centile_loo: bool = False,
-               robust: bool = False, given=None) -> List[Dict[str, np.ndarray]]:
+               robust: bool = False, given=None, draws: Optional[int] = None,
+               draw_seed: Optional[int] = None) -> List[Dict[str, np.ndarray]]:
     """test_fold for ALL folds of a procedure as one launch: jobs[i] is the trained model of fold i, folds[i] its
     (train_rows, test_rows); one evaluation job per fold, each on its own test tables (seed, scaler and covariates per fold
     exactly as test_fold), all in ONE JobSet -- a fold's ~N / K test rows are a single workgroup, K of them in a row leave
@@ -791,7 +806,15 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
     own experts, the same draw, every decoder) -- all folds in one launch per table height -- and each fold's dict gains
     "given": {tag: {modality: per-subject reconstruction error from the modalities of `tag` alone}}; with out_dirs, per target
     modality reconstruction_error_<m>_given_<tag>.csv next to reconstruction_error_<m>.csv, in its layout.  A set holding a
-    model the subset kernel does not take (JobSet.forward_subsets) raises ValueError.  Without `given` nothing changes."""
+    model the subset kernel does not take (JobSet.forward_subsets) raises ValueError.  Without `given` nothing changes.
+
+    draws (1..64): after the pass above the evaluation jobs run the posterior-predictive pass (JobSet.forward_draws: the
+    encoders once, `draws` latent draws folded on the device) -- all folds in one launch per table height -- and each fold's
+    dict gains "predictive": {modality: {"mean", "var", "msq", "z", "rowdev", "rowz2"}}; with out_dirs, the files of
+    io.write_predictive_csvs next to the five kinds.  Draw 0 is keyed by the evaluation job's own seed (one draw reproduces
+    the pass above), draw s by engine.draw_seeds; draw_seed: fold i's draws are keyed from draw_seed + i instead.  A set
+    holding a model the kernel does not take raises ValueError.  Without `draws` nothing changes."""
+    draws, draw_seed = check_draws(draws, draw_seed)
     subsets = given_subsets(given, modalities) if given is not None else []
     for name, on in (("centile", centile is not None), ("normative", normative is not None), ("roi_significance", roi_significance),
                      ("roi_regress", roi_regress is not None)):
@@ -829,7 +852,12 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
             ev.enable_subset_exports([idx for _, idx in subsets], loc=True, sqerr=False, rowdev=False)
         for group in _by_height([ev for ev, _ in evs]):
             JobSet(group).forward_subsets()
-    queued = []                 # (statistic, its device entry per table of t.mats): everything is queued before the one synchronise
+    if draws is not None:
+        for i, (ev, _) in enumerate(evs):
+            ev.enable_predictive_exports(draws, seeds=None if draw_seed is None else draw_seeds(draw_seed + i, draws))
+        for group in _by_height([ev for ev, _ in evs]):
+            JobSet(group).forward_draws()
+    queued = []               # (statistic, its device entry per table of t.mats): everything is queued before the one synchronise
     if roi_effect:
         nm_ = len(modalities)
         tests = [te for _, te in folds]
@@ -854,6 +882,17 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
                 if d is not None:
                     for i, m in enumerate(modalities):
                         io.write_given_csv(Path(d) / m, m, tag, _meta_frame(cohort, te), xs[i], x_hats[i])
+    if draws is not None:
+        kinds = (("mean", "pred_mean"), ("var", "pred_var"), ("msq", "pred_msq"), ("z", "pred_z"), ("rowdev", "pred_rowdev"),
+                 ("rowz2", "pred_rowz2"))
+        for res, (ev, xs), (_, te), d in zip(out, evs, folds, dirs):
+            res["predictive"] = {m: {k: getattr(ev, name)[i][:len(te)].cpu().numpy() for k, name in kinds}
+                                 for i, m in enumerate(modalities)}
+            if d is not None:
+                for i, m in enumerate(modalities):
+                    p = res["predictive"][m]
+                    io.write_predictive_csvs(Path(d) / m, m, _meta_frame(cohort, te), _roi_columns(roi_columns, m, xs[i].shape[1]),
+                                             p["mean"], p["msq"], p["z"])
     for st, entries in queued:
         entries = [_host(e) for e in entries]
         pooled = {m: entries[t.n_fold + i] for i, m in enumerate(modalities)}
@@ -1280,6 +1319,13 @@ def main_test(argv=None):
                          "all (every non-empty subset), loo (every set that leaves one modality out), single (every one-modality "
                          "set), or sets of their own as names joined by + (T1w+T2w): per fold and all folds "
                          "reconstruction_error_<m>_given_<SET>.csv per target modality m; procedures with several modalities only")
+    ap.add_argument("--draws", type=int, default=None, metavar="S",
+                    help="also the posterior-predictive score over S latent draws (1..64), folded on the device: per fold and all "
+                         "folds reconstruction_mc_<m>.csv (the mean reconstruction), reconstruction_error_roi_mc_<m>.csv and "
+                         "reconstruction_error_mc_<m>.csv (the Monte-Carlo mean squared error), predictive_z_<m>.csv (the residual "
+                         "over the model's own predictive sd) and predictive_subject_<m>.csv")
+    ap.add_argument("--draw-seed", dest="draw_seed", type=int, default=None, metavar="N",
+                    help="with --draws: key the draws of fold i from N + i instead of the fold's own seed")
     _driver_common(ap)
     args = ap.parse_args(argv)
     if args.given:
@@ -1301,7 +1347,10 @@ def main_test(argv=None):
                 (args.roi_significance and not args.roi_effect, "--roi-significance needs --roi-effect"),
                 (args.latent_pvalues and not args.latent, "--latent-pvalues needs --latent"),
                 (args.roi_regress and not args.roi_effect, "--roi-regress needs --roi-effect"),
-                (args.roi_adjust and not args.roi_regress, "--roi-adjust needs --roi-regress"))
+                (args.roi_adjust and not args.roi_regress, "--roi-adjust needs --roi-regress"),
+                (args.draw_seed is not None and args.draws is None, "--draw-seed needs --draws"),
+                (args.draws is not None and not 1 <= args.draws <= _lib.NM_MAX_DRAWS, f"--draws must be 1 to {_lib.NM_MAX_DRAWS}"),
+                (args.draw_seed is not None and not 0 <= args.draw_seed < 1 << 64, "--draw-seed must lie inside [0, 2^64)"))
     for refused, message in refusals:
         if refused:
             ap.error(message)
@@ -1344,7 +1393,7 @@ def main_test(argv=None):
                         normative=args.normative, z_thr=args.z_thr, robust=args.robust, centile=args.centile, tail=args.tail,
                         quantiles=args.quantiles, centile_loo=args.centile_loo)
     results = test_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs, given=args.given,
-                         **vars(o)) if my else []
+                         draws=args.draws, draw_seed=args.draw_seed, **vars(o)) if my else []
     given_tags = [tag for tag, _ in given_subsets(args.given, mods)] if args.given else []
     # the pooled entries of every statistic that is on: this rank's folds' test subjects as one set (the maps: against their controls)
     pooled_stats = [st for st in ROI_STATS if getattr(o, st.key)] if results else []
@@ -1360,6 +1409,9 @@ def main_test(argv=None):
         for tag in given_tags if my else []:
             parts = [pd.read_csv(root / f"{k:03d}" / m / io.given_filename(m, tag)) for k in my]
             pd.concat(parts, ignore_index=True).to_csv(out_root / m / io.given_filename(m, tag), index=False)
+        for kind in io.PREDICTIVE_KINDS if (args.draws is not None and my) else ():
+            parts = [pd.read_csv(root / f"{k:03d}" / m / f"{kind}_{m}.csv") for k in my]
+            pd.concat(parts, ignore_index=True).to_csv(out_root / m / f"{kind}_{m}.csv", index=False)
         for st in pooled_stats:
             e = results[0][st.key + "_pooled"][m]
             st.write(out_root / m, m, _roi_columns(None, m, _n_roi(e)), meta_all, e, o)
@@ -1484,8 +1536,12 @@ ANALYSIS_SCORES = {
     # (--centile-score tails / depth: a flag of its own, the --score choice list is pinned)
     "centile_tails": ("centile_subject_{m}.csv", lambda d: d["n_hi"] + d["n_lo"], " with --roi-effect --centile"),
     "centile_depth": ("centile_subject_{m}.csv", lambda d: d["mean_abs_dev"], " with --roi-effect --centile"),
+    # (--predictive-score msq / z2: likewise a flag of its own; the files of `test --draws S`)
+    "predictive_msq": ("reconstruction_error_mc_{m}.csv", lambda d: d["Reconstruction error"], " with --draws S"),
+    "predictive_z2": ("predictive_subject_{m}.csv", lambda d: d["Mean z2"], " with --draws S"),
 }
 CENTILE_SCORES = ("tails", "depth")
+PREDICTIVE_SCORES = ("msq", "z2")
 
 
 def _analysis_scores(root: Path, mods: Sequence[str], procedure: str, score: str, n_splits: int, hc: int):
@@ -1731,6 +1787,11 @@ def main_analysis(argv=None):
                     help="instead of --score: the per-subject score from centile_subject_<m>.csv (`test --roi-effect --centile`), "
                          "averaged over the modalities -- tails: n_hi + n_lo, the ROIs in the tails; depth: mean_abs_dev, the mean "
                          "distance of the percentile ranks from 50; writes group_analysis_centile_<kind>.csv")
+    ap.add_argument("--predictive-score", dest="predictive_score", choices=PREDICTIVE_SCORES, default=None,
+                    help="instead of --score: the posterior-predictive score of `test --draws S`, averaged over the modalities -- msq: "
+                         "`Reconstruction error` of reconstruction_error_mc_<m>.csv, the Monte-Carlo mean squared error; z2: `Mean z2` "
+                         "of predictive_subject_<m>.csv, the squared residual over the model's own predictive variance; writes "
+                         "group_analysis_predictive_<kind>.csv")
     ap.add_argument("--roi", action="store_true",
                     help="instead: which ROIs separate patients from controls -- per fold and modality every ROI's Cliff's delta and "
                          "ROC-AUC on reconstruction_error_roi_<m>.csv, their mean and std over folds to group_analysis_roi_<m>.csv")
@@ -1777,6 +1838,8 @@ def main_analysis(argv=None):
                          "group_analysis_given_<P>_bootstrap.csv")
     args = ap.parse_args(argv)
     if args.given:
+        if args.predictive_score:
+            ap.error("--given scores the reconstruction error of modality subsets: it does not go with --predictive-score")
         if args.score != "reconstruction" or args.centile_score or args.roi or args.against or args.threshold_rule or args.roc_grid:
             ap.error("--given scores the reconstruction error of modality subsets: it does not go with --score, --centile-score, "
                      "--roi, --against, --threshold-rule or --roc-grid")
@@ -1790,6 +1853,14 @@ def main_analysis(argv=None):
         if args.roi:
             ap.error("--centile-score is a per-subject score: it does not go with --roi")
         args.score = f"centile_{args.centile_score}"
+    if args.predictive_score:
+        if args.centile_score:
+            ap.error("--predictive-score is a score of its own: it does not go with --centile-score")
+        if args.score != "reconstruction":
+            ap.error("--predictive-score is a score of its own: it does not go with --score")
+        if args.roi:
+            ap.error("--predictive-score is a per-subject score: it does not go with --roi")
+        args.score = f"predictive_{args.predictive_score}"
     if args.threshold_from == "others" and not args.threshold_rule:
         ap.error("--threshold-from others needs --threshold-rule")
     if (args.threshold_rule or args.roc_grid) and args.roi:

@@ -72,6 +72,10 @@ LIMITS = {
     # (the kernel above with the fusion and the decoders inside a loop over expert subsets: the build shows 128 VGPRs and 111
     #  SGPR spills -- the entry's mask, presence and export pointers stay alive across the decoders; the ceiling is that count)
     "nm_devpass_subsets_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 111, "vgpr_count": 128},
+    # (the subsets kernel's shape with the loop over latent draws and the fold of the S reconstructions in the output epilogue:
+    #  the build shows 128 VGPRs and 121 SGPR spills -- the seven export pointers of a decoder stay alive across its chunks; the
+    #  ceiling is that count)
+    "nm_devpass_draws_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 121, "vgpr_count": 128},
     # (the encoder half of the kernel above: the build shows 76 VGPRs and 30 SGPR spills -- plus the same margin of 64)
     "nm_latent_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 94, "vgpr_count": 128},
     "nm_rs_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 540},
