@@ -911,7 +911,7 @@ int nm_prep_scaler_fit(const double* const* srcs_dev, const int32_t* src_D_dev, 
                        int n_rows, double* center_dev, double* scale_dev, void* stream);
 /* c = [eye(age_bins)[qcut(rank_first(AGE))] | eye(gender_bins)[qcut(rank_first(PTGENDER))]] as fp32 [n_rows][age_bins +
  * gender_bins] (:107-126).  *_edges_dev: the q + 1 bin edges numpy computes for the ranks 1..n_rows (they depend on
- * n_rows only; prep.qcut_edges). */
+ * n_rows only; prep.qcut_edges).  Equal values rank by their position in rows_dev; -0.0 and +0.0 are equal values. */
 int nm_prep_onehot(const double* age_dev, const double* gender_dev, const int32_t* rows_dev, int n_rows, const double* age_edges_dev,
                    int age_bins, const double* gender_edges_dev, int gender_bins, float* c_out_dev, void* stream);
 /* nm_pack_table fed from the raw cohort: x = (float)((raw - center) / scale) for the given rows (RobustScaler.transform +

@@ -25,9 +25,10 @@ constexpr int PREP_WG = 512;
 constexpr int PREP_MAX_N = 8192;
 constexpr int LDX = 72, XCH = 64, ROWS = NM_BATCH;
 
-// order-preserving map double -> uint64 (ascending)
+// order-preserving map double -> uint64 (ascending); -0.0 and +0.0 share the key of +0.0, as they compare equal in numpy /
+// pandas: among zeros of either sign the payload (position) decides the rank, and a sorted zero reads back as +0.0
 __device__ __forceinline__ uint64_t key_of(double v) {
-  uint64_t u = (uint64_t)__double_as_longlong(v);
+  uint64_t u = v == 0.0 ? 0ull : (uint64_t)__double_as_longlong(v);
   return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
 }
 __device__ __forceinline__ double val_of(uint64_t k) {

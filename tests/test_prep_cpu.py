@@ -97,3 +97,66 @@ def test_cyclic_lr_schedule():
     gs = 13
     cycle = np.floor(1 + gs / (2 * ss)); x = np.abs(gs / ss - 2 * cycle + 1)
     assert lr[gs - 1] == 1e-6 + (5e-5 - 1e-6) * max(0, 1 - x) * 0.98 ** cycle
+
+
+# ---- the sizes and edges the device kernels are held to prep.py at (tests/test_gpu_prep.py) ------------------------------
+
+def _scaler_inputs(n, rng):
+    base = rng.standard_normal(n) * 3.0 + 0.5
+    return np.stack([base, np.rint(rng.standard_normal(n) * 2.0) + 0.0, rng.choice(base, size=n, replace=True), np.full(n, 2.5),
+                     rng.standard_normal(n) * 1e-300, rng.standard_normal(n) * 1e300, -np.abs(rng.standard_normal(n)) - 1e-3], axis=1)
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 4, 5, 7, 8, 9, 255, 256, 257, 1023, 1024, 1025])
+def test_robust_scaler_matches_sklearn_at_small_sizes(n):
+    """Exactly: continuous, tied, resampled, constant, tiny, huge and all-negative columns; rows as they are, resampled with
+    replacement (bootstrap duplicates), and one row n times."""
+    rng = np.random.default_rng(9000 + n)
+    x = _scaler_inputs(n + 3, rng)
+    boot = prep.rows_of_ids(np.arange(n + 3), rng.choice(n + 3, size=n, replace=True))
+    for rows in (np.arange(n), rng.permutation(n + 3)[:n], boot, np.full(n, 1)):
+        c, s = prep.robust_scaler_fit(x[rows])
+        ref = RobustScaler().fit(x[rows])
+        assert np.array_equal(c, ref.center_) and np.array_equal(s, ref.scale_)
+        assert np.isfinite(c).all() and np.isfinite(s).all() and (s > 0).all()
+        assert s[3] == 1.0 and c[3] == 2.5                          # zero IQR scales by 1
+
+
+def _pandas_bins(col, q):
+    return pd.qcut(pd.Series(col).rank(method="first"), q=q, labels=list(range(q))).to_numpy().astype(np.int64)
+
+
+@pytest.mark.parametrize("n", [2, 5, 26, 27, 28])
+def test_qcut_rank_bins_matches_pandas_below_and_at_the_bin_count(n):
+    """27 bins over fewer rows than bins leave bins empty; the edges stay strictly increasing from n = 2, so pandas accepts them."""
+    rng = np.random.default_rng(40 + n)
+    assert (np.diff(prep.qcut_edges(n, 27)) > 0).all()
+    for col in (rng.integers(22, 37, size=n).astype(float), np.full(n, 31.0), np.arange(n, 0, -1) + 0.5,
+                rng.integers(22, 37, size=n + 3).astype(float)[rng.integers(0, n + 3, size=n)]):
+        assert np.array_equal(prep.qcut_rank_bins(col, 27), _pandas_bins(col, 27))
+        assert np.array_equal(prep.qcut_rank_bins(col, 2), _pandas_bins(col, 2))
+
+
+def test_qcut_edges_of_one_row_are_one():
+    """n = 1: all q + 1 edges are 1.0 and the single row falls in bin 0 (pandas itself refuses duplicate edges)."""
+    assert (prep.qcut_edges(1, 27) == 1.0).all() and len(prep.qcut_edges(1, 27)) == 28
+    assert np.array_equal(prep.qcut_rank_bins(np.array([30.0]), 27), [0])
+    with pytest.raises(ValueError):
+        _pandas_bins(np.array([30.0]), 27)
+    c = prep.one_hot_covariates(np.array([30.0]), np.array([1.0]))
+    assert c.shape == (1, 29) and c[0, 0] == 1 and c[0, 27] == 1 and c.sum() == 2
+
+
+@pytest.mark.parametrize("n", [4, 5, 28, 257])
+def test_signed_zeros_rank_as_a_tie(n):
+    """A column coded 0.0 / -0.0: pandas ranks the zeros as equal, first come first; so does rank_first."""
+    col = np.where(np.arange(n) % 2 == 1, -0.0, 0.0)
+    assert np.array_equal(pd.Series(col).rank(method="first").to_numpy(), np.arange(1, n + 1))
+    assert np.array_equal(prep.rank_first(col), np.arange(1, n + 1))
+    assert np.array_equal(prep.qcut_rank_bins(col, 2), _pandas_bins(col, 2))
+    if n == 4:
+        assert list(prep.qcut_rank_bins(col, 2)) == [0, 0, 1, 1]
+    rng = np.random.default_rng(n)
+    mixed = rng.integers(-1, 2, size=n).astype(float)
+    mixed[::3] *= -1.0                                                  # -0.0 among -1, 0, 1
+    assert np.array_equal(prep.qcut_rank_bins(mixed, 27 if n > 27 else 2), _pandas_bins(mixed, 27 if n > 27 else 2))
