@@ -583,6 +583,7 @@ class DmSpec:
     latent: int
     c_dim: int
     cls: str = "DMVAE"             # DMVAE | WeightedDMVAE | mmVAEPlus
+    non_linear: bool = True        # the classes apply ReLU unconditionally; False: the linear stack of tests/grad_check.py
 
     @property
     def M(self) -> int:
@@ -612,11 +613,12 @@ def dm_param_names(spec: DmSpec) -> List[str]:
 def dm_forward(P, spec: DmSpec, xes, eps):
     """forward_multimodal of the DMVAE family (cVAE.py:1536-1558): eps [B, >= Z - s] is the draw of the shared latent."""
     S, Zc = spec.n_private, spec.latent - spec.n_private
+    act = torch.relu if spec.non_linear else (lambda h: h)
     mus, lvs = [], []
     for m in range(spec.M):
         p = f"encoder_list.{m}."
-        h = torch.relu(linear(xes[m], P[p + "fc1.weight"], P[p + "fc1.bias"]))
-        h = torch.relu(linear(h, P[p + "fc2.weight"], P[p + "fc2.bias"]))
+        h = act(linear(xes[m], P[p + "fc1.weight"], P[p + "fc1.bias"]))
+        h = act(linear(h, P[p + "fc2.weight"], P[p + "fc2.bias"]))
         mus.append(linear(h, P[p + "fc_mu.weight"], P[p + "fc_mu.bias"]))
         lvs.append(linear(h, P[p + "fc_logvar.weight"], P[p + "fc_logvar.bias"]))
     mu_c = torch.stack([m_[:, S:] for m_ in mus])
@@ -629,8 +631,8 @@ def dm_forward(P, spec: DmSpec, xes, eps):
     for m in range(spec.M):
         p = f"decoder_list.{m}."
         zc = torch.cat((z, mus[m][:, :S]), dim=1)
-        h = torch.relu(linear(zc, P[p + "fc1.weight"], P[p + "fc1.bias"]))
-        h = torch.relu(linear(h, P[p + "fc2.weight"], P[p + "fc2.bias"]))
+        h = act(linear(zc, P[p + "fc1.weight"], P[p + "fc1.bias"]))
+        h = act(linear(h, P[p + "fc2.weight"], P[p + "fc2.bias"]))
         recons.append(torch.sigmoid(linear(h, P[p + "fc_out.weight"], P[p + "fc_out.bias"])))
     return {"x_recons": recons, "mu_c": mu_j, "logvar_c": lv_j}
 

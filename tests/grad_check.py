@@ -53,6 +53,28 @@ below it.
 `seeded_faults` yields the structural faults a kernel could have (a dropped row / column, swapped 16 x 16 tiles, a stale
 128 x 128 block, a repeated bias element, a 2 % scale error, a pad row that leaks); test_grad_check_cpu.py seeds each into
 the oracle's own gradients and requires the checker to flag it.
+
+The baseline zoo (cases D*, M*, DW*).  Job.struct() turns on switches for the DMVAE family and mvtCAE that no
+cVAE_multimodal case reaches -- ReLU (act_slope 0), the sigmoid output with -0.5 sum (x - x_hat)^2, private latent columns
+that go from fc_mu straight into the modality's own decoder, tables without the covariate block, learnable loss weights
+with their own gradient, and on the fused kernel mvtCAE's ProductOfExperts2 on variances, the variance floor and the
+total-correlation term -- so those kinds get cases of their own, with the same two statistics, twin and bounds:
+  * the oracle is R.dm_forward / R.dm_loss; the twin permutes the hidden units of fc1 and fc2; inputs are uniform in
+    [0, 1); a WeightedDMVAE carries the unequal weights DM_WEIGHTS;
+  * the linear run (statistic A) needs non_linear = 0, which Job.struct() never sends for these kinds: LinearDmJob clears
+    the flag in the descriptor, and R.DmSpec(non_linear=False) is the oracle of that run.  The sigmoid output stays;
+  * the ReLU run (statistic B) uses the flip handling as it is: slope 0 in place of 0.01, the same margin and the same
+    cap.  tests/test_grad_check_cpu.py shows what a perturbation of the margin's size flips under ReLU;
+  * rows [:n_private] of every fc_logvar weight and bias have no gradient at all (private_rows): they are held to the
+    rule for a tensor that is zero -- untouched poison or exact zeros -- not to the slice floor;
+  * zoo_faults seeds what these branches could get wrong: the private / shared boundary off by one, a private fc_logvar
+    row that is not zero, the sigmoid's derivative missing on the last partial output chunk, weights[i] applied to another
+    modality, the weights' gradients swapped, the total-correlation gradient stopping short of a ragged batch's end.
+Every shape is the one the issue names: nm_validate_job accepts each as it stands, none had to move.  M1T is an addition:
+M1 with the total-correlation weight at 0.1 per modality instead of the class's 1e-4.  At 1e-4 the term moves
+enc_mean_layer's gradient by about 1e-3 of its largest element, and a fault in its last 8 batch rows by less than the
+bf16 rounding of the delta it rides on (3.8e-4, FLOOR_A is 2e-3): M1, M2 and M3 run that code but cannot pin it.  At 0.1
+the same fault is 4e-2 of the largest element, and M1T pins the term's backward pass on a ragged batch.
 """
 from __future__ import annotations
 
@@ -81,15 +103,34 @@ class GradCase:
     c_dim: int
     B: int
     combine: str
-    kind: str            # "multimodal" | "mvtcae"
+    kind: str            # "multimodal" | "mvtcae" | "dmvae" | "weighted_dmvae" | "mmvaeplus"
     wide: bool           # which root kernel must serve it
     seed: int
     bound_A: float       # linear stack, statistic A
-    bound_B: float       # LeakyReLU, statistic B
+    bound_B: float       # LeakyReLU (the DMVAE family: ReLU), statistic B
+    tc_beta: float = R.MVT_BETA      # mvtCAE: weight of the total-correlation term per modality (the class has 1e-4)
+
+    @property
+    def is_dm(self) -> bool:
+        return self.kind in DM_CLS
+
+    @property
+    def slope(self) -> float:
+        """Negative slope of the activation: the DMVAE family's ReLU has none."""
+        return 0.0 if self.is_dm else R.LEAKY_SLOPE
+
+    @property
+    def n_private(self) -> int:
+        """DMVAE family: the first min(c_dim, Z) latent columns are private to their modality."""
+        return min(self.c_dim, self.Z) if self.is_dm else 0
 
 
-def _c(id, dims, hidden, Z, c_dim, B, combine, wide, seed, bound_A, bound_B, kind="multimodal"):
-    return GradCase(id, tuple(dims), tuple(hidden), Z, c_dim, B, combine, kind, wide, seed, bound_A, bound_B)
+DM_CLS = {"dmvae": "DMVAE", "weighted_dmvae": "WeightedDMVAE", "mmvaeplus": "mmVAEPlus"}
+DM_WEIGHTS = (0.8, 1.1, 1.3, 0.9)       # unequal, so that each weight's own gradient and scaling is seen
+
+
+def _c(id, dims, hidden, Z, c_dim, B, combine, wide, seed, bound_A, bound_B, kind="multimodal", **kw):
+    return GradCase(id, tuple(dims), tuple(hidden), Z, c_dim, B, combine, kind, wide, seed, bound_A, bound_B, **kw)
 
 
 # bound_A / bound_B: 5.7 x the oracle-to-twin distance or the floor (see the module docstring); the distances are
@@ -112,7 +153,26 @@ CASES: Dict[str, GradCase] = {c.id: c for c in [
     _c("F4", [129], (16, 127, 8), 5, 3, 255, "gpoe", False, 204, 2e-3, 8e-3),
     _c("F5", [60], (100,), 64, 63, 83, "poe", False, 205, 4.1e-3, 8e-3),
     _c("F6", [50, 41], (90, 40, 127, 16, 64, 8, 100, 24), 20, 29, 19, "mopoe", False, 206, 2e-3, 8e-3),
+    # -- the baseline zoo on the fused step kernel (c_dim of a DMVAE-family case = its number of private latent columns) ---
+    # twin distances measured on the CPU (A linear / B ReLU or LeakyReLU): D1 3.2e-5 / 5.8e-7, D2 5.4e-6 / 2.2e-8,
+    # D3 2.9e-7 / 1.5e-4, D4 2.9e-4 / 1.2e-3, D5 0 / 0, D6 0 / 0, M1 3.4e-4 / 5.7e-4, M2 4.0e-8 / 6.1e-6, M3 1.1e-7 / 5.4e-8:
+    # 4 x each is below its floor.  DW1 3.8e-4 / 2.9e-4, DW2 7.0e-4 / 3.2e-5, DW3 7.5e-4 / 8.9e-4: bound_A at 5.7 x.
+    _c("D1", [77, 60], (127, 64), 20, 7, 130, "poe", False, 301, 2e-3, 8e-3, kind="dmvae"),
+    _c("D2", [129, 61, 47], (64, 48), 12, 29, 255, "poe", False, 302, 2e-3, 8e-3, kind="dmvae"),
+    _c("D3", [61, 90, 47], (64, 48), 12, 4, 256, "poe", False, 303, 2e-3, 8e-3, kind="weighted_dmvae"),
+    _c("D4", [379, 379, 379, 1137], (110, 110), 10, 3, 256, "poe", False, 304, 2e-3, 8e-3, kind="mmvaeplus"),
+    _c("D5", [60], (16, 127), 64, 63, 19, "poe", False, 305, 2e-3, 8e-3, kind="dmvae"),
+    _c("D6", [45, 61], (100, 8), 17, 1, 1, "poe", False, 306, 2e-3, 8e-3, kind="dmvae"),
+    _c("M1", [40, 40, 40, 40], (127,), 64, 5, 200, "poe", False, 311, 2e-3, 8e-3, kind="mvtcae"),
+    _c("M1T", [40, 40, 40, 40], (127,), 64, 5, 200, "poe", False, 311, 2e-3, 8e-3, kind="mvtcae", tc_beta=0.1),
+    _c("M2", [129, 33], (16, 127, 8), 5, 3, 255, "gpoe", False, 312, 2e-3, 8e-3, kind="mvtcae"),
+    _c("M3", [50, 41], (90, 40), 20, 29, 19, "mopoe", False, 313, 2e-3, 8e-3, kind="mvtcae"),
+    # -- the baseline zoo on the general-shape path ---------------------------------------------------------------------------
+    _c("DW1", [70, 55, 33], (129, 257), 65, 6, 255, "poe", True, 321, 2.1e-3, 8e-3, kind="dmvae"),
+    _c("DW2", [60, 45, 70], (300, 160), 128, 64, 200, "poe", True, 322, 4.0e-3, 8e-3, kind="weighted_dmvae"),
+    _c("DW3", [37], (1024, 129), 100, 100, 83, "poe", True, 323, 4.3e-3, 8e-3, kind="mmvaeplus"),
 ]}
+ZOO_IDS = [k for k, c in CASES.items() if k[0] in "DM"]
 WIDE_IDS = [k for k, c in CASES.items() if c.wide]
 FUSED_IDS = [k for k, c in CASES.items() if not c.wide]
 
@@ -127,29 +187,56 @@ def onehot(gen, B, c_dim):
 
 class CaseData:
     """Seeded data of one case: B + 1 table rows (the last one is the pad row of the leak fault; every run but that one
-    uses the first B), covariates, draws, reference-rule weights."""
+    uses the first B), covariates, draws, reference-rule weights.  The DMVAE family: inputs in [0, 1) (its outputs are
+    sigmoids), tables without the covariate block (its networks take none), unequal loss weights for WeightedDMVAE."""
 
     def __init__(self, case: GradCase):
         gen = torch.Generator().manual_seed(case.seed)
         self.case = case
         n = case.B + 1
-        self.xs = [torch.randn(n, d, generator=gen) * 1.2 for d in case.dims]
-        self.c = onehot(gen, n, case.c_dim)
+        if case.is_dm:
+            self.xs = [torch.rand(n, d, generator=gen) for d in case.dims]
+            self.c = torch.zeros(n, 0)
+        else:
+            self.xs = [torch.randn(n, d, generator=gen) * 1.2 for d in case.dims]
+            self.c = onehot(gen, n, case.c_dim)
         self.eps = torch.randn(n, case.Z, generator=gen)
         self.P = nm.ParamLayout(self.spec(True)).init_reference_rule(case.seed)
+        if "weights" in self.P:
+            self.P["weights"] = torch.tensor(DM_WEIGHTS[:len(case.dims)])
 
     def spec(self, non_linear: bool) -> "nm.ModelSpec":
         c = self.case
         return nm.ModelSpec(list(c.dims), list(c.hidden), c.Z, c.c_dim, non_linear, c.kind)
 
+    def ref_spec(self, non_linear: bool):
+        """The oracle's description of the case."""
+        c = self.case
+        if c.is_dm:
+            return R.DmSpec(list(c.dims), list(c.hidden), c.Z, c.c_dim, DM_CLS[c.kind], non_linear)
+        return R.Spec(list(c.dims), list(c.hidden), c.Z, c.c_dim, non_linear)
+
     def job(self, non_linear: bool, device):
         """The case as a Job on `device`, gradient buffer NaN-poisoned."""
         c = self.case
         tables = [nm.Table(x[:c.B], self.c[:c.B], device) for x in self.xs]
-        job = nm.Job(self.spec(non_linear), tables, combine=c.combine, state=self.P)
+        cls = LinearDmJob if c.is_dm and not non_linear else nm.Job
+        job = cls(self.spec(non_linear), tables, combine=c.combine, state=self.P)
+        if c.kind == "mvtcae":
+            job.tc_weight = len(c.dims) * c.tc_beta
         job.set_eps(self.eps[:c.B])
         job.grads.fill_(float("nan"))
         return job
+
+
+class LinearDmJob(nm.Job):
+    """A DMVAE-family job as a LINEAR stack (statistic A).  The classes apply ReLU unconditionally, so Job.struct() forces
+    non_linear = 1 for them; the kernels read that flag on its own, apart from act_slope, and this descriptor clears it."""
+
+    def struct(self):
+        j = super().struct()
+        j.non_linear = 0
+        return j
 
 
 @functools.lru_cache(maxsize=None)
@@ -157,23 +244,35 @@ def data(case_id: str) -> CaseData:
     return CaseData(CASES[case_id])
 
 
-def _run(cd: CaseData, P, non_linear: bool, rows: int, mode: str, trace: Optional[dict] = None, force: Optional[dict] = None):
+def _run(cd: CaseData, P, non_linear: bool, rows: int, mode: str, trace: Optional[dict] = None, force: Optional[dict] = None,
+         tweak: Optional[dict] = None, tc_mask: Optional[Tuple[int, int]] = None):
     """Loss dict and gradients of the oracle on the first `rows` rows, with `mode` operand rounding.  `trace`, if given,
-    receives name -> (input, pre-activation with its gradient retained) of every hidden layer's linear map (each layer
-    runs once per forward pass).  `force`: name -> [(batch row, unit), ...] whose pre-activation is mirrored at zero (a
-    constant is added, the gradient passes unchanged), so that LeakyReLU takes its other branch there."""
+    receives name -> [input, pre-activation, the layer's output as the layer after it receives it], the last two with
+    their gradients retained, of every hidden layer's linear map (each layer runs once per forward pass).  `force`:
+    name -> [(batch row, unit), ...] whose pre-activation is mirrored at zero (a constant is added, the gradient passes
+    unchanged), so that the activation takes its other branch there.  `tweak`: name -> function applied to the result of
+    that weight's linear map (seeded faults).  `tc_mask` (mvtCAE): (expert, first row) -- that expert's means of the rows
+    from `first row` on enter the total-correlation term as constants (the value stays, their gradient is gone)."""
     c = cd.case
-    rs = R.Spec(list(c.dims), list(c.hidden), c.Z, c.c_dim, non_linear)
+    rs = cd.ref_spec(non_linear)
     xs, cov, eps = [x[:rows] for x in cd.xs], cd.c[:rows].long(), cd.eps[:rows]
     fwd_fn, loss_fn = (R.mvt_forward, R.mvt_loss) if c.kind == "mvtcae" else (R.forward_multimodal, R.loss_multimodal)
     R.set_operand_rounding(mode)
+    beta, R.MVT_BETA = R.MVT_BETA, c.tc_beta
     try:
         leaves = {k: v.clone().requires_grad_(True) for k, v in P.items()}
-        if trace is not None or force:
-            trace, force = ({} if trace is None else trace), (force or {})
+        if trace is not None or force or tweak:
+            trace, force, tweak = ({} if trace is None else trace), (force or {}), (tweak or {})
             hidden_of = {id(leaves[w]): w for ws, _, _ in _chains(c) for w in ws}
+            fed_by = {id(leaves[b]): a for ws, _, heads in _chains(c) for a, b in zip(ws, ws[1:] + heads[:1])}
+            tweaked = {id(leaves[w]): f for w, f in tweak.items()}
 
             def hook(a, W, y):
+                if id(W) in tweaked:
+                    y = tweaked[id(W)](y)
+                if id(W) in fed_by and fed_by[id(W)] in trace:          # (this map's input is the output of the layer before)
+                    a.retain_grad()
+                    trace[fed_by[id(W)]][2] = a
                 name = hidden_of.get(id(W))
                 if name is None:
                     return y
@@ -184,15 +283,23 @@ def _run(cd: CaseData, P, non_linear: bool, rows: int, mode: str, trace: Optiona
                         shift[b_, j_] = -2.0 * float(y.detach()[b_, j_])
                     y = y + shift
                 y.retain_grad()
-                trace[name] = (a.detach(), y)
+                trace[name] = [a.detach(), y, None]
                 return y
             R.set_linear_hook(hook)
-        fwd = fwd_fn(leaves, rs, xs, [cov] * len(xs), c.combine, eps)
-        loss = loss_fn(rs, xs, fwd)
+        if c.is_dm:
+            fwd = R.dm_forward(leaves, rs, xs, eps)
+            loss = R.dm_loss(leaves, rs, xs, fwd)
+        else:
+            fwd = fwd_fn(leaves, rs, xs, [cov] * len(xs), c.combine, eps)
+            if tc_mask is not None:
+                e, r0 = tc_mask
+                fwd = {**fwd, "mus": [torch.cat((mu[:r0], mu[r0:].detach())) if m == e else mu for m, mu in enumerate(fwd["mus"])]}
+            loss = loss_fn(rs, xs, fwd)
         loss["total"].sum().backward()
         grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
         return {k: float(torch.as_tensor(v).detach().sum()) for k, v in loss.items() if k != "ll_m"}, grads
     finally:
+        R.MVT_BETA = beta
         R.set_linear_hook(None)
         R.set_operand_rounding("fp32")
 
@@ -210,12 +317,15 @@ def oracle_grads(case_id: str, non_linear: bool) -> Dict[str, torch.Tensor]:
 
 @functools.lru_cache(maxsize=None)
 def oracle_ll32(case_id: str, non_linear: bool) -> float:
-    """Reconstruction log-likelihood (summed over the modalities) of the fp32 oracle: the reference of run_case's bound."""
+    """Reconstruction log-likelihood (summed over the modalities) of the fp32 oracle: the reference of run_case's bound.
+    The DMVAE family: the oracle's `ll`, -0.5 sum (x - x_hat)^2 (times weights[i] for WeightedDMVAE)."""
     cd = data(case_id)
     c = cd.case
-    rs = R.Spec(list(c.dims), list(c.hidden), c.Z, c.c_dim, non_linear)
+    rs = cd.ref_spec(non_linear)
     xs, cov = [x[:c.B] for x in cd.xs], cd.c[:c.B].long()
     with torch.no_grad():
+        if c.is_dm:
+            return float(R.dm_loss(cd.P, rs, xs, R.dm_forward(cd.P, rs, xs, cd.eps[:c.B]))["ll"])
         if c.kind == "mvtcae":
             fwd = R.mvt_forward(cd.P, rs, xs, [cov] * len(xs), c.combine, cd.eps[:c.B])
         else:
@@ -236,6 +346,10 @@ def _chains(case: GradCase) -> List[Tuple[List[str], List[str], List[str]]]:
     L, out = len(case.hidden), []
     for m in range(len(case.dims)):
         e, d = f"encoder_list.{m}.", f"decoder_list.{m}."
+        if case.is_dm:
+            for p, heads in ((e, ["fc_mu", "fc_logvar"]), (d, ["fc_out"])):
+                out.append(([f"{p}fc1.weight", f"{p}fc2.weight"], [f"{p}fc1.bias", f"{p}fc2.bias"], [f"{p}{h}.weight" for h in heads]))
+            continue
         out.append(([f"{e}encoder_layers.{i}.weight" for i in range(L)], [f"{e}encoder_layers.{i}.bias" for i in range(L)],
                     [f"{e}enc_mean_layer.weight", f"{e}enc_logvar_layer.weight"]))
         out.append(([f"{d}decoder_layers.{i}.weight" for i in range(L)], [f"{d}decoder_layers.{i}.bias" for i in range(L)],
@@ -305,13 +419,37 @@ def _zero_rule(name, a, what):
                                  f"{_where(name, a, int(bad.flatten().nonzero()[0]))}")
 
 
+def private_rows(case_id: str) -> Dict[str, int]:
+    """name -> n: rows [:n] of the tensor have an identically zero oracle gradient inside a tensor that is not zero.  The
+    DMVAE family's private latent columns go from fc_mu straight into the modality's own decoder: no draw, no KL, so
+    rows [:n_private] of every fc_logvar weight and bias get no gradient (with n_private == latent that is the whole
+    tensor).  Statistic B would hold such a row to SLICE_FLOOR of the largest row only; _zero_rule holds it exactly."""
+    c = CASES[case_id]
+    return {f"encoder_list.{m}.fc_logvar.{t}": c.n_private for m in range(len(c.dims)) for t in ("weight", "bias")} if c.n_private else {}
+
+
+def _hold_zero_rows(got, want, zero_rows: Optional[Dict[str, int]], what: str):
+    """Rows [:n] of the tensors named in `zero_rows` held to _zero_rule; returns `got` with those rows set to zero, so
+    that what follows sees neither the poison an untouched row still holds nor those rows again."""
+    out = dict(got)
+    for name, n in (zero_rows or {}).items():
+        if name in want:
+            assert float(want[name][:n].abs().max()) == 0.0, (name, n, "the oracle's gradient is not zero there")
+            _zero_rule(f"{name}[:{n}]", got[name][:n], what)
+            out[name] = got[name].clone()
+            out[name][:n] = 0
+    return out
+
+
 def element_distance(got: Dict[str, torch.Tensor], want: Dict[str, torch.Tensor]) -> Dict[str, float]:
     """Statistic A per tensor: max |got - want| / max |want| (tensors with want == 0 left out)."""
     return {k: float((got[k] - w).abs().max()) / float(w.abs().max()) for k, w in want.items() if float(w.abs().max()) > 0}
 
 
-def assert_every_element(got, want, bound: float, what: str = "") -> Dict[str, float]:
-    """Statistic A on every tensor of `want`; returns error / bound per tensor."""
+def assert_every_element(got, want, bound: float, what: str = "", zero_rows: Optional[Dict[str, int]] = None) -> Dict[str, float]:
+    """Statistic A on every tensor of `want`; returns error / bound per tensor.  `zero_rows` (private_rows of the case):
+    rows of a non-zero tensor the oracle leaves at zero, held to the rule for a tensor that is zero."""
+    got = _hold_zero_rows(got, want, zero_rows, what)
     out = {}
     for name, w in want.items():
         a = got[name]
@@ -408,14 +546,16 @@ def _take_out_flips(got, want, bound: float, flips: Dict[str, FlipModel], flippe
 
 
 def assert_every_slice(got, want, bound: float, what: str = "", flips: Optional[Dict[str, FlipModel]] = None,
-                       flipped: Optional[list] = None) -> Dict[Tuple[str, str], float]:
+                       flipped: Optional[list] = None, zero_rows: Optional[Dict[str, int]] = None) -> Dict[Tuple[str, str], float]:
     """Statistic B on every tensor of `want`; returns error / bound per (tensor, slice kind).
 
     `flips` (flip_model of the case): a ROW of a hidden layer's weight gradient that is beyond the bound is held instead
     against the oracle with ONE LeakyReLU unit of that row on the other side of zero -- a unit whose pre-activation lies
     inside its margin -- at the same bound; that flip's term is then taken out of the row and of the bias element, and every
     row, column and piece is checked as usual.  At most MAX_FLIPPED_ROWS of a tensor's rows (at least one) may pass that
-    way; each is appended to `flipped` as (tensor, unit, batch row, pre-activation, margin, relative L2 before, after)."""
+    way; each is appended to `flipped` as (tensor, unit, batch row, pre-activation, margin, relative L2 before, after).
+    `zero_rows`: as in assert_every_element."""
+    got = _hold_zero_rows(got, want, zero_rows, what)
     for name, w in want.items():
         a = got[name]
         assert tuple(a.shape) == tuple(w.shape), (what, name, tuple(a.shape), tuple(w.shape))
@@ -443,18 +583,18 @@ def assert_every_slice_of_case(case_id: str, got, what: str = "", flipped: Optio
     and that one admissible flip explains (_take_out_flips) name the flipped units; the oracle is then run again with
     exactly those units on LeakyReLU's other branch -- which also moves, for that batch row, everything the unit's gradient
     flows back into -- and EVERY row, column and piece is held to that run at the same bound, with no further allowance."""
-    bound, want = CASES[case_id].bound_B, oracle_grads(case_id, True)
+    bound, want, zero = CASES[case_id].bound_B, oracle_grads(case_id, True), private_rows(case_id)
     flipped = [] if flipped is None else flipped
     clean = {k: torch.nan_to_num(v) for k, v in got.items()}
     _take_out_flips(clean, want, bound, flip_model(case_id), flipped)
     if not flipped:
-        return assert_every_slice(got, want, bound, what)
+        return assert_every_slice(got, want, bound, what, zero_rows=zero)
     force: dict = {}
     for name, j, b, *_ in flipped:
         force.setdefault(name, []).append((b, j))
     cd = data(case_id)
     _, want2 = _run(cd, cd.P, True, cd.case.B, "bf16", force=force)
-    return assert_every_slice(got, want2, bound, what + f" ({len(flipped)} sign flips)")
+    return assert_every_slice(got, want2, bound, what + f" ({len(flipped)} sign flips)", zero_rows=zero)
 
 
 def twin_distance(case_id: str) -> Tuple[float, float]:
@@ -477,12 +617,13 @@ class FlipModel:
     margin: torch.Tensor
     dh: torch.Tensor
     a: torch.Tensor
+    slope: float = R.LEAKY_SLOPE
 
     def row_candidates(self, j: int) -> Iterator[Tuple[int, torch.Tensor, float]]:
         """(batch row b, change of row j of the weight gradient, change of element j of the bias gradient) for every
-        pre-activation of unit j inside its margin: the derivative 0.01 becomes 1, or the reverse."""
+        pre-activation of unit j inside its margin: the derivative `slope` (0.01; ReLU: 0) becomes 1, or the reverse."""
         for b in (self.pre[:, j].abs() < self.margin[:, j]).nonzero().flatten().tolist():
-            d = (1.0 - R.LEAKY_SLOPE) * float(self.dh[b, j]) * (1.0 if float(self.pre[b, j]) < 0 else -1.0)
+            d = (1.0 - self.slope) * float(self.dh[b, j]) * (1.0 if float(self.pre[b, j]) < 0 else -1.0)
             yield b, d * self.a[b], d
 
 
@@ -504,10 +645,11 @@ def flip_model(case_id: str) -> Dict[str, FlipModel]:
     trace: dict = {}
     _run(cd, cd.P, True, cd.case.B, "bf16", trace)
     out = {}
-    for name, (a, y) in trace.items():
+    for name, (a, y, h) in trace.items():
         W, a, pre = R._bf(cd.P[name]).double(), R._bf(a).double(), y.detach().double()
-        dh = y.grad.double() / torch.where(pre >= 0, 1.0, R.LEAKY_SLOPE)
-        out[name] = FlipModel(pre, 2.0 ** -8 * (a.square() @ W.square().T).sqrt(), dh, a)
+        # dL/dh of the unit's output, read where the layer after it receives it (ReLU's inactive side passes nothing back
+        # to the pre-activation to divide out)
+        out[name] = FlipModel(pre, 2.0 ** -8 * (a.square() @ W.square().T).sqrt(), h.grad.double(), a, cd.case.slope)
     return out
 
 
@@ -523,20 +665,25 @@ def seeded_faults(case_id: str, non_linear: bool, structural_only: bool = False)
     One row / one column zeroed at 0, 127, 128 and last; a 16 x 16 tile swapped with its right neighbour; a 128 x 128
     block replaced by its neighbour block; bias element 128 replaced by element 127; the tensor scaled by 1.02; one extra
     table row leaking in (the oracle at B + 1 rows, rescaled to the mean over B, minus the oracle at B).
-    structural_only: the zeroed rows and columns alone (what statistic B is for)."""
+    structural_only: the zeroed rows and columns alone (what statistic B is for); otherwise a zoo case's own faults
+    (zoo_faults) follow."""
     cd = data(case_id)
     B = cd.case.B
     g = oracle_grads(case_id, non_linear)
     g1 = None if structural_only else oracle_run(case_id, non_linear, True)[1]
     for name, w in g.items():
-        if not (name.endswith(".weight") and w.dim() == 2):
+        if not (name.endswith(".weight") and w.dim() == 2 and bool(w.any())):      # (all private: fc_logvar has no gradient)
             continue
         n, k = w.shape
         for r in _edge_indices(n):
+            if not bool(w[r].any()):          # (a private fc_logvar row, a ReLU unit no row of the batch switches on:
+                continue                      # zeroing zeros seeds nothing)
             f = w.clone()
             f[r] = 0
             yield f"row {r} zeroed", name, f, w[r]
         for c in _edge_indices(k):
+            if not bool(w[:, c].any()):
+                continue
             f = w.clone()
             f[:, c] = 0
             yield f"column {c} zeroed", name, f, w[:, c]
@@ -566,3 +713,69 @@ def seeded_faults(case_id: str, non_linear: bool, structural_only: bool = False)
         yield "scaled by 1.02", name, w * 1.02, w
         leak = g1[name] * ((B + 1) / B) - w
         yield "one pad row leaks in", name, w + leak, leak
+    if not structural_only and case_id in ZOO_IDS:
+        yield from zoo_faults(case_id, non_linear)
+
+
+# ---- the baseline zoo's own faults ------------------------------------------------------------------------------------------
+class _NoSigmoidFactor(torch.autograd.Function):
+    """The identity, whose backward pass divides the incoming gradient by sigmoid'(y): behind it the output layer's delta
+    is x_hat - x without the factor x_hat (1 - x_hat)."""
+
+    @staticmethod
+    def forward(ctx, y):
+        s = torch.sigmoid(y)
+        ctx.save_for_backward(s)
+        return y.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        s, = ctx.saved_tensors
+        return g / (s * (1.0 - s))
+
+
+def zoo_faults(case_id: str, non_linear: bool):
+    """Yields (label, tensor name, faulty tensor, region), as seeded_faults does, for the faults the zoo's own branches of
+    the kernels could have; `region` is what the fault removes from, moves in or adds to the ORACLE's gradient.
+
+    DMVAE family: rows n_private - 1 and n_private of fc_mu (weight and bias) swapped; row n_private - 1 of fc_logvar.weight
+    set to 1e-6 of the encoder's largest gradient element instead of zero; the sigmoid's derivative dropped on the last
+    d % 16 output rows of fc_out (the oracle run again with _NoSigmoidFactor on those columns); with learnable weights,
+    the gradients of weights[0] and weights[1] swapped, and decoder 0's gradients scaled as if by weights[1].
+    mvtCAE: the total-correlation term's contribution of the last B % 64 batch rows missing in the last expert's
+    enc_mean_layer gradient (the oracle run again with those rows masked out of the term, _run's tc_mask)."""
+    cd = data(case_id)
+    c, g = cd.case, oracle_grads(case_id, non_linear)
+    M, S = len(c.dims), c.n_private
+    if c.kind == "mvtcae":
+        r0, e = c.B - c.B % 64, M - 1
+        assert r0 < c.B
+        name = f"encoder_list.{e}.enc_mean_layer.weight"
+        _, g2 = _run(cd, cd.P, non_linear, c.B, "bf16", tc_mask=(e, r0))
+        yield f"TC gradient stops at batch row {r0}", name, g2[name], g[name] - g2[name]
+        return
+    for m in range(M):
+        p = f"encoder_list.{m}."
+        if 0 < S < c.Z:
+            for t in ("weight", "bias"):
+                f = g[f"{p}fc_mu.{t}"].clone()
+                f[[S - 1, S]] = f[[S, S - 1]]
+                yield "boundary: fc_mu rows n_private - 1 and n_private swapped", f"{p}fc_mu.{t}", f, g[f"{p}fc_mu.{t}"][S - 1:S + 1]
+        if S > 0:
+            f = g[f"{p}fc_logvar.weight"].clone()
+            f[S - 1] = 1e-6 * max(float(f.abs().max()), float(g[f"{p}fc_mu.weight"].abs().max()))
+            yield "private: fc_logvar row n_private - 1 not zero", f"{p}fc_logvar.weight", f, f[S - 1]
+    tail = {m: (d % 16 or 16) for m, d in enumerate(c.dims)}
+    cut = lambda t: (lambda y: torch.cat((y[:, :-t], _NoSigmoidFactor.apply(y[:, -t:])), dim=1))
+    _, g2 = _run(cd, cd.P, non_linear, c.B, "bf16", tweak={f"decoder_list.{m}.fc_out.weight": cut(t) for m, t in tail.items()})
+    for m, t in tail.items():
+        for name in (f"decoder_list.{m}.fc_out.weight", f"decoder_list.{m}.fc_out.bias"):
+            yield f"sigmoid: no derivative on the last {t} output rows", name, g2[name], g2[name][-t:] - g[name][-t:]
+    if "weights" in g:
+        f = g["weights"].clone()
+        f[[0, 1]] = f[[1, 0]]
+        yield "weights: gradients of weights[0] and weights[1] swapped", "weights", f, g["weights"][:2]
+        scale = float(cd.P["weights"][1] / cd.P["weights"][0])
+        for k, v in g.items():
+            if k.startswith("decoder_list.0."):
+                yield "scaling: decoder 0 by weights[1]", k, v * scale, v

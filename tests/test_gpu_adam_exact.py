@@ -17,7 +17,7 @@ the gradient's own comparison with the oracle this closes the chain: each single
   b. 8 isolated steps on every training form -- whole, scalar_tr, split, rowsplit 2 / 4 with 0, 3 and the default number of
      helpers, the general-shape path -- on six goldens (a fresh batch per step), six fuzz shapes over a 531-row table
      (walking batch index, ragged 19-row tail), two general-shape fuzz shapes, the full size 3 x 379 / [110, 110] / B = 256,
-     mvtCAE from the zoo, and 3 steps on the general-shape path at its limits (W1, W3, W4 of tests/grad_check.py: width
+     mvtCAE and the DMVAE family from the zoo (partly private, all private, learnable loss weights), and 3 steps on the general-shape path at its limits (W1, W3, W4 of tests/grad_check.py: width
      4096 with latent 128, the block boundaries, eight layers).  A mixed set (one- and three-modality model in one launch) runs the mixed row-split entry:
      grads() drives it whenever the set's modality counts differ.
   c. the flat-buffer invariants above, after those 8 steps.
@@ -33,9 +33,13 @@ error / bound per form (m' / v' / p'; 1.0 = at the bound; the CPU emulation peak
     flat kernel 0.25 / 0.50 / 0.50      whole 0.46 / 0.69 / 0.50          scalar_tr 0.46 / 0.69 / 0.50
     split 0.46 / 0.69 / 0.50            row-split 2 0.45 / 0.71 / 0.50    row-split 4 0.46 / 0.73 / 0.50   (any helpers)
     general-shape 0.47 / 0.68 / 0.50    head models, whole and split, 0.46 / 0.69 / 0.50
+The DMVAE-family jobs (whole, scalar_tr, split) lie inside the same figures: the learnable weights move on their own
+gradient, an all-private fc_logvar keeps every bit.
 (p' sits at 0.50: the half-ulp rounding of p' itself is 1 eps |p'| of the 2 eps allowed.)  The module prints the table of
 the run at hand when it finishes (pytest -s).
 """
+import ctypes as C
+
 import numpy as np
 import pytest
 import torch
@@ -292,6 +296,60 @@ def test_zoo_mvtcae(form):
     """mvtCAE (variance clamp, total-correlation term, its own fusion rule): the same Adam behind another loss."""
     job = table_job([40, 55, 33], [32, 24], 6, 5, "poe", True, 300, 5, kind="mvtcae")
     isolated_steps(nm.JobSet([job]), form, "mvtCAE")
+
+
+ZOO_DM = {"private 4 of 12": ("dmvae", 4), "all private": ("dmvae", 29), "weighted": ("weighted_dmvae", 4)}
+
+
+@pytest.mark.parametrize("form", ["whole", "scalar_tr", "split"])
+@pytest.mark.parametrize("which", list(ZOO_DM))
+def test_zoo_dm(which, form):
+    """The DMVAE family (ReLU, sigmoid output, private latent columns, learnable loss weights) over a 300-row table, in
+    every form the library admits for it: whole, scalar_tr and split (one workgroup per modality).  The row-split launch
+    and the plain-training instantiation refuse these kinds -- asked of Job.rowsplit_ok / nm_rowsplit_ok and Job.plain_ok
+    / nm_plain_ok below, and of JobSet, whose automatic pick stays at one slice -- and the general-shape path has the one
+    form that test_general_shape_path covers.  The learnable `weights` are updated by Adam on their own gradient like every
+    other element (assert_adam_step covers the whole flat buffer) and do move; with every column private no element of
+    any fc_logvar ever sees a gradient, a moment or a changed bit."""
+    kind, c_dim = ZOO_DM[which]
+    dims, hidden, Z, N = [61, 90, 47], [64, 48], 12, 300
+    gen = torch.Generator().manual_seed(23)
+    spec = nm.ModelSpec(dims, hidden, Z, c_dim, True, kind)
+    P = nm.ParamLayout(spec).init_reference_rule(23)
+    if kind == "weighted_dmvae":
+        P["weights"] = torch.tensor([0.8, 1.1, 1.3])
+    job = nm.Job(spec, [nm.Table(torch.rand(N, d, generator=gen), torch.zeros(N, 0), DEV) for d in dims], combine="poe", state=P)
+    job.set_eps(torch.randn(N_STEPS, 256, Z, generator=gen))
+    js = nm.JobSet([job])
+    st = job.struct()
+    assert not job.spec.wide and job.batches_per_epoch == 2
+    assert not job.rowsplit_ok() and js.lib.nm_rowsplit_ok(C.byref(st)) != 0 and js.rowsplit_k() == 1
+    assert not job.plain_ok() and js.lib.nm_plain_ok(C.byref(st)) != 0
+    before = job.params.detach().cpu().clone()
+    lay = job.layout
+
+    def flat(name):
+        n = lay.tiles[name][0] * lay.tiles[name][1] * 256 if name in lay.tiles else lay.numel(name)
+        return slice(lay.offsets[name], lay.offsets[name] + n)
+
+    seen_weight_grads = []
+    if kind == "weighted_dmvae":
+        grads = lambda s: (js.grads(s, export=False, **FORMS[form]), seen_weight_grads.append(job.grads[flat("weights")].cpu().clone()))
+    else:
+        grads = None
+    isolated_steps(js, form, f"zoo {which}", grads=grads)
+    assert job.t == N_STEPS
+    after = job.params.detach().cpu()
+    if kind == "weighted_dmvae":
+        assert all(bool((g != 0).all()) for g in seen_weight_grads) and len(seen_weight_grads) == N_STEPS
+        assert bool((after[flat("weights")] != before[flat("weights")]).all())          # each weight is learned
+    if c_dim >= Z:
+        for m in range(len(dims)):
+            for t in ("weight", "bias"):
+                sl = flat(f"encoder_list.{m}.fc_logvar.{t}")
+                for buf in (job.grads, job.adam_m, job.adam_v):
+                    assert not bool(buf[sl].cpu().view(torch.int32).any()), (m, t)
+                assert torch.equal(after[sl].view(torch.int32), before[sl].view(torch.int32)), (m, t)
 
 
 @pytest.mark.parametrize("form", ["rs2", "rs4"])
