@@ -469,6 +469,43 @@ int nm_devpass_draws_ok(const nm_job_t* job_host);
  * NM_E_NULL for a null pointer.  NM_F_TRACE: read out by nm_trace_read_dv. */
 int nm_latent_pass(const nm_job_t* jobs_dev, int n_jobs, int tile0, int n_tiles, int flags, void* stream);   /* flags: 0 or NM_F_TRACE */
 int nm_latent_pass_ok(const nm_job_t* job_host);
+/* The decoder half alone (csrc/nm_devpass.hip: nm_decode_kernel): a table of latent rows z decoded by the job's decoders,
+ * under the rows' own covariates (n_cells == 0) or under EVERY row of a covariate grid (n_cells >= 1: cell g decodes every
+ * row of z with row g of cgrid in the place of the row's covariates) -- what the model expects at a covariate setting
+ * (normative trajectories: prior draws of z under every (age, sex) cell; counterfactual reconstructions: a subject's own
+ * latent under another cell).  No encoder, no fusion, no draw, no workspace tile.  One request per job, [n_jobs] entries in
+ * device memory next to the descriptors; the request carries its own row count (the job's tables play no part: their
+ * n_rows is not read), rows [tile0 * 128, (tile0 + n_tiles) * 128) of it are decoded, tiles past a request's last 256-row
+ * tile are left alone (one launch may hold requests of different heights).
+ *   z is rounded to bf16 once per tile with the conversion the decoder input of every other pass goes through; a cell's
+ *   z | c | 1 | 0 rows, hidden layers and 64-ROI output chunks are those of nm_devpass_multi, operation for operation: with
+ *   z = out_z, the tables' own cz and x, loc / sqerr / rowdev equal out_loc / out_sqerr / out_rowdev of that pass (and of
+ *   nm_forward) bit for bit, and cell g equals a per-row launch whose cz table repeats grid row g.
+ *   Exports per decoder m and cell g (slab g of the buffer; pad columns 0; rows from n_rows to the end of its last 256-row
+ *   tile 0, whatever the buffers held): loc = x_hat; sqerr = (x - x_hat)^2; rowdev = the row mean of sqerr over D (summation
+ *   order of out_rowdev in the several-expert pass).  sqerr / rowdev are taken against x[m] and are written only where it
+ *   is given.  Plain stores, no atomics: the same bytes on every run.
+ * Admitted (nm_decode_pass_ok): exactly what nm_latent_pass_ok admits -- the two halves cover the same models; NM_E_DEVPASS
+ * otherwise (such a job decodes through nm_forward with NM_F_ZGIVEN), NM_E_NULL for a null pointer.  Status is decided on
+ * the host before the device is asked anything: NM_E_NULL for a missing table, NM_E_GEOMETRY by the geometry rules of
+ * every launch.  The request's own rules (n_cells 0..NM_MAX_CELLS, rows_alloc a multiple of 256 and >= n_rows, sqerr /
+ * rowdev only with x, buffers of the stated sizes) are the caller's; the kernel makes the workgroups of a refused job or
+ * of a request with counts out of range leave at once.  128-row tiles, 79 KB of LDS: two workgroups per CU.  NM_F_TRACE:
+ * read out by nm_trace_read_dv. */
+#define NM_MAX_CELLS 64
+typedef struct nm_decode_t {
+  const float* z;                    /* [rows_alloc][Z] fp32 latent rows (not the job's tables: its own row count) */
+  int32_t n_rows, rows_alloc;        /* rows_alloc: multiple of 256, >= n_rows */
+  int32_t n_cells;                   /* 0: per-row covariates cz[m]; 1..NM_MAX_CELLS: row g of cgrid for EVERY row, g = 0..n_cells-1 */
+  const uint16_t* cgrid;             /* [n_cells][Cz] bf16  c | 1 | 0, the layout of one row of nm_modality_t.cz */
+  const uint16_t* cz[NM_MAX_EXP];    /* n_cells == 0: [rows_alloc][Cz] per decoder (pointers may coincide) */
+  const float* x[NM_MAX_EXP];        /* optional [rows_alloc][x_pitch]: the values sqerr / rowdev are taken against */
+  float* loc[NM_MAX_EXP];            /* [max(n_cells,1)][rows_alloc][x_pitch]; NULL: decoder m is skipped */
+  float* sqerr[NM_MAX_EXP];          /* same shape, or NULL; needs x[m] */
+  float* rowdev[NM_MAX_EXP];         /* [max(n_cells,1)][rows_alloc], or NULL; needs x[m] */
+} nm_decode_t;
+int nm_decode_pass(const nm_job_t* jobs_dev, int n_jobs, const nm_decode_t* req_dev, int tile0, int n_tiles, int flags, void* stream);   /* flags: 0 or NM_F_TRACE */
+int nm_decode_pass_ok(const nm_job_t* job_host);
 /* NM_F_TRACE read-out of the row-split kernels ([8 waves][64 tags], as nm_trace_read) */
 int nm_trace_read_rs(unsigned long long* out512, int reset);
 /* out_dev[j] (device, n_jobs ints) != 0: a hand-off of job j timed out in a split launch since the word was last

@@ -92,6 +92,8 @@ NM_OP_MAX_LINSPACE = 65536
 NM_MAX_SUBSETS = 15
 # nm_devpass_draws: the most latent draws per row
 NM_MAX_DRAWS = 64
+# nm_decode_pass: the most covariate cells of a request
+NM_MAX_CELLS = 64
 
 # status codes (nmhip.h; nm_status_string gives the text)
 NM_OK = 0
@@ -188,6 +190,13 @@ class NmPred(C.Structure):
                 ("noise_var", C.c_void_p * NM_MAX_EXP)]
 
 
+class NmDecode(C.Structure):
+    """nm_decode_t: one job's request, nm_decode_pass' [n_jobs] table (device memory)."""
+    _fields_ = [("z", C.c_void_p), ("n_rows", C.c_int32), ("rows_alloc", C.c_int32), ("n_cells", C.c_int32),
+                ("cgrid", C.c_void_p), ("cz", C.c_void_p * NM_MAX_EXP), ("x", C.c_void_p * NM_MAX_EXP),
+                ("loc", C.c_void_p * NM_MAX_EXP), ("sqerr", C.c_void_p * NM_MAX_EXP), ("rowdev", C.c_void_p * NM_MAX_EXP)]
+
+
 class NmRoiSet(C.Structure):
     """nm_roi_set_t: one matrix of nm_roi_effect's pointer table."""
     _fields_ = [("x", C.c_void_p), ("group", C.c_void_p), ("rows", C.c_int32), ("pitch", C.c_int32)]
@@ -267,6 +276,8 @@ def load():
     lib.nm_devpass_draws_ok.argtypes = [C.POINTER(NmJob)]
     lib.nm_latent_pass.argtypes = [vp, i32, i32, i32, i32, vp]
     lib.nm_latent_pass_ok.argtypes = [C.POINTER(NmJob)]
+    lib.nm_decode_pass.argtypes = [vp, i32, vp, i32, i32, i32, vp]
+    lib.nm_decode_pass_ok.argtypes = [C.POINTER(NmJob)]
     lib.nm_latent_stats.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.nm_latent_score.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.nm_combine_latent.argtypes = [vp, vp, i32, i64, i32, vp, i32, i32, i32, f32, vp, vp, vp]
@@ -342,6 +353,7 @@ EXPORTED_SYMBOLS = [
     "nm_cohort_quantiles", "nm_normative_centile_workspace", "nm_normative_centile",
     "nm_devpass_subsets", "nm_devpass_subsets_ok",
     "nm_devpass_draws", "nm_devpass_draws_ok",
+    "nm_decode_pass", "nm_decode_pass_ok",
 ]
 
 

@@ -19,6 +19,7 @@ All arithmetic runs in libnmhip.so; there is no CPU fallback (NmError without a 
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Optional, Sequence
 
 import numpy as np
@@ -26,7 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .engine import Job, JobSet, Table, adam_step, draw_seeds, latent_scores, latent_stats, require_gpu
+from .engine import DECODE_AUTO, Job, JobSet, Table, adam_step, draw_seeds, latent_scores, latent_stats, require_gpu
 from .layout import ModelSpec, ParamLayout
 
 
@@ -311,6 +312,101 @@ class _Base(nn.Module):
         return [{"mean": j.pred_mean[m][:B].cpu().numpy(), "var": j.pred_var[m][:B].cpu().numpy(),
                  "msq": j.pred_msq[m][:B].cpu().numpy(), "z": j.pred_z[m][:B].cpu().numpy()} for m in range(len(j.kmods))]
 
+    # -- the decoder pass (nm_decode_pass): the decoders alone, under the rows' covariates or a covariate grid -------------
+    def _decode_job(self):
+        """A Job of this model for the decoder pass -- the current parameters, one-row placeholder tables (the pass reads a
+        request of its own, not the tables) -- and its JobSet; kept from call to call."""
+        self._dev()
+        j = self.__dict__.get("_dec_job")
+        if j is None or j.device != self._device:
+            s = self.spec
+            tables = [Table(torch.zeros(1, d), torch.zeros(1, s.net_c_dim), self._device) for d in s.input_dims]
+            j = Job(s, tables, combine="poe", state=_Base.state_dict(self), lr=self._lr, kl_weight=self._kl_weight, loss_cap=1,
+                    single_bypass=getattr(self, "_single_bypass", s.kind != "endtoend"))
+            self.__dict__["_dec_job"], self.__dict__["_dec_js"] = j, JobSet([j])
+        self.layout.nat_to_kernel(self._flat.data, j.params)
+        j.params_changed()
+        return j, self.__dict__["_dec_js"]
+
+    def _decode_route(self):
+        """(job, set) where decode(z, c, m) takes the decoder pass -- the set passes decode_pick() -- else None."""
+        if os.environ.get("NMHIP_DECODE", "auto") != "1" and not DECODE_AUTO.get(self.spec.M, False):
+            return None
+        j, js = self._decode_job()
+        return (j, js) if js.decode_pick() else None
+
+    def _decode_request(self, z, c=None, c_grid=None, decoders=None, via=None):
+        """One launch of the decoder pass on this model: z [R, Z] under per-row covariates c or every row of c_grid.  The job,
+        its dec_loc[m] ([cells, R, D]) filled.  via: the (job, set) pair _decode_route has already refreshed."""
+        j, js = via if via is not None else self._decode_job()
+        why = js._decode_refusal()
+        if why is not None:
+            raise ValueError("the decoder pass (nm_decode_pass) does not take this model: " + why)
+        z = torch.as_tensor(np.asarray(z) if not torch.is_tensor(z) else z, dtype=torch.float32)
+        if z.dim() != 2 or int(z.shape[1]) != self.spec.latent:
+            raise ValueError(f"z must be [rows, {self.spec.latent}], got {tuple(z.shape)}")
+        G = 0 if c_grid is None else int(c_grid.shape[0])
+        want = tuple(range(len(j.kmods))) if decoders is None else tuple(decoders)
+        if (j.dec_rows, j.dec_cells, j.dec_decoders) != (int(z.shape[0]), G, want):
+            j.enable_decode_exports(int(z.shape[0]), G, decoders=want)
+        j.set_decode_inputs(z, c=c, c_grid=c_grid, x=None)
+        js.decode()
+        return j
+
+    @staticmethod
+    def _grid(c_grid) -> torch.Tensor:
+        g = torch.as_tensor(np.asarray(c_grid) if not torch.is_tensor(c_grid) else c_grid)
+        if g.dim() != 2 or not 1 <= int(g.shape[0]) <= _lib.NM_MAX_CELLS:
+            raise ValueError(f"c_grid must be [1..{_lib.NM_MAX_CELLS} cells, C], got {tuple(g.shape)}")
+        return g
+
+    def decode_grid(self, z, c_grid):
+        """Every decoder on the latent rows z [R, Z] under EVERY row of c_grid [G, C] (G <= 64) in one launch: per modality a
+        [G, R, D] device tensor -- slab g is what decode(z, c, m) gives with c = row g of the grid for every row."""
+        j = self._decode_request(z, c_grid=self._grid(c_grid))
+        return [t.clone() for t in j.dec_loc]
+
+    def normative_trajectory(self, c_grid, n_draws=256, seed=0, z=None):
+        """What the model expects at every covariate setting of c_grid [G, C]: n_draws prior rows z ~ N(0, I) -- drawn on the
+        host from torch.Generator().manual_seed(seed), the SAME rows in every cell, so the curves are smooth in the
+        covariate; or the rows `z` -- decoded under every grid row in one launch, then per cell the moments of the
+        reconstructions over the rows (metrics.cohort_moments, ddof = 1).  Per modality a dict of fp64 numpy arrays: "mean"
+        [G, D], "var_latent" [G, D] (the spread the latent induces), "noise_var" [D] (exp(logvar_out) in fp32, as
+        Job.refresh_noise_var forms it) and "sd_pred" = sqrt(var_latent + noise_var) [G, D]: the predictive sd of the chart."""
+        from . import metrics
+        g = self._grid(c_grid)
+        if z is None:
+            z = torch.randn(int(n_draws), self.spec.latent, generator=torch.Generator().manual_seed(int(seed)))
+        j = self._decode_request(z, c_grid=g)
+        G = int(g.shape[0])
+        out = []
+        for k, (_, _, dp) in enumerate(j.kmods):
+            sets = [j.dec_loc[k][c] for c in range(G)]
+            mom = metrics.cohort_moments(sets, [torch.zeros(int(s.shape[0]), dtype=torch.int32) for s in sets], ddof=1).cpu().numpy()
+            lv = j.layout.get(j.params, f"{dp}logvar_out").reshape(-1)
+            nv = torch.exp(lv).cpu().numpy().astype(np.float64)
+            out.append({"mean": mom[:, :, 0].copy(), "var_latent": mom[:, :, 2].copy(), "noise_var": nv,
+                        "sd_pred": np.sqrt(mom[:, :, 2] + nv[None, :])})
+        return out
+
+    def _counterfactual(self, xs, cs, combine: str, c_grid, latent: str):
+        """Per grid row the reconstructions of every modality from the subjects' own latent -- latent="mean": the joint
+        posterior mean (JobSet.latent); "draw": out_z of the forward pass, the draw pred_recon would use -- decoded as if in
+        that cell."""
+        if latent not in ("mean", "draw"):
+            raise ValueError(f'latent must be "mean" or "draw", got {latent!r}')
+        g = self._grid(c_grid)
+        self._dev()
+        if latent == "mean":
+            j, B = self._run(xs, cs, combine, _lib.NM_F_EXPORT, latent_only=True,
+                             eps=torch.zeros(int(xs[0].shape[0]), self.spec.latent, device=self._device))
+            z = j.out_mu[:B].clone()
+        else:
+            j, B = self._run(xs, cs, combine, _lib.NM_F_EXPORT)
+            z = j.out_z[:B].clone()
+        d = self._decode_request(z, c_grid=g)
+        return [[t[c].cpu().numpy() for t in d.dec_loc] for c in range(int(g.shape[0]))]
+
     # -- the latent deviation (utils_vae.py:155-161) ----------------------------------------------------
     def _latent_joint(self, xes, c, combine: str = "poe"):
         """Joint posterior (mu, logvar) of a cohort as device tensors: DataFrames / arrays in (one, or one per modality)."""
@@ -524,7 +620,12 @@ class cVAE_multimodal(_ExpertOps, _Base):
         return j.out_mu[:B].clone(), j.out_logvar[:B].clone()
 
     def decode(self, z, c, m):
-        """Decoder m alone on a given z (cVAE.py:1135)."""
+        """Decoder m alone on a given z (cVAE.py:1135).  Through the decoder pass where the model is admitted and the route is
+        picked (JobSet.decode_pick: DECODE_AUTO, NMHIP_DECODE=1); else a one-modality copy on the general kernel."""
+        via = self._decode_route()
+        if via is not None:
+            j = self._decode_request(z, c=c, decoders=(m,), via=via)
+            return NormalLike(j.dec_loc[m][0].clone(), self._scale(m))
         one = self._unimodal(m)
         x0 = torch.zeros(int(z.shape[0]), self.input_dim_list[m], device=self._dev())
         j, B = one._run([x0], [c], "poe", _lib.NM_F_EXPORT | _lib.NM_F_ZGIVEN, eps=z)
@@ -573,6 +674,14 @@ class cVAE_multimodal(_ExpertOps, _Base):
         xs = [torch.tensor(np.asarray(x.values if hasattr(x, "values") else x), dtype=torch.float32) for x in xes]
         ct = torch.tensor(np.asarray(c), dtype=torch.long)
         return self._pred_draws(xs, [ct] * self.modalities, combine, n_draws, seed)
+
+    def pred_recon_counterfactual(self, xes, c, DEVICE, combine, c_grid, latent="mean"):
+        """pred_recon "as if": the subjects' own joint latent -- latent="mean": the posterior mean; "draw": the sampled z
+        pred_recon would use -- decoded under every row of c_grid [G, C] in the place of their own covariates, one decode
+        launch for all cells.  DataFrames in; per grid row pred_recon's list per modality out."""
+        xs = [torch.tensor(np.asarray(x.values if hasattr(x, "values") else x), dtype=torch.float32) for x in xes]
+        ct = torch.tensor(np.asarray(c), dtype=torch.long)
+        return self._counterfactual(xs, [ct] * self.modalities, combine, c_grid, latent)
 
     def pred_latent(self, xes, c, DEVICE, combine):
         """The joint counterpart of cVAE.pred_latent (cVAE.py:539-545): DataFrames in, (mu_joint, var_joint) as numpy out."""
@@ -762,6 +871,9 @@ class mmJSD(cVAE_multimodal):
     def pred_recon_draws(self, xes, c, DEVICE, combine, n_draws, seed=None):
         return super().pred_recon_draws(xes, c, DEVICE, "poe", n_draws, seed)
 
+    def pred_recon_counterfactual(self, xes, c, DEVICE, combine, c_grid, latent="mean"):
+        return super().pred_recon_counterfactual(xes, c, DEVICE, "poe", c_grid, latent)
+
     def pred_latent(self, xes, c, DEVICE, combine="poe"):
         return super().pred_latent(xes, c, DEVICE, "poe")
 
@@ -796,6 +908,10 @@ class cVAE(_Base):
         return j.out_mu[:B].clone(), j.out_logvar[:B].clone()
 
     def decode(self, z, c):
+        via = self._decode_route()
+        if via is not None:                           # (the decoder pass, where the route is picked: JobSet.decode_pick)
+            j = self._decode_request(z, c=c, via=via)
+            return NormalLike(j.dec_loc[0][0].clone(), self._scale(0))
         x0 = torch.zeros(int(z.shape[0]), self.input_dim, device=self._dev())
         j, B = self._run([x0], [c], "poe", _lib.NM_F_EXPORT | _lib.NM_F_ZGIVEN, eps=z)
         return NormalLike(j.out_loc[0][:B].clone(), self._scale(0))
@@ -819,6 +935,16 @@ class cVAE(_Base):
         xt = torch.as_tensor(np.asarray(x.to_numpy() if hasattr(x, "to_numpy") else x), dtype=torch.float32)
         ct = torch.as_tensor(np.asarray(c), dtype=torch.long)
         return self._pred_draws([xt], [ct], "poe", n_draws, seed)[0]
+
+    def pred_recon_counterfactual(self, x, c, DEVICE, combine=None, c_grid=None, latent="mean"):
+        """pred_recon "as if": x's own latent -- latent="mean": the posterior mean, what pred_recon decodes; "draw": a sampled
+        z -- decoded under every row of c_grid [G, C] in one launch: per grid row a numpy array [subjects, ROIs].  combine
+        plays no part in a one-expert model."""
+        if c_grid is None:
+            raise ValueError("c_grid is needed: one covariate row per cell")
+        xt = torch.as_tensor(np.asarray(x.to_numpy() if hasattr(x, "to_numpy") else x), dtype=torch.float32)
+        ct = torch.as_tensor(np.asarray(c), dtype=torch.long)
+        return [cell[0] for cell in self._counterfactual([xt], [ct], "poe", c_grid, latent)]
 
 
 # =========================================================================================================
@@ -920,6 +1046,9 @@ class cVAE_multimodal_regression(_ExpertOps, _HeadBase):
 
     def pred_recon_draws(self, xes, c, DEVICE, combine, n_draws, seed=None):
         return cVAE_multimodal.pred_recon_draws(self, xes, c, DEVICE, combine, n_draws, seed)
+
+    def pred_recon_counterfactual(self, xes, c, DEVICE, combine, c_grid, latent="mean"):
+        return cVAE_multimodal.pred_recon_counterfactual(self, xes, c, DEVICE, combine, c_grid, latent)
 
     def encode(self, x, c, m):
         return cVAE_multimodal.encode(self, x, c, m)

@@ -1546,6 +1546,283 @@ __global__ __launch_bounds__(WG, 4) void nm_devpass_draws_kernel(const nm_job_t*
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// nm_decode_kernel -- the decoder half of nm_devpass_multi_kernel and nothing else: a table of latent rows z decoded under
+// the rows' own covariates or under every row of a covariate grid (nmhip.h: nm_decode_t).  No encoder, no fusion, no draw,
+// no workspace tile.  The sources of the kernels above stay as they are: their decoder loop and output-chunk epilogue are
+// repeated here inside the loop over the grid's cells, the export pointers taken from the request.
+//
+// A workgroup owns 128 rows of the REQUEST (its own row count, not the job's tables'), two workgroups share a CU.  LDS: the
+// plan of nm_devpass_multi_kernel (P, W, two vector slots, scalars, Z [128][32] bf16).  Per tile: z fp32 -> bf16 into Z once
+// (the conversion build_zc and the draw code apply; zeros past the request's rows), then per cell g and wanted decoder m:
+// z | c | 1 | 0 into P (dec_build_zc: the covariate block of the row itself, or row g of the grid for every row), the hidden
+// layers through dv_layer, the 64-ROI chunks with nm_devpass_kernel's wave-per-16-rows epilogue.  Every value of a cell
+// goes through the operations nm_devpass_multi_kernel applies to a row with that z and that covariate block, so with
+// z = out_z and the tables' own cz / x the exports equal that kernel's (and the general kernel's) bit for bit, and cell g
+// equals a per-row launch whose cz table repeats grid row g.
+// A job dec_refused refuses, or a request whose counts are out of range, must not reach this kernel (the caller checks on
+// the host); its workgroups leave at once, exports untouched.
+__host__ __device__ inline int dec_refused(const nm_job_t* j) { return lat_refused(j); }     // the domain of the encoder half
+
+// build_zc with the z columns from LDS and the covariate block from `cz` + r * cstride: cstride = Cz with cz at the tile's
+// first row -- the table's own rows, build_zc's bytes -- or cstride = 0 -- ONE row for every row of the tile: the bytes
+// build_zc produces from a table whose every row is that row.
+__device__ __forceinline__ void dec_build_zc(const Ctx& c, __bf16* dst, const GAS uint16_t* cz, int cstride, int Z, int C,
+                                             const __bf16* zsrc) {
+  constexpr int ROWS = DV_ROWS;
+  const int wz = wpad(Z + C);
+  const float rz = 1.0f / (float)Z;
+  {
+    const int npc = (C + 1 + 7) >> 3;
+    const float rnp = 1.0f / (float)npc;
+    for (int p = c.tid; p < ROWS * npc; p += WG) {
+      const int r = idiv(p, npc, rnp), col0 = 8 * (p - r * npc);
+      const u32x4 v = *(const GAS u32x4*)(cz + (int64_t)r * cstride + col0);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int j = col0 + i;
+        const uint16_t h = (uint16_t)(v[i >> 1] >> (16 * (i & 1)));
+        if (j <= C) reinterpret_cast<uint16_t*>(dst)[r * LDP + Z + j] = h;
+      }
+    }
+  }
+  {                                                 // zero pad columns (Z + C, wz)
+    const int nz = wz - (Z + C + 1);
+    if (nz > 0) {
+      const float rnz = 1.0f / (float)nz;
+      for (int e = c.tid; e < ROWS * nz; e += WG) {
+        const int r = idiv(e, nz, rnz);
+        dst[r * LDP + Z + C + 1 + (e - r * nz)] = (__bf16)0.0f;
+      }
+    }
+  }
+#pragma unroll 4
+  for (int e = c.tid; e < ROWS * Z; e += WG) {
+    int r = idiv(e, Z, rz), k = e - r * Z;
+    dst[r * LDP + k] = zsrc[r * 32 + k];
+  }
+}
+
+__global__ __launch_bounds__(WG, 4) void nm_decode_kernel(const nm_job_t* __restrict__ jobs, const nm_decode_t* __restrict__ reqs,
+                                                            int tile0, int flags) {
+  constexpr int ROWS = DV_ROWS;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const nm_job_t* J = jobs + blockIdx.x;
+  const nm_decode_t* const rq = reqs + blockIdx.x;
+  if (dec_refused(J)) return;
+  const int n_rows = rq->n_rows, ralloc = rq->rows_alloc, n_cells = rq->n_cells;
+  if (n_rows < 0 || ralloc < n_rows || ralloc % TROWS != 0 || n_cells < 0 || n_cells > NM_MAX_CELLS || !rq->z) return;
+  if (n_cells > 0 && !rq->cgrid) return;
+  const int M = J->M;
+  const int cells = n_cells > 0 ? n_cells : 1;
+  const int t128 = tile0 + (int)blockIdx.y;
+  const int row0 = t128 * ROWS;
+  if (row0 >= n_rows) {
+    // the second half of a ragged last 256-row tile: every cell's export rows come back as zeros (tiles beyond it -- the
+    // grid is as tall as the launch's tallest request -- are not this request's)
+    if (row0 < (n_rows + TROWS - 1) / TROWS * TROWS)
+      for (int g = 0; g < cells; ++g)
+        for (int m = 0; m < M; ++m) {
+          const int xp = J->mod[m].x_pitch;
+          const bool hx = rq->x[m] != nullptr;
+          gf32 oloc = asg(rq->loc[m]), osq = hx ? asg(rq->sqerr[m]) : (gf32)nullptr, ordv = hx ? asg(rq->rowdev[m]) : (gf32)nullptr;
+          if (oloc) oloc += (int64_t)g * ralloc * xp;
+          if (osq) osq += (int64_t)g * ralloc * xp;
+          if (ordv) ordv += (int64_t)g * ralloc;
+          dvs_zero_dead_rows((int)threadIdx.x, xp, oloc, osq, ordv, row0, 0);
+        }
+    return;
+  }
+  Ctx c;
+  c.job = J;
+  c.part = -1; c.nparts = 1; c.lstep = 0;
+  c.slope = J->act_slope;
+  dv_carve(c, smem);
+  relaunder(c);
+  c.flags = NM_F_EXPORT | (flags & NM_F_TRACE);
+  c.t_last = 0;
+  c.ws = nullptr;
+  for (int i = c.tid; i < DVM_SMEM / 4; i += WG) reinterpret_cast<uint32_t*>(smem)[i] = 0u;
+  __syncthreads();
+  if (c.flags & 64) c.tlast[c.wave_s] = clock64();
+  c.row0 = row0;
+  c.rloc0 = row0 % TROWS;
+  c.nrows = min(ROWS, n_rows - row0);
+  c.inv_b = 1.0f / (float)c.nrows;
+  const int live = c.nrows;
+  const int L = J->L, Z = J->Z, C = J->C;
+  const bool nl = J->non_linear != 0;
+  const bool vec4 = (Z & 3) == 0;
+  GAS char* const wsh = (GAS char*)J->wsh;
+  char* const Wb = reinterpret_cast<char*>(c.Q);
+  __bf16* const zlds = reinterpret_cast<__bf16*>(smem + DV_SMEM);
+  auto to_W = [&](const GAS char* blob, int vs, int rows, int K) {
+    return Next{blob, Wb, IMG_BYTES >> 10, blob + cimg_bytes(rows, K), reinterpret_cast<char*>(c.vec) + vs * VEC_BYTES, rows, blob_kp(K)};
+  };
+  // the first decoder that is wanted (workgroup-uniform; none: nothing to do but the tile's rows are nobody's either)
+  int mf = 0;
+  while (mf < M && !rq->loc[mf]) ++mf;
+  if (mf == M) return;
+  // W and P are free: the first decoder's image lands while z is converted
+  issue_next(c, to_W(wsh + J->mod[mf].dec_s[0], 0, J->H[L - 1], Z + C));
+
+  // ---- z: fp32 rows -> bf16 [128][32] in LDS, once per tile; rows past the request's end hold zeros ----
+  {
+    gcf32 zg = asg(rq->z) + (int64_t)row0 * Z;
+    if (vec4) {
+      const int nq4 = Z >> 2;
+      const float rq4 = 1.0f / (float)nq4;
+#pragma unroll 2
+      for (int e = c.tid; e < ROWS * nq4; e += WG) {
+        const int r = idiv(e, nq4, rq4), z0 = 4 * (e - r * nq4);
+        f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (r < live) v = *(const GAS f32x4*)(zg + (int64_t)r * Z + z0);
+        bf16x4 zk;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) zk[i] = (__bf16)v[i];
+        *reinterpret_cast<bf16x4*>(zlds + r * 32 + z0) = zk;
+      }
+    } else {
+      const float rZ = 1.0f / (float)Z;
+#pragma unroll 2
+      for (int e = c.tid; e < ROWS * Z; e += WG) {
+        const int r = idiv(e, Z, rZ), z = e - r * Z;
+        const float v = r < live ? zg[(int64_t)r * Z + z] : 0.f;
+        zlds[r * 32 + z] = (__bf16)v;
+      }
+    }
+  }
+  lds_barrier();                                   // z is complete (the decoder image requested above stays in flight)
+  tr(c, 3);
+
+  // ---- per cell: every wanted decoder ----
+  const int Hl = J->H[0];
+  const int ob = L & 1;                            // (see nm_devpass_kernel: chunk 0's vectors avoid the last hidden layer's bias)
+  for (int g = 0; g < cells; ++g) {
+    for (int m = mf; m < M; ++m) {
+      relaunder(c);
+      const nm_modality_t& md = J->mod[m];
+      const int D = md.D, xp = md.x_pitch;
+      gcf32 xf = asg(rq->x[m]);
+      gf32 oloc = asg(rq->loc[m]);
+      if (!oloc) continue;                         // (workgroup-uniform) this decoder is not wanted: skipped entirely
+      gf32 osq = xf ? asg(rq->sqerr[m]) : (gf32)nullptr, ordv = xf ? asg(rq->rowdev[m]) : (gf32)nullptr;
+      oloc += (int64_t)g * ralloc * xp;
+      if (osq) osq += (int64_t)g * ralloc * xp;
+      if (ordv) ordv += (int64_t)g * ralloc;
+      if (g != 0 || m != mf) {
+        lds_barrier();                             // the previous decoder's last chunk is finished everywhere: P, W, vectors free
+        issue_next(c, to_W(wsh + md.dec_s[0], 0, J->H[L - 1], Z + C));
+      }
+      if (n_cells > 0) dec_build_zc(c, c.P, asg(rq->cgrid) + (int64_t)g * md.Cz, 0, Z, C, zlds);
+      else dec_build_zc(c, c.P, asg(rq->cz[m]) + (int64_t)row0 * md.Cz, md.Cz, Z, C, zlds);
+      tr(c, 4);
+      int vs = 0;
+      const GAS char* oblob = wsh + md.out_s;
+      const int nck = (D + OCH - 1) / OCH;
+      auto out_blob = [&](int ch) {
+        return Next{oblob + (int64_t)ch * OBLOB_BYTES, Wb + (ch & 1) * OIMG_BYTES, OIMG_BYTES >> 10,
+                    oblob + (int64_t)ch * OBLOB_BYTES + OIMG_BYTES, reinterpret_cast<char*>(c.vec) + ((ch + ob) & 1) * VEC_BYTES, 0, 0};
+      };
+      for (int d = 0; d < L; ++d) {
+        const int Kin = (d == 0) ? Z + C : J->H[L - d], Nout = J->H[L - 1 - d];
+        const Next nx = (d + 1 < L) ? to_W(wsh + md.dec_s[d + 1], vs ^ 1, J->H[L - 2 - d], Nout) : out_blob(0);
+        dv_layer(c, vs, nx, Nout, Kin, nl, live);    // (its first barrier also publishes z | c | 1)
+        vs ^= 1;
+      }
+      tr(c, 5);
+      // output layer in 64-ROI chunks, wave w owns rows [16 w, 16 w + 16) and all 64 columns: see nm_devpass_kernel
+      float rdev = 0.f;
+      const int orow = c.wave * 16 + c.c16;
+      const bool wave_live = c.wave * 16 < live;
+      const bool rv = orow < c.nrows;
+      auto load_xin = [&](int chx, f32x4 (&xv)[4]) {
+#pragma unroll
+        for (int ft = 0; ft < 4; ++ft) {
+          const int dcl = min(chx * OCH + ft * 16 + 4 * c.g, xp - 4);
+          xv[ft] = *(const GAS f32x4*)(xf + (int64_t)(row0 + orow) * xp + dcl);
+        }
+      };
+      int stores_prev = 0;
+      auto chunk = [&](const int ch, f32x4 (&xin)[4], f32x4 (&xnx)[4]) {
+        relaunder(c);
+        const int d0 = ch * OCH;
+        const __bf16* Wc = reinterpret_cast<const __bf16*>(Wb + (ch & 1) * OIMG_BYTES);
+        const float* vb = c.vec + ((ch + ob) & 1) * (VEC_BYTES / 4);
+        wait_vm(ch > 0 ? stores_prev : 0);
+        lds_barrier();
+        if (ch + 1 < nck) { issue_next(c, out_blob(ch + 1)); if (wave_live && xf) load_xin(ch + 1, xnx); }
+        stores_prev = 0;
+        if (!wave_live) return;
+        f32x4 acc[4];
+#pragma unroll
+        for (int ft = 0; ft < 4; ++ft) acc[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
+        const int ksteps = wpad(Hl) / 32;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+          if (ks < ksteps) {
+            const bf16x8 a = lds_frag(c.P, LDP, orow, ks * 32 + 8 * c.g);
+#pragma unroll
+            for (int ft = 0; ft < 4; ++ft) acc[ft] = mfma(lds_frag(Wc, LDP, ft * 16 + c.c16, ks * 32 + 8 * c.g), a, acc[ft]);
+          }
+        }
+        tr(c, 6);
+        const bool full = live == ROWS && d0 + OCH <= D;                   // no row / column masks needed (wave-uniform)
+#pragma unroll
+        for (int ft = 0; ft < 4; ++ft) {
+          const int dg0 = d0 + ft * 16 + 4 * c.g;
+          const f32x4 bo = *reinterpret_cast<const f32x4*>(vb + ft * 16 + 4 * c.g);
+          f32x4 lo, sq;
+          if (full) {
+            lo = acc[ft] + bo;
+            const f32x4 diff = lo - xin[ft];
+            sq = diff * diff;
+          } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const float xh = acc[ft][i] + bo[i];
+              const bool dv = rv && dg0 + i < D;
+              const float diff = xh - xin[ft][i];
+              lo[i] = dv ? xh : 0.f;
+              sq[i] = dv ? diff * diff : 0.f;
+            }
+          }
+          rdev += ((sq[0] + sq[1]) + sq[2]) + sq[3];
+          if (d0 + ft * 16 < xp) {                      // wave-uniform
+            if (dg0 < xp) {
+              const int64_t gi = (int64_t)(row0 + orow) * xp + dg0;
+              *(GAS f32x4*)(oloc + gi) = lo;
+              if (osq) *(GAS f32x4*)(osq + gi) = sq;
+            }
+            stores_prev += 1 + (osq ? 1 : 0);
+          }
+        }
+        tr(c, 7);
+      };
+      {
+        f32x4 xa[4], xb[4];
+#pragma unroll
+        for (int ft = 0; ft < 4; ++ft) { xa[ft] = f32x4{0.f, 0.f, 0.f, 0.f}; xb[ft] = xa[ft]; }
+        if (wave_live && xf) load_xin(0, xa);
+        for (int ch = 0; ch < nck; ch += 2) {
+          chunk(ch, xa, xb);
+          if (ch + 1 < nck) chunk(ch + 1, xb, xa);
+        }
+      }
+      if (ordv && wave_live) {
+        float v = rdev;
+        v += __shfl_xor(v, 16, 64);
+        v += __shfl_xor(v, 32, 64);
+        if (c.g == 0 && orow < c.nrows) ordv[row0 + orow] = v / (float)D;
+      }
+      // (a ragged tile only: the rows no wave has stored; the laundered thread index keeps the loop's addresses from being
+      //  hoisted out of the cell loop and held in registers across it)
+      if (live < ROWS) { relaunder(c); dvs_zero_dead_rows(c.tid, xp, oloc, osq, ordv, row0, live); }
+      tr(c, 8);
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1641,6 +1918,23 @@ int nm_latent_pass_ok(const nm_job_t* j) {
 int nm_latent_pass(const nm_job_t* jobs_dev, int n_jobs, int tile0, int n_tiles, int flags, void* stream) {
   if (int bad = check_launch_geometry(jobs_dev, n_jobs, n_tiles, 1, tile0, 0)) return bad;
   return launch_kernel(nm_latent_kernel, dim3(n_jobs, n_tiles), dim3(WG), DV_SMEM, stream, jobs_dev, tile0, flags & NM_F_TRACE);
+}
+
+/* 0: the job's decoders can run on the decoder-only kernel: exactly what nm_latent_pass_ok admits, so the two halves cover
+ * the same models; NM_E_DEVPASS otherwise. */
+int nm_decode_pass_ok(const nm_job_t* j) {
+  if (!j) return NM_E_NULL;
+  return dec_refused(j);
+}
+
+/* The decoder half alone over rows [tile0 * 128, (tile0 + n_tiles) * 128) of every job's request (nmhip.h: nm_decode_t): z
+ * decoded under the rows' own covariates or under every row of a covariate grid, loc / sqerr / rowdev per cell.  Status is
+ * decided here, on the host, before the device is asked anything -- the descriptors and the requests live in device memory:
+ * the request's own rules (n_cells, rows_alloc, sqerr / rowdev only with x) are the caller's.  No workspace tile. */
+int nm_decode_pass(const nm_job_t* jobs_dev, int n_jobs, const nm_decode_t* req_dev, int tile0, int n_tiles, int flags, void* stream) {
+  if (!jobs_dev || !req_dev) return NM_E_NULL;
+  if (int bad = check_launch_geometry(jobs_dev, n_jobs, n_tiles, 1, tile0, 0)) return bad;
+  return launch_kernel(nm_decode_kernel, dim3(n_jobs, n_tiles), dim3(WG), DVM_SMEM, stream, jobs_dev, req_dev, tile0, flags & NM_F_TRACE);
 }
 
 /* NM_F_TRACE read-out of nm_devpass ([8 waves][64 tags] interval cycles of workgroup (0, 0), as nm_trace_read) */

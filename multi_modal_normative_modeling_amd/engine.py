@@ -33,7 +33,66 @@ DEVPASS_MULTI_AUTO = {2: True, 3: True, 4: True}
 # stays on the general kernel until it does (JobSet.latent(compact=True) reaches nm_latent_pass all the same)
 LATENT_AUTO = {1: True, 2: False, 3: True, 4: True}
 
+# nm_decode_pass as the automatic route of the drop-in classes' decode(z, c, m), per number of decoders of the model: on only
+# where the decoder-only kernel's slowest repeat beat the fastest of today's route (the one-modality copy on the general
+# kernel with NM_F_ZGIVEN) at every set size measured (tools/bench_decode.py, profiles/decode_pass.json, DESIGN.md section
+# 4b).  The record times the grid workload (54 cells a launch), not single decode() calls: no class holds a record of those
+# yet, so decode() reaches the pass with NMHIP_DECODE=1; decode_grid, normative_trajectory and pred_recon_counterfactual have
+# no other route and take it wherever the job is admitted
+DECODE_AUTO = {1: False, 2: False, 3: False, 4: False}
+
 _MASK64 = (1 << 64) - 1
+
+
+def pack_covariates(c, Cz: int, rows_alloc: int, device) -> torch.Tensor:
+    """Covariate rows c [R, C] -> the bf16 block [rows_alloc, Cz] the decoders read beside z: c | 1 | 0 per row, zero rows
+    past R -- byte for byte what Table holds in .cz for the same c (the same float32 -> bf16 rounding)."""
+    c = torch.as_tensor(np.asarray(c) if not torch.is_tensor(c) else c)
+    if c.dim() != 2:
+        raise ValueError(f"covariates must be [rows, C], got {tuple(c.shape)}")
+    R, Cc = int(c.shape[0]), int(c.shape[1])
+    if Cc + 1 > Cz or Cz % 8 != 0 or R > rows_alloc:
+        raise ValueError(f"covariates [{R}, {Cc}] do not fit a block of {rows_alloc} rows of pitch {Cz}")
+    out = torch.zeros(rows_alloc, Cz, dtype=torch.bfloat16, device=device)
+    if Cc:
+        out[:R, :Cc] = c.to(device=device, dtype=torch.float32).to(torch.bfloat16)
+    out[:R, Cc] = 1.0
+    return out
+
+
+def check_decode_request(n_rows: int, rows_alloc: int, n_cells: int, Z: int, Cz: int, pitches: Sequence[int], z, cgrid, cz, x,
+                         loc, sqerr, rowdev):
+    """The rules of an nm_decode_t the library cannot check (the request lives in device memory): raised here, before the
+    upload.  pitches: x_pitch per decoder; z / cgrid: tensors or None; cz, x, loc, sqerr, rowdev: per decoder a tensor (its
+    whole storage) or None.  Only sizes are read: the tensors may live anywhere."""
+    if not 0 <= int(n_cells) <= _lib.NM_MAX_CELLS:
+        raise ValueError(f"n_cells must be 0 to {_lib.NM_MAX_CELLS}, got {n_cells}")
+    if n_rows < 1 or rows_alloc % BATCH != 0 or rows_alloc < n_rows:
+        raise ValueError(f"rows_alloc must be a multiple of {BATCH} and at least n_rows >= 1, got {rows_alloc} for {n_rows} rows")
+    if len(pitches) > _lib.NM_MAX_EXP:
+        raise ValueError(f"a request holds at most {_lib.NM_MAX_EXP} decoders, got {len(pitches)}")
+    if z is None or z.numel() < rows_alloc * Z:
+        raise ValueError(f"z must hold [{rows_alloc}, {Z}] values")
+    cells = max(int(n_cells), 1)
+    if n_cells > 0 and (cgrid is None or cgrid.numel() < n_cells * Cz):
+        raise ValueError(f"c_grid must hold [{n_cells}, {Cz}] packed values")
+    if not any(t is not None for t in loc):
+        raise ValueError("no decoder is wanted: every loc is None")
+    for m, xp in enumerate(pitches):
+        if loc[m] is None:
+            if sqerr[m] is not None or rowdev[m] is not None:
+                raise ValueError(f"decoder {m}: sqerr / rowdev without loc (a decoder without loc is skipped)")
+            continue
+        if n_cells == 0 and (cz[m] is None or cz[m].numel() < rows_alloc * Cz):
+            raise ValueError(f"decoder {m}: per-row covariates must hold [{rows_alloc}, {Cz}] packed values")
+        if (sqerr[m] is not None or rowdev[m] is not None) and x[m] is None:
+            raise ValueError(f"decoder {m}: sqerr / rowdev are taken against x, which is not given")
+        if x[m] is not None and x[m].numel() < rows_alloc * xp:
+            raise ValueError(f"decoder {m}: x must hold [{rows_alloc}, {xp}] values")
+        for what, t, need in (("loc", loc[m], cells * rows_alloc * xp), ("sqerr", sqerr[m], cells * rows_alloc * xp),
+                              ("rowdev", rowdev[m], cells * rows_alloc)):
+            if t is not None and t.numel() < need:
+                raise ValueError(f"decoder {m}: {what} holds {t.numel()} values, its declared shape needs {need}")
 
 
 def draw_seeds(seed: int, n_draws: int) -> List[int]:
@@ -226,6 +285,10 @@ class Job:
         # the posterior-predictive pass (enable_predictive_exports): draws per row, their keys / injected noise, exports per modality
         self.n_draws = self.pred_seeds = self.pred_eps = self.noise_var = None
         self.pred_mean = self.pred_var = self.pred_msq = self.pred_z = self.pred_rowdev = self.pred_rowz2 = None
+        # the decoder pass (enable_decode_exports / set_decode_inputs): the request's rows and cells, its inputs and exports
+        self.dec_rows = self.dec_rows_alloc = self.dec_cells = self.dec_decoders = self.dec_full = None
+        self.dec_z = self.dec_cgrid = self.dec_cz = self.dec_x = self.dec_loc = self.dec_sqerr = self.dec_rowdev = None
+        self._dec_epoch = 0              # bumped whenever the request would change
         self._params_epoch = 0           # bumped by every host-side write of the parameters (refresh_noise_var)
         self._nv_state = None
 
@@ -575,6 +638,120 @@ class Job:
             self._latent_stash = (self.out_mu, self.out_logvar, self.out_z)
             self.out_mu = self.out_logvar = self.out_z = None
         self._version += 1
+
+    # -- the decoder pass (nm_decode_pass) -------------------------------------------------------
+    def decode_ok(self) -> bool:
+        """nm_decode_pass_ok for this job: exactly what latent_ok() admits -- the encoder half and the decoder half cover the
+        same models (tests/test_cabi_decode_cpu.py holds this to the library)."""
+        return self.latent_ok()
+
+    def enable_decode_exports(self, n_rows, n_cells=0, loc=True, sqerr=False, rowdev=False, decoders=None):
+        """Buffers of the decoder pass (JobSet.decode, nm_decode_pass) for a request of n_rows latent rows -- its own row count,
+        not the tables' -- decoded under the rows' own covariates (n_cells = 0) or under each of n_cells rows of a covariate
+        grid (1..64).  decoders: the modalities to decode (None: every one); a decoder left out is skipped by the kernel.
+        Afterwards dec_loc[m], dec_sqerr[m] ([cells, n_rows, D] views, cells = max(n_cells, 1)) and dec_rowdev[m] ([cells,
+        n_rows]) hold the exports of decoder m, None where the decoder or the kind was not asked for; dec_full["loc" /
+        "sqerr" / "rowdev"][m] are the whole buffers ([cells, rows_alloc, x_pitch] / [cells, rows_alloc]).  sqerr / rowdev
+        are taken against x (set_decode_inputs).  Refused (ValueError): n_cells outside 0..64, no rows, loc=False (the
+        kernel skips a decoder without loc), a decoder index beyond the model's."""
+        R, G, M = int(n_rows), int(n_cells), len(self.kmods)
+        if not 0 <= G <= _lib.NM_MAX_CELLS:
+            raise ValueError(f"n_cells must be 0 to {_lib.NM_MAX_CELLS}, got {n_cells}")
+        if R < 1:
+            raise ValueError(f"n_rows must be at least 1, got {n_rows}")
+        if not loc:
+            raise ValueError("loc=False: the kernel skips a decoder without loc -- leave it out of `decoders` instead")
+        decoders = tuple(range(M)) if decoders is None else tuple(int(m) for m in decoders)
+        if not decoders or any(m < 0 or m >= M or m >= _lib.NM_MAX_EXP for m in decoders):
+            raise ValueError(f"decoders: modalities 0..{min(M, _lib.NM_MAX_EXP) - 1}, at least one")
+        ra, cells = (R + BATCH - 1) // BATCH * BATCH, max(G, 1)
+        pitch = [self.tables[m].x_pitch for m, _, _ in self.kmods]
+        width = [self.tables[m].D for m, _, _ in self.kmods]
+        mat = lambda on: [torch.zeros(cells, ra, pitch[m], device=self.device) if on and m in decoders else None for m in range(M)]
+        row = lambda on: [torch.zeros(cells, ra, device=self.device) if on and m in decoders else None for m in range(M)]
+        self.dec_rows, self.dec_rows_alloc, self.dec_cells, self.dec_decoders = R, ra, G, decoders
+        self.dec_full = {"loc": mat(True), "sqerr": mat(sqerr), "rowdev": row(rowdev)}
+        cut = lambda ts: [t[:, :R, :width[m]] if t is not None else None for m, t in enumerate(ts)]
+        self.dec_loc, self.dec_sqerr = cut(self.dec_full["loc"]), cut(self.dec_full["sqerr"])
+        self.dec_rowdev = [t[:, :R] if t is not None else None for t in self.dec_full["rowdev"]]
+        self.dec_z = self.dec_cgrid = None
+        self.dec_cz, self.dec_x = [None] * M, [None] * M
+        self._dec_epoch += 1
+
+    def set_decode_inputs(self, z, c=None, c_grid=None, x="tables"):
+        """Inputs of the decoder pass.  z: [n_rows, Z] fp32 latent rows (copied).  Per-row requests (n_cells = 0): c is one
+        covariate table [n_rows, C] for every decoder, a list with one per decoder, or None -- the job's own tables' packed
+        covariates, and then n_rows must equal the tables' rows.  Grid requests: c_grid [n_cells, C], one row per cell.
+        Covariates are packed to bf16 c | 1 | 0 rows of pitch Cz (pack_covariates: the bytes Table holds in .cz for the same
+        c).  x: "tables" -- sqerr / rowdev are taken against the tables' own x (n_rows must equal the tables' rows) -- or
+        None (requests with loc alone; the default falls back to None where neither sqerr nor rowdev was asked for)."""
+        if self.dec_rows is None:
+            raise ValueError("enable_decode_exports() first")
+        R, ra, G, M, Z = self.dec_rows, self.dec_rows_alloc, self.dec_cells, len(self.kmods), self.spec.latent
+        z = torch.as_tensor(np.asarray(z) if not torch.is_tensor(z) else z)
+        if z.dim() != 2 or int(z.shape[0]) != R or int(z.shape[1]) != Z:
+            raise ValueError(f"z must be [{R}, {Z}], got {tuple(z.shape)}")
+        if self.dec_z is None:
+            self.dec_z = torch.zeros(ra, Z, device=self.device)
+        self.dec_z[:R].copy_(z.to(device=self.device, dtype=torch.float32))
+        Cz, N = self.tables[0].Cz, self.tables[0].N
+        if G > 0:
+            if c is not None or c_grid is None:
+                raise ValueError("a grid request takes c_grid (one covariate row per cell), not per-row c")
+            g = torch.as_tensor(np.asarray(c_grid) if not torch.is_tensor(c_grid) else c_grid)
+            if g.dim() != 2 or int(g.shape[0]) != G or int(g.shape[1]) != self.spec.net_c_dim:
+                raise ValueError(f"c_grid must be [{G}, {self.spec.net_c_dim}], got {tuple(g.shape)}")
+            self.dec_cgrid = pack_covariates(g, Cz, G, self.device)
+            self.dec_cz = [None] * M
+        else:
+            if c_grid is not None:
+                raise ValueError("c_grid needs a grid request: enable_decode_exports(n_rows, n_cells=G)")
+            if c is None:
+                if R != N or ra != self.tables[0].rows_alloc:
+                    raise ValueError(f"c=None reads the tables' own covariates: the request has {R} rows, the tables {N}")
+                self.dec_cz = [self.tables[m].cz for m, _, _ in self.kmods]
+            else:
+                per = list(c) if isinstance(c, (list, tuple)) else [c] * M
+                if len(per) != M:
+                    raise ValueError(f"c: one covariate table, or one per decoder ({M}), got {len(per)}")
+                packed = {}
+                for t in per:
+                    if int(t.shape[0]) != R or int(t.shape[1]) != self.spec.net_c_dim:
+                        raise ValueError(f"c must be [{R}, {self.spec.net_c_dim}], got {tuple(t.shape)}")
+                    if id(t) not in packed:
+                        packed[id(t)] = pack_covariates(t, Cz, ra, self.device)
+                self.dec_cz = [packed[id(t)] for t in per]
+            self.dec_cgrid = None
+        wants_x = any(t is not None for t in self.dec_full["sqerr"]) or any(t is not None for t in self.dec_full["rowdev"])
+        if x is None or (isinstance(x, str) and x == "tables" and not wants_x):
+            if wants_x:
+                raise ValueError("sqerr / rowdev are taken against x: x=None leaves them without it")
+            self.dec_x = [None] * M
+        elif isinstance(x, str) and x == "tables":
+            if R != N or ra != self.tables[0].rows_alloc:
+                raise ValueError(f'x="tables" reads the tables\' own x: the request has {R} rows, the tables {N}')
+            self.dec_x = [self.tables[m].x_f32 for m, _, _ in self.kmods]
+        else:
+            raise ValueError('x: "tables" or None')
+        self._dec_epoch += 1
+
+    def decode_struct(self) -> "_lib.NmDecode":
+        """This job's entry of nm_decode_pass' request table, validated (check_decode_request) before it travels."""
+        if self.dec_rows is None or self.dec_z is None:
+            raise ValueError("enable_decode_exports() and set_decode_inputs() first")
+        M = len(self.kmods)
+        full = self.dec_full
+        check_decode_request(self.dec_rows, self.dec_rows_alloc, self.dec_cells, self.spec.latent, self.tables[0].Cz,
+                             [self.tables[m].x_pitch for m, _, _ in self.kmods], self.dec_z, self.dec_cgrid, self.dec_cz,
+                             self.dec_x, full["loc"], full["sqerr"], full["rowdev"])
+        r = _lib.NmDecode()
+        r.z, r.n_rows, r.rows_alloc, r.n_cells = self.dec_z.data_ptr(), self.dec_rows, self.dec_rows_alloc, self.dec_cells
+        r.cgrid = self.dec_cgrid.data_ptr() if self.dec_cgrid is not None else None
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        for m in range(M):
+            r.cz[m], r.x[m] = ptr(self.dec_cz[m]), ptr(self.dec_x[m])
+            r.loc[m], r.sqerr[m], r.rowdev[m] = ptr(full["loc"][m]), ptr(full["sqerr"][m]), ptr(full["rowdev"][m])
+        return r
 
     # -- descriptor ----------------------------------------------------------------------------
     def struct(self) -> _lib.NmJob:
@@ -1205,6 +1382,59 @@ class JobSet:
                         f"{len(j.kmods)} in the kernel, hidden {list(s.hidden)}, latent {s.latent}, private {s.n_private}, "
                         f"tc_weight {j.tc_weight})")
         return "nothing"
+
+    def decode_ok(self) -> bool:
+        """Can the set's decoders run on the decoder-only kernel (nm_decode_pass)?  The conditions of nm_decode_pass_ok, read
+        off the jobs as in latent_ok (tests/test_cabi_decode_cpu.py holds the two to each other); NMHIP_DECODE=0 switches
+        the kernel off."""
+        if self.wide or os.environ.get("NMHIP_DECODE", "1") == "0":
+            return False
+        return all(j.decode_ok() for j in self.jobs)
+
+    def decode_pick(self) -> bool:
+        """The automatic route of the drop-in classes' decode(z, c, m) through nm_decode_pass: decode_ok() and a shape class in
+        which the decoder-only kernel's slowest measured repeat beat today's route's fastest (DECODE_AUTO, DESIGN.md
+        section 4b).  NMHIP_DECODE=1 forces the route on where the set passes decode_ok()."""
+        if not self.decode_ok():
+            return False
+        return os.environ.get("NMHIP_DECODE", "auto") == "1" or all(DECODE_AUTO.get(len(j.kmods), False) for j in self.jobs)
+
+    def decode(self, tile0: int = 0, n_tiles: Optional[int] = None, trace: bool = False):
+        """The decoder pass (nm_decode_pass): every job's request (Job.enable_decode_exports / set_decode_inputs) -- latent
+        rows decoded under their own covariates or under every cell of a covariate grid -- in ONE launch, into job.dec_loc /
+        dec_sqerr / dec_rowdev.  The requests may differ in height and in their number of cells: the grid is as tall as the
+        tallest, n_tiles (256-row tiles, from tile0) defaults to that.  A set holding a job the kernel does not take
+        (general-shape path, first hidden width > 112, latent rounded to 16 > 32, an end-to-end trunk, a non-Gaussian
+        output) or NMHIP_DECODE=0 raises ValueError naming the refusal.  trace: the kernel records its phase cycles
+        (nm_trace_read_dv)."""
+        if any(j.dec_rows is None or j.dec_z is None for j in self.jobs):
+            raise ValueError("decode: Job.enable_decode_exports() and set_decode_inputs() first, on every job of the set")
+        why = self._decode_refusal()
+        if why is not None:
+            raise ValueError("decode: the set cannot run on nm_decode_pass: " + why)
+        # the request table on the device: rebuilt when a job's request changed; kept until then -- the launch reads it in
+        # stream order
+        sig = tuple(j._dec_epoch for j in self.jobs)
+        if getattr(self, "_dec_sig", None) != sig:
+            arr = (_lib.NmDecode * len(self.jobs))(*[j.decode_struct() for j in self.jobs])
+            self._dec_keep = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
+            self._dec_sig = sig
+        nt = max(j.dec_rows_alloc for j in self.jobs) // BATCH if n_tiles is None else n_tiles
+        self._issue("nm_decode_pass", 1, self._dec_keep.data_ptr(), tile0 * 2, nt * 2, _lib.NM_F_TRACE if trace else 0)
+
+    def _decode_refusal(self) -> Optional[str]:
+        """Why the set cannot run the decoder pass; None: it can."""
+        if os.environ.get("NMHIP_DECODE", "1") == "0":
+            return "NMHIP_DECODE=0"
+        if self.wide:
+            return "general-shape path (a hidden width or latent beyond the fused kernel's tile)"
+        for i, j in enumerate(self.jobs):
+            if not j.decode_ok():
+                s = j.spec
+                return (f"job {i}: nm_decode_pass_ok refuses its shape (kind {s.kind!r}, {s.M} modalities of which "
+                        f"{len(j.kmods)} in the kernel, hidden {list(s.hidden)}, latent {s.latent}, private {s.n_private}, "
+                        f"tc_weight {j.tc_weight})")
+        return None
 
     def latent_stats(self):
         """Per job the column means and population variances of its exported joint mu over the table's rows (the training

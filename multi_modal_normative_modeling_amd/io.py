@@ -183,6 +183,11 @@ def write_normative_csvs(out_dir, dataset_name: str, covariates: pd.DataFrame, r
       normative_z_{name}.csv        participant_id, DIA, AGE, PTGENDER, then one z per ROI
       normative_subject_{name}.csv  participant_id, DIA, AGE, PTGENDER, then metrics.NORMATIVE_ROW_COLUMNS
       normative_map_{name}.csv      ROI, then metrics.NORMATIVE_COL_COLUMNS (the extreme-deviation map)"""
+    return _write_z_map_csvs("normative", out_dir, dataset_name, covariates, roi_columns, z, rows, cols)
+
+
+def _write_z_map_csvs(prefix: str, out_dir, dataset_name: str, covariates: pd.DataFrame, roi_columns: Sequence[str], z, rows, cols):
+    """{prefix}_z / _subject / _map _{name}.csv: the three files of a z-map (write_normative_csvs, write_trajectory_csvs)."""
     from .metrics import NORMATIVE_COL_COLUMNS, NORMATIVE_ROW_COLUMNS
     z, rows, cols = np.asarray(z), np.asarray(rows, dtype=np.float64), np.asarray(cols, dtype=np.float64)
     if z.shape != (len(covariates), len(roi_columns)) or rows.shape != (len(covariates), len(NORMATIVE_ROW_COLUMNS)) or \
@@ -192,13 +197,43 @@ def write_normative_csvs(out_dir, dataset_name: str, covariates: pd.DataFrame, r
     out_dir = Path(out_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
     cov = covariates[META_COLS].copy().reset_index(drop=True)
-    paths = {k: out_dir / f"normative_{k}_{dataset_name}.csv" for k in ("z", "subject", "map")}
+    paths = {k: out_dir / f"{prefix}_{k}_{dataset_name}.csv" for k in ("z", "subject", "map")}
     pd.concat([cov, pd.DataFrame(z, columns=list(roi_columns))], axis=1).to_csv(paths["z"], index=False)
     pd.concat([cov, pd.DataFrame(rows, columns=list(NORMATIVE_ROW_COLUMNS))], axis=1).to_csv(paths["subject"], index=False)
     df = pd.DataFrame(cols, columns=list(NORMATIVE_COL_COLUMNS))
     df.insert(0, "ROI", list(roi_columns))
     df.to_csv(paths["map"], index=False)
     return paths
+
+
+TRAJECTORY_CHART_COLUMNS = ["cell", "age_bin", "gender_bin", "age_lo", "age_hi", "n_test"]
+
+
+def write_trajectory_chart_csvs(out_dir, dataset_name: str, roi_columns: Sequence[str], cells: pd.DataFrame, mean: np.ndarray,
+                                sd: np.ndarray) -> Dict[str, Path]:
+    """The normative chart of one fold and modality (the model's expectation per covariate cell), one row per cell:
+      normative_trajectory_mean_{name}.csv  cell, age_bin, gender_bin, age_lo, age_hi, n_test, then the mean per ROI
+      normative_trajectory_sd_{name}.csv    the same columns, then the predictive sd per ROI
+    cells: a frame with TRAJECTORY_CHART_COLUMNS (age_lo / age_hi NaN -- an empty field -- where no test subject is in the bin)."""
+    mean, sd = np.asarray(mean, dtype=np.float64), np.asarray(sd, dtype=np.float64)
+    if list(cells.columns) != TRAJECTORY_CHART_COLUMNS or mean.shape != (len(cells), len(roi_columns)) or sd.shape != mean.shape:
+        raise ValueError(f"cells with {TRAJECTORY_CHART_COLUMNS} and mean / sd [{len(cells)}, {len(roi_columns)}] are needed, got "
+                         f"{list(cells.columns)}, {mean.shape}, {sd.shape}")
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    head = cells.reset_index(drop=True)
+    paths = {k: out_dir / f"normative_trajectory_{k}_{dataset_name}.csv" for k in ("mean", "sd")}
+    for k, tab in (("mean", mean), ("sd", sd)):
+        pd.concat([head, pd.DataFrame(tab, columns=list(roi_columns))], axis=1).to_csv(paths[k], index=False)
+    return paths
+
+
+def write_trajectory_csvs(out_dir, dataset_name: str, covariates: pd.DataFrame, roi_columns: Sequence[str], z: np.ndarray,
+                          rows: np.ndarray, cols: np.ndarray) -> Dict[str, Path]:
+    """The trajectory z-scores of one set of subjects -- every ROI against the chart row of the subject's own cell -- in the
+    layouts of write_normative_csvs: trajectory_z_{name}.csv, trajectory_subject_{name}.csv (metrics.NORMATIVE_ROW_COLUMNS)
+    and trajectory_map_{name}.csv (metrics.NORMATIVE_COL_COLUMNS, summed over the cells)."""
+    return _write_z_map_csvs("trajectory", out_dir, dataset_name, covariates, roi_columns, z, rows, cols)
 
 
 def quantile_column(p: float) -> str:

@@ -777,6 +777,136 @@ def check_draws(draws, draw_seed=None):
     return int(draws), (None if draw_seed is None else int(draw_seed))
 
 
+TRAJ_AGE_BINS, TRAJ_GENDER_BINS = 27, 2
+TRAJ_MIN_ROWS, TRAJ_MAX_ROWS = 16, 4096
+
+
+def check_trajectory(trajectory, traj_seed=0, c_dim: Optional[int] = None):
+    """(trajectory, traj_seed) of test_folds / `test --trajectory S [--traj-seed N]` as integers, or (None, 0) where the chart
+    is off.  Refused (ValueError): S outside 16..4096 or no multiple of 16, a negative or non-integer seed, a model whose
+    networks take no covariates (c_dim == 0: its decoders have no covariate to vary)."""
+    if trajectory is None:
+        return None, 0
+    if int(trajectory) != trajectory or not TRAJ_MIN_ROWS <= int(trajectory) <= TRAJ_MAX_ROWS or int(trajectory) % 16:
+        raise ValueError(f"trajectory must be a multiple of 16 from {TRAJ_MIN_ROWS} to {TRAJ_MAX_ROWS} prior rows, got {trajectory}")
+    if traj_seed is None or int(traj_seed) != traj_seed or not 0 <= int(traj_seed) < 1 << 62:
+        raise ValueError(f"traj_seed must be an integer inside [0, 2^62), got {traj_seed}")
+    if c_dim is not None and c_dim != TRAJ_AGE_BINS + TRAJ_GENDER_BINS:
+        raise ValueError(f"trajectory varies the {TRAJ_AGE_BINS} + {TRAJ_GENDER_BINS} one-hot covariates of the decoders: a model "
+                         f"with net_c_dim {c_dim} has no such covariates to vary")
+    return int(trajectory), int(traj_seed)
+
+
+def trajectory_grid() -> np.ndarray:
+    """The covariate grid of the chart, [54, 29] fp32: cell = age_bin * 2 + gender_bin, row `cell` that one-hot pair in
+    prep.one_hot_covariates' layout (27 age columns, then 2 gender columns)."""
+    cell = np.arange(TRAJ_AGE_BINS * TRAJ_GENDER_BINS)
+    return np.concatenate((np.eye(TRAJ_AGE_BINS)[cell // TRAJ_GENDER_BINS], np.eye(TRAJ_GENDER_BINS)[cell % TRAJ_GENDER_BINS]),
+                          axis=1).astype(np.float32)
+
+
+def trajectory_cells(age: np.ndarray, gender: np.ndarray):
+    """(cell, age_bin, gender_bin) of subjects binned among themselves exactly as prep.one_hot_covariates bins them (the
+    evaluation tables re-bin the covariates on the fold's test rows): subject i's covariate row is trajectory_grid()[cell[i]]."""
+    a = prep.qcut_rank_bins(age, TRAJ_AGE_BINS)
+    s = prep.qcut_rank_bins(gender, TRAJ_GENDER_BINS)
+    return a * TRAJ_GENDER_BINS + s, a, s
+
+
+def cell_order(cell: np.ndarray):
+    """(order, inverse, spans): `order` sorts the rows by cell, stably; inverse returns sorted rows to their places
+    (sorted[inverse] is the original order); spans: (cell, first, last + 1) of every occupied cell in the sorted rows."""
+    cell = np.asarray(cell)
+    order = np.argsort(cell, kind="stable")
+    inverse = np.empty_like(order)
+    inverse[order] = np.arange(len(order))
+    sc = cell[order]
+    starts = np.flatnonzero(np.r_[True, sc[1:] != sc[:-1]]) if len(sc) else np.zeros(0, dtype=np.int64)
+    ends = np.r_[starts[1:], len(sc)] if len(sc) else starts
+    return order, inverse, [(int(sc[a]), int(a), int(b)) for a, b in zip(starts, ends)]
+
+
+def trajectory_cell_frame(age: np.ndarray, cell: np.ndarray, age_bin: np.ndarray):
+    """The leading columns of the chart files (io.TRAJECTORY_CHART_COLUMNS), one row per cell: the smallest and largest AGE of
+    the subjects in the cell's age bin (NaN where none) and the subjects in the cell."""
+    import pandas as pd
+    G = TRAJ_AGE_BINS * TRAJ_GENDER_BINS
+    age = np.asarray(age, dtype=np.float64)
+    lo = np.array([age[age_bin == a].min() if (age_bin == a).any() else np.nan for a in range(TRAJ_AGE_BINS)])
+    hi = np.array([age[age_bin == a].max() if (age_bin == a).any() else np.nan for a in range(TRAJ_AGE_BINS)])
+    g = np.arange(G)
+    return pd.DataFrame({"cell": g, "age_bin": g // TRAJ_GENDER_BINS, "gender_bin": g % TRAJ_GENDER_BINS,
+                         "age_lo": lo[g // TRAJ_GENDER_BINS], "age_hi": hi[g // TRAJ_GENDER_BINS],
+                         "n_test": np.bincount(np.asarray(cell), minlength=G)[:G]})
+
+
+def chart_moments(mean: torch.Tensor, sd: torch.Tensor, n_ref: int) -> torch.Tensor:
+    """A chart (mean, sd_pred per cell and ROI, fp64 [G, D]) as a moments table for metrics.normative_z, built by hand as
+    metrics.robust_moments builds one (COHORT_MOMENTS_COLUMNS): mean, sd, var := sd^2, n_ref, min and max NaN, n_nonfinite 0,
+    status -2 where mean or sd is not finite or sd is 0."""
+    nan = torch.full_like(mean, float("nan"))
+    bad = ~torch.isfinite(mean) | ~torch.isfinite(sd) | (sd == 0.0)
+    status = torch.where(bad, torch.full_like(mean, -2.0), torch.zeros_like(mean))
+    return torch.stack([mean, sd, sd * sd, torch.full_like(mean, float(n_ref)), nan, nan, torch.zeros_like(mean), status], dim=-1)
+
+
+def pool_cell_columns(cols: np.ndarray) -> np.ndarray:
+    """The per-cell column summaries of metrics.normative_z ([cells, D, 8], NORMATIVE_COL_COLUMNS) summed over the cells: the
+    six counts add, the two mean z pool with their counts as weights (NaN where the group is empty)."""
+    cols = np.asarray(cols, dtype=np.float64)
+    out = cols[:, :, :6].sum(0)
+    means = []
+    for k, nk in ((6, 4), (7, 5)):
+        n = cols[:, :, nk]
+        tot = n.sum(0)
+        s = np.where(n > 0, np.nan_to_num(cols[:, :, k]) * n, 0.0).sum(0)
+        means.append(np.where(tot > 0, s / np.where(tot > 0, tot, 1.0), np.nan))
+    return np.concatenate([out, np.stack(means, 1)], axis=1)
+
+
+def _trajectory_pass(evs, folds, cohort, modalities, S: int, seed: int, z_thr: float, disease_label, device):
+    """The chart and the trajectory z-scores of every fold's evaluation job: S prior rows per fold (keyed seed + fold, the SAME
+    rows in every cell) decoded under the 54 cells -- all folds of one table height in one JobSet.decode() launch -- then per
+    fold and modality the moments of the reconstructions per cell (metrics.cohort_moments, ddof = 1: what
+    normative_trajectory forms) and the test subjects' scaled x z-scored against the chart row of their own cell through
+    the unchanged metrics.normative_z.  Returns per fold {modality: entry}, everything on the host."""
+    grid = torch.from_numpy(trajectory_grid())
+    G = int(grid.shape[0])
+    for i, (ev, _) in enumerate(evs):
+        z = torch.randn(S, ev.spec.latent, generator=torch.Generator().manual_seed(seed + i))
+        ev.enable_decode_exports(S, G)
+        ev.set_decode_inputs(z, c_grid=grid, x=None)
+    for group in _by_height([ev for ev, _ in evs]):
+        JobSet(group).decode()
+    out = []
+    zero = torch.zeros(S, dtype=torch.int32)
+    for (ev, _), (_, te) in zip(evs, folds):
+        n = len(te)
+        cell, a_bin, _ = trajectory_cells(cohort.age[te], cohort.gender[te])
+        order, inverse, spans = cell_order(cell)
+        frame = trajectory_cell_frame(cohort.age[te], cell, a_bin)
+        grp = roi_groups(cohort.dia[te], disease_label)[order]
+        order_dev = torch.from_numpy(order).to(device)
+        res = {}
+        for i, m in enumerate(modalities):
+            mom = metrics.cohort_moments([ev.dec_loc[i][g] for g in range(G)], [zero] * G, ddof=1, device=device)
+            dp = ev.kmods[i][2]
+            nv = torch.exp(ev.layout.get(ev.params, f"{dp}logvar_out").reshape(-1)).to(torch.float64)
+            mean, var = mom[:, :, 0], mom[:, :, 2]
+            sd = torch.sqrt(var + nv[None, :])
+            t = ev.tables[i]
+            gathered = t.x_f32[:n, :t.D][order_dev].contiguous()          # the scaled x rows, sorted by cell, gathered once
+            sets = [gathered[a:b] for _, a, b in spans]
+            zs, rows, cols = metrics.normative_z(sets, [grp[a:b] for _, a, b in spans], chart_moments(mean, sd, S),
+                                                 ref_of=[c for c, _, _ in spans], thr=z_thr, device=device)
+            inv = torch.from_numpy(inverse).to(device)
+            res[m] = {"mean": mean.cpu().numpy(), "var_latent": var.cpu().numpy(), "noise_var": nv.cpu().numpy(),
+                      "sd_pred": sd.cpu().numpy(), "cell": cell, "cells": frame, "z": torch.cat(zs)[inv].cpu().numpy(),
+                      "rows": rows[inv].cpu().numpy(), "cols": pool_cell_columns(cols.cpu().numpy())}
+        out.append(res)
+    return out
+
+
 def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequence[tuple], modalities: Sequence[str],
                combines, device, out_dirs: Optional[Sequence] = None,
                roi_columns: Optional[Dict[str, Sequence[str]]] = None, roi_effect: bool = False,
@@ -786,7 +916,8 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
                z_thr: float = 1.96, centile: Optional[str] = None, tail: float = 2.5,
                quantiles: Sequence[float] = CENTILE_QUANTILES, centile_loo: bool = False,
                robust: bool = False, given=None, draws: Optional[int] = None,
-               draw_seed: Optional[int] = None) -> List[Dict[str, np.ndarray]]:
+               draw_seed: Optional[int] = None, trajectory: Optional[int] = None,
+               traj_seed: int = 0) -> List[Dict[str, np.ndarray]]:
     """test_fold for ALL folds of a procedure as one launch: jobs[i] is the trained model of fold i, folds[i] its
     (train_rows, test_rows); one evaluation job per fold, each on its own test tables (seed, scaler and covariates per fold
     exactly as test_fold), all in ONE JobSet -- a fold's ~N / K test rows are a single workgroup, K of them in a row leave
@@ -813,8 +944,21 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
     dict gains "predictive": {modality: {"mean", "var", "msq", "z", "rowdev", "rowz2"}}; with out_dirs, the files of
     io.write_predictive_csvs next to the five kinds.  Draw 0 is keyed by the evaluation job's own seed (one draw reproduces
     the pass above), draw s by engine.draw_seeds; draw_seed: fold i's draws are keyed from draw_seed + i instead.  A set
-    holding a model the kernel does not take raises ValueError.  Without `draws` nothing changes."""
+    holding a model the kernel does not take raises ValueError.  Without `draws` nothing changes.
+
+    trajectory (S: 16..4096 prior rows, a multiple of 16): after the passes above the normative chart -- what the model expects
+    at every (age bin, sex bin) cell of the covariates, trajectory_grid() -- and the classical normative deviation against it
+    (_trajectory_pass): per fold S rows z ~ N(0, I) keyed traj_seed + fold are decoded under all 54 cells, all folds of one
+    table height in one JobSet.decode() launch; mean and predictive sd per cell and ROI; every test subject's scaled x
+    z-scored against the chart row of its OWN cell, (x - mean_c) / sd_c, with no encoder pass of the subject, the ROIs beyond
+    +-z_thr counted (metrics.normative_z, unchanged).  Each fold's dict gains "trajectory": {modality: {"mean", "sd_pred",
+    "var_latent" [54, D], "noise_var" [D], "cell" [n], "cells" (the chart files' leading columns), "z" [n, D], "rows" [n, 8],
+    "cols" [D, 8]}}; with out_dirs, normative_trajectory_mean_<m>.csv / normative_trajectory_sd_<m>.csv (one row per cell)
+    and trajectory_z_<m>.csv / trajectory_subject_<m>.csv / trajectory_map_<m>.csv in the layouts of their normative_*
+    counterparts.  Refused for models whose networks take no covariates and for sets the decoder pass does not take
+    (JobSet.decode).  Without `trajectory` nothing changes."""
     draws, draw_seed = check_draws(draws, draw_seed)
+    trajectory, traj_seed = check_trajectory(trajectory, traj_seed, jobs[0].spec.net_c_dim if len(jobs) else None)
     subsets = given_subsets(given, modalities) if given is not None else []
     for name, on in (("centile", centile is not None), ("normative", normative is not None), ("roi_significance", roi_significance),
                      ("roi_regress", roi_regress is not None)):
@@ -827,7 +971,7 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
             raise ValueError(f"{name} must be None or one of {NORMATIVE_KINDS}, got {kind!r}")
     if centile is not None:
         tail, quantiles = metrics._tail_check(tail), metrics._probs_check(quantiles)
-    if normative is not None:
+    if normative is not None or trajectory is not None:
         z_thr = float(z_thr)
         if not (np.isfinite(z_thr) and z_thr > 0.0):
             raise ValueError(f"z_thr must be finite and > 0, got {z_thr}")
@@ -857,6 +1001,8 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
             ev.enable_predictive_exports(draws, seeds=None if draw_seed is None else draw_seeds(draw_seed + i, draws))
         for group in _by_height([ev for ev, _ in evs]):
             JobSet(group).forward_draws()
+    traj = _trajectory_pass(evs, folds, cohort, modalities, trajectory, traj_seed, z_thr, disease_label, device) \
+        if trajectory is not None else None
     queued = []               # (statistic, its device entry per table of t.mats): everything is queued before the one synchronise
     if roi_effect:
         nm_ = len(modalities)
@@ -893,6 +1039,14 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
                     p = res["predictive"][m]
                     io.write_predictive_csvs(Path(d) / m, m, _meta_frame(cohort, te), _roi_columns(roi_columns, m, xs[i].shape[1]),
                                              p["mean"], p["msq"], p["z"])
+    if traj is not None:
+        for res, entry, (ev, xs), (_, te), d in zip(out, traj, evs, folds, dirs):
+            res["trajectory"] = entry
+            if d is not None:
+                for i, m in enumerate(modalities):
+                    e, rois = entry[m], _roi_columns(roi_columns, m, xs[i].shape[1])
+                    io.write_trajectory_chart_csvs(Path(d) / m, m, rois, e["cells"], e["mean"], e["sd_pred"])
+                    io.write_trajectory_csvs(Path(d) / m, m, _meta_frame(cohort, te), rois, e["z"], e["rows"], e["cols"])
     for st, entries in queued:
         entries = [_host(e) for e in entries]
         pooled = {m: entries[t.n_fold + i] for i, m in enumerate(modalities)}
@@ -1326,6 +1480,14 @@ def main_test(argv=None):
                          "over the model's own predictive sd) and predictive_subject_<m>.csv")
     ap.add_argument("--draw-seed", dest="draw_seed", type=int, default=None, metavar="N",
                     help="with --draws: key the draws of fold i from N + i instead of the fold's own seed")
+    ap.add_argument("--trajectory", type=int, default=None, metavar="S",
+                    help="also the normative chart and the deviation against it: S prior draws (16..4096, a multiple of 16) decoded "
+                         "under every (age bin, sex bin) cell in one launch -- per fold normative_trajectory_mean_<m>.csv and "
+                         "normative_trajectory_sd_<m>.csv (the model's mean and predictive sd per cell and ROI) -- and every test "
+                         "subject z-scored against the chart row of its own cell: trajectory_z_<m>.csv, trajectory_subject_<m>.csv "
+                         "(the ROIs beyond +-z-thr) and trajectory_map_<m>.csv; models with covariates only")
+    ap.add_argument("--traj-seed", dest="traj_seed", type=int, default=None, metavar="N",
+                    help="with --trajectory: key the prior rows of fold i from N + i (default 0)")
     _driver_common(ap)
     args = ap.parse_args(argv)
     if args.given:
@@ -1350,7 +1512,12 @@ def main_test(argv=None):
                 (args.roi_adjust and not args.roi_regress, "--roi-adjust needs --roi-regress"),
                 (args.draw_seed is not None and args.draws is None, "--draw-seed needs --draws"),
                 (args.draws is not None and not 1 <= args.draws <= _lib.NM_MAX_DRAWS, f"--draws must be 1 to {_lib.NM_MAX_DRAWS}"),
-                (args.draw_seed is not None and not 0 <= args.draw_seed < 1 << 64, "--draw-seed must lie inside [0, 2^64)"))
+                (args.draw_seed is not None and not 0 <= args.draw_seed < 1 << 64, "--draw-seed must lie inside [0, 2^64)"),
+                (args.traj_seed is not None and args.trajectory is None, "--traj-seed needs --trajectory"),
+                (args.trajectory is not None and (not TRAJ_MIN_ROWS <= args.trajectory <= TRAJ_MAX_ROWS or args.trajectory % 16 != 0),
+                 f"--trajectory must be a multiple of 16 from {TRAJ_MIN_ROWS} to {TRAJ_MAX_ROWS}"),
+                (args.traj_seed is not None and not 0 <= args.traj_seed < 1 << 62, "--traj-seed must lie inside [0, 2^62)"),
+                (args.trajectory is not None and not (np.isfinite(args.z_thr) and args.z_thr > 0), "--z-thr must be finite and > 0"))
     for refused, message in refusals:
         if refused:
             ap.error(message)
@@ -1381,6 +1548,8 @@ def main_test(argv=None):
         if (fold_dir / "train_ids.csv").exists() and (fold_dir / "test_ids.csv").exists():
             tr = prep.rows_of_ids(cohort.iid, pd.read_csv(fold_dir / "train_ids.csv")["IID"].to_numpy())
             te = prep.rows_of_ids(cohort.iid, pd.read_csv(fold_dir / "test_ids.csv")["IID"].to_numpy())
+        if args.trajectory is not None and no_cov:
+            ap.error(f"--trajectory: the networks of {meta['model']} take no covariates, there is no cell to vary")
         fold_jobs.append(load_model(fold_dir, dc.fold_tables_cached(k, mods, tr, with_covariates=not no_cov), device, seed=1000 * k))
         # models whose class fixes the fusion (mmJSD, the DMVAE family: MODEL_KINDS[...][2]) reconstruct with the saved
         # one, whatever the procedure name says (mmJSD.pred_recon ignores its combine argument, cVAE.py:1405-1420)
@@ -1393,7 +1562,8 @@ def main_test(argv=None):
                         normative=args.normative, z_thr=args.z_thr, robust=args.robust, centile=args.centile, tail=args.tail,
                         quantiles=args.quantiles, centile_loo=args.centile_loo)
     results = test_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs, given=args.given,
-                         draws=args.draws, draw_seed=args.draw_seed, **vars(o)) if my else []
+                         draws=args.draws, draw_seed=args.draw_seed, trajectory=args.trajectory, traj_seed=args.traj_seed or 0,
+                         **vars(o)) if my else []
     given_tags = [tag for tag, _ in given_subsets(args.given, mods)] if args.given else []
     # the pooled entries of every statistic that is on: this rank's folds' test subjects as one set (the maps: against their controls)
     pooled_stats = [st for st in ROI_STATS if getattr(o, st.key)] if results else []
@@ -1539,7 +1709,11 @@ ANALYSIS_SCORES = {
     # (--predictive-score msq / z2: likewise a flag of its own; the files of `test --draws S`)
     "predictive_msq": ("reconstruction_error_mc_{m}.csv", lambda d: d["Reconstruction error"], " with --draws S"),
     "predictive_z2": ("predictive_subject_{m}.csv", lambda d: d["Mean z2"], " with --draws S"),
+    # (--trajectory-score zmean / extreme: likewise a flag of its own; the files of `test --trajectory S`)
+    "trajectory_zmean": ("trajectory_subject_{m}.csv", lambda d: d["mean_abs_z"], " with --trajectory S"),
+    "trajectory_extreme": ("trajectory_subject_{m}.csv", lambda d: d["n_hi"] + d["n_lo"], " with --trajectory S"),
 }
+TRAJECTORY_SCORES = ("zmean", "extreme")
 CENTILE_SCORES = ("tails", "depth")
 PREDICTIVE_SCORES = ("msq", "z2")
 
@@ -1792,6 +1966,10 @@ def main_analysis(argv=None):
                          "`Reconstruction error` of reconstruction_error_mc_<m>.csv, the Monte-Carlo mean squared error; z2: `Mean z2` "
                          "of predictive_subject_<m>.csv, the squared residual over the model's own predictive variance; writes "
                          "group_analysis_predictive_<kind>.csv")
+    ap.add_argument("--trajectory-score", dest="trajectory_score", choices=TRAJECTORY_SCORES, default=None,
+                    help="instead of --score: the per-subject score from trajectory_subject_<m>.csv (`test --trajectory S`), averaged "
+                         "over the modalities -- zmean: mean_abs_z against the chart row of the subject's own cell; extreme: n_hi + "
+                         "n_lo, the ROIs beyond the threshold; writes group_analysis_trajectory_<kind>.csv")
     ap.add_argument("--roi", action="store_true",
                     help="instead: which ROIs separate patients from controls -- per fold and modality every ROI's Cliff's delta and "
                          "ROC-AUC on reconstruction_error_roi_<m>.csv, their mean and std over folds to group_analysis_roi_<m>.csv")
@@ -1861,6 +2039,16 @@ def main_analysis(argv=None):
         if args.roi:
             ap.error("--predictive-score is a per-subject score: it does not go with --roi")
         args.score = f"predictive_{args.predictive_score}"
+    if args.trajectory_score:
+        if args.centile_score or args.predictive_score:
+            ap.error("--trajectory-score is a score of its own: it does not go with --centile-score or --predictive-score")
+        if args.score != "reconstruction":
+            ap.error("--trajectory-score is a score of its own: it does not go with --score")
+        if args.roi:
+            ap.error("--trajectory-score is a per-subject score: it does not go with --roi")
+        if args.given:
+            ap.error("--given scores the reconstruction error of modality subsets: it does not go with --trajectory-score")
+        args.score = f"trajectory_{args.trajectory_score}"
     if args.threshold_from == "others" and not args.threshold_rule:
         ap.error("--threshold-from others needs --threshold-rule")
     if (args.threshold_rule or args.roc_grid) and args.roi:

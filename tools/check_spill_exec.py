@@ -78,6 +78,9 @@ LIMITS = {
     "nm_devpass_draws_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 121, "vgpr_count": 128},
     # (the encoder half of the kernel above: the build shows 76 VGPRs and 30 SGPR spills -- plus the same margin of 64)
     "nm_latent_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 94, "vgpr_count": 128},
+    # (the decoder half of the several-expert kernel inside a loop over covariate cells: the build shows 91 VGPRs and 51 SGPR
+    #  spills -- the request's counts and a decoder's export pointers stay alive across its chunks; the ceiling is that count)
+    "nm_decode_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 51, "vgpr_count": 128},
     "nm_rs_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 540},
     "nm_wide_step_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 400},
     # (both instantiations: one workgroup per model / one per decoder, nm_train_steps_head_split)
