@@ -911,7 +911,8 @@ int    nm_normative_centile(const nm_norm_set_t* sets_dev, int n_sets, int D, in
  *   mmJSD.combine_latent(mus, logvars) (combine = NM_COMBINE_POE, in_log = 1)    cVAE.py:1399-1402
  * combine: NM_COMBINE_POE / GPOE / MOE / MOPOE; alpha_raw [M]: the un-normalised alpha_m_list (softmax inside), gPoE only;
  * single_bypass: M == 1 returns the expert itself; in_log: `variances` holds log-variances; out_log: out_var receives
- * log(variance); var_floor > 0: clamp of the result from below.  Status as nm_launch. */
+ * log(variance); var_floor > 0: clamp of the result from below (a NaN stays NaN, as torch.clamp leaves it).  The flags are
+ * independent: out_log and var_floor apply to a bypassed single expert as well.  Status as nm_launch. */
 int nm_combine_latent(const float* mus, const float* variances, int M, int64_t n, int combine, const float* alpha_raw,
                       int single_bypass, int in_log, int out_log, float var_floor, float* out_mu, float* out_var,
                       void* stream);

@@ -5,7 +5,8 @@
 // product_of_experts / mixture_of_experts / mixture_of_product_of_experts (:1118-1126, classes :986-1083), the same on
 // cVAE_multimodal_regression (:2265-2307), mvtCAE's variants (ProductOfExperts2 :1481-1489, clamp :1823,
 // total_correlation :1859-1866) and mmJSD.combine_latent (:1399-1402).  These are the forward-only entry points behind
-// those methods: elementwise over [M][n] fp32 tensors, one element per thread, 16-byte accesses when n % 4 == 0.
+// those methods: elementwise over [M][n] fp32 tensors, one element per thread, scalar 4-byte loads and stores (consecutive
+// lanes on consecutive addresses, so a wave still reads whole cache lines).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
@@ -71,7 +72,8 @@ __global__ void combine_latent_kernel(FuseArgs a) {
   float omu, ovar;
   fuse_one(a, al, mu, vin, omu, ovar);
   if (a.out_log) ovar = logf(ovar);                                    // ProductOfExperts2 returns log(var), cVAE.py:1487
-  if (a.var_floor > 0.f) ovar = fmaxf(ovar, a.var_floor);              // torch.clamp(variance_multimodal, min=1e-6), :1823
+  // torch.clamp(variance_multimodal, min=1e-6), :1823 -- a NaN stays NaN as it does there (fmaxf would hand back the floor)
+  if (a.var_floor > 0.f && ovar < a.var_floor) ovar = a.var_floor;
   a.out_mu[i] = omu;
   a.out_var[i] = ovar;
 }
