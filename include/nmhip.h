@@ -902,6 +902,63 @@ int    nm_normative_centile(const nm_norm_set_t* sets_dev, int n_sets, int D, in
                             double tail, int loo, void* workspace, size_t workspace_bytes,
                             double* rows_out /* [total_rows][8] */, double* cols_out /* [n_sets][D][8] */, void* stream);
 
+/* Model fit per ROI: does the model predict a healthy brain at all, ROI by ROI, and is its predictive variance honest?  The
+ * standard suite of the normative-modelling literature on the hold-out controls; it needs no patient labels.  Set s of the
+ * device array sets_dev holds the observed table x[rows][pitch], the prediction loc[rows][loc_pitch], an optional per-element
+ * predictive variance var[rows][var_pitch] and an optional per-column variance col_var[D] added to it (all fp32, read where they
+ * lie), and group[rows] (int32): 0 = evaluated, anything else left out.  Per (set, column), over the n rows with group 0 in row
+ * order: y = (double)x, f = (double)loc, e = y - f, s2 = (var ? var[r][d] : 0) + (col_var ? col_var[d] : 0), z = e / sqrt(s2).
+ * fp64 from the load on, contraction off, no atomics, every output element written on every call, two runs give the same
+ * bytes, a set's output does not depend on its place in the launch.  A set with rows < 0, rows > max_rows, pitch or loc_pitch
+ * (or var_pitch with var) below D, or a null x, loc or group with rows > 0 is refused: nothing of it is read, its rows are NaN
+ * with n_obs = n_var = 0 and status -2.
+ *
+ * nm_fit_quality: every centred sum in two passes -- the means first, then the sums of the centred values, corrected by the sum
+ *   of the centred values (sum d^2 - (sum d)^2 / n, as nm_cohort_moments) -- so an offset of 1e4 on unit spread keeps its value.
+ *   fit_out [n_sets][D][NM_METRICS_STRIDE] = {rho, p_rho, smse, expv, msll, rmse, n_obs, status}:
+ *     Syy = sum (y - my)^2, Sff = sum (f - mf)^2, Syf = sum (y - my)(f - mf), See = sum (e - me)^2, SSE = sum e^2;
+ *     rho = Syf / sqrt(Syy Sff); p_rho = nm_student_t_two_sided(t, n - 2) at t = rho sqrt((n - 2) / ((1 - rho)(1 + rho))), 0 where
+ *     rho^2 >= 1; smse = SSE / Syy (1 - sklearn's r2_score); expv = 1 - See / Syy (sklearn's explained_variance_score);
+ *     rmse = sqrt(SSE / n); msll = mean[0.5 log(2 pi s2) + e^2 / (2 s2)] - (0.5 log(2 pi v_t) + sum (y - m_t)^2 / (2 v_t n)), where
+ *     (m_t, v_t) = columns 0 and 2 of row ref_of[s] (ref_of NULL: s) of moments [n_moments][D][NM_METRICS_STRIDE] as
+ *     nm_cohort_moments writes it: the trivial model, the train cohort's mean and variance.  moments NULL, or a row outside
+ *     0..n_moments-1 (ref_of[s] = -1 is the way to say so), means no trivial model.
+ *   cal_out [n_sets][D][NM_METRICS_STRIDE] = {bias, mae, mean_z, sd_z, skew_z, kurt_z, coverage, n_var}: bias = mean e,
+ *     mae = sum |e| / n; mean, population sd, skewness m3 / m2^1.5 and excess kurtosis m4 / m2^2 - 3 of z (scipy.stats.skew /
+ *     kurtosis with bias=True; the central moments about mean_z + dl from the sums about mean_z, dl = sum (z - mean_z) / n);
+ *     coverage = the share of the n rows with |z| <= thr (fp64); n_var = the evaluated rows with a finite s2 > 0.
+ *   status -2: both rows NaN except n_obs and n_var -- n < 2, an evaluated y or f not finite, or Syy == 0 (told by min == max
+ *     of y, not by a rounded sum).  Otherwise the sum of 1 (Sff == 0, told by min == max of f: rho and p_rho NaN; also n < 3:
+ *     p_rho NaN), 2 (no var and no col_var, or an evaluated s2 not finite or <= 0: msll and the five z columns NaN) and 4 (no
+ *     trivial model, or its moments status != 0 or v_t <= 0: msll NaN).
+ *   One workgroup per (set, 64 columns), a lane per column, the four waves take every fourth row, partials merged through LDS
+ *   in wave order; the (up to) three tables are read twice: 24 n D bytes of traffic.
+ * nm_fit_rank: rank_out [n_sets][D][NM_METRICS_STRIDE] = {spearman, p_spearman, t_spearman, n_obs, n_tied_y, n_tied_loc, 0,
+ *   status}.  Per evaluated row and for each of y and f, k2 = #{a < v} + #{a <= v} among the evaluated values of the same column
+ *   (twice the mid-rank minus one, nm_normative_centile's quantity; -0 == +0).  In exact int64: A = n sum k2y k2f - sum k2y
+ *   sum k2f, B = n sum k2y^2 - (sum k2y)^2, C likewise for f (at n = NM_METRICS_MAX_N = 8192, k2 <= 2^14 and n sum k2y k2f <=
+ *   2^54 < 2^63).  spearman = (double)A / sqrt((double)B * (double)C), t_spearman = spearman sqrt((double)(n - 2) / ((1 -
+ *   spearman)(1 + spearman))) (+-inf where spearman^2 >= 1, then p = 0), p_spearman = nm_student_t_two_sided(t, n - 2); n_tied_* =
+ *   the rows whose value occurs more than once.  status -2 (NaN except n_obs): n < 2 or an evaluated value not finite; 1: B == 0
+ *   or C == 0 (spearman, t, p NaN), also n < 3 (t, p NaN).  One workgroup per (set, column): both columns as 32-bit
+ *   order-preserving keys sorted in dynamic LDS (2 x 4 bytes x max_rows rounded up to a power of two, 64 KB at the cap), two
+ *   binary searches per row and array; integer sums, so any reduction shape gives the same bytes.
+ * Status, decided before the device is asked anything: NM_E_NULL a required pointer missing (ref_of without moments included);
+ * NM_E_METRICS n_sets < 1, D < 1, max_rows outside 1..NM_METRICS_MAX_N, thr not finite or <= 0, n_moments < 1 with moments,
+ * more than 2^31 - 1 workgroups. */
+typedef struct nm_fit_set {
+  const float*   x;        /* [rows][pitch]     the observed table, read where it lies            */
+  const float*   loc;      /* [rows][loc_pitch] the prediction (out_loc, pred_mean, a chart row...) */
+  const float*   var;      /* [rows][var_pitch] per-element predictive variance, or NULL          */
+  const float*   col_var;  /* [D] per-column variance added to var (exp(logvar_out)), or NULL     */
+  const int32_t* group;    /* [rows]: 0 = evaluated (the hold-out controls), anything else left out */
+  int32_t rows, pitch, loc_pitch, var_pitch;
+} nm_fit_set_t;
+int nm_fit_quality(const nm_fit_set_t* sets_dev, int n_sets, int D, int max_rows, const double* moments, int n_moments,
+                   const int32_t* ref_of, double thr, double* fit_out, double* cal_out /* both [n_sets][D][NM_METRICS_STRIDE] */,
+                   void* stream);
+int nm_fit_rank(const nm_fit_set_t* sets_dev, int n_sets, int D, int max_rows, double* rank_out /* [n_sets][D][8] */, void* stream);
+
 /* The expert-fusion operators the reference exposes as public methods, as forward-only launches (elementwise over
  * [M][n] fp32 device tensors; csrc/nm_fusion.hip):
  *   cVAE_multimodal.combine_latent(mus, variances, combine)                      cVAE.py:1144-1164   (also :2292-2307)

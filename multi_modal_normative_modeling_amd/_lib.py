@@ -215,6 +215,12 @@ class NmNormSet(C.Structure):
                 ("row_off", C.c_int32), ("pad", C.c_int32)]
 
 
+class NmFitSet(C.Structure):
+    """nm_fit_set_t: one entry of the pointer table of nm_fit_quality and nm_fit_rank."""
+    _fields_ = [("x", C.c_void_p), ("loc", C.c_void_p), ("var", C.c_void_p), ("col_var", C.c_void_p), ("group", C.c_void_p),
+                ("rows", C.c_int32), ("pitch", C.c_int32), ("loc_pitch", C.c_int32), ("var_pitch", C.c_int32)]
+
+
 class NmOpRule(C.Structure):
     """nm_op_rule_t: one row of nm_operating_points' rule table (host memory)."""
     _fields_ = [("kind", C.c_int32), ("n", C.c_int32), ("a", C.c_double), ("b", C.c_double),
@@ -315,6 +321,8 @@ def load():
     lib.nm_normative_centile_workspace.restype = C.c_size_t
     lib.nm_normative_centile_workspace.argtypes = [i32, i32]
     lib.nm_normative_centile.argtypes = [vp, i32, i32, i32, i32, vp, C.c_double, i32, vp, C.c_size_t, vp, vp, vp]
+    lib.nm_fit_quality.argtypes = [vp, i32, i32, i32, vp, i32, vp, C.c_double, vp, vp, vp]
+    lib.nm_fit_rank.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.nm_student_t_two_sided.restype = C.c_double
     lib.nm_student_t_two_sided.argtypes = [C.c_double, C.c_double]
     lib.nm_adam_step.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, i64, vp]
@@ -354,6 +362,7 @@ EXPORTED_SYMBOLS = [
     "nm_devpass_subsets", "nm_devpass_subsets_ok",
     "nm_devpass_draws", "nm_devpass_draws_ok",
     "nm_decode_pass", "nm_decode_pass_ok",
+    "nm_fit_quality", "nm_fit_rank",
 ]
 
 

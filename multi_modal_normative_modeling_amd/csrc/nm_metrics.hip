@@ -28,6 +28,10 @@
 //   nm_cohort_quantiles, nm_normative_centile
 //                         ROI tables -> a reference cohort's quantiles, median and MAD per ROI; every subject's percentile rank
 //                         in it, the per-subject and per-ROI counts in the tails (nm_centile.inc, included at the end of this file)
+//   nm_fit_quality, nm_fit_rank
+//                         observed and predicted ROI tables -> per ROI the model's fit on the hold-out controls: Pearson and
+//                         Spearman rho, SMSE, EXPV, MSLL, RMSE and the shape of the z distribution (nm_fit.inc, included at the
+//                         end of this file)
 //
 // One workgroup per score set (a (fold, procedure) cell); sets are segments of one concatenated array.  The
 // whole set lives in LDS: order-preserving 64-bit keys (score, label) are bitonic-sorted descending, label
@@ -1624,3 +1628,4 @@ int nm_auc_bootstrap(const float* scores, const int32_t* labels, const int32_t* 
 #include "nm_normative.inc"
 #include "nm_curve.inc"
 #include "nm_centile.inc"
+#include "nm_fit.inc"

@@ -177,6 +177,29 @@ def write_roi_regress_csv(out_dir, dataset_name: str, roi_columns: Sequence[str]
     return write_roi_table_csv("roi_regress", out_dir, dataset_name, roi_columns, table)
 
 
+def fit_csv_columns(rank: bool = False) -> list:
+    """The columns of fit_quality_{name}.csv after "ROI": metrics.FIT_COLUMNS, metrics.CALIBRATION_COLUMNS and, with rank,
+    metrics.FIT_RANK_COLUMNS -- a name the rank table shares with the fit table (n_obs, status) carries the suffix _rank."""
+    from . import metrics
+    cols = list(metrics.FIT_COLUMNS) + list(metrics.CALIBRATION_COLUMNS)
+    if rank:
+        cols += [c + "_rank" if c in cols else c for c in metrics.FIT_RANK_COLUMNS]
+    return cols
+
+
+def write_fit_csv(out_dir, dataset_name: str, roi_columns: Sequence[str], fit: np.ndarray, cal: np.ndarray,
+                  rank: Optional[np.ndarray] = None) -> Path:
+    """fit_quality_{name}.csv: one row per ROI -- its column name, then fit_csv_columns(): the model's fit on the hold-out
+    controls (rho, p_rho, smse, expv, msll, rmse, n_obs, status), the calibration of its z (bias, mae, mean_z, sd_z, skew_z,
+    kurt_z, coverage, n_var) and, where the rank table was asked for, Spearman's rho with its p, t, n and tie counts."""
+    tabs = [np.asarray(v, dtype=np.float64) for v in (fit, cal) + (() if rank is None else (rank,))]
+    for v in tabs:
+        if v.shape != (len(roi_columns), 8):
+            raise ValueError(f"[{len(roi_columns)}, 8] tables are needed, got {v.shape}")
+    return write_roi_table_csv("fit_quality", out_dir, dataset_name, roi_columns, np.concatenate(tabs, axis=1),
+                               columns=fit_csv_columns(rank is not None))
+
+
 def write_normative_csvs(out_dir, dataset_name: str, covariates: pd.DataFrame, roi_columns: Sequence[str], z: np.ndarray,
                          rows: np.ndarray, cols: np.ndarray) -> Dict[str, Path]:
     """The normative z-map of one set of subjects (metrics.normative_z), with the metadata columns of write_test_csvs:

@@ -19,6 +19,8 @@ selected on one score set and scored on another, with PR-AUC, partial AUC and th
 `cohort_moments` / `normative_z` = the normative z-map: per ROI column the reference cohort's mean and sd, every subject's
 z-score against them with the per-subject extreme-deviation counts and the per-ROI extreme-deviation map; `cohort_cov` /
 `mahalanobis` = the full-covariance counterpart in latent space (the sigma-normalised extra of SURVEY.md, never the parity output).
+`fit_quality` = the model's fit per ROI on the hold-out controls, with no patient label: Pearson and Spearman rho, SMSE, EXPV,
+MSLL against the trivial train-moments model, RMSE, and the shape of the z distribution (bias, sd, skewness, kurtosis, coverage).
 `cohort_quantiles` / `normative_centile` = the normative centiles: per ROI column the reference cohort's quantiles, median and MAD,
 and every subject's percentile rank in that cohort (with an exact leave-one-out form), the per-subject counts in the tails and the
 per-ROI extreme-centile map; `robust_moments` turns median and MAD into a moments table for `normative_z`.
@@ -145,6 +147,10 @@ def _reg_table(mats, targets, covs, incs, n_cov: int):
 
 def _norm_table(mats, groups=None, subs=None, zs=None):
     return _set_table(_lib.NmNormSet, mats, group=groups, sub=subs, sub_pitch=subs, z=zs, z_pitch=zs)
+
+
+def _fit_table(mats, locs, groups, var=None, col_var=None):
+    return _set_table(_lib.NmFitSet, mats, loc=locs, loc_pitch=locs, var=var, var_pitch=var, col_var=col_var, group=groups)
 
 
 def _table_check(mats: Sequence[torch.Tensor], per_row: Optional[Sequence] = None) -> int:
@@ -600,8 +606,9 @@ def _norm_check(mats, groups, sub) -> int:
     return D
 
 
-def _ref_check(ref_of, n_sets, n_ref):
-    """ref_of as a list of ints inside 0..n_ref-1 (None: set k takes row k, so n_sets <= n_ref)."""
+def _ref_check(ref_of, n_sets, n_ref, lowest: int = 0):
+    """ref_of as a list of ints inside lowest..n_ref-1 (None: set k takes row k, so n_sets <= n_ref); lowest = -1 where an
+    entry point reads -1 as "no reference"."""
     if ref_of is None:
         if n_sets > n_ref:
             raise ValueError(f"{n_sets} sets but {n_ref} reference entries: ref_of is needed")
@@ -609,8 +616,8 @@ def _ref_check(ref_of, n_sets, n_ref):
     ref = [int(v) for v in np.asarray(ref_of).reshape(-1)]
     if len(ref) != n_sets:
         raise ValueError("ref_of must have one entry per set")
-    if any(not 0 <= v < n_ref for v in ref):
-        raise ValueError(f"ref_of entries must lie in 0..{n_ref - 1}")
+    if any(not lowest <= v < n_ref for v in ref):
+        raise ValueError(f"ref_of entries must lie in {lowest}..{n_ref - 1}")
     return ref
 
 
@@ -874,3 +881,84 @@ def robust_moments(stats: torch.Tensor, scale: float = 1.4826) -> torch.Tensor:
     bad = (stats[..., 7] == -2.0) | (mad == 0.0)
     status = torch.where(bad, torch.full_like(med, -2.0), torch.zeros_like(med))
     return torch.stack([med, sd, sd * sd, stats[..., 5], nan, nan, stats[..., 6], status], dim=-1)
+
+
+FIT_COLUMNS = ("rho", "p_rho", "smse", "expv", "msll", "rmse", "n_obs", "status")
+CALIBRATION_COLUMNS = ("bias", "mae", "mean_z", "sd_z", "skew_z", "kurt_z", "coverage", "n_var")
+FIT_RANK_COLUMNS = ("spearman", "p_spearman", "t_spearman", "n_obs", "n_tied_y", "n_tied_loc", "reserved", "status")
+
+
+def _fit_check(mats, locs, groups, var, col_var, moments, ref_of, thr):
+    """nm_fit_quality's argument checks on the host (no device is looked for): D, thr, ref_of as a list or None."""
+    thr = float(thr)
+    if not (np.isfinite(thr) and thr > 0.0):
+        raise ValueError(f"thr must be finite and > 0, got {thr}")
+    D = _table_check(mats, groups)
+    for name, seq in (("locs", locs), ("var", var)):
+        if seq is None:
+            if name == "locs":
+                raise ValueError("locs is needed: one prediction table per set")
+            continue
+        if len(seq) != len(mats):
+            raise ValueError(f"{name} must have one entry per set")
+        for k, (m, b) in enumerate(zip(mats, seq)):
+            if b is None and name == "var":                          # (a set without a per-element variance)
+                continue
+            if not isinstance(b, torch.Tensor) or b.dtype != torch.float32 or b.shape != m.shape:
+                raise ValueError(f"set {k}: {name} must be a float32 tensor of the table's shape {tuple(m.shape)}")
+            if b.shape[0] > 0 and b.stride(1) != 1:
+                raise ValueError(f"set {k}: the columns of {name} must be contiguous")
+            if b.shape[0] > 1 and b.stride(0) < D:
+                raise ValueError(f"set {k}: row stride {b.stride(0)} of {name} below the {D} columns")
+            if b.device != m.device:
+                raise ValueError(f"set {k}: {name} is on {b.device}, the table on {m.device}")
+    if col_var is not None:
+        if len(col_var) != len(mats):
+            raise ValueError("col_var must have one entry per set")
+        for k, c in enumerate(col_var):
+            if c is not None and int(torch.as_tensor(c).numel()) != D:
+                raise ValueError(f"set {k}: col_var must hold one variance per column ({D})")
+    ref = None
+    if moments is None:
+        if ref_of is not None:
+            raise ValueError("ref_of needs moments")
+    else:
+        if not isinstance(moments, torch.Tensor) or moments.dtype != torch.float64 or moments.dim() != 3 or \
+                int(moments.shape[0]) < 1 or tuple(moments.shape[1:]) != (D, _lib.NM_METRICS_STRIDE):
+            raise ValueError(f"moments must be a float64 [n >= 1, {D}, {_lib.NM_METRICS_STRIDE}] tensor as cohort_moments returns it")
+        ref = _ref_check(ref_of, len(mats), int(moments.shape[0]), lowest=-1)
+    return D, thr, ref
+
+
+def fit_quality(mats: Sequence[torch.Tensor], locs: Sequence[torch.Tensor], groups: Sequence, var: Optional[Sequence[torch.Tensor]] = None,
+                col_var: Optional[Sequence] = None, moments: Optional[torch.Tensor] = None, ref_of=None, thr: float = 1.96,
+                rank: bool = False, device=None):
+    """(fit, cal), or (fit, cal, rank) with rank=True: each [n_sets, D, 8] fp64 on the device, per (set, column) over the rows
+    whose group word is 0 (the hold-out controls) -- does the model predict the column, and is its predictive variance honest?
+    fit = rho, p_rho, smse, expv, msll, rmse, n_obs, status (FIT_COLUMNS); cal = bias, mae, mean_z, sd_z, skew_z, kurt_z,
+    coverage, n_var (CALIBRATION_COLUMNS); rank = spearman, p_spearman, t_spearman, n_obs, n_tied_y, n_tied_loc, 0, status
+    (FIT_RANK_COLUMNS); include/nmhip.h has the definitions.  mats[k]: the observed [n_k, D] fp32 device table, read where it
+    lies, as for roi_effect; locs[k]: the prediction, the same shape; var[k] (optional, the same shape, or None for a set): the
+    per-element predictive variance; col_var[k] (optional, [D], or None for a set): a per-column variance added to it (exp(logvar_out));
+    z = (x - loc) / sqrt(var + col_var).  moments (optional, [n, D, 8] as cohort_moments returns it, formed with ddof=0 on the
+    train cohort) is the trivial model of msll, set k against row ref_of[k] (default k; -1: none).  status -2: fewer than two
+    evaluated rows, a non-finite value among them, a constant column; else bits 1 (a constant prediction, or n < 3), 2 (no
+    usable variance: msll and the z columns NaN), 4 (no trivial model: msll NaN).  One launch for all sets, one more for rank."""
+    D, thr, ref = _fit_check(mats, locs, groups, var, col_var, moments, ref_of, thr)
+    dev = _table_device(mats, device)
+    grp = _row_words(groups, dev, torch.int32)
+    cvs = _row_words(col_var, dev, torch.float32) if col_var is not None else None
+    sets = _to_dev(_fit_table(mats, locs, grp, var, cvs), dev)
+    mom = moments.to(dev).contiguous() if moments is not None else None
+    rf = torch.tensor(ref, dtype=torch.int32, device=dev) if ref is not None else None
+    n_sets, max_rows, lib = len(mats), _max_rows(mats), _lib.load()
+    fit = torch.empty(n_sets, D, _lib.NM_METRICS_STRIDE, dtype=torch.float64, device=dev)
+    cal = torch.empty_like(fit)
+    _lib.check(lib.nm_fit_quality(sets.data_ptr(), n_sets, D, max_rows, mom.data_ptr() if mom is not None else None,
+                                  int(mom.shape[0]) if mom is not None else 0, rf.data_ptr() if rf is not None else None, thr,
+                                  fit.data_ptr(), cal.data_ptr(), _stream_ptr(dev)), "nm_fit_quality")
+    if not rank:
+        return fit, cal
+    rk = torch.empty_like(fit)
+    _lib.check(lib.nm_fit_rank(sets.data_ptr(), n_sets, D, max_rows, rk.data_ptr(), _stream_ptr(dev)), "nm_fit_rank")
+    return fit, cal, rk

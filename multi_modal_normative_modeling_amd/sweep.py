@@ -12,6 +12,7 @@ from __future__ import annotations
 import argparse
 import os
 import time
+import warnings
 from dataclasses import dataclass
 from pathlib import Path
 from types import SimpleNamespace
@@ -548,6 +549,8 @@ def parse_regress_spec(spec: str):
 
 
 NORMATIVE_KINDS = ("squared", "signed")
+FIT_SUMMARY = ("rho", "expv", "smse", "msll", "sd_z", "coverage")     # what `test` prints of --fit: the median over the ROIs
+FIT_ANALYSIS = ("rho", "expv", "smse", "msll", "coverage")            # what `analysis --fit` averages over the folds
 CENTILE_QUANTILES = (0.05, 0.25, 0.5, 0.75, 0.95)
 
 
@@ -572,7 +575,8 @@ def _by_height(jobs: Sequence[Job]) -> List[List[Job]]:
 # on the device: the all-folds tables of the test script, :157-178; at most NM_METRICS_MAX_N subjects in all); t.grp, their
 # roi_groups words (cohort.dia; disease_label picks one diagnosis as the patients); t.tables(export), the same list of another
 # export; t.rows_of, the cohort rows of every fold and then of all of them, t.per_table(seq), a value per entry of t.rows_of
-# repeated for its tables; t.n_fold, where the pooled tables begin; t.cohort, t.device.
+# repeated for its tables; t.n_fold, where the pooled tables begin; t.cohort, t.device; t.evs, the evaluation jobs with their host
+# tables, t.jobs, the trained jobs on their train tables, t.draws, whether the posterior-predictive pass has run (the fit statistic).
 # ---------------------------------------------------------------------------------------------------------------
 class RoiStat(NamedTuple):
     key: str                # of a fold's result dict: {modality: entry}; key + "_pooled" holds the pooled entries
@@ -589,7 +593,9 @@ def _host(entry):
 
 
 def _n_roi(entry) -> int:
-    return (entry["cols"] if isinstance(entry, dict) else entry).shape[0]
+    if isinstance(entry, dict):
+        entry = entry["cols"] if "cols" in entry else entry["fit"]
+    return entry.shape[0]
 
 
 def _folds_then_pooled(call, t) -> list:
@@ -685,6 +691,59 @@ def _queue_centile(t, o):
     return _scored(t, o.centile, one_width)
 
 
+def _queue_fit(t, o):
+    """fit: the model's fit per ROI on the fold's healthy test subjects (group 0 of roi_groups) -- the question that comes before
+    every patient contrast, and the only comparison of procedures that needs no patient label.  Per fold and modality x = the
+    scaled table, loc = out_loc and the per-column variance exp(logvar_out) (fp32); after a posterior-predictive pass (draws)
+    loc = pred_mean and the per-element variance pred_var on top of the same per-column one.  The trivial model of msll is the
+    mean and variance (ddof 0) of the fold's scaled TRAIN table -- the tables of the trained jobs, one metrics.cohort_moments
+    launch per width.  The pooled sets hold rows of several scalers and several models: they get no trivial model (msll NaN,
+    status bit 4), and their variance travels per element, pred_var + exp(logvar_out) of the row's own fold formed in fp32.
+    One metrics.fit_quality call per table width over all folds, modalities and pooled sets; fit_rank adds Spearman's rho.
+    Entries {"fit" [D, 8] (metrics.FIT_COLUMNS), "cal" [D, 8] (metrics.CALIBRATION_COLUMNS), "rank" [D, 8] or None
+    (metrics.FIT_RANK_COLUMNS), and the fp32 tables that were read: "x", "loc", "var" or None, "col_var" or None}; with
+    out_dirs, fit_quality_<m>.csv."""
+    nm_ = len(t.mats) - t.n_fold
+    n_folds = t.n_fold // nm_
+    xs = t.tables(lambda ev, i: ev.tables[i].x_f32[:, :ev.tables[i].D])
+    locs = t.tables((lambda ev, i: ev.pred_mean[i]) if t.draws else (lambda ev, i: ev.out_loc[i]))
+    pv = t.tables(lambda ev, i: ev.pred_var[i]) if t.draws else None
+    cvs = [torch.exp(ev.layout.get(ev.params, f"{ev.kmods[i][2]}logvar_out").reshape(-1).to(torch.float32))
+           for ev, _ in t.evs for i in range(nm_)]
+    var = list(pv[:t.n_fold]) if pv is not None else [None] * t.n_fold
+    for i in range(nm_):
+        parts = [cvs[f * nm_ + i][None, :].expand(len(t.rows_of[f]), -1) for f in range(n_folds)]
+        if pv is not None:
+            parts = [pv[f * nm_ + i] + p for f, p in enumerate(parts)]
+        var.append(torch.cat(parts))
+    train = [j.tables[i].x_f32[:j.tables[i].N, :j.tables[i].D] for j in t.jobs for i in range(nm_)]
+    mom = _per_width(lambda ms, gs: metrics.cohort_moments(ms, gs, ddof=0, device=t.device), train,
+                     [torch.zeros(int(m.shape[0]), dtype=torch.int32) for m in train])
+
+    def one_width(ms, ls, gs, vs, cs, moms):
+        have = [m for m in moms if m is not None]
+        ref, k = [], 0
+        for m in moms:
+            ref.append(-1 if m is None else k)
+            k += m is not None
+        res = metrics.fit_quality(ms, ls, gs, var=vs, col_var=cs, moments=torch.stack(have), ref_of=ref, thr=o.z_thr,
+                                  rank=bool(o.fit_rank), device=t.device)
+        return [{"fit": res[0][a], "cal": res[1][a], "rank": res[2][a] if o.fit_rank else None, "x": ms[a], "loc": ls[a],
+                 "var": vs[a], "col_var": cs[a]} for a in range(len(ms))]
+    return _per_width(one_width, xs, locs, t.grp, var, cvs + [None] * nm_, mom + [None] * nm_)
+
+
+def _fit_medians(e) -> str:
+    tabs = {**dict(zip(metrics.FIT_COLUMNS, e["fit"].T)), **dict(zip(metrics.CALIBRATION_COLUMNS, e["cal"].T))}
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)                # (a column that is NaN throughout: its median is NaN)
+        return ", ".join(f"{k} {float(np.nanmedian(tabs[k])):.4f}" for k in FIT_SUMMARY)
+
+
+def _fit_summary(e, g, o) -> str:
+    return f"pooled model fit on the controls, median over ROIs: {_fit_medians(e)}"
+
+
 def _effect_summary(tab, g, o) -> str:
     top = int(np.nanargmax(np.abs(tab[:, 0]))) if np.isfinite(tab[:, 0]).any() else 0
     return f"pooled ROI effect, largest |delta| {tab[top, 0]:+.4f} (AUC {tab[top, 1]:.4f}) at ROI {top}"
@@ -726,7 +785,8 @@ ROI_STATS = (
             lambda d, m, rois, meta, e, o: io.write_normative_csvs(d, m, meta, rois, e["z"], e["rows"], e["cols"]), _normative_summary),
     RoiStat("centile", _queue_centile,
             lambda d, m, rois, meta, e, o: io.write_centile_csvs(d, m, meta, rois, e["pct"], e["rows"], e["cols"], o.quantiles, e["q"],
-                                                                 e["stats"]), _centile_summary))
+                                                                 e["stats"]), _centile_summary),
+    RoiStat("fit", _queue_fit, lambda d, m, rois, meta, e, o: io.write_fit_csv(d, m, rois, e["fit"], e["cal"], e["rank"]), _fit_summary))
 
 
 GIVEN_KINDS = ("all", "loo", "single")
@@ -917,7 +977,7 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
                quantiles: Sequence[float] = CENTILE_QUANTILES, centile_loo: bool = False,
                robust: bool = False, given=None, draws: Optional[int] = None,
                draw_seed: Optional[int] = None, trajectory: Optional[int] = None,
-               traj_seed: int = 0) -> List[Dict[str, np.ndarray]]:
+               traj_seed: int = 0, fit: bool = False, fit_rank: bool = False) -> List[Dict[str, np.ndarray]]:
     """test_fold for ALL folds of a procedure as one launch: jobs[i] is the trained model of fold i, folds[i] its
     (train_rows, test_rows); one evaluation job per fold, each on its own test tables (seed, scaler and covariates per fold
     exactly as test_fold), all in ONE JobSet -- a fold's ~N / K test rows are a single workgroup, K of them in a row leave
@@ -956,22 +1016,28 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
     "cols" [D, 8]}}; with out_dirs, normative_trajectory_mean_<m>.csv / normative_trajectory_sd_<m>.csv (one row per cell)
     and trajectory_z_<m>.csv / trajectory_subject_<m>.csv / trajectory_map_<m>.csv in the layouts of their normative_*
     counterparts.  Refused for models whose networks take no covariates and for sets the decoder pass does not take
-    (JobSet.decode).  Without `trajectory` nothing changes."""
+    (JobSet.decode).  Without `trajectory` nothing changes.
+
+    fit (needs roi_effect; fit_rank needs fit): the model's fit per ROI on the healthy test subjects (_queue_fit): rho, SMSE,
+    EXPV, MSLL against the train cohort's mean and variance, RMSE and the calibration of z -- with draws on the predictive
+    mean and variance -- and with fit_rank Spearman's rho; coverage counts |z| <= z_thr.  Without `fit` nothing changes."""
     draws, draw_seed = check_draws(draws, draw_seed)
     trajectory, traj_seed = check_trajectory(trajectory, traj_seed, jobs[0].spec.net_c_dim if len(jobs) else None)
     subsets = given_subsets(given, modalities) if given is not None else []
     for name, on in (("centile", centile is not None), ("normative", normative is not None), ("roi_significance", roi_significance),
-                     ("roi_regress", roi_regress is not None)):
+                     ("roi_regress", roi_regress is not None), ("fit", fit)):
         if on and not roi_effect:
             raise ValueError(f"{name} needs roi_effect=True (the evaluation jobs export the ROI-wise squared errors for it)")
     if robust and normative is None:
         raise ValueError("robust needs normative (it replaces the moments the z-map is scored against)")
+    if fit_rank and not fit:
+        raise ValueError("fit_rank needs fit=True (it adds Spearman's rho to the fit tables)")
     for name, kind in (("centile", centile), ("normative", normative)):
         if kind is not None and kind not in NORMATIVE_KINDS:
             raise ValueError(f"{name} must be None or one of {NORMATIVE_KINDS}, got {kind!r}")
     if centile is not None:
         tail, quantiles = metrics._tail_check(tail), metrics._probs_check(quantiles)
-    if normative is not None or trajectory is not None:
+    if normative is not None or trajectory is not None or fit:
         z_thr = float(z_thr)
         if not (np.isfinite(z_thr) and z_thr > 0.0):
             raise ValueError(f"z_thr must be finite and > 0, got {z_thr}")
@@ -984,7 +1050,8 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
         raise ValueError(f"{len(jobs)} models for {len(folds)} folds")
     o = SimpleNamespace(roi_effect=roi_effect, disease_label=disease_label, roi_significance=roi_significance, roi_perm=roi_perm,
                         roi_seed=roi_seed, roi_regress=roi_regress, roi_adjust=roi_adjust, normative=normative, z_thr=z_thr,
-                        robust=robust, centile=centile, tail=tail, quantiles=quantiles, centile_loo=centile_loo)
+                        robust=robust, centile=centile, tail=tail, quantiles=quantiles, centile_loo=centile_loo, fit=fit,
+                        fit_rank=fit_rank)
     combs = [combines] * len(jobs) if isinstance(combines, str) else list(combines)
     dirs = [None] * len(jobs) if out_dirs is None else list(out_dirs)
     evs = [_fold_eval_job(j, cohort, tr, te, modalities, cb, device, sqerr=roi_effect)
@@ -1011,7 +1078,8 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
         def tables(export):
             tabs = [export(ev, i)[:len(te)] for (ev, _), te in zip(evs, tests) for i in range(nm_)]
             return tabs + [torch.cat(tabs[i::nm_]) for i in range(nm_)]
-        t = SimpleNamespace(cohort=cohort, device=device, tables=tables, rows_of=tests + [np.concatenate(tests)],
+        t = SimpleNamespace(cohort=cohort, device=device, tables=tables, rows_of=tests + [np.concatenate(tests)], evs=evs, jobs=jobs,
+                            draws=draws is not None,
                             n_fold=len(folds) * nm_, per_table=lambda seq: [v for v in seq for _ in range(nm_)])
         t.grp = t.per_table([roi_groups(cohort.dia[r], disease_label) for r in t.rows_of])
         t.mats = tables(lambda ev, i: ev.out_sqerr[i])
@@ -1488,6 +1556,12 @@ def main_test(argv=None):
                          "(the ROIs beyond +-z-thr) and trajectory_map_<m>.csv; models with covariates only")
     ap.add_argument("--traj-seed", dest="traj_seed", type=int, default=None, metavar="N",
                     help="with --trajectory: key the prior rows of fold i from N + i (default 0)")
+    ap.add_argument("--fit", action="store_true",
+                    help="with --roi-effect: does the model predict a healthy brain at all -- per ROI on the fold's healthy test subjects "
+                         "rho, SMSE, EXPV, MSLL against the train cohort's mean and variance, RMSE, and the calibration of z (bias, sd, "
+                         "skewness, kurtosis, coverage of +-z-thr); with --draws on the predictive mean and variance: per fold and "
+                         "pooled fit_quality_<m>.csv.  No patient label enters")
+    ap.add_argument("--fit-rank", dest="fit_rank", action="store_true", help="with --fit: also Spearman's rho per ROI, with its t and p")
     _driver_common(ap)
     args = ap.parse_args(argv)
     if args.given:
@@ -1517,7 +1591,10 @@ def main_test(argv=None):
                 (args.trajectory is not None and (not TRAJ_MIN_ROWS <= args.trajectory <= TRAJ_MAX_ROWS or args.trajectory % 16 != 0),
                  f"--trajectory must be a multiple of 16 from {TRAJ_MIN_ROWS} to {TRAJ_MAX_ROWS}"),
                 (args.traj_seed is not None and not 0 <= args.traj_seed < 1 << 62, "--traj-seed must lie inside [0, 2^62)"),
-                (args.trajectory is not None and not (np.isfinite(args.z_thr) and args.z_thr > 0), "--z-thr must be finite and > 0"))
+                (args.trajectory is not None and not (np.isfinite(args.z_thr) and args.z_thr > 0), "--z-thr must be finite and > 0"),
+                (args.fit and not args.roi_effect, "--fit needs --roi-effect"),
+                (args.fit_rank and not args.fit, "--fit-rank needs --fit"),
+                (args.fit and not (np.isfinite(args.z_thr) and args.z_thr > 0), "--z-thr must be finite and > 0"))
     for refused, message in refusals:
         if refused:
             ap.error(message)
@@ -1560,7 +1637,7 @@ def main_test(argv=None):
     o = SimpleNamespace(roi_effect=args.roi_effect, disease_label=args.disease_label, roi_significance=args.roi_significance,
                         roi_perm=args.roi_perm, roi_seed=args.roi_seed, roi_regress=roi_regress, roi_adjust=args.roi_adjust,
                         normative=args.normative, z_thr=args.z_thr, robust=args.robust, centile=args.centile, tail=args.tail,
-                        quantiles=args.quantiles, centile_loo=args.centile_loo)
+                        quantiles=args.quantiles, centile_loo=args.centile_loo, fit=args.fit, fit_rank=args.fit_rank)
     results = test_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs, given=args.given,
                          draws=args.draws, draw_seed=args.draw_seed, trajectory=args.trajectory, traj_seed=args.traj_seed or 0,
                          **vars(o)) if my else []
@@ -1662,6 +1739,31 @@ def _analysis_roi(root: Path, mods: Sequence[str], n_splits: int, hc: int, proce
         for r in order:
             print(f"[analysis]   {df['ROI'][r]}: delta {df['cliff_delta_mean'][r]:+.4f} +- {df['cliff_delta_std'][r]:.4f}  "
                   f"AUC {df['auc_mean'][r]:.4f} +- {df['auc_std'][r]:.4f}", flush=True)
+    return out
+
+
+def _analysis_fit(root: Path, mods: Sequence[str], n_splits: int, procedure: str) -> Dict[str, np.ndarray]:
+    """`analysis --fit`: the per-fold fit_quality_<m>.csv files (`test --roi-effect --fit`), and per modality
+    group_analysis_fit_<m>.csv: per ROI the mean and population sd over folds of FIT_ANALYSIS (rho, expv, smse, msll,
+    coverage), in fp64 on the host (K small tables).  Prints one line per procedure, the median over the ROIs of the fold
+    means -- the comparison of procedures that needs no patient label.  Returns {modality: [folds, D, 5]}."""
+    import pandas as pd
+    out, line = {}, []
+    for m in mods:
+        paths = [root / f"{k:03d}" / m / f"fit_quality_{m}.csv" for k in range(n_splits)]
+        frames = [pd.read_csv(p, float_precision="round_trip") for p in paths if p.exists()]     # (the fp64 values as written)
+        if not frames:
+            raise FileNotFoundError(f"no fit_quality_{m}.csv under {root}: run `test --roi-effect --fit` first")
+        tab = np.stack([f[list(FIT_ANALYSIS)].to_numpy(dtype=np.float64) for f in frames])
+        df = pd.DataFrame({"ROI": frames[0]["ROI"]})
+        for j, k in enumerate(FIT_ANALYSIS):
+            df[f"{k}_mean"], df[f"{k}_sd"] = tab[:, :, j].mean(0), tab[:, :, j].std(0)
+        df.to_csv(root / f"group_analysis_fit_{m}.csv", index=False)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)
+            line.append(f"{m} ({len(frames)} folds): " + ", ".join(f"{k} {float(np.nanmedian(df[f'{k}_mean'])):.4f}" for k in FIT_ANALYSIS))
+        out[m] = tab
+    print(f"[analysis] {procedure} model fit on the controls, median over ROIs of the fold means: " + "; ".join(line), flush=True)
     return out
 
 
@@ -2014,7 +2116,15 @@ def main_analysis(argv=None):
                          "reconstruction_error_<m>_given_<SET>.csv (`test --given`), to group_analysis_given_<P>.csv; with "
                          "--bootstrap B also every subset's pooled interval and its paired difference against the full set, to "
                          "group_analysis_given_<P>_bootstrap.csv")
+    ap.add_argument("--fit", action="store_true",
+                    help="instead: how well the model predicts the healthy test subjects -- per ROI the mean and sd over folds of rho, "
+                         "expv, smse, msll and coverage from fit_quality_<m>.csv (`test --roi-effect --fit`), to "
+                         "group_analysis_fit_<m>.csv, and one line with their medians over the ROIs: the label-free comparison of "
+                         "procedures")
     args = ap.parse_args(argv)
+    if args.fit and (args.given or args.roi or args.bootstrap or args.threshold_rule or args.roc_grid or args.score != "reconstruction"
+                     or args.centile_score or args.predictive_score or args.trajectory_score):
+        ap.error("--fit reads the fit tables alone: it goes with no score, --roi, --given, --bootstrap, --threshold-rule or --roc-grid")
     if args.given:
         if args.predictive_score:
             ap.error("--given scores the reconstruction error of modality subsets: it does not go with --predictive-score")
@@ -2077,6 +2187,11 @@ def main_analysis(argv=None):
     if args.given:
         try:
             return _analysis_given(root, args, mods, hc)
+        except FileNotFoundError as e:
+            ap.error(str(e))
+    if args.fit:
+        try:
+            return _analysis_fit(root, mods, args.n_splits, args.procedure)
         except FileNotFoundError as e:
             ap.error(str(e))
     if args.roi and args.roi_significance:
