@@ -457,6 +457,43 @@ typedef struct nm_pred_t {
 int nm_devpass_draws(const nm_job_t* jobs_dev, int n_jobs, const nm_draw_t* draws_dev, int n_draws, const nm_pred_t* pred_dev,
                      int tile0, int n_tiles, int flags, void* stream);   /* flags: 0 or NM_F_TRACE */
 int nm_devpass_draws_ok(const nm_job_t* job_host);
+/* The likelihood pass (csrc/nm_iw.inc: nm_devpass_iw_kernel): the importance-weighted estimate of log p(x | c) per row
+ * (IWAE, Burda et al.), the model's own posterior as the proposal.  The shape of nm_devpass_draws -- encoders once per
+ * 128-row tile, then S = n_draws times the fusion, the draw of draws[j * n_draws + s] (nm_draw_t, as there) and every
+ * decoder of the request's mask -- with no per-element accumulator and no [N, D] export: per row and draw
+ *   a_s     = -0.5 sum_k (z_k^2 - eps_k^2 - lv_k)           = log p(z_s) - log q(z_s | x, c); k ascending, k < Z; lv the
+ *             fused log-variance, z the fp32 value nm_forward exports as out_z for that draw
+ *   q_m     = sum_d (x_d - x_hat_d)^2 / noise_var_d,  ll_m,s = ll_const[m] - 0.5 q_m
+ *             (ll_const[m] = -0.5 sum_d (logvar_out_d + log 2 pi), formed in fp64 by the caller and rounded once;
+ *              q_m: four columns per lane and chunk, chunks ascending, then the row's four lanes)
+ *   log w_s = (sum over the mask's decoders, ascending m, of ll_m,s) + a_s
+ * and across the draws, in draw order, in the registers of the lane that owns the row: an online log-sum-exp (running
+ * maximum mx, s1 = sum exp(log w - mx), s2 = sum exp(2 (log w - mx)), rescaled when mx moves; library expf / logf) and
+ * running sums.  All fp32, contraction off.  Exports per job: row [rows_alloc][NM_IW_ROW_COLUMNS] =
+ *   log_px = mx + log s1 - log S | elbo = mean_s log w_s | ess = s1^2 / s2 | kl_mc = -mean_s a_s |
+ *   kl = 0.5 sum_k (mu_k^2 + exp(lv_k) - 1 - lv_k) | recon_ll = mean_s sum_m ll_m,s | logw_max | logw_min
+ * and optionally recon_ll[m] [rows_alloc] = mean_s ll_m,s per decoder of the mask.  A decoder outside the mask is skipped
+ * entirely: the estimate is log p(x_mask | c) with the full posterior as proposal.  Rows from the table's end to the end
+ * of its last 256-row tile come back as zeros; nothing a buffer held before the launch enters a result; a row's bytes
+ * do not depend on the launch's other jobs or tiles.
+ *   Admitted (nm_devpass_iw_ok): what nm_devpass_draws_ok admits; NM_E_DEVPASS otherwise.  Status of the launch is decided
+ * on the host before the device is asked anything: NM_E_NULL for a missing array, NM_E_GEOMETRY for n_draws outside
+ * 1..NM_MAX_IW_DRAWS and the geometry rules of every launch.  The tables live in device memory, so the rules of one
+ * request are asked of its host copy (nm_iw_check): NM_E_NULL a row export that is NULL or a wanted decoder without
+ * noise_var, NM_E_GEOMETRY an empty mask or a mask bit at or above M, NM_E_DEVPASS a job outside the domain. */
+#define NM_MAX_IW_DRAWS 1024
+#define NM_IW_ROW_COLUMNS 8
+typedef struct nm_iw_t {
+  float* row;                        /* [rows_alloc][NM_IW_ROW_COLUMNS] */
+  float* recon_ll[NM_MAX_EXP];       /* [rows_alloc] per decoder, or NULL */
+  const float* noise_var[NM_MAX_EXP];/* [x_pitch of modality m]: exp(logvar_out); required for every decoder of the mask */
+  float ll_const[NM_MAX_EXP];
+  uint32_t dec_mask;                 /* bit m: decoder m enters the weight */
+} nm_iw_t;
+int nm_devpass_iw(const nm_job_t* jobs_dev, int n_jobs, const nm_draw_t* draws_dev, int n_draws, const nm_iw_t* iw_dev,
+                  int tile0, int n_tiles, int flags, void* stream);      /* flags: 0 or NM_F_TRACE */
+int nm_devpass_iw_ok(const nm_job_t* job_host);
+int nm_iw_check(const nm_job_t* job_host, const nm_iw_t* iw_host);
 /* The encoder half alone (csrc/nm_devpass.hip: nm_latent_kernel): the joint posterior of every row, what cVAE.pred_latent
  * returns (cVAE.py:539-545), over table rows [tile0 * 128, (tile0 + n_tiles) * 128).  Every expert's encoder and the fusion
  * of nm_forward, no latent draw and no decoder; writes out_mu / out_logvar and nothing else -- bit for bit nm_forward's

@@ -92,6 +92,9 @@ NM_OP_MAX_LINSPACE = 65536
 NM_MAX_SUBSETS = 15
 # nm_devpass_draws: the most latent draws per row
 NM_MAX_DRAWS = 64
+# nm_devpass_iw: the most latent draws per row (no accumulators between the draws), and the columns of its row export
+NM_MAX_IW_DRAWS = 1024
+NM_IW_ROW_COLUMNS = 8
 # nm_decode_pass: the most covariate cells of a request
 NM_MAX_CELLS = 64
 
@@ -190,6 +193,12 @@ class NmPred(C.Structure):
                 ("noise_var", C.c_void_p * NM_MAX_EXP)]
 
 
+class NmIw(C.Structure):
+    """nm_iw_t: one job's likelihood request, nm_devpass_iw's [n_jobs] table (device memory)."""
+    _fields_ = [("row", C.c_void_p), ("recon_ll", C.c_void_p * NM_MAX_EXP), ("noise_var", C.c_void_p * NM_MAX_EXP),
+                ("ll_const", C.c_float * NM_MAX_EXP), ("dec_mask", C.c_uint32)]
+
+
 class NmDecode(C.Structure):
     """nm_decode_t: one job's request, nm_decode_pass' [n_jobs] table (device memory)."""
     _fields_ = [("z", C.c_void_p), ("n_rows", C.c_int32), ("rows_alloc", C.c_int32), ("n_cells", C.c_int32),
@@ -280,6 +289,9 @@ def load():
     lib.nm_devpass_subsets_ok.argtypes = [C.POINTER(NmJob)]
     lib.nm_devpass_draws.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, vp]
     lib.nm_devpass_draws_ok.argtypes = [C.POINTER(NmJob)]
+    lib.nm_devpass_iw.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, vp]
+    lib.nm_devpass_iw_ok.argtypes = [C.POINTER(NmJob)]
+    lib.nm_iw_check.argtypes = [C.POINTER(NmJob), C.POINTER(NmIw)]
     lib.nm_latent_pass.argtypes = [vp, i32, i32, i32, i32, vp]
     lib.nm_latent_pass_ok.argtypes = [C.POINTER(NmJob)]
     lib.nm_decode_pass.argtypes = [vp, i32, vp, i32, i32, i32, vp]
@@ -361,6 +373,7 @@ EXPORTED_SYMBOLS = [
     "nm_cohort_quantiles", "nm_normative_centile_workspace", "nm_normative_centile",
     "nm_devpass_subsets", "nm_devpass_subsets_ok",
     "nm_devpass_draws", "nm_devpass_draws_ok",
+    "nm_devpass_iw", "nm_devpass_iw_ok", "nm_iw_check",
     "nm_decode_pass", "nm_decode_pass_ok",
     "nm_fit_quality", "nm_fit_rank",
 ]

@@ -216,8 +216,12 @@ class _Base(nn.Module):
         return self._device
 
     def _run(self, xes: Sequence[torch.Tensor], cs: Sequence[torch.Tensor], combine: str, flags: int, eps=None,
-             kl_w=None, ll_w=1.0, recon_only: bool = False, latent_only: bool = False, subsets=None, present=None, draws=None):
-        """draws (pred_recon_draws: (S, the S generator keys)): the launch is the posterior-predictive pass
+             kl_w=None, ll_w=1.0, recon_only: bool = False, latent_only: bool = False, subsets=None, present=None, draws=None,
+             loglik=None):
+        """loglik (pred_loglik: (S, the S generator keys, the decoder indices or None)): the launch is the likelihood pass
+        (JobSet.forward_loglik: encoders once, the S importance weights folded per subject on the device), its values in
+        job.iw_row / iw_recon_ll.
+        draws (pred_recon_draws: (S, the S generator keys)): the launch is the posterior-predictive pass
         (JobSet.forward_draws: encoders once, S draws folded on the device), its statistics in job.pred_mean / pred_var /
         pred_msq / pred_z.
         subsets (pred_recon_given: a list of tuples of modality indices): the launch is the modality-subset pass
@@ -289,6 +293,13 @@ class _Base(nn.Module):
             if j.n_draws != S or j.pred_seeds != seeds or j.pred_mean[0].shape[0] != j.tables[0].rows_alloc:
                 j.enable_predictive_exports(S, seeds=seeds, rowdev=False, rowz2=False)
             self._js.forward_draws(0, nt)
+        elif loglik is not None:
+            S, seeds, dec = int(loglik[0]), [int(v) for v in loglik[1]], loglik[2]
+            mask = sum(1 << int(m) for m in set(dec)) if dec is not None else (1 << len(j.kmods)) - 1
+            if (j.iw_draws != S or j.iw_seeds != seeds or j.iw_mask != mask or j.iw_eps is not None
+                    or j.iw_row.shape[0] != j.tables[0].rows_alloc):
+                j.enable_likelihood_exports(S, seeds=seeds, decoders=dec, per_modality=True)
+            self._js.forward_loglik(0, nt)
         elif recon_only and flags == _lib.NM_F_EXPORT:
             self._js.forward(0, nt, loss=False)
         elif latent_only and flags == _lib.NM_F_EXPORT:
@@ -311,6 +322,29 @@ class _Base(nn.Module):
         j, B = self._run(xs, cs, combine, _lib.NM_F_EXPORT, eps=zeros, recon_only=True, draws=(S, draw_seeds(seed, S)))
         return [{"mean": j.pred_mean[m][:B].cpu().numpy(), "var": j.pred_var[m][:B].cpu().numpy(),
                  "msq": j.pred_msq[m][:B].cpu().numpy(), "z": j.pred_z[m][:B].cpu().numpy()} for m in range(len(j.kmods))]
+
+    def _pred_loglik(self, xs, cs, combine: str, n_draws: int, seed, decoders):
+        """The importance-weighted estimate of log p(x | c) per subject (IWAE; the model's own posterior as the proposal) over
+        n_draws in-kernel latent draws, one launch: a DataFrame of metrics.LOGLIK_ROW_COLUMNS -- log_px, elbo, ess (effective
+        sample size of the weights), kl_mc, kl (analytic), recon_ll, logw_max, logw_min -- plus recon_ll_<m> per decoder that
+        enters the weight (decoders: their indices; default all -- a subset gives log p(x_subset | c) under the full
+        posterior).  seed as in _pred_draws; n_draws is 1 to 1024."""
+        import pandas as pd
+        from .metrics import LOGLIK_ROW_COLUMNS
+        self._dev()
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        S = int(n_draws)
+        if not 1 <= S <= _lib.NM_MAX_IW_DRAWS:
+            raise ValueError(f"n_draws must be 1 to {_lib.NM_MAX_IW_DRAWS}, got {n_draws}")
+        zeros = torch.zeros(int(xs[0].shape[0]), self.spec.latent)     # (the job's own draw buffer is not read by this pass)
+        j, B = self._run(xs, cs, combine, _lib.NM_F_EXPORT, eps=zeros, recon_only=True,
+                         loglik=(S, draw_seeds(seed, S), None if decoders is None else [int(m) for m in decoders]))
+        out = pd.DataFrame(j.iw_row[:B].cpu().numpy(), columns=list(LOGLIK_ROW_COLUMNS))
+        for m, t in enumerate(j.iw_recon_ll):
+            if t is not None:
+                out[f"recon_ll_{m}"] = t[:B].cpu().numpy()
+        return out
 
     # -- the decoder pass (nm_decode_pass): the decoders alone, under the rows' covariates or a covariate grid -------------
     def _decode_job(self):
@@ -675,6 +709,14 @@ class cVAE_multimodal(_ExpertOps, _Base):
         ct = torch.tensor(np.asarray(c), dtype=torch.long)
         return self._pred_draws(xs, [ct] * self.modalities, combine, n_draws, seed)
 
+    def pred_loglik(self, xes, c, DEVICE, combine, n_draws=64, seed=0, decoders=None):
+        """log p(x | c) per subject, importance-weighted over n_draws posterior draws in ONE launch (JobSet.forward_loglik):
+        DataFrames in, a DataFrame out -- log_px, elbo, ess, kl_mc, kl, recon_ll, logw_max, logw_min and recon_ll_<m> per
+        decoder (see _Base._pred_loglik).  n_draws is 1 to 1024."""
+        xs = [torch.tensor(np.asarray(x.values if hasattr(x, "values") else x), dtype=torch.float32) for x in xes]
+        ct = torch.tensor(np.asarray(c), dtype=torch.long)
+        return self._pred_loglik(xs, [ct] * self.modalities, combine, n_draws, seed, decoders)
+
     def pred_recon_counterfactual(self, xes, c, DEVICE, combine, c_grid, latent="mean"):
         """pred_recon "as if": the subjects' own joint latent -- latent="mean": the posterior mean; "draw": the sampled z
         pred_recon would use -- decoded under every row of c_grid [G, C] in the place of their own covariates, one decode
@@ -871,6 +913,9 @@ class mmJSD(cVAE_multimodal):
     def pred_recon_draws(self, xes, c, DEVICE, combine, n_draws, seed=None):
         return super().pred_recon_draws(xes, c, DEVICE, "poe", n_draws, seed)
 
+    def pred_loglik(self, xes, c, DEVICE, combine="poe", n_draws=64, seed=0, decoders=None):
+        return super().pred_loglik(xes, c, DEVICE, "poe", n_draws, seed, decoders)
+
     def pred_recon_counterfactual(self, xes, c, DEVICE, combine, c_grid, latent="mean"):
         return super().pred_recon_counterfactual(xes, c, DEVICE, "poe", c_grid, latent)
 
@@ -935,6 +980,14 @@ class cVAE(_Base):
         xt = torch.as_tensor(np.asarray(x.to_numpy() if hasattr(x, "to_numpy") else x), dtype=torch.float32)
         ct = torch.as_tensor(np.asarray(c), dtype=torch.long)
         return self._pred_draws([xt], [ct], "poe", n_draws, seed)[0]
+
+    def pred_loglik(self, x, c, DEVICE, combine=None, n_draws=64, seed=0, decoders=None):
+        """log p(x | c) per subject, importance-weighted over n_draws posterior draws in one launch (JobSet.forward_loglik): a
+        DataFrame of log_px, elbo, ess, kl_mc, kl, recon_ll, logw_max, logw_min and recon_ll_0 (see _Base._pred_loglik).
+        combine plays no part in a one-expert model."""
+        xt = torch.as_tensor(np.asarray(x.to_numpy() if hasattr(x, "to_numpy") else x), dtype=torch.float32)
+        ct = torch.as_tensor(np.asarray(c), dtype=torch.long)
+        return self._pred_loglik([xt], [ct], "poe", n_draws, seed, decoders)
 
     def pred_recon_counterfactual(self, x, c, DEVICE, combine=None, c_grid=None, latent="mean"):
         """pred_recon "as if": x's own latent -- latent="mean": the posterior mean, what pred_recon decodes; "draw": a sampled
@@ -1046,6 +1099,9 @@ class cVAE_multimodal_regression(_ExpertOps, _HeadBase):
 
     def pred_recon_draws(self, xes, c, DEVICE, combine, n_draws, seed=None):
         return cVAE_multimodal.pred_recon_draws(self, xes, c, DEVICE, combine, n_draws, seed)
+
+    def pred_loglik(self, xes, c, DEVICE, combine, n_draws=64, seed=0, decoders=None):
+        return cVAE_multimodal.pred_loglik(self, xes, c, DEVICE, combine, n_draws, seed, decoders)
 
     def pred_recon_counterfactual(self, xes, c, DEVICE, combine, c_grid, latent="mean"):
         return cVAE_multimodal.pred_recon_counterfactual(self, xes, c, DEVICE, combine, c_grid, latent)

@@ -1943,3 +1943,5 @@ int nm_trace_read_dv(unsigned long long* out512, int reset) {
 }
 
 }  // extern "C"
+
+#include "nm_iw.inc"

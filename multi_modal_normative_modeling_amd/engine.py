@@ -289,6 +289,8 @@ class Job:
         self.dec_rows = self.dec_rows_alloc = self.dec_cells = self.dec_decoders = self.dec_full = None
         self.dec_z = self.dec_cgrid = self.dec_cz = self.dec_x = self.dec_loc = self.dec_sqerr = self.dec_rowdev = None
         self._dec_epoch = 0              # bumped whenever the request would change
+        # the likelihood pass (enable_likelihood_exports): draws per row, decoder mask, the row export and per-decoder terms
+        self.iw_draws = self.iw_seeds = self.iw_eps = self.iw_mask = self.iw_row = self.iw_recon_ll = self.iw_noise_var = None
         self._params_epoch = 0           # bumped by every host-side write of the parameters (refresh_noise_var)
         self._nv_state = None
 
@@ -541,6 +543,38 @@ class Job:
         Gaussian output, first hidden width <= 112, latent <= 32."""
         return self.latent_ok()
 
+    def _draw_request(self, n_draws, seeds, eps, most):
+        """The draws of a request, checked: -> (S, one generator key per draw, the injected draws on the device or None)."""
+        S = int(n_draws)
+        if not 1 <= S <= most:
+            raise ValueError(f"n_draws must be 1 to {most}, got {n_draws}")
+        if seeds is not None and eps is not None:
+            raise ValueError("give seeds or eps, not both: an injected draw has no generator key")
+        if seeds is not None and len(seeds) != S:
+            raise ValueError(f"seeds: one per draw ({S}), got {len(seeds)}")
+        if eps is not None and len(eps) != S:
+            raise ValueError(f"eps: one tensor per draw ({S}), got {len(eps)}")
+        keys = [int(v) & _MASK64 for v in seeds] if seeds is not None else draw_seeds(self.seed, S)
+        if eps is None:
+            return S, keys, None
+        Z, out = self.spec.latent, []
+        for e in eps:
+            e = torch.as_tensor(e, dtype=torch.float32)
+            if e.dim() == 2:
+                e = e.unsqueeze(0)
+            if e.dim() != 3 or e.shape[2] != Z or e.shape[1] > BATCH:
+                raise ValueError(f"eps: every draw is [steps, <= {BATCH}, {Z}], got {tuple(e.shape)}")
+            steps = self.eps_cap if self.eps is not None else (out[0].shape[0] if out else e.shape[0])
+            if e.shape[0] != steps:
+                raise ValueError(f"eps: every draw holds the same number of steps (the job's eps_cap, {steps}), "
+                                 f"got {e.shape[0]}")
+            pad = torch.zeros(e.shape[0], BATCH, Z, dtype=torch.float32)
+            pad[:, :e.shape[1]] = e
+            out.append(pad.to(self.device).contiguous())
+        if self.eps is None:
+            self.eps_cap = int(out[0].shape[0])      # (the draws' step count indexes as the job's own eps would)
+        return S, keys, out
+
     def enable_predictive_exports(self, n_draws, seeds=None, eps=None, msq=True, z=True, rowdev=True, rowz2=True):
         """Buffers of the posterior-predictive pass (JobSet.forward_draws, nm_devpass_draws): S = n_draws latent draws per row,
         folded on the device.  seeds: one generator key per draw (default: draw_seeds(job.seed, S)); eps: a list of S tensors
@@ -549,35 +583,7 @@ class Job:
         None where the kind was not asked for.  With z or rowz2 the observation variance exp(logvar_out) of the current
         parameters travels along (refreshed by forward_draws whenever the parameters have changed).  Refused (ValueError):
         n_draws outside 1..64, seeds / eps of another length, both given, eps draws of differing step counts."""
-        S = int(n_draws)
-        if not 1 <= S <= _lib.NM_MAX_DRAWS:
-            raise ValueError(f"n_draws must be 1 to {_lib.NM_MAX_DRAWS}, got {n_draws}")
-        if seeds is not None and eps is not None:
-            raise ValueError("give seeds or eps, not both: an injected draw has no generator key")
-        if seeds is not None and len(seeds) != S:
-            raise ValueError(f"seeds: one per draw ({S}), got {len(seeds)}")
-        if eps is not None and len(eps) != S:
-            raise ValueError(f"eps: one tensor per draw ({S}), got {len(eps)}")
-        self.pred_seeds = [int(v) & _MASK64 for v in seeds] if seeds is not None else draw_seeds(self.seed, S)
-        self.pred_eps = None
-        if eps is not None:
-            Z, out = self.spec.latent, []
-            for e in eps:
-                e = torch.as_tensor(e, dtype=torch.float32)
-                if e.dim() == 2:
-                    e = e.unsqueeze(0)
-                if e.dim() != 3 or e.shape[2] != Z or e.shape[1] > BATCH:
-                    raise ValueError(f"eps: every draw is [steps, <= {BATCH}, {Z}], got {tuple(e.shape)}")
-                steps = self.eps_cap if self.eps is not None else (out[0].shape[0] if out else e.shape[0])
-                if e.shape[0] != steps:
-                    raise ValueError(f"eps: every draw holds the same number of steps (the job's eps_cap, {steps}), "
-                                     f"got {e.shape[0]}")
-                pad = torch.zeros(e.shape[0], BATCH, Z, dtype=torch.float32)
-                pad[:, :e.shape[1]] = e
-                out.append(pad.to(self.device).contiguous())
-            if self.eps is None:
-                self.eps_cap = int(out[0].shape[0])      # (the draws' step count indexes as the job's own eps would)
-            self.pred_eps = out
+        S, self.pred_seeds, self.pred_eps = self._draw_request(n_draws, seeds, eps, _lib.NM_MAX_DRAWS)
         ra, M = self.tables[0].rows_alloc, len(self.kmods)
         pitch = [self.tables[m].x_pitch for m, _, _ in self.kmods]
         width = [self.tables[m].D for m, _, _ in self.kmods]
@@ -622,6 +628,61 @@ class Job:
             if p.pred_z[m] and not p.noise_var[m]:
                 raise ValueError("pred_z needs noise_var: the score is scaled by exp(logvar_out) + the draw variance")
         return draws, p
+
+    def enable_likelihood_exports(self, n_draws, seeds=None, eps=None, decoders=None, per_modality=False):
+        """Buffers of the likelihood pass (JobSet.forward_loglik, nm_devpass_iw): S = n_draws latent draws per row from the
+        model's own posterior, their importance weights folded on the device.  seeds / eps as in enable_predictive_exports;
+        decoders: the indices of the decoders whose likelihood enters the weight (default: all).  Afterwards iw_row
+        [rows_alloc, 8] holds metrics.LOGLIK_ROW_COLUMNS per subject and, with per_modality, iw_recon_ll[m] [rows_alloc] the
+        mean reconstruction log-likelihood of decoder m (None for a decoder left out).  Refused (ValueError): n_draws
+        outside 1..1024, seeds / eps of another length, both given, an empty or out-of-range decoder list."""
+        M = len(self.kmods)
+        dec = list(range(M)) if decoders is None else sorted({int(m) for m in decoders})
+        if not dec or dec[0] < 0 or dec[-1] >= M:
+            raise ValueError(f"decoders: a non-empty subset of 0..{M - 1}, got {decoders}")
+        S, keys, draws = self._draw_request(n_draws, seeds, eps, _lib.NM_MAX_IW_DRAWS)
+        ra = self.tables[0].rows_alloc
+        self.iw_draws, self.iw_seeds, self.iw_eps = S, keys, draws
+        self.iw_mask = sum(1 << m for m in dec)
+        self.iw_row = torch.zeros(ra, _lib.NM_IW_ROW_COLUMNS, device=self.device)
+        self.iw_recon_ll = [torch.zeros(ra, device=self.device) if (per_modality and m in dec) else None for m in range(M)]
+        self.iw_noise_var = [torch.ones(self.tables[k].x_pitch, device=self.device) if j in dec else None
+                             for j, (k, _, _) in enumerate(self.kmods)]
+        self.iw_ll_const = [0.0] * M
+        self._iw_state = None
+        self._version += 1
+
+    def refresh_likelihood_constants(self) -> bool:
+        """iw_noise_var[m] = exp(logvar_out) (in place) and iw_ll_const[m] = -0.5 sum_d (logvar_out_d + log 2 pi) (fp64, rounded
+        once where the request is packed) of the CURRENT parameters; True when they changed."""
+        state = (self.t, self._params_epoch)
+        if self._iw_state == state:
+            return False
+        for k, (m, _, dp) in enumerate(self.kmods):
+            if self.iw_noise_var[k] is not None:
+                lv = self.layout.get(self.params, f"{dp}logvar_out").reshape(-1)
+                self.iw_noise_var[k][: lv.numel()] = torch.exp(lv)
+                self.iw_ll_const[k] = float(-0.5 * (lv.double() + math.log(2.0 * math.pi)).sum())
+        self._iw_state = state
+        return True
+
+    def iw_structs(self):
+        """This job's rows of nm_devpass_iw's two tables: ([NmDraw] * n_draws, NmIw)."""
+        if getattr(self, "iw_draws", None) is None:
+            raise ValueError("enable_likelihood_exports() first")
+        draws = []
+        for s in range(self.iw_draws):
+            d = _lib.NmDraw()
+            d.seed = self.iw_seeds[s]
+            d.eps = self.iw_eps[s].data_ptr() if self.iw_eps is not None else None
+            draws.append(d)
+        q = _lib.NmIw()
+        q.row, q.dec_mask = self.iw_row.data_ptr(), self.iw_mask
+        for m in range(len(self.kmods)):
+            q.recon_ll[m] = self.iw_recon_ll[m].data_ptr() if self.iw_recon_ll[m] is not None else None
+            q.noise_var[m] = self.iw_noise_var[m].data_ptr() if self.iw_noise_var[m] is not None else None
+            q.ll_const[m] = self.iw_ll_const[m]
+        return draws, q
 
     def set_latent_exports(self, on: bool):
         """Switch the joint-latent exports (out_mu / out_logvar / out_z) of a job that has them off and back on; the
@@ -754,6 +815,16 @@ class Job:
         return r
 
     # -- descriptor ----------------------------------------------------------------------------
+    def kernel_combine(self) -> str:
+        """The combiner the descriptor carries.  gPoE weighs the experts by softmax(alpha); a one-expert model whose class
+        has no alpha parameter (class cVAE: its descriptor holds alpha = -1) with the bypass off would make every kernel read
+        the float in front of the parameter buffer for it -- an address that need not be mapped.  One expert's softmax weight
+        is exactly 1 whatever alpha holds, and 1 * (1 / var) is 1 / var: such a job is a product of experts, bit for bit,
+        and is described as one."""
+        if self.combine == "gpoe" and self.spec.M == 1 and "alpha_m_list.0" not in self.layout.offsets:
+            return "poe"
+        return self.combine
+
     def struct(self) -> _lib.NmJob:
         s, j = self.spec, _lib.NmJob()
         j.M, j.M_enc, j.C, j.L, j.Z = len(self.kmods), s.M, s.net_c_dim, len(s.hidden), s.latent
@@ -765,7 +836,7 @@ class Job:
         j.var_floor, j.tc_weight = self.var_floor, self.tc_weight
         for i, h in enumerate(s.hidden):
             j.H[i] = h
-        j.combine = _lib.NM_COMBINE[self.combine]
+        j.combine = _lib.NM_COMBINE[self.kernel_combine()]
         j.single_bypass = 1 if self.single_bypass else 0
         j.n_rows = self.tables[0].N
         j.non_linear = 1 if (s.non_linear or s.is_dm) else 0        # (torch.relu unconditionally, cVAE.py:1462-1463)
@@ -1334,6 +1405,39 @@ class JobSet:
             j.refresh_noise_var()
         nt = self.jobs[0].tables[0].n_tiles if n_tiles is None else n_tiles
         self._issue("nm_devpass_draws", nt, self._draw_keep[0].data_ptr(), S, self._draw_keep[1].data_ptr(), tile0 * 2, nt * 2,
+                    _lib.NM_F_TRACE if trace else 0)
+
+    def forward_loglik(self, tile0: int = 0, n_tiles: Optional[int] = None, trace: bool = False):
+        """The likelihood pass (nm_devpass_iw): every expert's encoder once per 128-row tile, then per draw of
+        Job.enable_likelihood_exports the fusion, the latent draw and every decoder of the request, the importance weights
+        log w_s = log p(x | z_s, c) + log p(z_s) - log q(z_s | x, c) folded per subject on the device into job.iw_row
+        (metrics.LOGLIK_ROW_COLUMNS: log p(x | c), ELBO, effective sample size, ...) and job.iw_recon_ll.  All jobs of the set
+        in one launch; they must ask for the same number of draws.  A set holding a job the kernel does not take raises
+        ValueError naming the refusal, as forward_draws does."""
+        if any(getattr(j, "iw_draws", None) is None for j in self.jobs):
+            raise ValueError("forward_loglik: Job.enable_likelihood_exports() first, on every job of the set")
+        S = self.jobs[0].iw_draws
+        if any(j.iw_draws != S for j in self.jobs):
+            raise ValueError("forward_loglik: the jobs of one set must ask for the same number of draws")
+        why = self._draws_refusal()                 # (nm_devpass_iw_ok is nm_devpass_draws_ok: one domain)
+        if why is not None:
+            raise ValueError("forward_loglik: the set cannot run on nm_devpass_iw: " + why)
+        changed = [j.refresh_likelihood_constants() for j in self.jobs]
+        sig = tuple(j._version for j in self.jobs)
+        if getattr(self, "_iw_sig", None) != sig or any(changed):
+            rows = [j.iw_structs() for j in self.jobs]
+            for i, (j, (_, q)) in enumerate(zip(self.jobs, rows)):
+                st = self.lib.nm_iw_check(C.byref(j.struct()), C.byref(q))
+                if st != 0:
+                    raise ValueError(f"forward_loglik: job {i}: nm_iw_check refuses the request with status {st} "
+                                     f"({self.lib.nm_status_string(st).decode()})")
+            draws = (_lib.NmDraw * (S * len(rows)))(*[d for dr, _ in rows for d in dr])
+            reqs = (_lib.NmIw * len(rows))(*[q for _, q in rows])
+            self._iw_keep = (torch.frombuffer(bytearray(bytes(draws)), dtype=torch.uint8).to(self.device),
+                             torch.frombuffer(bytearray(bytes(reqs)), dtype=torch.uint8).to(self.device))
+            self._iw_sig = sig
+        nt = self.jobs[0].tables[0].n_tiles if n_tiles is None else n_tiles
+        self._issue("nm_devpass_iw", nt, self._iw_keep[0].data_ptr(), S, self._iw_keep[1].data_ptr(), tile0 * 2, nt * 2,
                     _lib.NM_F_TRACE if trace else 0)
 
     def latent_ok(self) -> bool:

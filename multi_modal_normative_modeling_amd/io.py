@@ -115,6 +115,23 @@ def write_predictive_csvs(out_dir, dataset_name: str, covariates: pd.DataFrame, 
     return paths
 
 
+def write_loglik_csv(out_dir, name: str, covariates: pd.DataFrame, row: np.ndarray, columns: Sequence[str],
+                     recon_ll: Dict[str, np.ndarray]) -> Path:
+    """loglik_<name>.csv of the likelihood pass (sweep.test_folds(loglik=S)): the metadata columns of write_test_csvs, the
+    columns of the pass's row export (metrics.LOGLIK_ROW_COLUMNS: log_px, elbo, ess, kl_mc, kl, recon_ll, logw_max, logw_min)
+    and recon_ll_<m> per modality -- one file per procedure, the model's own log p(x | c) of every test subject."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    df = covariates[META_COLS].copy().reset_index(drop=True)
+    for j, c in enumerate(columns):
+        df[c] = np.asarray(row)[:, j]
+    for m, v in recon_ll.items():
+        df[f"recon_ll_{m}"] = np.asarray(v)
+    path = out_dir / f"loglik_{name}.csv"
+    df.to_csv(path, index=False)
+    return path
+
+
 def write_latent_csvs(out_dir, name: str, covariates: pd.DataFrame, mu: np.ndarray, var: np.ndarray, score: np.ndarray,
                       zsep: np.ndarray) -> Dict[str, Path]:
     """The latent-space deviation of one fold's test subjects (pred_latent + latent_deviation / separate_latent_deviation,

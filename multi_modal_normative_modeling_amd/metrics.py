@@ -41,6 +41,9 @@ CONFUSION_COLUMNS = ("accuracy", "auroc", "sensitivity", "specificity", "f1_scor
 ROI_EFFECT_COLUMNS = ("cliff_delta", "auc", "n_more", "n_less", "n_x", "n_y", "mean_x", "mean_y")
 ROI_SIGNIFICANCE_COLUMNS = ("u_x", "tie_term", "z", "p_mwu", "q_bh", "p_perm", "p_maxt", "n_perm")
 COLUMN_REGRESS_COLUMNS = ("const", "coef", "se_const", "se_coef", "p_const", "p_coef", "n_obs", "n_iter")
+# the row export of the likelihood pass (nm_devpass_iw, JobSet.forward_loglik): NM_IW_ROW_COLUMNS values per subject
+LOGLIK_ROW_COLUMNS = ("log_px", "elbo", "ess", "kl_mc", "kl", "recon_ll", "logw_max", "logw_min")
+assert len(LOGLIK_ROW_COLUMNS) == _lib.NM_IW_ROW_COLUMNS
 COLUMN_REGRESS_KINDS = {"ols": _lib.NM_REG_OLS, "logit": _lib.NM_REG_LOGIT}
 
 

@@ -841,6 +841,20 @@ TRAJ_AGE_BINS, TRAJ_GENDER_BINS = 27, 2
 TRAJ_MIN_ROWS, TRAJ_MAX_ROWS = 16, 4096
 
 
+def check_loglik(loglik, loglik_seed=None):
+    """(loglik, loglik_seed) of test_folds / `test --loglik S [--loglik-seed N]` as integers, or (None, None) where the pass is
+    off.  Refused (ValueError): loglik outside 1..NM_MAX_IW_DRAWS, a loglik_seed without loglik or outside [0, 2^64)."""
+    if loglik is None:
+        if loglik_seed is not None:
+            raise ValueError("loglik_seed needs loglik (it keys the latent draws of the likelihood pass)")
+        return None, None
+    if int(loglik) != loglik or not 1 <= int(loglik) <= _lib.NM_MAX_IW_DRAWS:
+        raise ValueError(f"loglik must be an integer from 1 to {_lib.NM_MAX_IW_DRAWS}, got {loglik}")
+    if loglik_seed is not None and (int(loglik_seed) != loglik_seed or not 0 <= int(loglik_seed) < 1 << 64):
+        raise ValueError(f"loglik_seed must be an integer inside [0, 2^64), got {loglik_seed}")
+    return int(loglik), (None if loglik_seed is None else int(loglik_seed))
+
+
 def check_trajectory(trajectory, traj_seed=0, c_dim: Optional[int] = None):
     """(trajectory, traj_seed) of test_folds / `test --trajectory S [--traj-seed N]` as integers, or (None, 0) where the chart
     is off.  Refused (ValueError): S outside 16..4096 or no multiple of 16, a negative or non-integer seed, a model whose
@@ -977,7 +991,8 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
                quantiles: Sequence[float] = CENTILE_QUANTILES, centile_loo: bool = False,
                robust: bool = False, given=None, draws: Optional[int] = None,
                draw_seed: Optional[int] = None, trajectory: Optional[int] = None,
-               traj_seed: int = 0, fit: bool = False, fit_rank: bool = False) -> List[Dict[str, np.ndarray]]:
+               traj_seed: int = 0, fit: bool = False, fit_rank: bool = False, loglik: Optional[int] = None,
+               loglik_seed: Optional[int] = None, loglik_name: Optional[str] = None) -> List[Dict[str, np.ndarray]]:
     """test_fold for ALL folds of a procedure as one launch: jobs[i] is the trained model of fold i, folds[i] its
     (train_rows, test_rows); one evaluation job per fold, each on its own test tables (seed, scaler and covariates per fold
     exactly as test_fold), all in ONE JobSet -- a fold's ~N / K test rows are a single workgroup, K of them in a row leave
@@ -1020,8 +1035,16 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
 
     fit (needs roi_effect; fit_rank needs fit): the model's fit per ROI on the healthy test subjects (_queue_fit): rho, SMSE,
     EXPV, MSLL against the train cohort's mean and variance, RMSE and the calibration of z -- with draws on the predictive
-    mean and variance -- and with fit_rank Spearman's rho; coverage counts |z| <= z_thr.  Without `fit` nothing changes."""
+    mean and variance -- and with fit_rank Spearman's rho; coverage counts |z| <= z_thr.  Without `fit` nothing changes.
+
+    loglik (S: 1..1024): after the passes above the evaluation jobs run the likelihood pass (JobSet.forward_loglik: the
+    encoders once, S posterior draws, their importance weights folded per subject on the device) -- all folds of a table
+    height in one launch -- and each fold's dict gains "loglik": {"row" [n, 8] (metrics.LOGLIK_ROW_COLUMNS: log p(x | c),
+    ELBO, effective sample size, ...), "recon_ll": {modality: [n]}}; with out_dirs and loglik_name (the procedure), loglik_<name>.csv
+    in the fold's directory (io.write_loglik_csv).  Draws keyed as for `draws`: from the evaluation job's own seed, or fold i
+    from loglik_seed + i.  A set holding a model the kernel does not take raises ValueError.  Without `loglik` nothing changes."""
     draws, draw_seed = check_draws(draws, draw_seed)
+    loglik, loglik_seed = check_loglik(loglik, loglik_seed)
     trajectory, traj_seed = check_trajectory(trajectory, traj_seed, jobs[0].spec.net_c_dim if len(jobs) else None)
     subsets = given_subsets(given, modalities) if given is not None else []
     for name, on in (("centile", centile is not None), ("normative", normative is not None), ("roi_significance", roi_significance),
@@ -1068,6 +1091,12 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
             ev.enable_predictive_exports(draws, seeds=None if draw_seed is None else draw_seeds(draw_seed + i, draws))
         for group in _by_height([ev for ev, _ in evs]):
             JobSet(group).forward_draws()
+    if loglik is not None:
+        for i, (ev, _) in enumerate(evs):
+            ev.enable_likelihood_exports(loglik, seeds=None if loglik_seed is None else draw_seeds(loglik_seed + i, loglik),
+                                         per_modality=True)
+        for group in _by_height([ev for ev, _ in evs]):
+            JobSet(group).forward_loglik()
     traj = _trajectory_pass(evs, folds, cohort, modalities, trajectory, traj_seed, z_thr, disease_label, device) \
         if trajectory is not None else None
     queued = []               # (statistic, its device entry per table of t.mats): everything is queued before the one synchronise
@@ -1107,6 +1136,13 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
                     p = res["predictive"][m]
                     io.write_predictive_csvs(Path(d) / m, m, _meta_frame(cohort, te), _roi_columns(roi_columns, m, xs[i].shape[1]),
                                              p["mean"], p["msq"], p["z"])
+    if loglik is not None:
+        for res, (ev, xs), (_, te), d in zip(out, evs, folds, dirs):
+            res["loglik"] = {"row": ev.iw_row[:len(te)].cpu().numpy(),
+                             "recon_ll": {m: ev.iw_recon_ll[i][:len(te)].cpu().numpy() for i, m in enumerate(modalities)}}
+            if d is not None and loglik_name is not None:
+                io.write_loglik_csv(d, loglik_name, _meta_frame(cohort, te), res["loglik"]["row"], metrics.LOGLIK_ROW_COLUMNS,
+                                    res["loglik"]["recon_ll"])
     if traj is not None:
         for res, entry, (ev, xs), (_, te), d in zip(out, traj, evs, folds, dirs):
             res["trajectory"] = entry
@@ -1548,6 +1584,13 @@ def main_test(argv=None):
                          "over the model's own predictive sd) and predictive_subject_<m>.csv")
     ap.add_argument("--draw-seed", dest="draw_seed", type=int, default=None, metavar="N",
                     help="with --draws: key the draws of fold i from N + i instead of the fold's own seed")
+    ap.add_argument("--loglik", type=int, default=None, metavar="S",
+                    help="also the model's own score of every test subject: the importance-weighted estimate of log p(x | c) over S "
+                         "posterior draws (1..%d), folded on the device -- per fold and all folds pooled loglik_<P>.csv (log_px, elbo, "
+                         "ess, kl_mc, kl, recon_ll, logw_max, logw_min, recon_ll_<m>), and per fold the held-out controls' mean ELBO: "
+                         "the label-free model-selection criterion" % _lib.NM_MAX_IW_DRAWS)
+    ap.add_argument("--loglik-seed", dest="loglik_seed", type=int, default=None, metavar="N",
+                    help="with --loglik: key the draws of fold i from N + i instead of the fold's own seed")
     ap.add_argument("--trajectory", type=int, default=None, metavar="S",
                     help="also the normative chart and the deviation against it: S prior draws (16..4096, a multiple of 16) decoded "
                          "under every (age bin, sex bin) cell in one launch -- per fold normative_trajectory_mean_<m>.csv and "
@@ -1587,6 +1630,10 @@ def main_test(argv=None):
                 (args.draw_seed is not None and args.draws is None, "--draw-seed needs --draws"),
                 (args.draws is not None and not 1 <= args.draws <= _lib.NM_MAX_DRAWS, f"--draws must be 1 to {_lib.NM_MAX_DRAWS}"),
                 (args.draw_seed is not None and not 0 <= args.draw_seed < 1 << 64, "--draw-seed must lie inside [0, 2^64)"),
+                (args.loglik_seed is not None and args.loglik is None, "--loglik-seed needs --loglik"),
+                (args.loglik is not None and not 1 <= args.loglik <= _lib.NM_MAX_IW_DRAWS,
+                 f"--loglik must be 1 to {_lib.NM_MAX_IW_DRAWS}"),
+                (args.loglik_seed is not None and not 0 <= args.loglik_seed < 1 << 64, "--loglik-seed must lie inside [0, 2^64)"),
                 (args.traj_seed is not None and args.trajectory is None, "--traj-seed needs --trajectory"),
                 (args.trajectory is not None and (not TRAJ_MIN_ROWS <= args.trajectory <= TRAJ_MAX_ROWS or args.trajectory % 16 != 0),
                  f"--trajectory must be a multiple of 16 from {TRAJ_MIN_ROWS} to {TRAJ_MAX_ROWS}"),
@@ -1640,7 +1687,7 @@ def main_test(argv=None):
                         quantiles=args.quantiles, centile_loo=args.centile_loo, fit=args.fit, fit_rank=args.fit_rank)
     results = test_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs, given=args.given,
                          draws=args.draws, draw_seed=args.draw_seed, trajectory=args.trajectory, traj_seed=args.traj_seed or 0,
-                         **vars(o)) if my else []
+                         loglik=args.loglik, loglik_seed=args.loglik_seed, loglik_name=args.procedure, **vars(o)) if my else []
     given_tags = [tag for tag, _ in given_subsets(args.given, mods)] if args.given else []
     # the pooled entries of every statistic that is on: this rank's folds' test subjects as one set (the maps: against their controls)
     pooled_stats = [st for st in ROI_STATS if getattr(o, st.key)] if results else []
@@ -1663,6 +1710,16 @@ def main_test(argv=None):
             e = results[0][st.key + "_pooled"][m]
             st.write(out_root / m, m, _roi_columns(None, m, _n_roi(e)), meta_all, e, o)
             print(f"[test] {args.procedure} {m}: {st.summary(e, g_all, o)}", flush=True)
+    if args.loglik is not None and my:
+        out_root.mkdir(parents=True, exist_ok=True)
+        parts = [pd.read_csv(root / f"{k:03d}" / f"loglik_{args.procedure}.csv") for k in my]
+        pd.concat(parts, ignore_index=True).to_csv(out_root / f"loglik_{args.procedure}.csv", index=False)
+        hc = prep.HC_LABEL.get(args.dataset_resourse, 1)
+        for k, part in zip(my, parts):
+            ctl = part[healthy(part["DIA"].to_numpy(), hc)]
+            print(f"[test] {args.procedure} fold {k}: {len(ctl)} held-out controls, mean elbo {float(ctl['elbo'].mean()):.4f}  "
+                  f"mean log_px {float(ctl['log_px'].mean()):.4f}  median ess {float(ctl['ess'].median()):.2f} of {args.loglik}",
+                  flush=True)
     if args.latent and my:
         # the folds' train cohorts and test subjects in one latent launch each, one statistics and one score launch
         lat = latent_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs, name=args.procedure,
@@ -1814,8 +1871,13 @@ ANALYSIS_SCORES = {
     # (--trajectory-score zmean / extreme: likewise a flag of its own; the files of `test --trajectory S`)
     "trajectory_zmean": ("trajectory_subject_{m}.csv", lambda d: d["mean_abs_z"], " with --trajectory S"),
     "trajectory_extreme": ("trajectory_subject_{m}.csv", lambda d: d["n_hi"] + d["n_lo"], " with --trajectory S"),
+    # (--loglik-score logpx / elbo: likewise a flag of its own; the file of `test --loglik S`.  The sign: a larger score is more
+    #  deviant, and an improbable subject has a LOW log p(x | c))
+    "loglik_logpx": ("loglik_{p}.csv", lambda d: -d["log_px"], " with --loglik S"),
+    "loglik_elbo": ("loglik_{p}.csv", lambda d: -d["elbo"], " with --loglik S"),
 }
 TRAJECTORY_SCORES = ("zmean", "extreme")
+LOGLIK_SCORES = ("logpx", "elbo")
 CENTILE_SCORES = ("tails", "depth")
 PREDICTIVE_SCORES = ("msq", "z2")
 
@@ -1844,6 +1906,25 @@ def _analysis_scores(root: Path, mods: Sequence[str], procedure: str, score: str
         what = f"{pattern.format(m='*')} of {mods}" if per_modality else pattern.format(p=procedure)
         raise FileNotFoundError(f"no {what} under {root}/<fold>/ -- run the `test` subcommand{hint} first")
     return scores, positive, folds, ids
+
+
+def _analysis_loglik(root: Path, procedure: str, n_splits: int, hc: int):
+    """`analysis --loglik-score`: the model-selection table group_analysis_loglik.csv from the per-fold loglik_<P>.csv files
+    (`test --loglik S`) -- one row for the procedure: the number of folds, and the mean and population sd over folds of the
+    held-out controls' mean elbo and mean log_px (fp64 on the host: K numbers).  Needs no patient label."""
+    import pandas as pd
+    files = [root / f"{k:03d}" / f"loglik_{procedure}.csv" for k in range(n_splits)]
+    frames = [pd.read_csv(f, float_precision="round_trip") for f in files if f.exists()]
+    if not frames:
+        raise FileNotFoundError(f"no loglik_{procedure}.csv under {root}/<fold>/ -- run the `test` subcommand with --loglik S first")
+    per = np.array([[d[healthy(d["DIA"].to_numpy(), hc)][c].to_numpy(dtype=np.float64).mean() for c in ("elbo", "log_px")]
+                    for d in frames])
+    df = pd.DataFrame({"procedure": [procedure], "folds": [len(frames)], "elbo_mean": [per[:, 0].mean()], "elbo_sd": [per[:, 0].std()],
+                       "log_px_mean": [per[:, 1].mean()], "log_px_sd": [per[:, 1].std()]})
+    df.to_csv(root / "group_analysis_loglik.csv", index=False)
+    print(f"[analysis] {procedure} held-out controls over {len(frames)} folds: elbo {per[:, 0].mean():.4f} +- {per[:, 0].std():.4f}  "
+          f"log_px {per[:, 1].mean():.4f} +- {per[:, 1].std():.4f}", flush=True)
+    return df
 
 
 def _with_pooled(scores, positive, flag: str = ""):
@@ -2072,6 +2153,11 @@ def main_analysis(argv=None):
                     help="instead of --score: the per-subject score from trajectory_subject_<m>.csv (`test --trajectory S`), averaged "
                          "over the modalities -- zmean: mean_abs_z against the chart row of the subject's own cell; extreme: n_hi + "
                          "n_lo, the ROIs beyond the threshold; writes group_analysis_trajectory_<kind>.csv")
+    ap.add_argument("--loglik-score", dest="loglik_score", choices=LOGLIK_SCORES, default=None,
+                    help="instead of --score: the model's own score from loglik_<P>.csv (`test --loglik S`) -- logpx: minus the "
+                         "importance-weighted log p(x | c); elbo: minus the ELBO; writes group_analysis_loglik_<kind>.csv, and "
+                         "group_analysis_loglik.csv: the mean and sd over folds of the held-out controls' mean elbo and log_px, the "
+                         "label-free comparison of procedures")
     ap.add_argument("--roi", action="store_true",
                     help="instead: which ROIs separate patients from controls -- per fold and modality every ROI's Cliff's delta and "
                          "ROC-AUC on reconstruction_error_roi_<m>.csv, their mean and std over folds to group_analysis_roi_<m>.csv")
@@ -2123,7 +2209,7 @@ def main_analysis(argv=None):
                          "procedures")
     args = ap.parse_args(argv)
     if args.fit and (args.given or args.roi or args.bootstrap or args.threshold_rule or args.roc_grid or args.score != "reconstruction"
-                     or args.centile_score or args.predictive_score or args.trajectory_score):
+                     or args.centile_score or args.predictive_score or args.trajectory_score or args.loglik_score):
         ap.error("--fit reads the fit tables alone: it goes with no score, --roi, --given, --bootstrap, --threshold-rule or --roc-grid")
     if args.given:
         if args.predictive_score:
@@ -2159,6 +2245,17 @@ def main_analysis(argv=None):
         if args.given:
             ap.error("--given scores the reconstruction error of modality subsets: it does not go with --trajectory-score")
         args.score = f"trajectory_{args.trajectory_score}"
+    if args.loglik_score:
+        if args.centile_score or args.predictive_score or args.trajectory_score:
+            ap.error("--loglik-score is a score of its own: it does not go with --centile-score, --predictive-score or "
+                     "--trajectory-score")
+        if args.score != "reconstruction":
+            ap.error("--loglik-score is a score of its own: it does not go with --score")
+        if args.roi:
+            ap.error("--loglik-score is a per-subject score: it does not go with --roi")
+        if args.given:
+            ap.error("--given scores the reconstruction error of modality subsets: it does not go with --loglik-score")
+        args.score = f"loglik_{args.loglik_score}"
     if args.threshold_from == "others" and not args.threshold_rule:
         ap.error("--threshold-from others needs --threshold-rule")
     if (args.threshold_rule or args.roc_grid) and args.roi:
@@ -2198,6 +2295,8 @@ def main_analysis(argv=None):
         return _analysis_roi_significance(root, mods, args.n_splits, hc, args.procedure, args.roi_perm, args.roi_seed)
     if args.roi:
         return _analysis_roi(root, mods, args.n_splits, hc, args.procedure)
+    if args.loglik_score:
+        _analysis_loglik(root, args.procedure, args.n_splits, hc)
     scores, positive, folds, ids = _analysis_scores(root, mods, args.procedure, args.score, args.n_splits, hc)
     table = metrics.posthoc_metrics(scores, positive).cpu()
     df = pd.DataFrame(table.numpy(), columns=list(metrics.POSTHOC_COLUMNS))

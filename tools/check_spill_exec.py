@@ -81,6 +81,10 @@ LIMITS = {
     # (the decoder half of the several-expert kernel inside a loop over covariate cells: the build shows 91 VGPRs and 51 SGPR
     #  spills -- the request's counts and a decoder's export pointers stay alive across its chunks; the ceiling is that count)
     "nm_decode_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 51, "vgpr_count": 128},
+    # (the draws kernel's shape with the importance weights folded in the registers of the lane that owns the row, no element
+    #  accumulators: the build shows 113 VGPRs and 108 SGPR spills -- the request's pointers and constants stay alive across the
+    #  decoders; the ceiling is that count)
+    "nm_devpass_iw_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 108, "vgpr_count": 128},
     "nm_rs_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 540},
     "nm_wide_step_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 400},
     # (both instantiations: one workgroup per model / one per decoder, nm_train_steps_head_split)
