@@ -543,6 +543,43 @@ typedef struct nm_decode_t {
 } nm_decode_t;
 int nm_decode_pass(const nm_job_t* jobs_dev, int n_jobs, const nm_decode_t* req_dev, int tile0, int n_tiles, int flags, void* stream);   /* flags: 0 or NM_F_TRACE */
 int nm_decode_pass_ok(const nm_job_t* job_host);
+/* The normative chart pass (csrc/nm_chart.inc: nm_chart_kernel, nm_chart_merge_kernel): the grid request of nm_decode_pass
+ * with the cells dealt to workgroups and the per-cell moments folded in the kernel -- per (cell, ROI) the mean and the
+ * unbiased variance of x_hat over the request's rows, with no [cells][rows][D] export.  One workgroup owns one (128-row
+ * tile, cell, decoder) of a job; everything up to the output accumulators is nm_decode_kernel's code, operation for
+ * operation, so the optional loc export equals nm_decode_pass' loc bit for bit (pad columns 0; rows from n_rows to the end
+ * of the last 256-row tile 0).
+ *   Fold (fp64 from the conversion of the fp32 x_hat on, no fused multiply-add): per tile and column the sum over the
+ *   tile's rows -- within the wave a butterfly over the 16 row lanes (xor 1, 2, 4, 8; dead rows add +0), then the live waves
+ *   in wave order through LDS -- the tile mean sum / live, and M2 = sum (x_hat - mean_t)^2 in the same order: two-pass inside
+ *   the tile.  part[m] receives (mean_t, M2_t) per (cell, tile, column); the count follows from n_rows and the tile index.
+ *   Merge: one thread per (job, decoder, cell, column) takes the tiles in ascending order with the pairwise update
+ *   (n = n_a + n_b, delta = mean_b - mean_a, mean_a + delta n_b / n, M2_a + M2_b + delta^2 n_a n_b / n) and writes chart[m]
+ *   [cell][column] = (mean, var_latent = M2 / (n - 1), n_rows, status); status 0, or -2 with NaN statistics where n_rows < 2
+ *   or the column's sum is not finite; pad columns hold zeros.  Plain stores, no atomics: the chart's bytes depend neither on
+ *   the number of jobs in the launch nor on its geometry.
+ * The merge is launched, on the same stream behind the fold, only when tile0 == 0, and it merges a request only when
+ * n_tiles covers it (n_tiles * 128 >= n_rows): a caller that splits the rows over several launches finishes with one
+ * launch of all tiles, or merges the partials itself.  max_cells sizes the grid (the requests are not readable on the
+ * host): cells of a request at or beyond it are not computed.
+ * Admitted (nm_chart_pass_ok): exactly nm_decode_pass_ok.  Status is decided on the host: NM_E_NULL for a missing table,
+ * NM_E_GEOMETRY by the geometry rules of every launch or for max_cells outside 1..NM_MAX_CELLS.  The request's own rules
+ * (n_cells 1..NM_MAX_CELLS, n_rows 1..NM_CHART_MAX_ROWS, rows_alloc a multiple of 256 and >= n_rows, chart only with part,
+ * buffers of the stated sizes) are the caller's; the workgroups of a refused job or of a request with counts out of range
+ * leave at once, exports untouched.  A decoder with neither part nor loc is skipped.  flags: 0. */
+#define NM_CHART_MAX_ROWS 1048576   /* 2^20 rows: 8192 tiles */
+#define NM_CHART_COLUMNS 4           /* mean, var_latent, n_rows, status */
+typedef struct nm_chart_t {
+  const float* z;                    /* [rows_alloc][Z] fp32 latent rows, as nm_decode_t.z */
+  int32_t n_rows, rows_alloc;        /* as nm_decode_t; n_rows <= NM_CHART_MAX_ROWS */
+  int32_t n_cells;                   /* 1..NM_MAX_CELLS (a chart needs a grid) */
+  const uint16_t* cgrid;             /* [n_cells][Cz] bf16  c | 1 | 0 */
+  double* part[NM_MAX_EXP];          /* [n_cells][rows_alloc / 128][x_pitch][2]: (mean_t, M2_t); NULL: no chart of decoder m */
+  double* chart[NM_MAX_EXP];         /* [n_cells][x_pitch][NM_CHART_COLUMNS]; needs part[m] */
+  float*  loc[NM_MAX_EXP];           /* optional [n_cells][rows_alloc][x_pitch], nm_decode_t.loc's shape */
+} nm_chart_t;
+int nm_chart_pass(const nm_job_t* jobs_dev, int n_jobs, const nm_chart_t* req_dev, int tile0, int n_tiles, int max_cells, int flags, void* stream);
+int nm_chart_pass_ok(const nm_job_t* job_host);
 /* NM_F_TRACE read-out of the row-split kernels ([8 waves][64 tags], as nm_trace_read) */
 int nm_trace_read_rs(unsigned long long* out512, int reset);
 /* out_dev[j] (device, n_jobs ints) != 0: a hand-off of job j timed out in a split launch since the word was last

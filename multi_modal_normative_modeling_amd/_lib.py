@@ -97,6 +97,9 @@ NM_MAX_IW_DRAWS = 1024
 NM_IW_ROW_COLUMNS = 8
 # nm_decode_pass: the most covariate cells of a request
 NM_MAX_CELLS = 64
+# nm_chart_pass: the most rows of a request, and the columns of a chart row (mean, var_latent, n_rows, status)
+NM_CHART_MAX_ROWS = 1 << 20
+NM_CHART_COLUMNS = 4
 
 # status codes (nmhip.h; nm_status_string gives the text)
 NM_OK = 0
@@ -206,6 +209,13 @@ class NmDecode(C.Structure):
                 ("loc", C.c_void_p * NM_MAX_EXP), ("sqerr", C.c_void_p * NM_MAX_EXP), ("rowdev", C.c_void_p * NM_MAX_EXP)]
 
 
+class NmChart(C.Structure):
+    """nm_chart_t: one job's request, nm_chart_pass' [n_jobs] table (device memory)."""
+    _fields_ = [("z", C.c_void_p), ("n_rows", C.c_int32), ("rows_alloc", C.c_int32), ("n_cells", C.c_int32),
+                ("cgrid", C.c_void_p), ("part", C.c_void_p * NM_MAX_EXP), ("chart", C.c_void_p * NM_MAX_EXP),
+                ("loc", C.c_void_p * NM_MAX_EXP)]
+
+
 class NmRoiSet(C.Structure):
     """nm_roi_set_t: one matrix of nm_roi_effect's pointer table."""
     _fields_ = [("x", C.c_void_p), ("group", C.c_void_p), ("rows", C.c_int32), ("pitch", C.c_int32)]
@@ -296,6 +306,8 @@ def load():
     lib.nm_latent_pass_ok.argtypes = [C.POINTER(NmJob)]
     lib.nm_decode_pass.argtypes = [vp, i32, vp, i32, i32, i32, vp]
     lib.nm_decode_pass_ok.argtypes = [C.POINTER(NmJob)]
+    lib.nm_chart_pass.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp]
+    lib.nm_chart_pass_ok.argtypes = [C.POINTER(NmJob)]
     lib.nm_latent_stats.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.nm_latent_score.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.nm_combine_latent.argtypes = [vp, vp, i32, i64, i32, vp, i32, i32, i32, f32, vp, vp, vp]
@@ -375,6 +387,7 @@ EXPORTED_SYMBOLS = [
     "nm_devpass_draws", "nm_devpass_draws_ok",
     "nm_devpass_iw", "nm_devpass_iw_ok", "nm_iw_check",
     "nm_decode_pass", "nm_decode_pass_ok",
+    "nm_chart_pass", "nm_chart_pass_ok",
     "nm_fit_quality", "nm_fit_rank",
 ]
 

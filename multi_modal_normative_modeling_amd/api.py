@@ -27,7 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .engine import DECODE_AUTO, Job, JobSet, Table, adam_step, draw_seeds, latent_scores, latent_stats, require_gpu
+from .engine import CHART_AUTO, DECODE_AUTO, Job, JobSet, Table, adam_step, draw_seeds, latent_scores, latent_stats, require_gpu
 from .layout import ModelSpec, ParamLayout
 
 
@@ -394,33 +394,67 @@ class _Base(nn.Module):
             raise ValueError(f"c_grid must be [1..{_lib.NM_MAX_CELLS} cells, C], got {tuple(g.shape)}")
         return g
 
-    def decode_grid(self, z, c_grid):
+    def _chart_request(self, z, c_grid, chart=True, loc=False):
+        """One launch of the chart pass (nm_chart_pass) on this model: z [R, Z] under every row of c_grid, a workgroup per
+        (tile, cell, decoder).  The job, its chart[m] ([G, D, 4] fp64) and / or chart_loc[m] ([G, R, D]) filled."""
+        j, js = self._decode_job()
+        why = js._decode_refusal()
+        if why is not None:
+            raise ValueError("the chart pass (nm_chart_pass) does not take this model: " + why)
+        z = torch.as_tensor(np.asarray(z) if not torch.is_tensor(z) else z, dtype=torch.float32)
+        if z.dim() != 2 or int(z.shape[1]) != self.spec.latent:
+            raise ValueError(f"z must be [rows, {self.spec.latent}], got {tuple(z.shape)}")
+        key = (int(z.shape[0]), int(c_grid.shape[0]), bool(chart), bool(loc))
+        if j.__dict__.get("_chart_key") != key:
+            j.enable_chart_exports(key[0], key[1], loc=loc, chart=chart)
+            j.__dict__["_chart_key"] = key
+        j.set_chart_inputs(z, c_grid)
+        js.chart()
+        return j
+
+    def decode_grid(self, z, c_grid, deal=False):
         """Every decoder on the latent rows z [R, Z] under EVERY row of c_grid [G, C] (G <= 64) in one launch: per modality a
-        [G, R, D] device tensor -- slab g is what decode(z, c, m) gives with c = row g of the grid for every row."""
+        [G, R, D] device tensor -- slab g is what decode(z, c, m) gives with c = row g of the grid for every row.
+        deal=True: the cells dealt to workgroups (the chart kernel with its loc export alone): the same bytes."""
+        if deal:
+            j = self._chart_request(z, self._grid(c_grid), chart=False, loc=True)
+            return [t.clone() for t in j.chart_loc]
         j = self._decode_request(z, c_grid=self._grid(c_grid))
         return [t.clone() for t in j.dec_loc]
 
-    def normative_trajectory(self, c_grid, n_draws=256, seed=0, z=None):
+    def normative_trajectory(self, c_grid, n_draws=256, seed=0, z=None, fold=None):
         """What the model expects at every covariate setting of c_grid [G, C]: n_draws prior rows z ~ N(0, I) -- drawn on the
         host from torch.Generator().manual_seed(seed), the SAME rows in every cell, so the curves are smooth in the
         covariate; or the rows `z` -- decoded under every grid row in one launch, then per cell the moments of the
-        reconstructions over the rows (metrics.cohort_moments, ddof = 1).  Per modality a dict of fp64 numpy arrays: "mean"
-        [G, D], "var_latent" [G, D] (the spread the latent induces), "noise_var" [D] (exp(logvar_out) in fp32, as
-        Job.refresh_noise_var forms it) and "sd_pred" = sqrt(var_latent + noise_var) [G, D]: the predictive sd of the chart."""
+        reconstructions over the rows.  fold="export": the [G, S, D] reconstructions are exported and folded by
+        metrics.cohort_moments (ddof = 1); fold="kernel": the chart pass (JobSet.chart) folds them in the decoder kernel, a
+        workgroup per (tile, cell, decoder), with no export; None: "export", or "kernel" where JobSet.chart_pick() says so
+        (engine.CHART_AUTO, NMHIP_CHART=1).  Per modality a dict of fp64 numpy arrays: "mean" [G, D], "var_latent" [G, D]
+        (the spread the latent induces), "noise_var" [D] (exp(logvar_out) in fp32, as Job.refresh_noise_var forms it) and
+        "sd_pred" = sqrt(var_latent + noise_var) [G, D]: the predictive sd of the chart."""
         from . import metrics
+        if fold not in (None, "export", "kernel"):
+            raise ValueError(f'fold must be "export" or "kernel", got {fold!r}')
         g = self._grid(c_grid)
         if z is None:
             z = torch.randn(int(n_draws), self.spec.latent, generator=torch.Generator().manual_seed(int(seed)))
-        j = self._decode_request(z, c_grid=g)
+        if fold is None:
+            fold = "kernel" if (os.environ.get("NMHIP_CHART", "auto") == "1" or CHART_AUTO.get(self.spec.M, False)) \
+                and self._decode_job()[1].chart_pick() else "export"
+        j = self._chart_request(z, g) if fold == "kernel" else self._decode_request(z, c_grid=g)
         G = int(g.shape[0])
         out = []
         for k, (_, _, dp) in enumerate(j.kmods):
-            sets = [j.dec_loc[k][c] for c in range(G)]
-            mom = metrics.cohort_moments(sets, [torch.zeros(int(s.shape[0]), dtype=torch.int32) for s in sets], ddof=1).cpu().numpy()
+            if fold == "kernel":
+                tab = j.chart[k].cpu().numpy()
+                mean, var = tab[:, :, 0].copy(), tab[:, :, 1].copy()
+            else:
+                sets = [j.dec_loc[k][c] for c in range(G)]
+                mom = metrics.cohort_moments(sets, [torch.zeros(int(s.shape[0]), dtype=torch.int32) for s in sets], ddof=1).cpu().numpy()
+                mean, var = mom[:, :, 0].copy(), mom[:, :, 2].copy()
             lv = j.layout.get(j.params, f"{dp}logvar_out").reshape(-1)
             nv = torch.exp(lv).cpu().numpy().astype(np.float64)
-            out.append({"mean": mom[:, :, 0].copy(), "var_latent": mom[:, :, 2].copy(), "noise_var": nv,
-                        "sd_pred": np.sqrt(mom[:, :, 2] + nv[None, :])})
+            out.append({"mean": mean, "var_latent": var, "noise_var": nv, "sd_pred": np.sqrt(var + nv[None, :])})
         return out
 
     def _counterfactual(self, xs, cs, combine: str, c_grid, latent: str):

@@ -1945,3 +1945,4 @@ int nm_trace_read_dv(unsigned long long* out512, int reset) {
 }  // extern "C"
 
 #include "nm_iw.inc"
+#include "nm_chart.inc"

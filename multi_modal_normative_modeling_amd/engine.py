@@ -41,6 +41,11 @@ LATENT_AUTO = {1: True, 2: False, 3: True, 4: True}
 # no other route and take it wherever the job is admitted
 DECODE_AUTO = {1: False, 2: False, 3: False, 4: False}
 
+# nm_chart_pass as the automatic route of normative_trajectory, per number of decoders: by the same rule (the new route's
+# slowest repeat against decode() + cohort_moments' fastest at every set size measured, tools/bench_chart.py,
+# profiles/chart_pass.json).  All off: the route is reached with fold="kernel" or NMHIP_CHART=1
+CHART_AUTO = {1: False, 2: False, 3: False, 4: False}
+
 _MASK64 = (1 << 64) - 1
 
 
@@ -91,6 +96,35 @@ def check_decode_request(n_rows: int, rows_alloc: int, n_cells: int, Z: int, Cz:
             raise ValueError(f"decoder {m}: x must hold [{rows_alloc}, {xp}] values")
         for what, t, need in (("loc", loc[m], cells * rows_alloc * xp), ("sqerr", sqerr[m], cells * rows_alloc * xp),
                               ("rowdev", rowdev[m], cells * rows_alloc)):
+            if t is not None and t.numel() < need:
+                raise ValueError(f"decoder {m}: {what} holds {t.numel()} values, its declared shape needs {need}")
+
+
+def check_chart_request(n_rows: int, rows_alloc: int, n_cells: int, Z: int, Cz: int, pitches: Sequence[int], z, cgrid, part,
+                        chart, loc):
+    """The rules of an nm_chart_t the library cannot check (the request lives in device memory): raised here, before the
+    upload, as check_decode_request does for nm_decode_t.  part, chart, loc: per decoder a tensor (its whole storage) or
+    None.  Only sizes are read."""
+    if not 1 <= int(n_cells) <= _lib.NM_MAX_CELLS:
+        raise ValueError(f"n_cells must be 1 to {_lib.NM_MAX_CELLS} (a chart needs a grid), got {n_cells}")
+    if n_rows < 1 or n_rows > _lib.NM_CHART_MAX_ROWS or rows_alloc % BATCH != 0 or rows_alloc < n_rows:
+        raise ValueError(f"rows_alloc must be a multiple of {BATCH} and at least n_rows (1 to {_lib.NM_CHART_MAX_ROWS}), "
+                         f"got {rows_alloc} for {n_rows} rows")
+    if len(pitches) > _lib.NM_MAX_EXP:
+        raise ValueError(f"a request holds at most {_lib.NM_MAX_EXP} decoders, got {len(pitches)}")
+    if z is None or z.numel() < rows_alloc * Z:
+        raise ValueError(f"z must hold [{rows_alloc}, {Z}] values")
+    if cgrid is None or cgrid.numel() < n_cells * Cz:
+        raise ValueError(f"c_grid must hold [{n_cells}, {Cz}] packed values")
+    if not any(t is not None for t in part) and not any(t is not None for t in loc):
+        raise ValueError("no decoder is wanted: every part and every loc is None")
+    for m, xp in enumerate(pitches):
+        if chart[m] is not None and part[m] is None:
+            raise ValueError(f"decoder {m}: chart without part (the merge reads the tile partials)")
+        if part[m] is not None and chart[m] is None:
+            raise ValueError(f"decoder {m}: part without chart")
+        for what, t, need in (("part", part[m], n_cells * (rows_alloc // 128) * xp * 2),
+                              ("chart", chart[m], n_cells * xp * _lib.NM_CHART_COLUMNS), ("loc", loc[m], n_cells * rows_alloc * xp)):
             if t is not None and t.numel() < need:
                 raise ValueError(f"decoder {m}: {what} holds {t.numel()} values, its declared shape needs {need}")
 
@@ -289,6 +323,10 @@ class Job:
         self.dec_rows = self.dec_rows_alloc = self.dec_cells = self.dec_decoders = self.dec_full = None
         self.dec_z = self.dec_cgrid = self.dec_cz = self.dec_x = self.dec_loc = self.dec_sqerr = self.dec_rowdev = None
         self._dec_epoch = 0              # bumped whenever the request would change
+        # the chart pass (enable_chart_exports / set_chart_inputs): the request, its inputs, partials, chart and optional loc
+        self.chart_rows = self.chart_rows_alloc = self.chart_cells = self.chart_decoders = self.chart_full = None
+        self.chart_z = self.chart_cgrid = self.chart = self.chart_loc = None
+        self._chart_epoch = 0
         # the likelihood pass (enable_likelihood_exports): draws per row, decoder mask, the row export and per-decoder terms
         self.iw_draws = self.iw_seeds = self.iw_eps = self.iw_mask = self.iw_row = self.iw_recon_ll = self.iw_noise_var = None
         self._params_epoch = 0           # bumped by every host-side write of the parameters (refresh_noise_var)
@@ -812,6 +850,77 @@ class Job:
         for m in range(M):
             r.cz[m], r.x[m] = ptr(self.dec_cz[m]), ptr(self.dec_x[m])
             r.loc[m], r.sqerr[m], r.rowdev[m] = ptr(full["loc"][m]), ptr(full["sqerr"][m]), ptr(full["rowdev"][m])
+        return r
+
+    # -- the chart pass (nm_chart_pass) ----------------------------------------------------------
+    def chart_ok(self) -> bool:
+        """nm_chart_pass_ok for this job: exactly decode_ok() (tests/test_cabi_chart_cpu.py holds this to the library)."""
+        return self.decode_ok()
+
+    def enable_chart_exports(self, n_rows, n_cells, decoders=None, loc=False, chart=True):
+        """Buffers of the chart pass (JobSet.chart, nm_chart_pass) for a request of n_rows latent rows decoded under each of
+        n_cells rows of a covariate grid (1..64), the per-cell moments folded in the kernel.  decoders: the modalities wanted
+        (None: every one); a decoder left out is skipped.  Afterwards chart[m] ([n_cells, D, 4] fp64 view: CHART_COLUMNS of
+        metrics) holds the table of decoder m, chart_full["part" / "chart" / "loc"][m] the whole buffers; loc=True adds
+        the [n_cells, rows_alloc, x_pitch] export of nm_decode_pass (chart_loc[m]: [n_cells, n_rows, D] views); chart=False
+        with loc=True asks for loc alone (the cell-parallel decode).  Refused (ValueError): n_cells outside 1..64, n_rows
+        outside 1..NM_CHART_MAX_ROWS, a decoder index beyond the model's, neither chart nor loc."""
+        R, G, M = int(n_rows), int(n_cells), len(self.kmods)
+        if not 1 <= G <= _lib.NM_MAX_CELLS:
+            raise ValueError(f"n_cells must be 1 to {_lib.NM_MAX_CELLS}, got {n_cells}")
+        if not 1 <= R <= _lib.NM_CHART_MAX_ROWS:
+            raise ValueError(f"n_rows must be 1 to {_lib.NM_CHART_MAX_ROWS}, got {n_rows}")
+        if not chart and not loc:
+            raise ValueError("chart=False and loc=False: nothing is wanted")
+        decoders = tuple(range(M)) if decoders is None else tuple(int(m) for m in decoders)
+        if not decoders or any(m < 0 or m >= M or m >= _lib.NM_MAX_EXP for m in decoders):
+            raise ValueError(f"decoders: modalities 0..{min(M, _lib.NM_MAX_EXP) - 1}, at least one")
+        ra = (R + BATCH - 1) // BATCH * BATCH
+        pitch = [self.tables[m].x_pitch for m, _, _ in self.kmods]
+        width = [self.tables[m].D for m, _, _ in self.kmods]
+        f64 = lambda *shape: torch.zeros(*shape, dtype=torch.float64, device=self.device)
+        per = lambda on, make: [make(m) if on and m in decoders else None for m in range(M)]
+        self.chart_rows, self.chart_rows_alloc, self.chart_cells, self.chart_decoders = R, ra, G, decoders
+        self.chart_full = {"part": per(chart, lambda m: f64(G, ra // 128, pitch[m], 2)),
+                           "chart": per(chart, lambda m: f64(G, pitch[m], _lib.NM_CHART_COLUMNS)),
+                           "loc": per(loc, lambda m: torch.zeros(G, ra, pitch[m], device=self.device))}
+        self.chart = [t[:, :width[m]] if t is not None else None for m, t in enumerate(self.chart_full["chart"])]
+        self.chart_loc = [t[:, :R, :width[m]] if t is not None else None for m, t in enumerate(self.chart_full["loc"])]
+        self.chart_z = self.chart_cgrid = None
+        self._chart_epoch += 1
+
+    def set_chart_inputs(self, z, c_grid):
+        """Inputs of the chart pass: z [n_rows, Z] fp32 latent rows (copied) and c_grid [n_cells, C], one covariate row per
+        cell, packed to bf16 c | 1 | 0 rows (pack_covariates), as set_decode_inputs does for a grid request."""
+        if self.chart_rows is None:
+            raise ValueError("enable_chart_exports() first")
+        R, ra, G, Z = self.chart_rows, self.chart_rows_alloc, self.chart_cells, self.spec.latent
+        z = torch.as_tensor(np.asarray(z) if not torch.is_tensor(z) else z)
+        if z.dim() != 2 or int(z.shape[0]) != R or int(z.shape[1]) != Z:
+            raise ValueError(f"z must be [{R}, {Z}], got {tuple(z.shape)}")
+        if self.chart_z is None:
+            self.chart_z = torch.zeros(ra, Z, device=self.device)
+        self.chart_z[:R].copy_(z.to(device=self.device, dtype=torch.float32))
+        g = torch.as_tensor(np.asarray(c_grid) if not torch.is_tensor(c_grid) else c_grid)
+        if g.dim() != 2 or int(g.shape[0]) != G or int(g.shape[1]) != self.spec.net_c_dim:
+            raise ValueError(f"c_grid must be [{G}, {self.spec.net_c_dim}], got {tuple(g.shape)}")
+        self.chart_cgrid = pack_covariates(g, self.tables[0].Cz, G, self.device)
+        self._chart_epoch += 1
+
+    def chart_struct(self) -> "_lib.NmChart":
+        """This job's entry of nm_chart_pass' request table, validated (check_chart_request) before it travels."""
+        if self.chart_rows is None or self.chart_z is None:
+            raise ValueError("enable_chart_exports() and set_chart_inputs() first")
+        full = self.chart_full
+        check_chart_request(self.chart_rows, self.chart_rows_alloc, self.chart_cells, self.spec.latent, self.tables[0].Cz,
+                            [self.tables[m].x_pitch for m, _, _ in self.kmods], self.chart_z, self.chart_cgrid,
+                            full["part"], full["chart"], full["loc"])
+        r = _lib.NmChart()
+        r.z, r.n_rows, r.rows_alloc, r.n_cells = self.chart_z.data_ptr(), self.chart_rows, self.chart_rows_alloc, self.chart_cells
+        r.cgrid = self.chart_cgrid.data_ptr()
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        for m in range(len(self.kmods)):
+            r.part[m], r.chart[m], r.loc[m] = ptr(full["part"][m]), ptr(full["chart"][m]), ptr(full["loc"][m])
         return r
 
     # -- descriptor ----------------------------------------------------------------------------
@@ -1539,6 +1648,37 @@ class JobSet:
                         f"{len(j.kmods)} in the kernel, hidden {list(s.hidden)}, latent {s.latent}, private {s.n_private}, "
                         f"tc_weight {j.tc_weight})")
         return None
+
+    def chart_ok(self) -> bool:
+        """Can the set's charts run on nm_chart_pass?  decode_ok(): the same kernel code, the same switch (NMHIP_DECODE=0)."""
+        return self.decode_ok()
+
+    def chart_pick(self) -> bool:
+        """The automatic route of normative_trajectory through the chart pass: chart_ok() and a shape class CHART_AUTO has
+        switched on; NMHIP_CHART=1 forces the route on where the set passes chart_ok()."""
+        if not self.chart_ok():
+            return False
+        return os.environ.get("NMHIP_CHART", "auto") == "1" or all(CHART_AUTO.get(len(j.kmods), False) for j in self.jobs)
+
+    def chart(self, tile0: int = 0, n_tiles: Optional[int] = None):
+        """The chart pass (nm_chart_pass): every job's request (Job.enable_chart_exports / set_chart_inputs) in ONE launch --
+        a workgroup per (128-row tile, cell, decoder), the per-cell moments folded in the kernel, then the merge of the
+        tile partials -- into job.chart[m] ([n_cells, D, 4] fp64: metrics.CHART_COLUMNS) and, where asked for, job.chart_loc.
+        The requests may differ in height and in their number of cells.  n_tiles (256-row tiles, from tile0) defaults to
+        the tallest request; the merge runs only from tile0 = 0 and for requests the launch covers.  A set the decoder pass
+        refuses raises ValueError in _decode_refusal's wording."""
+        if any(j.chart_rows is None or j.chart_z is None for j in self.jobs):
+            raise ValueError("chart: Job.enable_chart_exports() and set_chart_inputs() first, on every job of the set")
+        why = self._decode_refusal()
+        if why is not None:
+            raise ValueError("chart: the set cannot run on nm_chart_pass: " + why)
+        sig = tuple(j._chart_epoch for j in self.jobs)
+        if getattr(self, "_chart_sig", None) != sig:
+            arr = (_lib.NmChart * len(self.jobs))(*[j.chart_struct() for j in self.jobs])
+            self._chart_keep = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
+            self._chart_sig = sig
+        nt = max(j.chart_rows_alloc for j in self.jobs) // BATCH if n_tiles is None else n_tiles
+        self._issue("nm_chart_pass", 1, self._chart_keep.data_ptr(), tile0 * 2, nt * 2, max(j.chart_cells for j in self.jobs), 0)
 
     def latent_stats(self):
         """Per job the column means and population variances of its exported joint mu over the table's rows (the training

@@ -839,6 +839,7 @@ def check_draws(draws, draw_seed=None):
 
 TRAJ_AGE_BINS, TRAJ_GENDER_BINS = 27, 2
 TRAJ_MIN_ROWS, TRAJ_MAX_ROWS = 16, 4096
+TRAJ_FOLDS = ("export", "kernel")        # the route of the chart's moments: decode() + cohort_moments, or JobSet.chart()
 
 
 def check_loglik(loglik, loglik_seed=None):
@@ -938,20 +939,38 @@ def pool_cell_columns(cols: np.ndarray) -> np.ndarray:
     return np.concatenate([out, np.stack(means, 1)], axis=1)
 
 
-def _trajectory_pass(evs, folds, cohort, modalities, S: int, seed: int, z_thr: float, disease_label, device):
+def check_trajectory_fold(trajectory_fold, trajectory):
+    """trajectory_fold of test_folds / `test --trajectory S --trajectory-fold F`: "export" or "kernel", None where it was not
+    given ("export").  Refused (ValueError): another name, or a fold without trajectory."""
+    if trajectory_fold is None:
+        return "export"
+    if trajectory_fold not in TRAJ_FOLDS:
+        raise ValueError(f"trajectory_fold must be one of {TRAJ_FOLDS}, got {trajectory_fold!r}")
+    if trajectory is None:
+        raise ValueError("trajectory_fold needs trajectory (it names the route of the chart's moments)")
+    return trajectory_fold
+
+
+def _trajectory_pass(evs, folds, cohort, modalities, S: int, seed: int, z_thr: float, disease_label, device, fold: str = "export"):
     """The chart and the trajectory z-scores of every fold's evaluation job: S prior rows per fold (keyed seed + fold, the SAME
     rows in every cell) decoded under the 54 cells -- all folds of one table height in one JobSet.decode() launch -- then per
     fold and modality the moments of the reconstructions per cell (metrics.cohort_moments, ddof = 1: what
     normative_trajectory forms) and the test subjects' scaled x z-scored against the chart row of their own cell through
-    the unchanged metrics.normative_z.  Returns per fold {modality: entry}, everything on the host."""
+    the unchanged metrics.normative_z.  fold="kernel": mean and var_latent come from the chart pass instead (JobSet.chart: a
+    workgroup per (tile, cell, decoder), the moments folded in the kernel, no [54, S, D] export); everything after the
+    moments is the same code.  Returns per fold {modality: entry}, everything on the host."""
     grid = torch.from_numpy(trajectory_grid())
     G = int(grid.shape[0])
     for i, (ev, _) in enumerate(evs):
         z = torch.randn(S, ev.spec.latent, generator=torch.Generator().manual_seed(seed + i))
-        ev.enable_decode_exports(S, G)
-        ev.set_decode_inputs(z, c_grid=grid, x=None)
+        if fold == "kernel":
+            ev.enable_chart_exports(S, G)
+            ev.set_chart_inputs(z, grid)
+        else:
+            ev.enable_decode_exports(S, G)
+            ev.set_decode_inputs(z, c_grid=grid, x=None)
     for group in _by_height([ev for ev, _ in evs]):
-        JobSet(group).decode()
+        JobSet(group).chart() if fold == "kernel" else JobSet(group).decode()
     out = []
     zero = torch.zeros(S, dtype=torch.int32)
     for (ev, _), (_, te) in zip(evs, folds):
@@ -963,10 +982,13 @@ def _trajectory_pass(evs, folds, cohort, modalities, S: int, seed: int, z_thr: f
         order_dev = torch.from_numpy(order).to(device)
         res = {}
         for i, m in enumerate(modalities):
-            mom = metrics.cohort_moments([ev.dec_loc[i][g] for g in range(G)], [zero] * G, ddof=1, device=device)
+            if fold == "kernel":
+                mean, var = ev.chart[i][:, :, 0].contiguous(), ev.chart[i][:, :, 1].contiguous()
+            else:
+                mom = metrics.cohort_moments([ev.dec_loc[i][g] for g in range(G)], [zero] * G, ddof=1, device=device)
+                mean, var = mom[:, :, 0], mom[:, :, 2]
             dp = ev.kmods[i][2]
             nv = torch.exp(ev.layout.get(ev.params, f"{dp}logvar_out").reshape(-1)).to(torch.float64)
-            mean, var = mom[:, :, 0], mom[:, :, 2]
             sd = torch.sqrt(var + nv[None, :])
             t = ev.tables[i]
             gathered = t.x_f32[:n, :t.D][order_dev].contiguous()          # the scaled x rows, sorted by cell, gathered once
@@ -992,7 +1014,8 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
                robust: bool = False, given=None, draws: Optional[int] = None,
                draw_seed: Optional[int] = None, trajectory: Optional[int] = None,
                traj_seed: int = 0, fit: bool = False, fit_rank: bool = False, loglik: Optional[int] = None,
-               loglik_seed: Optional[int] = None, loglik_name: Optional[str] = None) -> List[Dict[str, np.ndarray]]:
+               loglik_seed: Optional[int] = None, loglik_name: Optional[str] = None,
+               trajectory_fold: Optional[str] = None) -> List[Dict[str, np.ndarray]]:
     """test_fold for ALL folds of a procedure as one launch: jobs[i] is the trained model of fold i, folds[i] its
     (train_rows, test_rows); one evaluation job per fold, each on its own test tables (seed, scaler and covariates per fold
     exactly as test_fold), all in ONE JobSet -- a fold's ~N / K test rows are a single workgroup, K of them in a row leave
@@ -1031,7 +1054,8 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
     "cols" [D, 8]}}; with out_dirs, normative_trajectory_mean_<m>.csv / normative_trajectory_sd_<m>.csv (one row per cell)
     and trajectory_z_<m>.csv / trajectory_subject_<m>.csv / trajectory_map_<m>.csv in the layouts of their normative_*
     counterparts.  Refused for models whose networks take no covariates and for sets the decoder pass does not take
-    (JobSet.decode).  Without `trajectory` nothing changes.
+    (JobSet.decode).  trajectory_fold: "export" (the default: the route above) or "kernel" -- mean and var_latent from the
+    chart pass (JobSet.chart), the same files within the rounding of the two folds.  Without `trajectory` nothing changes.
 
     fit (needs roi_effect; fit_rank needs fit): the model's fit per ROI on the healthy test subjects (_queue_fit): rho, SMSE,
     EXPV, MSLL against the train cohort's mean and variance, RMSE and the calibration of z -- with draws on the predictive
@@ -1045,6 +1069,7 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
     from loglik_seed + i.  A set holding a model the kernel does not take raises ValueError.  Without `loglik` nothing changes."""
     draws, draw_seed = check_draws(draws, draw_seed)
     loglik, loglik_seed = check_loglik(loglik, loglik_seed)
+    trajectory_fold = check_trajectory_fold(trajectory_fold, trajectory)
     trajectory, traj_seed = check_trajectory(trajectory, traj_seed, jobs[0].spec.net_c_dim if len(jobs) else None)
     subsets = given_subsets(given, modalities) if given is not None else []
     for name, on in (("centile", centile is not None), ("normative", normative is not None), ("roi_significance", roi_significance),
@@ -1097,7 +1122,7 @@ def test_folds(jobs: Sequence[Job], cohort: prep.SyntheticCohort, folds: Sequenc
                                          per_modality=True)
         for group in _by_height([ev for ev, _ in evs]):
             JobSet(group).forward_loglik()
-    traj = _trajectory_pass(evs, folds, cohort, modalities, trajectory, traj_seed, z_thr, disease_label, device) \
+    traj = _trajectory_pass(evs, folds, cohort, modalities, trajectory, traj_seed, z_thr, disease_label, device, trajectory_fold) \
         if trajectory is not None else None
     queued = []               # (statistic, its device entry per table of t.mats): everything is queued before the one synchronise
     if roi_effect:
@@ -1599,6 +1624,10 @@ def main_test(argv=None):
                          "(the ROIs beyond +-z-thr) and trajectory_map_<m>.csv; models with covariates only")
     ap.add_argument("--traj-seed", dest="traj_seed", type=int, default=None, metavar="N",
                     help="with --trajectory: key the prior rows of fold i from N + i (default 0)")
+    ap.add_argument("--trajectory-fold", dest="trajectory_fold", choices=TRAJ_FOLDS, default=None,
+                    help="with --trajectory: where the chart's moments are formed -- export (the default): the reconstructions are "
+                         "exported and folded by the cohort-moments kernel; kernel: folded in the decoder kernel, one workgroup per "
+                         "(tile, cell, decoder), no export")
     ap.add_argument("--fit", action="store_true",
                     help="with --roi-effect: does the model predict a healthy brain at all -- per ROI on the fold's healthy test subjects "
                          "rho, SMSE, EXPV, MSLL against the train cohort's mean and variance, RMSE, and the calibration of z (bias, sd, "
@@ -1635,6 +1664,7 @@ def main_test(argv=None):
                  f"--loglik must be 1 to {_lib.NM_MAX_IW_DRAWS}"),
                 (args.loglik_seed is not None and not 0 <= args.loglik_seed < 1 << 64, "--loglik-seed must lie inside [0, 2^64)"),
                 (args.traj_seed is not None and args.trajectory is None, "--traj-seed needs --trajectory"),
+                (args.trajectory_fold is not None and args.trajectory is None, "--trajectory-fold needs --trajectory"),
                 (args.trajectory is not None and (not TRAJ_MIN_ROWS <= args.trajectory <= TRAJ_MAX_ROWS or args.trajectory % 16 != 0),
                  f"--trajectory must be a multiple of 16 from {TRAJ_MIN_ROWS} to {TRAJ_MAX_ROWS}"),
                 (args.traj_seed is not None and not 0 <= args.traj_seed < 1 << 62, "--traj-seed must lie inside [0, 2^62)"),
@@ -1687,6 +1717,7 @@ def main_test(argv=None):
                         quantiles=args.quantiles, centile_loo=args.centile_loo, fit=args.fit, fit_rank=args.fit_rank)
     results = test_folds(fold_jobs, cohort, fold_rows, mods, fold_combines, device, out_dirs=fold_dirs, given=args.given,
                          draws=args.draws, draw_seed=args.draw_seed, trajectory=args.trajectory, traj_seed=args.traj_seed or 0,
+                         trajectory_fold=args.trajectory_fold,
                          loglik=args.loglik, loglik_seed=args.loglik_seed, loglik_name=args.procedure, **vars(o)) if my else []
     given_tags = [tag for tag, _ in given_subsets(args.given, mods)] if args.given else []
     # the pooled entries of every statistic that is on: this rank's folds' test subjects as one set (the maps: against their controls)

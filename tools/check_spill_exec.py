@@ -85,6 +85,10 @@ LIMITS = {
     #  accumulators: the build shows 113 VGPRs and 108 SGPR spills -- the request's pointers and constants stay alive across the
     #  decoders; the ceiling is that count)
     "nm_devpass_iw_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 108, "vgpr_count": 128},
+    # (the decode kernel's body for ONE (cell, decoder) with the fp64 fold in the chunk epilogue: the build shows 69 VGPRs and no
+    #  SGPR spill -- no loop over cells or decoders keeps pointers alive; and the merge of the tile partials, 34 VGPRs)
+    "nm_chart_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 0, "vgpr_count": 128},
+    "nm_chart_merge_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 0, "vgpr_count": 64},
     "nm_rs_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 540},
     "nm_wide_step_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 400},
     # (both instantiations: one workgroup per model / one per decoder, nm_train_steps_head_split)
