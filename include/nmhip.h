@@ -494,6 +494,48 @@ int nm_devpass_iw(const nm_job_t* jobs_dev, int n_jobs, const nm_draw_t* draws_d
                   int tile0, int n_tiles, int flags, void* stream);      /* flags: 0 or NM_F_TRACE */
 int nm_devpass_iw_ok(const nm_job_t* job_host);
 int nm_iw_check(const nm_job_t* job_host, const nm_iw_t* iw_host);
+/* The evaluation pass of cVAE_multimodal_endtoend (csrc/nm_e2e.inc: nm_e2e_kernel; cVAE.py:2021-2207) over table rows
+ * [tile0 * 128, (tile0 + n_tiles) * 128), one workgroup per (job, 128-row tile): every expert's encoder chain and the fusion
+ * of nm_forward (out_mu / out_logvar where the job has them), the latent -- use_mean = 1: z = mu_joint; use_mean = 0:
+ * nm_forward's draw of that row, keyed (seed, row / 256, row, z), or the job's injected eps -- (out_z), the classifier in
+ * eval mode on mu_joint (cls_use_mu) or on z: Linear, BatchNorm1d with the running statistics in params and
+ * 1 / sqrtf(var + 1e-5f), ReLU, no dropout, then the logits layer, in nm_head_classifier's order of operations
+ * (out_logits; the running statistics are never written), and all M = 2 M_enc decoders (health bank k < M_enc, disease bank
+ * M_enc <= k < M) with nm_devpass_multi's export epilogue: out_loc / out_sqerr / out_rowdev of decoder k where the pointer
+ * is set AND bit k of want_mask is, dead 16-row tiles skipped and their export rows zeroed.  A decoder with no export
+ * wanted is skipped unless the row table needs it.  Per subject, row [rows_alloc][NM_E2E_ROW_COLUMNS] fp32, each written by
+ * the lane that owns the row, no atomics, contraction off, C = cls_classes, logits l_k:
+ *   p_disease   = (sum_{k>=1} e_k) / (sum_k e_k), e_k = expf(l_k - max_k l_k), sums in index order
+ *   pred        = first index of the maximum logit, as a float
+ *   margin      = max_{k>=1} l_k - l_0
+ *   dev_health  = (((d_0 + d_1) + ...) + d_{M_enc-1}) / M_enc, d_m = the value out_rowdev of decoder m receives (cVAE.py:2170)
+ *   dev_disease = the same over decoders M_enc + m (:2171)
+ *   contrast    = dev_health - dev_disease
+ *   kl          = -0.5 * sum_z (((1 + lv) - mu^2) - expf(lv)) of the joint posterior (four interleaved partial sums p_i over
+ *                 z = i, i + 4, ... or, Z a multiple of 4, over the quads 4 i .., 4 (i + 4) ..; (p_0 + p_1) + (p_2 + p_3))
+ *   status      = 0; 1 if a logit, a deviation or a latent statistic of the row is not finite
+ * Rows from the table's end to the end of its last 256-row tile come back as zeros -- of the row table, of the wanted
+ * decoder exports and of out_mu / out_logvar / out_z / out_logits alike; nothing a buffer held before the launch enters a result; a row's bytes do not depend on the launch's other jobs or tiles.  row = NULL: no table, and the decoders
+ * run only for their exports.  LDS: 96,592 bytes, one workgroup per CU.  Workspace tiles as for nm_devpass_multi.
+ *   Admitted (nm_e2e_pass_ok): not wide; 1 <= M_enc <= NM_MAX_EXP and M == 2 M_enc; n_private == 0, tc_weight == 0,
+ * w_off < 0, out_kind == 0; 1 <= Z <= NM_MAX_LATENT and Z + C <= NM_MAX_WIDTH; H[0] <= 112, every H in 1..NM_MAX_WIDTH;
+ * 0..NM_MAX_CLS classifier blocks, each 1..128 wide (the one-tile head), 2..NM_MAX_CLASSES classes; with NM_COMBINE_GPOE
+ * every expert's alpha offset >= 0 (the end-to-end class registers none: its combiner is the product of experts);
+ * NM_E_DEVPASS otherwise
+ * (such a job is evaluated by nm_forward + nm_head_classifier), NM_E_NULL for a null pointer.  Status of the launch is
+ * decided on the host before the device is asked anything: NM_E_NULL for a missing array, NM_E_GEOMETRY by the geometry
+ * rules of every launch; the kernel makes a refused job's workgroups leave at once. */
+#define NM_E2E_ROW_COLUMNS 8
+typedef struct nm_e2e_t {
+  float*  row;                       /* [rows_alloc][NM_E2E_ROW_COLUMNS], or NULL */
+  int32_t use_mean;                  /* 1: z = mu_joint; 0: the draw */
+  int32_t want_mask;                 /* bit k: decoder k's out_loc / out_sqerr / out_rowdev are written */
+} nm_e2e_t;
+int nm_e2e_pass(const nm_job_t* jobs_dev, int n_jobs, const nm_e2e_t* req_dev, int tile0, int n_tiles, int flags, void* stream);
+int nm_e2e_pass_ok(const nm_job_t* job_host);
+/* NM_E_OFFSETS for a job that asks for NM_COMBINE_GPOE while an expert has no alpha offset (no route can evaluate it: every
+ * kernel would read params[-1]); NM_OK otherwise, NM_E_NULL for a null pointer. */
+int nm_e2e_alpha_ok(const nm_job_t* job_host);
 /* The encoder half alone (csrc/nm_devpass.hip: nm_latent_kernel): the joint posterior of every row, what cVAE.pred_latent
  * returns (cVAE.py:539-545), over table rows [tile0 * 128, (tile0 + n_tiles) * 128).  Every expert's encoder and the fusion
  * of nm_forward, no latent draw and no decoder; writes out_mu / out_logvar and nothing else -- bit for bit nm_forward's

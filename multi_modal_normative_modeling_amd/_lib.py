@@ -95,6 +95,7 @@ NM_MAX_DRAWS = 64
 # nm_devpass_iw: the most latent draws per row (no accumulators between the draws), and the columns of its row export
 NM_MAX_IW_DRAWS = 1024
 NM_IW_ROW_COLUMNS = 8
+NM_E2E_ROW_COLUMNS = 8
 # nm_decode_pass: the most covariate cells of a request
 NM_MAX_CELLS = 64
 # nm_chart_pass: the most rows of a request, and the columns of a chart row (mean, var_latent, n_rows, status)
@@ -202,6 +203,11 @@ class NmIw(C.Structure):
                 ("ll_const", C.c_float * NM_MAX_EXP), ("dec_mask", C.c_uint32)]
 
 
+class NmE2e(C.Structure):
+    """nm_e2e_t: one job's request, nm_e2e_pass' [n_jobs] table (device memory)."""
+    _fields_ = [("row", C.c_void_p), ("use_mean", C.c_int32), ("want_mask", C.c_int32)]
+
+
 class NmDecode(C.Structure):
     """nm_decode_t: one job's request, nm_decode_pass' [n_jobs] table (device memory)."""
     _fields_ = [("z", C.c_void_p), ("n_rows", C.c_int32), ("rows_alloc", C.c_int32), ("n_cells", C.c_int32),
@@ -302,6 +308,9 @@ def load():
     lib.nm_devpass_iw.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, vp]
     lib.nm_devpass_iw_ok.argtypes = [C.POINTER(NmJob)]
     lib.nm_iw_check.argtypes = [C.POINTER(NmJob), C.POINTER(NmIw)]
+    lib.nm_e2e_pass.argtypes = [vp, i32, vp, i32, i32, i32, vp]
+    lib.nm_e2e_pass_ok.argtypes = [C.POINTER(NmJob)]
+    lib.nm_e2e_alpha_ok.argtypes = [C.POINTER(NmJob)]
     lib.nm_latent_pass.argtypes = [vp, i32, i32, i32, i32, vp]
     lib.nm_latent_pass_ok.argtypes = [C.POINTER(NmJob)]
     lib.nm_decode_pass.argtypes = [vp, i32, vp, i32, i32, i32, vp]
@@ -389,6 +398,7 @@ EXPORTED_SYMBOLS = [
     "nm_decode_pass", "nm_decode_pass_ok",
     "nm_chart_pass", "nm_chart_pass_ok",
     "nm_fit_quality", "nm_fit_rank",
+    "nm_e2e_pass", "nm_e2e_pass_ok", "nm_e2e_alpha_ok",
 ]
 
 

@@ -27,7 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .engine import CHART_AUTO, DECODE_AUTO, Job, JobSet, Table, adam_step, draw_seeds, latent_scores, latent_stats, require_gpu
+from .engine import CHART_AUTO, DECODE_AUTO, E2E_AUTO, Job, JobSet, Table, adam_step, draw_seeds, latent_scores, latent_stats, require_gpu
 from .layout import ModelSpec, ParamLayout
 
 
@@ -217,8 +217,11 @@ class _Base(nn.Module):
 
     def _run(self, xes: Sequence[torch.Tensor], cs: Sequence[torch.Tensor], combine: str, flags: int, eps=None,
              kl_w=None, ll_w=1.0, recon_only: bool = False, latent_only: bool = False, subsets=None, present=None, draws=None,
-             loglik=None):
-        """loglik (pred_loglik: (S, the S generator keys, the decoder indices or None)): the launch is the likelihood pass
+             loglik=None, endtoend=None):
+        """endtoend (pred_scores / predict_proba of the end-to-end model: (latent, seed, compact, logits_only)): the launch is the
+        evaluation pass (JobSet.forward_endtoend: eval-mode classifier on the joint mean, both decoder banks, the per-subject
+        row table in job.e2e_row); a seed selects the in-kernel generator for latent="draw".
+        loglik (pred_loglik: (S, the S generator keys, the decoder indices or None)): the launch is the likelihood pass
         (JobSet.forward_loglik: encoders once, the S importance weights folded per subject on the device), its values in
         job.iw_row / iw_recon_ll.
         draws (pred_recon_draws: (S, the S generator keys)): the launch is the posterior-predictive pass
@@ -300,6 +303,20 @@ class _Base(nn.Module):
                     or j.iw_row.shape[0] != j.tables[0].rows_alloc):
                 j.enable_likelihood_exports(S, seeds=seeds, decoders=dec, per_modality=True)
             self._js.forward_loglik(0, nt)
+        elif endtoend is not None:
+            lat, seed, compact, logits_only = endtoend
+            if not getattr(j, "e2e_enabled", False) or j.e2e_row is None or j.e2e_row.shape[0] != j.tables[0].rows_alloc:
+                j.enable_endtoend_exports(rows=True, loc=True, sqerr=True, rowdev=True)
+            self._head_setup(j, use_mu=True)                     # classifier(mu_combined), cVAE.py:2202-2207; eval mode in the pass
+            held = (j.eps, j.eps_cap, j.seed)
+            if lat == "draw" and seed is not None:
+                j.seed = int(seed)
+                j.set_eps(None)
+            try:
+                self._js.forward_endtoend(lat, compact, 0, nt, logits_only=logits_only)
+            finally:
+                (j.eps, j.eps_cap, j.seed) = held
+                j.touch()
         elif recon_only and flags == _lib.NM_F_EXPORT:
             self._js.forward(0, nt, loss=False)
         elif latent_only and flags == _lib.NM_F_EXPORT:
@@ -1369,8 +1386,43 @@ class cVAE_multimodal_endtoend(_HeadBase):
         self._grads_ready = True
         self._assign_grads()
 
+    def _evaluate(self, xes, cs, latent: str = "mean", seed=None, compact=None, logits_only: bool = False):
+        """One evaluation pass in eval mode, classifier on the joint mean: (job, rows).  The module's mode, the running
+        statistics and the batch counters stay as they are."""
+        if latent not in ("mean", "draw"):
+            raise ValueError("latent: 'mean' or 'draw'")
+        B = int(xes[0].shape[0])
+        # (latent="draw" without a seed: the draw comes from torch's generator, as forward()'s does; else nothing is drawn)
+        eps = None if (latent == "draw" and seed is None) else torch.zeros(B, self.spec.latent)
+        return self._run(xes, cs, "poe", _lib.NM_F_EXPORT, eps=eps, endtoend=(latent, seed, compact, logits_only))
+
+    def pred_scores(self, xes, cs, latent: str = "mean", seed=None):
+        """Per subject, as a DataFrame: the eight columns of metrics.ENDTOEND_ROW_COLUMNS (p_disease, pred, margin, dev_health,
+        dev_disease, contrast, kl, status), logit_<k> per class and dev_health_<m> / dev_disease_<m> per modality, from one
+        evaluation pass (JobSet.forward_endtoend): always eval mode (running statistics, no dropout), classifier on the joint
+        mean as predict() has it.  latent: what the decoder banks see -- "mean": the joint mean; "draw": a draw from the joint
+        posterior (seed: the key of the in-kernel generator; None: torch's generator).  Nothing of the module changes."""
+        from .sweep import endtoend_scores_frame
+        with torch.no_grad():
+            j, B = self._evaluate(xes, cs, latent, seed)
+            return endtoend_scores_frame(j, B)
+
+    def predict_proba(self, xes, cs):
+        """[B, num_classes]: softmax of the evaluation pass's logits (predict()'s logits, bit for bit)."""
+        with torch.no_grad():
+            j, B = self._evaluate(xes, cs, logits_only=True)
+            return torch.softmax(j.out_logits[:B, : self.num_classes], dim=1)
+
     def predict(self, xes, cs):
         with torch.no_grad():
+            env = os.environ.get("NMHIP_E2E", "auto")
+            # the pass where E2E_AUTO / NMHIP_E2E=1 pick it, asked for the logits alone (no decoder runs) -- for one batch, where
+            # it returns this route's bytes; beyond 256 rows this route's classifier launch covers the first batch only, and
+            # predict() keeps what it returns there
+            if (not self.training and int(xes[0].shape[0]) <= _lib.NM_BATCH
+                    and (env == "1" or (env != "0" and E2E_AUTO.get(self.spec.M, False)))):
+                j, B = self._evaluate(xes, cs, logits_only=True)
+                return j.out_logits[:B, : self.num_classes].clone()
             j, B = self._run(xes, cs, "poe", _lib.NM_F_EXPORT)
             self._head_setup(j, use_mu=True)                     # classifier(mu_combined), cVAE.py:2202-2207
             JobSet([j]).head_classifier(backward=False, bn_stats=self.training)

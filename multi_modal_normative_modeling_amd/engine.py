@@ -46,6 +46,13 @@ DECODE_AUTO = {1: False, 2: False, 3: False, 4: False}
 # profiles/chart_pass.json).  All off: the route is reached with fold="kernel" or NMHIP_CHART=1
 CHART_AUTO = {1: False, 2: False, 3: False, 4: False}
 
+# nm_e2e_pass as the automatic route of JobSet.forward_endtoend (and of cVAE_multimodal_endtoend.predict), per number of
+# experts of the model: by the same rule (the new kernel's slowest repeat against the fastest of forward + head_classifier +
+# the torch fold at EVERY set size measured, tools/bench_endtoend_eval.py, profiles/endtoend_eval.json, DESIGN.md section
+# 4b).  All off: three experts win from 1 to 20 models and with five folds in one launch, and lose with the logits alone at
+# 256 models; the other classes have no record.  The route is reached with compact=True or NMHIP_E2E=1
+E2E_AUTO = {1: False, 2: False, 3: False, 4: False}
+
 _MASK64 = (1 << 64) - 1
 
 
@@ -722,6 +729,59 @@ class Job:
             q.ll_const[m] = self.iw_ll_const[m]
         return draws, q
 
+    # -- the end-to-end model's evaluation pass (nm_e2e_pass) --------------------------------------
+    def _e2e_answers(self):
+        """(nm_e2e_pass_ok, nm_e2e_alpha_ok) of this job's shape descriptor: the library's answers, no copy of its rules here.
+        Asked again whenever the descriptor or one of the attributes it carries beside the shape has changed."""
+        key = (getattr(self, "_version", 0), self.combine, getattr(self, "single_bypass", None), self.tc_weight, self.var_floor)
+        hit = getattr(self, "_e2e_cache", None)
+        if hit is None or hit[0] != key:
+            lib, d = _lib.load(), self._shape_struct()
+            hit = self._e2e_cache = (key, int(lib.nm_e2e_pass_ok(C.byref(d))), int(lib.nm_e2e_alpha_ok(C.byref(d))))
+        return hit[1], hit[2]
+
+    def e2e_ok(self) -> bool:
+        """nm_e2e_pass_ok, asked of this job's shape descriptor: can the job's evaluation run on nm_e2e_pass?"""
+        return self._e2e_answers()[0] == 0
+
+    def _e2e_require_alpha(self, caller: str):
+        """ValueError where the library says no route can fuse this job (nm_e2e_alpha_ok: gPoE without alpha offsets)."""
+        st = self._e2e_answers()[1]
+        if st != 0:
+            raise ValueError(f"{caller}: nm_e2e_alpha_ok refuses the job with status {st} ({_lib.load().nm_status_string(st).decode()}): "
+                             f"gPoE weighs the experts by softmax(alpha) and this model registers no alpha parameters")
+
+    def enable_endtoend_exports(self, rows=True, loc=False, sqerr=False, rowdev=True, latent=True, decoders=None):
+        """Buffers of the end-to-end model's evaluation (JobSet.forward_endtoend, nm_e2e_pass): out_logits always; with
+        rows, e2e_row [rows_alloc, 8] = metrics.ENDTOEND_ROW_COLUMNS per subject; out_loc / out_sqerr / out_rowdev of every
+        decoder (both banks: health k < M, disease M <= k < 2 M) as asked; decoders: the indices whose loc / sqerr /
+        rowdev exports the compact pass writes (default: all; the row table does not depend on it).  latent: out_mu /
+        out_logvar / out_z are results the caller reads; the buffers are allocated either way -- the descriptor's classifier
+        reads out_mu / out_z (nm_validate_job) and the two-launch route reads all three."""
+        if self.spec.kind != "endtoend" or not self.spec.classifier_layers:
+            raise ValueError("enable_endtoend_exports: an end-to-end model (kind 'endtoend' with a classifier) is needed")
+        self._e2e_require_alpha("enable_endtoend_exports")
+        nk = len(self.kmods)
+        dec = list(range(nk)) if decoders is None else sorted({int(m) for m in decoders})
+        if dec and (dec[0] < 0 or dec[-1] >= nk):
+            raise ValueError(f"decoders: a subset of 0..{nk - 1}, got {decoders}")
+        self.enable_exports(loc=loc, sqerr=sqerr, rowdev=rowdev, latent=True)
+        if self.out_logits is None:
+            self.out_logits = torch.zeros(self.tables[0].rows_alloc, _lib.NM_MAX_CLASSES, device=self.device)
+        self.e2e_latent = bool(latent)
+        self.e2e_mask = sum(1 << m for m in dec)
+        self.e2e_row = torch.zeros(self.tables[0].rows_alloc, _lib.NM_E2E_ROW_COLUMNS, device=self.device) if rows else None
+        self.e2e_enabled = True
+        self._version += 1
+
+    def e2e_struct(self, use_mean: bool) -> "_lib.NmE2e":
+        if not getattr(self, "e2e_enabled", False):
+            raise ValueError("enable_endtoend_exports() first")
+        q = _lib.NmE2e()
+        q.row = self.e2e_row.data_ptr() if self.e2e_row is not None else None
+        q.use_mean, q.want_mask = int(bool(use_mean)), self.e2e_mask
+        return q
+
     def set_latent_exports(self, on: bool):
         """Switch the joint-latent exports (out_mu / out_logvar / out_z) of a job that has them off and back on; the
         buffers are kept.  Off, a reconstruction-only forward (JobSet.forward(loss=False)) can run on the compact kernels."""
@@ -934,7 +994,10 @@ class Job:
             return "poe"
         return self.combine
 
-    def struct(self) -> _lib.NmJob:
+    def _shape_struct(self) -> _lib.NmJob:
+        """A descriptor holding the model's shape alone -- decoders, experts, widths, latent, output kind, the head's blocks
+        and offsets -- and no buffer: what struct() starts from, and what the library's *_ok predicates are asked about
+        where no device is needed (e2e_ok)."""
         s, j = self.spec, _lib.NmJob()
         j.M, j.M_enc, j.C, j.L, j.Z = len(self.kmods), s.M, s.net_c_dim, len(s.hidden), s.latent
         # DMVAE family: ReLU, sigmoid / squared-error output, private latent columns, learnable loss weights
@@ -945,15 +1008,22 @@ class Job:
         j.var_floor, j.tc_weight = self.var_floor, self.tc_weight
         for i, h in enumerate(s.hidden):
             j.H[i] = h
+        j.wide = int(s.wide)
         j.combine = _lib.NM_COMBINE[self.kernel_combine()]
         j.single_bypass = 1 if self.single_bypass else 0
+        for k in range(len(self.kmods)):              # every tensor's offset (alpha: -1 where the class registers none)
+            self.layout.fill_modality(j.mod[k], k)
+        self.layout.fill_head(j)
+        return j
+
+    def struct(self) -> _lib.NmJob:
+        s, j = self.spec, self._shape_struct()
         j.n_rows = self.tables[0].N
         j.non_linear = 1 if (s.non_linear or s.is_dm) else 0        # (torch.relu unconditionally, cVAE.py:1462-1463)
         j.dephase = int(self.dephase_sleeps)
         k0 = self.tables[0].c_key
         j.shared_cov = 1 if (k0 is not None and all(t.c_key == k0 for t in self.tables)) else 0
         self._shared_cov = int(j.shared_cov)
-        j.wide = int(s.wide)
         j.loss_cap, j.eps_cap = self.loss_cap, self.eps_cap
         j.lr, j.beta1, j.beta2, j.adam_eps = self.lr, self.betas[0], self.betas[1], self.adam_eps
         j.adam_off = self.t - self.step
@@ -975,7 +1045,6 @@ class Job:
         j.out_logvar = self.out_logvar.data_ptr() if self.out_logvar is not None else None
         j.out_z = self.out_z.data_ptr() if self.out_z is not None else None
         j.dz_extra = self.dz_extra.data_ptr() if self.dz_extra is not None else None
-        self.layout.fill_head(j)
         if j.reg_head:
             self.prepare_regression()
             j.reg_resid, j.reg_dres = self.reg_resid.data_ptr(), self.reg_dres.data_ptr()
@@ -1680,6 +1749,110 @@ class JobSet:
         nt = max(j.chart_rows_alloc for j in self.jobs) // BATCH if n_tiles is None else n_tiles
         self._issue("nm_chart_pass", 1, self._chart_keep.data_ptr(), tile0 * 2, nt * 2, max(j.chart_cells for j in self.jobs), 0)
 
+    # -- the end-to-end model's evaluation ---------------------------------------------------------
+    def e2e_ok(self) -> bool:
+        """Can the set's evaluation run on nm_e2e_pass (every job passes the library's nm_e2e_pass_ok)?  NMHIP_E2E=0
+        switches the kernel off."""
+        if self.wide or os.environ.get("NMHIP_E2E", "auto") == "0":
+            return False
+        return all(j.e2e_ok() for j in self.jobs)
+
+    def e2e_pick(self) -> bool:
+        """The automatic route of forward_endtoend: e2e_ok() and a class of sets E2E_AUTO has switched on (by the number of
+        experts); NMHIP_E2E=1 forces the pass on where the set passes e2e_ok()."""
+        if not self.e2e_ok():
+            return False
+        return os.environ.get("NMHIP_E2E", "auto") == "1" or all(E2E_AUTO.get(j.spec.M, False) for j in self.jobs)
+
+    def _e2e_refusal(self) -> str:
+        if os.environ.get("NMHIP_E2E", "auto") == "0":
+            return "NMHIP_E2E=0"
+        if self.wide:
+            return "general-shape path (a hidden width or latent beyond the fused kernel's tile)"
+        for i, j in enumerate(self.jobs):
+            if not j.e2e_ok():
+                s = j.spec
+                return (f"job {i}: nm_e2e_pass_ok refuses its shape (kind {s.kind!r}, {s.M} experts, {len(j.kmods)} decoders, "
+                        f"hidden {list(s.hidden)}, latent {s.latent}, classifier {list(s.classifier_layers or ())}, "
+                        f"{s.num_classes} classes)")
+        return "nothing"
+
+    def forward_endtoend(self, latent: str = "mean", compact: Optional[bool] = None, tile0: int = 0, n_tiles: Optional[int] = None,
+                         trace: bool = False, logits_only: bool = False):
+        """The evaluation of cVAE_multimodal_endtoend jobs over row tiles, all jobs of the set at once: the joint posterior,
+        the latent (latent="mean": z = mu_joint; "draw": the forward kernel's draw of every row, or the job's injected eps),
+        the classifier in eval mode (on mu_joint where job.cls_use_mu, else on z), both decoder banks, and per subject
+        job.e2e_row (metrics.ENDTOEND_ROW_COLUMNS) -- into the buffers of Job.enable_endtoend_exports.  compact: None = the
+        automatic pick (e2e_pick); True = insist on nm_e2e_pass, one launch (ValueError naming the refusal if the set cannot
+        run there); False = the two-launch route, forward(loss=False) + head_classifier + the row table folded with fp32
+        torch operations in the kernel's order -- also the route of every set nm_e2e_pass_ok refuses (a trunk on the
+        general-shape path, a classifier with blocks wider than 128).  Both routes leave cls_train off (model.eval()); the
+        running statistics are never written.  logits_only: this call wants out_logits (and the latent exports) alone, whatever
+        buffers the jobs hold -- the pass then runs no decoder and writes no row table, the two-launch route skips the fold.
+        The two-launch route keeps the jobs' descriptors as they are wherever it can: with latent="draw" nothing of a job
+        changes; with "mean" a job whose eps is not already the all-zero draw gets it installed for the call (a device
+        buffer kept with the job) and its own back afterwards, which costs that job a descriptor upload."""
+        if latent not in ("mean", "draw"):
+            raise ValueError("latent: 'mean' or 'draw'")
+        if any(not getattr(j, "e2e_enabled", False) for j in self.jobs):
+            raise ValueError("forward_endtoend: Job.enable_endtoend_exports() first, on every job of the set")
+        if compact and not self.e2e_ok():
+            raise ValueError("compact=True: the set cannot run on nm_e2e_pass: " + self._e2e_refusal())
+        nt = self.jobs[0].tables[0].n_tiles if n_tiles is None else n_tiles
+        for j in self.jobs:
+            j._e2e_require_alpha("forward_endtoend")
+            if j.cls_train:
+                j.cls_train = False
+                j._version += 1
+        if compact or (compact is None and self.e2e_pick()):
+            sig = (latent, logits_only, tuple(j._version for j in self.jobs))
+            if getattr(self, "_e2e_sig", None) != sig:
+                rows = [j.e2e_struct(latent == "mean") for j in self.jobs]
+                for q in rows:
+                    if logits_only:
+                        q.row, q.want_mask = None, 0
+                reqs = (_lib.NmE2e * len(self.jobs))(*rows)
+                self._e2e_keep = torch.frombuffer(bytearray(bytes(reqs)), dtype=torch.uint8).to(self.device)
+                self._e2e_sig = sig
+            # (one workspace tile per 256-row batch: the two 128-row workgroups of a batch share it on disjoint rows)
+            self._issue("nm_e2e_pass", nt, self._e2e_keep.data_ptr(), tile0 * 2, nt * 2, _lib.NM_F_TRACE if trace else 0)
+            return
+        # ---- the two-launch route ----
+        stash = []
+        for j in self.jobs:
+            held = None
+            # an all-zero draw: z = mu_joint + 0 * exp(logvar / 2) (not needed where only a classifier on mu is read)
+            if latent == "mean" and not (logits_only and j.cls_use_mu):
+                zero = getattr(j, "_e2e_zero_eps", None)
+                if zero is None or zero.shape[2] != j.spec.latent:
+                    zero = j._e2e_zero_eps = torch.zeros(1, BATCH, j.spec.latent, device=j.device)
+                if j.eps is not zero:
+                    held = (j.eps, j.eps_cap)
+                    j.eps, j.eps_cap = zero, 1
+                    j._version += 1
+            rowdev = None
+            if not logits_only and j.e2e_row is not None and any(o is None for o in j.out_rowdev):
+                rowdev = list(j.out_rowdev)
+                j.out_rowdev = [o if o is not None else torch.zeros(j.tables[0].rows_alloc, device=j.device) for o in j.out_rowdev]
+                j._version += 1
+            stash.append((held, rowdev))
+        self.forward(tile0=tile0, n_tiles=nt, loss=False, compact=False)
+        self.head_classifier(backward=False, tile0=tile0, n_tiles=nt)
+        for j, (held, rowdev) in zip(self.jobs, stash):
+            r0, r1 = tile0 * BATCH, min((tile0 + nt) * BATCH, j.tables[0].rows_alloc)
+            if not logits_only and j.e2e_row is not None:
+                _endtoend_row_fold(j, r0, r1)
+            if j.tables[0].N < r1:                      # rows past the table: zeros, as from the pass
+                for t in (j.out_mu, j.out_logvar, j.out_z, j.out_logits):
+                    if t is not None:
+                        t[max(r0, j.tables[0].N):r1] = 0.0
+            if held is not None:
+                j.eps, j.eps_cap = held
+                j._version += 1
+            if rowdev is not None:
+                j.out_rowdev = rowdev
+                j._version += 1
+
     def latent_stats(self):
         """Per job the column means and population variances of its exported joint mu over the table's rows (the training
         cohort's latent distribution, utils_vae.py:156-157) -- all jobs of the set in ONE launch of nm_latent_stats.
@@ -1855,6 +2028,43 @@ class JobSet:
         if not bool(ok.all()):
             bad = int((~ok).nonzero()[0])
             raise _lib.NmError(f"non-finite loss in job {bad} of {len(self.jobs)} (step {self.jobs[bad].step})")
+
+
+def _endtoend_row_fold(j: Job, r0: int, r1: int):
+    """job.e2e_row over table rows [r0, r1) from the job's exports (out_logits, out_rowdev of every decoder, out_mu,
+    out_logvar): nm_e2e_pass' definition (include/nmhip.h) in fp32 torch operations, operation by operation; rows past the
+    table's end are zeros."""
+    n1 = min(r1, j.tables[0].N)
+    j.e2e_row[r0:r1] = 0.0
+    if n1 <= r0:
+        return
+    Cn, Me, Z = j.spec.num_classes, j.spec.M, j.spec.latent
+    lg = j.out_logits[r0:n1, :Cn]
+    e = torch.exp(lg - lg.max(dim=1, keepdim=True).values)
+    sd, sa = e[:, 1].clone(), e[:, 0] + e[:, 1]
+    for k in range(2, Cn):
+        sd, sa = sd + e[:, k], sa + e[:, k]
+    dev = [o[r0:n1] for o in j.out_rowdev]
+    dh, dd = dev[0].clone(), dev[Me].clone()
+    for m in range(1, Me):
+        dh, dd = dh + dev[m], dd + dev[Me + m]
+    dh, dd = dh / torch.full_like(dh, Me), dd / torch.full_like(dd, Me)      # (a true division: by a Python scalar torch multiplies by 1 / Me)
+    mu, lv = j.out_mu[r0:n1], j.out_logvar[r0:n1]
+    t = ((1.0 + lv) - mu * mu) - torch.exp(lv)
+    # four interleaved partial sums: columns i, i + 4, ... (Z a multiple of 4: quads 4 i .., 4 (i + 4) ..), (p0 + p1) + (p2 + p3)
+    cols = [[z for q in range(i, Z // 4, 4) for z in range(4 * q, 4 * q + 4)] if Z % 4 == 0 else list(range(i, Z, 4)) for i in range(4)]
+    parts = []
+    for cs in cols:
+        p = torch.zeros(n1 - r0, device=t.device)
+        for z in cs:
+            p = p + t[:, z]
+        parts.append(p)
+    kl = -0.5 * ((parts[0] + parts[1]) + (parts[2] + parts[3]))
+    bad = ~(torch.isfinite(lg).all(dim=1) & torch.isfinite(mu).all(dim=1) & torch.isfinite(lv).all(dim=1))
+    for d in dev:
+        bad = bad | ~torch.isfinite(d)
+    j.e2e_row[r0:n1] = torch.stack([sd / sa, torch.argmax(lg, dim=1).float(), lg[:, 1:].max(dim=1).values - lg[:, 0], dh, dd, dh - dd,
+                                    kl, bad.float()], dim=1)
 
 
 def _latent_sets(arrays: Sequence[torch.Tensor]):

@@ -44,6 +44,11 @@ COLUMN_REGRESS_COLUMNS = ("const", "coef", "se_const", "se_coef", "p_const", "p_
 # the row export of the likelihood pass (nm_devpass_iw, JobSet.forward_loglik): NM_IW_ROW_COLUMNS values per subject
 LOGLIK_ROW_COLUMNS = ("log_px", "elbo", "ess", "kl_mc", "kl", "recon_ll", "logw_max", "logw_min")
 assert len(LOGLIK_ROW_COLUMNS) == _lib.NM_IW_ROW_COLUMNS
+# the row export of the end-to-end model's evaluation pass (nm_e2e_pass, JobSet.forward_endtoend): NM_E2E_ROW_COLUMNS values
+# per subject -- class probability, hard prediction, logit margin, mean deviation under the health / disease decoder bank and
+# their difference (positive: the disease bank fits the subject better), the analytic KL, status 0 / 1 (a non-finite value)
+ENDTOEND_ROW_COLUMNS = ("p_disease", "pred", "margin", "dev_health", "dev_disease", "contrast", "kl", "status")
+assert len(ENDTOEND_ROW_COLUMNS) == _lib.NM_E2E_ROW_COLUMNS
 # a row of the normative chart (engine.JobSet.chart, nm_chart_pass): per (cell, ROI) the mean and the unbiased variance of
 # x_hat over the request's latent rows, the row count, and status 0 / -2 (fewer than two rows, or a non-finite value)
 CHART_COLUMNS = ("mean", "var_latent", "n_rows", "status")

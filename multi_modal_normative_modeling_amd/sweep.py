@@ -347,14 +347,22 @@ def run_endtoend_folds(cohort: prep.SyntheticCohort, folds_to_run: Sequence[int]
                        modalities: Sequence[str] = prep.HCP_MODALITIES, latent: int = 64,
                        classifier_layers: Sequence[int] = (128, 64, 32), dropout_rate: float = 0.5, margin: float = 1.0,
                        weightcontrastive: float = 0.1, lr: float = 1e-4, hc_label: int = 1,
-                       hidden: Sequence[int] = workload.HIDDEN):
+                       hidden: Sequence[int] = workload.HIDDEN, scores: bool = False, score_latent: str = "mean", out_dir=None,
+                       procedure: str = "SE-PoE"):
     """multimodal_kfold_cvae_nmpmcont.py:180-320 for the given folds, all folds training concurrently:
     cVAE_multimodal_endtoend (shared encoders, PoE, health / disease decoder banks, classifier on z) on
     RobustScaler-ed tables with the 29 one-hot covariates and labels healthy = 0 / disease = 1 (:118), batches in
     table order (shuffle=False, :213); then evaluate() (:29-70) on the held-out fold -- eval mode, classifier on
     the joint mean, argmax -- with the confusion metrics computed on the device.  The cyclic learning-rate
     arithmetic of :266-270 is inert in the reference (it assigns an attribute the optimizer never reads), so
-    the optimizer runs at its constructor lr here as there."""
+    the optimizer runs at its constructor lr here as there.
+    scores: the held-out folds are evaluated as ONE JobSet in one launch (JobSet.forward_endtoend: class probabilities, the
+    per-bank deviations and their contrast per subject, metrics.ENDTOEND_ROW_COLUMNS) in the place of one forward +
+    head_classifier pair per fold; the returned dicts keep their keys and values (the hard predictions are the same) and
+    gain auroc_prob, the ROC-AUC of p_disease (metrics.posthoc_metrics).  score_latent: the latent the decoders of that pass
+    see ("mean" or "draw"; the classifier reads the joint mean either way).  out_dir (with scores): per fold
+    <out_dir>/<fold:03d>/endtoend_<procedure>.csv and the pooled <out_dir>/endtoend_<procedure>.csv -- participant_id, DIA,
+    label, fold, then endtoend_scores_frame's columns -- which `analysis --endtoend-score` reads."""
     folds = prep.kfold_indices(len(cohort.iid), n_folds, 42)
     labels_all = (cohort.dia != hc_label).astype(np.int32)
     jobs, scalers = [], []
@@ -383,8 +391,8 @@ def run_endtoend_folds(cohort: prep.SyntheticCohort, folds_to_run: Sequence[int]
     torch.cuda.synchronize(device)
     js.assert_finite()
     sps = n * len(jobs) / max(time.perf_counter() - t0, 1e-9)
-    preds, labs, finals = [], [], []
-    for k, j, sc in zip(folds_to_run, jobs, scalers):
+    preds, labs, finals, evs = [], [], [], []
+    for k, j, sc in zip(folds_to_run, jobs, scalers):        # the held-out fold of every model as an eval-mode job
         te = folds[k][1]
         xs = [prep.robust_scaler_transform(prep.source_table(cohort, m)[te], *sc[i]).astype(np.float32) for i, m in enumerate(modalities)]
         cov = prep.one_hot_covariates(cohort.age[te], cohort.gender[te])           # re-binned on the test rows (:203-209)
@@ -392,22 +400,71 @@ def run_endtoend_folds(cohort: prep.SyntheticCohort, folds_to_run: Sequence[int]
         ev = Job(j.spec, tables, combine="poe", state=j.state_dict(), seed=j.seed + 17, single_bypass=False,
                  n_tiles_ws=tables[0].n_tiles)
         ev.cls_train, ev.cls_use_mu = False, True                                   # model.eval(); predict(): classifier(mu)
-        ev.enable_exports(loc=False, sqerr=False, rowdev=False, latent=True)
-        es = JobSet([ev])
-        es.forward()
-        es.head_classifier(backward=False, tile0=0, n_tiles=tables[0].n_tiles)
-        preds.append(torch.argmax(ev.out_logits[: len(te), :2], dim=1).to(torch.int32))
+        evs.append(ev)
         labs.append(torch.as_tensor(labels_all[te]))
         last = (j.step - 1) % j.loss_cap
         finals.append([float(v) for v in j.loss_log[last, [0, 13, 14]]])
+    frames, auroc_prob = [], None
+    if scores:
+        for ev in evs:
+            ev.enable_endtoend_exports(rows=True, rowdev=True)
+        JobSet(evs).forward_endtoend(latent=score_latent, n_tiles=max(e.tables[0].n_tiles for e in evs))
+        torch.cuda.synchronize(device)
+        pcol, dcol = (metrics.ENDTOEND_ROW_COLUMNS.index(c) for c in ("pred", "p_disease"))
+        for k, ev in zip(folds_to_run, evs):
+            te = folds[k][1]
+            preds.append(ev.e2e_row[: len(te), pcol].to(torch.int32))               # (first index of the maximum logit: argmax)
+            df = endtoend_scores_frame(ev, len(te))
+            df.insert(0, "fold", k)
+            df.insert(0, "label", labels_all[te])
+            df.insert(0, "DIA", np.asarray(cohort.dia)[te])
+            df.insert(0, "participant_id", np.asarray(cohort.iid)[te])
+            frames.append(df)
+        ph = metrics.posthoc_metrics([e.e2e_row[: len(folds[k][1]), dcol].contiguous() for k, e in zip(folds_to_run, evs)],
+                                     [l.to(torch.int32) for l in labs], device=device).cpu()
+        auroc_prob = [float(v) for v in ph[:, metrics.POSTHOC_COLUMNS.index("roc_auc")]]
+        if out_dir is not None:
+            import pandas as pd
+            root = Path(out_dir)
+            for k, df in zip(folds_to_run, frames):
+                (root / f"{k:03d}").mkdir(parents=True, exist_ok=True)
+                df.to_csv(root / f"{k:03d}" / f"endtoend_{procedure}.csv", index=False)
+            pd.concat(frames, ignore_index=True).to_csv(root / f"endtoend_{procedure}.csv", index=False)
+    else:
+        for k, ev in zip(folds_to_run, evs):
+            ev.enable_exports(loc=False, sqerr=False, rowdev=False, latent=True)
+            es = JobSet([ev])
+            es.forward()
+            es.head_classifier(backward=False, tile0=0, n_tiles=ev.tables[0].n_tiles)
+            preds.append(torch.argmax(ev.out_logits[: len(folds[k][1]), :2], dim=1).to(torch.int32))
     cm = metrics.confusion_metrics(preds, labs, device=device).cpu()
     out = []
     for i, k in enumerate(folds_to_run):
         row = {"fold": k, "steps_per_s": sps, "final_trunk_total": finals[i][0], "final_ce": finals[i][1],
                "final_contrastive": finals[i][2]}
         row.update({name: float(cm[i, c]) for c, name in enumerate(metrics.CONFUSION_COLUMNS)})
+        if auroc_prob is not None:
+            row["auroc_prob"] = auroc_prob[i]
         out.append(row)
     return out
+
+
+def endtoend_scores_frame(job: Job, n_rows: int):
+    """The per-subject table of an end-to-end evaluation (JobSet.forward_endtoend) as a DataFrame: the eight columns of
+    metrics.ENDTOEND_ROW_COLUMNS, logit_<k> per class, dev_health_<m> / dev_disease_<m> per modality (the deviation under
+    each decoder of the two banks)."""
+    import pandas as pd
+    M, Cn = job.spec.M, job.spec.num_classes
+    row = job.e2e_row[:n_rows].cpu().numpy()
+    cols = {name: row[:, i] for i, name in enumerate(metrics.ENDTOEND_ROW_COLUMNS)}
+    lg = job.out_logits[:n_rows].cpu().numpy()
+    for k in range(Cn):
+        cols[f"logit_{k}"] = lg[:, k]
+    for bank, off in (("health", 0), ("disease", M)):
+        for m in range(M):
+            if job.out_rowdev[off + m] is not None:
+                cols[f"dev_{bank}_{m}"] = job.out_rowdev[off + m][:n_rows].cpu().numpy()
+    return pd.DataFrame(cols)
 
 
 def save_model(fold_dir, job: Job, model: str = "cVAE_multimodal", train_ids=None, test_ids=None) -> Path:
@@ -1519,17 +1576,29 @@ def main_endtoend(argv=None, _runner=None):
     ap.add_argument("-Weightrec", "--weight_rec", dest="weight_rec", type=float, default=1)
     ap.add_argument("-Dropout", "--dropout", dest="dropout", type=float, default=0.5)
     ap.add_argument("-Layers", "--layers", dest="layers", nargs="+", type=int, default=[128, 64, 32])
+    ap.add_argument("--scores", action="store_true",
+                    help="evaluate the held-out folds in one launch and keep the per-subject scores: class probability, margin, the "
+                         "deviations under the health / disease decoder banks and their contrast (auroc_prob in the metrics; with "
+                         "--out-dir <out>/<resource>/<procedure>/<fold>/endtoend_<P>.csv, which `analysis --endtoend-score` reads)")
+    ap.add_argument("--score-latent", dest="score_latent", choices=("mean", "draw"), default="mean",
+                    help="with --scores: the latent the decoder banks see -- the joint mean, or a draw from the joint posterior")
     _driver_common(ap)
     args = ap.parse_args(argv)
+    if args.score_latent != "mean" and not args.scores:
+        ap.error("--score-latent needs --scores")
     cohort = _cohort_from_args(args)
     proc = f"SM-{args.single_modality}" if args.single_modality else args.procedure
     mods = [m for m in prep.datasets_name(args.dataset_resourse, proc)]
     device = _local_device()
     runner = _runner or run_endtoend_folds
+    extra = {}
+    if args.scores:                                   # (without --scores the runner is called with the arguments it always had)
+        extra = dict(scores=True, score_latent=args.score_latent, procedure=proc,
+                     out_dir=(Path(args.out_dir) / args.dataset_resourse / proc) if args.out_dir is not None else None)
     res = runner(cohort, _my_folds(args), args.n_splits, args.epochs, device, modalities=mods, latent=int(args.hz_para_list[-1]),
                  classifier_layers=tuple(args.layers), dropout_rate=args.dropout, margin=args.margin,
                  weightcontrastive=args.weightcontrastive, lr=args.base_learning_rate, hc_label=1,
-                 hidden=list(args.hz_para_list[:-1]))
+                 hidden=list(args.hz_para_list[:-1]), **extra)
     for r in res:
         print("[endtoend] " + "  ".join(f"{k} {v:.5g}" if isinstance(v, float) else f"{k} {v}" for k, v in r.items()), flush=True)
     if args.out_dir is not None and res:
@@ -1906,7 +1975,13 @@ ANALYSIS_SCORES = {
     #  deviant, and an improbable subject has a LOW log p(x | c))
     "loglik_logpx": ("loglik_{p}.csv", lambda d: -d["log_px"], " with --loglik S"),
     "loglik_elbo": ("loglik_{p}.csv", lambda d: -d["elbo"], " with --loglik S"),
+    # (--endtoend-score prob / margin / contrast: likewise a flag of its own; the file of `endtoend --scores`.  Larger is more
+    #  patient-like in all three: the disease probability, the logit margin, dev_health - dev_disease)
+    "endtoend_prob": ("endtoend_{p}.csv", lambda d: d["p_disease"], " (the `endtoend` subcommand) with --scores"),
+    "endtoend_margin": ("endtoend_{p}.csv", lambda d: d["margin"], " (the `endtoend` subcommand) with --scores"),
+    "endtoend_contrast": ("endtoend_{p}.csv", lambda d: d["contrast"], " (the `endtoend` subcommand) with --scores"),
 }
+ENDTOEND_SCORES = ("prob", "margin", "contrast")
 TRAJECTORY_SCORES = ("zmean", "extreme")
 LOGLIK_SCORES = ("logpx", "elbo")
 CENTILE_SCORES = ("tails", "depth")
@@ -2189,6 +2264,10 @@ def main_analysis(argv=None):
                          "importance-weighted log p(x | c); elbo: minus the ELBO; writes group_analysis_loglik_<kind>.csv, and "
                          "group_analysis_loglik.csv: the mean and sd over folds of the held-out controls' mean elbo and log_px, the "
                          "label-free comparison of procedures")
+    ap.add_argument("--endtoend-score", dest="endtoend_score", choices=ENDTOEND_SCORES, default=None,
+                    help="instead of --score: the end-to-end model's own score from endtoend_<P>.csv (`endtoend --scores`) -- prob: "
+                         "the disease probability of its classifier; margin: the logit margin; contrast: the deviation under the "
+                         "health decoder bank minus that under the disease bank; writes group_analysis_endtoend_<kind>.csv")
     ap.add_argument("--roi", action="store_true",
                     help="instead: which ROIs separate patients from controls -- per fold and modality every ROI's Cliff's delta and "
                          "ROC-AUC on reconstruction_error_roi_<m>.csv, their mean and std over folds to group_analysis_roi_<m>.csv")
@@ -2240,7 +2319,8 @@ def main_analysis(argv=None):
                          "procedures")
     args = ap.parse_args(argv)
     if args.fit and (args.given or args.roi or args.bootstrap or args.threshold_rule or args.roc_grid or args.score != "reconstruction"
-                     or args.centile_score or args.predictive_score or args.trajectory_score or args.loglik_score):
+                     or args.centile_score or args.predictive_score or args.trajectory_score or args.loglik_score
+                     or args.endtoend_score):
         ap.error("--fit reads the fit tables alone: it goes with no score, --roi, --given, --bootstrap, --threshold-rule or --roc-grid")
     if args.given:
         if args.predictive_score:
@@ -2287,6 +2367,17 @@ def main_analysis(argv=None):
         if args.given:
             ap.error("--given scores the reconstruction error of modality subsets: it does not go with --loglik-score")
         args.score = f"loglik_{args.loglik_score}"
+    if args.endtoend_score:
+        if args.centile_score or args.predictive_score or args.trajectory_score or args.loglik_score:
+            ap.error("--endtoend-score is a score of its own: it does not go with --centile-score, --predictive-score, "
+                     "--trajectory-score or --loglik-score")
+        if args.score != "reconstruction":
+            ap.error("--endtoend-score is a score of its own: it does not go with --score")
+        if args.roi:
+            ap.error("--endtoend-score is a per-subject score: it does not go with --roi")
+        if args.given:
+            ap.error("--given scores the reconstruction error of modality subsets: it does not go with --endtoend-score")
+        args.score = f"endtoend_{args.endtoend_score}"
     if args.threshold_from == "others" and not args.threshold_rule:
         ap.error("--threshold-from others needs --threshold-rule")
     if (args.threshold_rule or args.roc_grid) and args.roi:
