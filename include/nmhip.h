@@ -536,6 +536,52 @@ int nm_e2e_pass_ok(const nm_job_t* job_host);
 /* NM_E_OFFSETS for a job that asks for NM_COMBINE_GPOE while an expert has no alpha offset (no route can evaluate it: every
  * kernel would read params[-1]); NM_OK otherwise, NM_E_NULL for a null pointer. */
 int nm_e2e_alpha_ok(const nm_job_t* job_host);
+/* The evaluation pass of cVAE_multimodal_regression (csrc/nm_fi.inc: nm_fi_kernel; cVAE.py:2249-2253, 2317-2323) over table
+ * rows [tile0 * 128, (tile0 + n_tiles) * 128), one workgroup per (job, 128-row tile): every expert's encoder chain and the
+ * fusion of nm_forward once (out_mu / out_logvar where the job has them), then for draw s = 0 .. n_draws - 1 the latent --
+ * draws_dev == NULL and n_draws == 1: nm_forward's draw of that row from job.seed / job.eps; otherwise entry
+ * draws[j * n_draws + s] (nm_draw_t, keyed as nm_devpass_draws keys it); use_mean: z = mu_joint + 0 * exp(logvar_joint / 2),
+ * the value the two-launch route forms under an all-zero eps -- every decoder, and the regressor on the residuals
+ * x - x_hat, which go through LDS as bf16 chunks [128][72] (rounded as nm_forward's reg_resid export rounds them) and never
+ * reach memory: first layer against the W1 chunk images and b1 of the shadow at job.reg_s in nm_head_regression's chunk and K
+ * order, fp32 accumulators that start at zero, b1 added in the activation epilogue (where nm_head_regression adds it: the
+ * predictions of the two routes are the same bits), layers 2 and 3 as there, the fmaf chain of layer 3 included.  Nothing is
+ * written to reg_resid, reg_dres, loss_log or the parameters; a job need not hold reg_resid / reg_dres.
+ *   Draw 0 writes out_z, out_fi_pred and, for the decoders of want_mask, nm_devpass_multi's export epilogue (out_loc /
+ * out_sqerr / out_rowdev; dead 16-row tiles skipped and zeroed); with n_draws > 1 these buffers hold draw 0 alone.  A decoder
+ * outside the mask still runs (the head needs its residual) and leaves its export buffers alone.  fi_draws[r][s] (optional)
+ * receives the prediction p_s of draw s.  Per subject, row [rows_alloc][NM_FI_ROW_COLUMNS] fp32, written by the lane that
+ * owns the row, no atomics, contraction off, the same bytes on every run:
+ *   fi_pred = the mean of the S predictions, folded as nm_devpass_draws folds a reconstruction: s = 0: mean = p_0, M2 = 0;
+ *             s >= 1: d = p_s - mean; mean += d * (1.0f / (float)(s + 1)); M2 += d * (p_s - mean)
+ *   fi_sd   = sqrtf(M2 * (1.0f / (float)(S - 1))); S = 1: 0
+ *   fi_min, fi_max = fminf / fmaxf over the draws
+ *   err     = fi_pred - fi_target[row]; no target: 0, and status carries 2
+ *   dev     = (((d_0 + d_1) + ...) + d_{M-1}) / M, d_m = the value out_rowdev of decoder m receives in draw 0
+ *   kl      = the joint posterior's analytic KL: formula and summation order of nm_e2e_pass
+ *   status  = 1 (a prediction, a deviation or a latent statistic of the row is not finite) | 2 (no fi_target)
+ * Rows from the table's end to the end of its last 256-row tile come back as zeros in every buffer the pass writes; nothing a
+ * buffer held before the launch enters a result; a row's bytes do not depend on the launch's other jobs or tiles.
+ * LDS: 122,368 bytes, one workgroup per CU (the residual chunk and the W1 image, 18 KiB each, cannot borrow P or W).
+ * Workspace tiles as for nm_devpass_multi, one-expert jobs included.
+ *   Admitted (nm_fi_pass_ok): not wide; reg_head == 1 with reg_w / reg_b offsets >= 0 and aligned and reg_s >= 0;
+ * 1..NM_MAX_EXP modalities, each with an encoder; n_private == 0, tc_weight == 0, w_off < 0, out_kind == 0; H[0] <= 112, every
+ * H in 1..NM_MAX_WIDTH; Z rounded to 16 <= 32; no classifier; NM_COMBINE_GPOE only with every expert's alpha offset >= 0;
+ * NM_E_DEVPASS otherwise (such a job is evaluated by nm_forward + nm_head_regression), NM_E_NULL for a null pointer.  Status
+ * of the launch is decided on the host before the device is asked anything: NM_E_NULL for a missing array (draws_dev may
+ * be NULL only with n_draws == 1), NM_E_GEOMETRY for n_draws outside 1..NM_MAX_DRAWS and by the geometry rules of every
+ * launch.  Whether use_mean comes with n_draws != 1 lives in the device-side request: the caller checks it (JobSet.forward_fi
+ * refuses it before any launch).  The kernel makes a refused job's workgroups leave at once. */
+#define NM_FI_ROW_COLUMNS 8
+typedef struct nm_fi_t {
+  float*  row;                       /* [rows_alloc][NM_FI_ROW_COLUMNS], or NULL */
+  float*  fi_draws;                  /* [rows_alloc][n_draws]: every draw's prediction, or NULL */
+  int32_t use_mean;                  /* 1: z = mu_joint (n_draws must be 1); 0: draws */
+  int32_t want_mask;                 /* bit m: decoder m's out_loc / out_sqerr / out_rowdev are written (draw 0) */
+} nm_fi_t;
+int nm_fi_pass(const nm_job_t* jobs_dev, int n_jobs, const nm_draw_t* draws_dev, int n_draws, const nm_fi_t* req_dev, int tile0,
+               int n_tiles, int flags, void* stream);                    /* flags: 0 or NM_F_TRACE */
+int nm_fi_pass_ok(const nm_job_t* job_host);
 /* The encoder half alone (csrc/nm_devpass.hip: nm_latent_kernel): the joint posterior of every row, what cVAE.pred_latent
  * returns (cVAE.py:539-545), over table rows [tile0 * 128, (tile0 + n_tiles) * 128).  Every expert's encoder and the fusion
  * of nm_forward, no latent draw and no decoder; writes out_mu / out_logvar and nothing else -- bit for bit nm_forward's

@@ -96,6 +96,7 @@ NM_MAX_DRAWS = 64
 NM_MAX_IW_DRAWS = 1024
 NM_IW_ROW_COLUMNS = 8
 NM_E2E_ROW_COLUMNS = 8
+NM_FI_ROW_COLUMNS = 8
 # nm_decode_pass: the most covariate cells of a request
 NM_MAX_CELLS = 64
 # nm_chart_pass: the most rows of a request, and the columns of a chart row (mean, var_latent, n_rows, status)
@@ -208,6 +209,11 @@ class NmE2e(C.Structure):
     _fields_ = [("row", C.c_void_p), ("use_mean", C.c_int32), ("want_mask", C.c_int32)]
 
 
+class NmFi(C.Structure):
+    """nm_fi_t: one job's request, nm_fi_pass' [n_jobs] table (device memory)."""
+    _fields_ = [("row", C.c_void_p), ("fi_draws", C.c_void_p), ("use_mean", C.c_int32), ("want_mask", C.c_int32)]
+
+
 class NmDecode(C.Structure):
     """nm_decode_t: one job's request, nm_decode_pass' [n_jobs] table (device memory)."""
     _fields_ = [("z", C.c_void_p), ("n_rows", C.c_int32), ("rows_alloc", C.c_int32), ("n_cells", C.c_int32),
@@ -311,6 +317,8 @@ def load():
     lib.nm_e2e_pass.argtypes = [vp, i32, vp, i32, i32, i32, vp]
     lib.nm_e2e_pass_ok.argtypes = [C.POINTER(NmJob)]
     lib.nm_e2e_alpha_ok.argtypes = [C.POINTER(NmJob)]
+    lib.nm_fi_pass.argtypes = [vp, i32, vp, i32, vp, i32, i32, i32, vp]
+    lib.nm_fi_pass_ok.argtypes = [C.POINTER(NmJob)]
     lib.nm_latent_pass.argtypes = [vp, i32, i32, i32, i32, vp]
     lib.nm_latent_pass_ok.argtypes = [C.POINTER(NmJob)]
     lib.nm_decode_pass.argtypes = [vp, i32, vp, i32, i32, i32, vp]
@@ -399,6 +407,7 @@ EXPORTED_SYMBOLS = [
     "nm_chart_pass", "nm_chart_pass_ok",
     "nm_fit_quality", "nm_fit_rank",
     "nm_e2e_pass", "nm_e2e_pass_ok", "nm_e2e_alpha_ok",
+    "nm_fi_pass", "nm_fi_pass_ok",
 ]
 
 

@@ -217,8 +217,11 @@ class _Base(nn.Module):
 
     def _run(self, xes: Sequence[torch.Tensor], cs: Sequence[torch.Tensor], combine: str, flags: int, eps=None,
              kl_w=None, ll_w=1.0, recon_only: bool = False, latent_only: bool = False, subsets=None, present=None, draws=None,
-             loglik=None, endtoend=None):
-        """endtoend (pred_scores / predict_proba of the end-to-end model: (latent, seed, compact, logits_only)): the launch is the
+             loglik=None, endtoend=None, fi=None):
+        """fi (pred_fi / predict_fi of the regression model: (latent, S, the S generator keys or None, compact)): the launch is
+        the FI evaluation (JobSet.forward_fi: encoders once, per draw the decoders and the regressor, the per-subject row table
+        in job.fi_row, every draw's prediction in job.fi_draws).
+        endtoend (pred_scores / predict_proba of the end-to-end model: (latent, seed, compact, logits_only)): the launch is the
         evaluation pass (JobSet.forward_endtoend: eval-mode classifier on the joint mean, both decoder banks, the per-subject
         row table in job.e2e_row); a seed selects the in-kernel generator for latent="draw".
         loglik (pred_loglik: (S, the S generator keys, the decoder indices or None)): the launch is the likelihood pass
@@ -317,6 +320,20 @@ class _Base(nn.Module):
             finally:
                 (j.eps, j.eps_cap, j.seed) = held
                 j.touch()
+        elif fi is not None:
+            lat, S, seeds, compact = fi
+            if not getattr(j, "fi_enabled", False) or j.fi_row is None or j.fi_row.shape[0] != j.tables[0].rows_alloc:
+                j.enable_fi_exports(rows=True, draws=True, loc=True, sqerr=False, rowdev=True)
+            held = j.fi_target                                   # (no target travels with a prediction: err = 0, status 2)
+            if held is not None:
+                j.fi_target = None
+                j.touch()
+            try:
+                self._js.forward_fi(lat, S, seeds=seeds, compact=compact, tile0=0, n_tiles=nt)
+            finally:
+                if held is not None:                             # the standing job keeps the target a loss call gave it
+                    j.fi_target = held
+                    j.touch()
         elif recon_only and flags == _lib.NM_F_EXPORT:
             self._js.forward(0, nt, loss=False)
         elif latent_only and flags == _lib.NM_F_EXPORT:
@@ -1156,6 +1173,38 @@ class cVAE_multimodal_regression(_ExpertOps, _HeadBase):
 
     def pred_recon_counterfactual(self, xes, c, DEVICE, combine, c_grid, latent="mean"):
         return cVAE_multimodal.pred_recon_counterfactual(self, xes, c, DEVICE, combine, c_grid, latent)
+
+    def _fi(self, xes, c, combine, latent, n_draws, seed, compact=None):
+        if combine.lower() not in _lib.NM_COMBINE:
+            raise ValueError("No such combination method")
+        xs = [torch.tensor(np.asarray(x.values if hasattr(x, "values") else x), dtype=torch.float32) for x in xes]
+        ct = torch.tensor(np.asarray(c.values if hasattr(c, "values") else c, dtype=np.float32))     # (raw covariates: AGE, PTGENDER)
+        self._dev()
+        S = int(n_draws)
+        seeds = None
+        if latent == "draw":
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            seeds = draw_seeds(int(seed), S) if 1 <= S <= _lib.NM_MAX_DRAWS else None
+        zeros = torch.zeros(int(xs[0].shape[0]), self.spec.latent)     # (the job's own draw buffer is not read by this pass)
+        return self._run(xs, [ct] * self.modalities, combine, _lib.NM_F_EXPORT, eps=zeros, fi=(latent, S, seeds, compact))
+
+    def pred_fi(self, xes, c, DEVICE, combine, latent="draw", n_draws=1, seed=None):
+        """The model's own FI prediction per subject, as a DataFrame of metrics.FI_ROW_COLUMNS -- fi_pred (the mean over
+        n_draws latent draws), fi_sd, fi_min, fi_max, err (0: no target travels with the call, so status always carries 2; a target the model's job holds
+        from a loss call is set aside for the launch and put back), dev, kl, status -- from one
+        evaluation (JobSet.forward_fi).  latent="draw": draw s is keyed draw_seeds(seed, n_draws)[s] (seed None: taken from
+        torch's generator, as forward_multimodal's draw is); "mean": the joint mean, one deterministic pass.  fi_sd is the
+        spread the latent draw alone causes -- not a predictive interval."""
+        import pandas as pd
+        from .metrics import FI_ROW_COLUMNS
+        j, B = self._fi(xes, c, combine, latent, n_draws, seed)
+        return pd.DataFrame(j.fi_row[:B].cpu().numpy(), columns=list(FI_ROW_COLUMNS))
+
+    def predict_fi(self, xes, c, DEVICE, combine):
+        """The FI prediction at the joint mean (no draw): an [N, 1] tensor, the same bytes on every call."""
+        j, B = self._fi(xes, c, combine, "mean", 1, None)
+        return j.out_fi_pred[:B].clone().reshape(B, 1)
 
     def encode(self, x, c, m):
         return cVAE_multimodal.encode(self, x, c, m)

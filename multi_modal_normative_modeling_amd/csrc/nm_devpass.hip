@@ -1947,3 +1947,4 @@ int nm_trace_read_dv(unsigned long long* out512, int reset) {
 #include "nm_iw.inc"
 #include "nm_chart.inc"
 #include "nm_e2e.inc"
+#include "nm_fi.inc"

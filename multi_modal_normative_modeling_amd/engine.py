@@ -53,6 +53,14 @@ CHART_AUTO = {1: False, 2: False, 3: False, 4: False}
 # 256 models; the other classes have no record.  The route is reached with compact=True or NMHIP_E2E=1
 E2E_AUTO = {1: False, 2: False, 3: False, 4: False}
 
+# nm_fi_pass as the automatic route of JobSet.forward_fi, per number of experts of the model: by the same rule (the new
+# kernel's slowest repeat against the fastest of the forward kernel + nm_head_regression per draw + the torch fold at EVERY set
+# size measured, tools/bench_fi_eval.py, profiles/fi_eval.json).  All off: three experts win at every
+# size with 32 draws, with five folds in one launch and at one model with one draw (161 against 270 us), but with one draw
+# the pass loses to forward + head_regression on standing descriptors from five models on (302 against 284 us, 733 against
+# 482 us at 20, 12.2 against 1.88 ms at 256: one workgroup per CU); the other classes have no record.  The route is reached with compact=True or NMHIP_FI=1
+FI_AUTO = {1: False, 2: False, 3: False, 4: False}
+
 _MASK64 = (1 << 64) - 1
 
 
@@ -780,6 +788,48 @@ class Job:
         q = _lib.NmE2e()
         q.row = self.e2e_row.data_ptr() if self.e2e_row is not None else None
         q.use_mean, q.want_mask = int(bool(use_mean)), self.e2e_mask
+        return q
+
+    # -- the regression model's evaluation pass (nm_fi_pass) ----------------------------------------
+    def fi_ok(self) -> bool:
+        """nm_fi_pass_ok, asked of this job's shape descriptor: can the job's FI evaluation run on nm_fi_pass?  Asked again
+        whenever the descriptor or one of the attributes it carries beside the shape has changed."""
+        key = (getattr(self, "_version", 0), self.combine, getattr(self, "single_bypass", None), self.tc_weight, self.var_floor)
+        hit = getattr(self, "_fi_cache", None)
+        if hit is None or hit[0] != key:
+            hit = self._fi_cache = (key, int(_lib.load().nm_fi_pass_ok(C.byref(self._shape_struct()))))
+        return hit[1] == 0
+
+    def enable_fi_exports(self, rows=True, draws=False, loc=False, sqerr=False, rowdev=True, latent=True, decoders=None):
+        """Buffers of the regression model's evaluation (JobSet.forward_fi, nm_fi_pass): out_fi_pred always; with rows,
+        fi_row [rows_alloc, 8] = metrics.FI_ROW_COLUMNS per subject; with draws, fi_draws [rows_alloc, n_draws] (allocated by
+        forward_fi for the number of draws it is asked for); out_loc / out_sqerr / out_rowdev of every decoder and the latent
+        exports as asked (they hold draw 0); decoders: the indices whose loc / sqerr / rowdev exports are written
+        (default: all; the row table does not depend on it)."""
+        if self.spec.kind != "regression":
+            raise ValueError("enable_fi_exports: a regression model (kind 'regression') is needed")
+        nk = len(self.kmods)
+        dec = list(range(nk)) if decoders is None else sorted({int(m) for m in decoders})
+        if dec and (dec[0] < 0 or dec[-1] >= nk):
+            raise ValueError(f"decoders: a subset of 0..{nk - 1}, got {decoders}")
+        self.enable_exports(loc=loc, sqerr=sqerr, rowdev=rowdev, latent=latent)
+        if not latent:
+            self.out_mu = self.out_logvar = self.out_z = None
+        self.fi_mask = sum(1 << m for m in dec)
+        self.fi_row = torch.zeros(self.tables[0].rows_alloc, _lib.NM_FI_ROW_COLUMNS, device=self.device) if rows else None
+        self.fi_want_draws, self.fi_draws = bool(draws), None
+        self.fi_enabled = True
+        self._version += 1
+
+    def fi_struct(self, use_mean: bool, n_draws: int) -> "_lib.NmFi":
+        if not getattr(self, "fi_enabled", False):
+            raise ValueError("enable_fi_exports() first")
+        if self.fi_want_draws and (self.fi_draws is None or self.fi_draws.shape[1] != n_draws):
+            self.fi_draws = torch.zeros(self.tables[0].rows_alloc, n_draws, device=self.device)
+        q = _lib.NmFi()
+        q.row = self.fi_row.data_ptr() if self.fi_row is not None else None
+        q.fi_draws = self.fi_draws.data_ptr() if self.fi_want_draws else None
+        q.use_mean, q.want_mask = int(bool(use_mean)), self.fi_mask
         return q
 
     def set_latent_exports(self, on: bool):
@@ -1853,6 +1903,141 @@ class JobSet:
                 j.out_rowdev = rowdev
                 j._version += 1
 
+    # -- the regression model's evaluation ---------------------------------------------------------
+    def fi_ok(self) -> bool:
+        """Can the set's FI evaluation run on nm_fi_pass (every job passes the library's nm_fi_pass_ok)?  NMHIP_FI=0 switches
+        the kernel off."""
+        if self.wide or os.environ.get("NMHIP_FI", "auto") == "0":
+            return False
+        return all(j.fi_ok() for j in self.jobs)
+
+    def fi_pick(self) -> bool:
+        """The automatic route of forward_fi: fi_ok() and a class of sets FI_AUTO has switched on (by the number of experts);
+        NMHIP_FI=1 forces the pass on where the set passes fi_ok()."""
+        if not self.fi_ok():
+            return False
+        return os.environ.get("NMHIP_FI", "auto") == "1" or all(FI_AUTO.get(j.spec.M, False) for j in self.jobs)
+
+    def _fi_refusal(self) -> str:
+        if os.environ.get("NMHIP_FI", "auto") == "0":
+            return "NMHIP_FI=0"
+        if self.wide:
+            return "general-shape path (a hidden width or latent beyond the fused kernel's tile)"
+        for i, j in enumerate(self.jobs):
+            if not j.fi_ok():
+                s = j.spec
+                return (f"job {i}: nm_fi_pass_ok refuses its shape (kind {s.kind!r}, {s.M} experts, {len(j.kmods)} decoders, "
+                        f"hidden {list(s.hidden)}, latent {s.latent})")
+        return "nothing"
+
+    def forward_fi(self, latent: str = "draw", n_draws: int = 1, seeds=None, eps=None, compact: Optional[bool] = None,
+                   tile0: int = 0, n_tiles: Optional[int] = None, trace: bool = False):
+        """The evaluation of cVAE_multimodal_regression jobs over row tiles, all jobs of the set at once: the joint posterior,
+        S = n_draws latents per row (latent="draw": with n_draws == 1 and neither seeds nor eps the forward kernel's own draw
+        of every row -- job.seed or the job's injected eps; otherwise one generator key per draw, seeds or
+        draw_seeds(job.seed, S), or eps, a list of S tensors in the layout set_eps takes; latent="mean": z = mu_joint, one
+        draw), every decoder and the regressor on the residuals, and per subject job.fi_row (metrics.FI_ROW_COLUMNS) -- into the
+        buffers of Job.enable_fi_exports; out_fi_pred, the latent and the decoder exports hold draw 0.  compact: None = the
+        automatic pick (fi_pick); True = insist on nm_fi_pass, one launch (ValueError naming the refusal if the set cannot run
+        there); False = the two-launch route per draw, the general forward kernel with exports + head_regression, the row
+        table folded with fp32 torch operations in the kernel's order -- also the route of every set nm_fi_pass_ok refuses
+        (a trunk on the general-shape path, a latent above 32).  The two-launch route installs each draw's key or eps (for
+        "mean": an all-zero eps) in the job for its launches and puts the job's own back afterwards."""
+        if latent not in ("mean", "draw"):
+            raise ValueError("latent: 'mean' or 'draw'")
+        if any(not getattr(j, "fi_enabled", False) for j in self.jobs):
+            raise ValueError("forward_fi: Job.enable_fi_exports() first, on every job of the set")
+        S = int(n_draws)
+        if latent == "mean" and (S != 1 or seeds is not None or eps is not None):
+            raise ValueError(f"forward_fi: latent='mean' is one deterministic pass (n_draws = 1, no seeds, no eps), got n_draws = {n_draws}")
+        if compact and not self.fi_ok():
+            raise ValueError("compact=True: the set cannot run on nm_fi_pass: " + self._fi_refusal())
+        own = latent == "mean" or (S == 1 and seeds is None and eps is None)      # the job's own seed / eps: no draw table
+        caps = [j.eps_cap for j in self.jobs]
+        reqs = [None if own else j._draw_request(S, seeds, eps, _lib.NM_MAX_DRAWS) for j in self.jobs]
+        for j, cap in zip(self.jobs, caps):
+            if j.eps_cap != cap:                         # (injected draws index as the job's own eps would)
+                j._version += 1
+        nt = self.jobs[0].tables[0].n_tiles if n_tiles is None else n_tiles
+        try:
+            if compact or (compact is None and self.fi_pick()):
+                structs = [j.fi_struct(latent == "mean", S) for j in self.jobs]
+                sig = (latent, S, own, tuple(j._version for j in self.jobs),
+                       tuple((tuple(r[1]), tuple(e.data_ptr() for e in r[2]) if r[2] is not None else None) if r else None for r in reqs),
+                       tuple((q.row, q.fi_draws) for q in structs))
+                if getattr(self, "_fi_sig", None) != sig:
+                    arr = (_lib.NmFi * len(structs))(*structs)
+                    draws = None
+                    if not own:
+                        flat = []
+                        for _, keys, ep in reqs:
+                            for s in range(S):
+                                d = _lib.NmDraw()
+                                d.seed, d.eps = keys[s], (ep[s].data_ptr() if ep is not None else None)
+                                flat.append(d)
+                        draws = torch.frombuffer(bytearray(bytes((_lib.NmDraw * len(flat))(*flat))), dtype=torch.uint8).to(self.device)
+                    self._fi_keep = (torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device), draws,
+                                     [r[2] for r in reqs if r])
+                    self._fi_sig = sig
+                # (one workspace tile per 256-row batch: the two 128-row workgroups of a batch share it on disjoint rows)
+                self._issue("nm_fi_pass", nt, self._fi_keep[1].data_ptr() if self._fi_keep[1] is not None else 0, S,
+                            self._fi_keep[0].data_ptr(), tile0 * 2, nt * 2, _lib.NM_F_TRACE if trace else 0)
+                return
+            self._forward_fi_two_launch(latent, S, reqs, tile0, nt)
+        finally:
+            for j, cap in zip(self.jobs, caps):
+                if j.eps_cap != cap:
+                    j.eps_cap = cap
+                    j._version += 1
+
+    def _forward_fi_two_launch(self, latent: str, S: int, reqs, tile0: int, nt: int):
+        """forward_fi's two-launch route: per draw the general forward kernel with exports and nm_head_regression; draw 0 runs
+        last, so that out_fi_pred, the latent and the decoder exports hold it, as from the pass."""
+        stash = []
+        for j in self.jobs:
+            j.fi_struct(latent == "mean", S)               # (fi_draws for this number of draws)
+            held = (j.eps, j.eps_cap, j.seed)
+            off = [k for k in range(len(j.kmods)) if not (j.fi_mask >> k) & 1]      # decoders whose exports stay as they are
+            bufs = (list(j.out_loc), list(j.out_sqerr), list(j.out_rowdev))
+            for k in off:
+                j.out_loc[k] = j.out_sqerr[k] = j.out_rowdev[k] = None
+            if j.fi_row is not None:
+                j.out_rowdev = [o if o is not None else torch.zeros(j.tables[0].rows_alloc, device=j.device) for o in j.out_rowdev]
+            stash.append((held, bufs))
+        preds = [[None] * S for _ in self.jobs]
+        for s in list(range(1, S)) + [0]:
+            for j, rq in zip(self.jobs, reqs):
+                if latent == "mean":
+                    # an all-zero draw: z = mu_joint + 0 * exp(logvar / 2)
+                    zero = getattr(j, "_fi_zero_eps", None)
+                    if zero is None or zero.shape[2] != j.spec.latent:
+                        zero = j._fi_zero_eps = torch.zeros(1, BATCH, j.spec.latent, device=j.device)
+                    j.eps, j.eps_cap = zero, 1
+                elif rq is not None:
+                    if rq[2] is not None:
+                        j.eps = rq[2][s]
+                    else:
+                        j.seed = rq[1][s]
+                j._version += 1
+            self._launch(tile0, 1, nt, _lib.NM_F_EXPORT)
+            self.head_regression(backward=False, tile0=tile0, n_tiles=nt)
+            for i, j in enumerate(self.jobs):
+                preds[i][s] = j.out_fi_pred.clone() if S > 1 else j.out_fi_pred
+        for i, (j, (held, bufs)) in enumerate(zip(self.jobs, stash)):
+            r0, r1 = tile0 * BATCH, min((tile0 + nt) * BATCH, j.tables[0].rows_alloc)
+            n0 = max(r0, min(j.tables[0].N, r1))
+            if j.fi_draws is not None:
+                j.fi_draws[r0:r1] = torch.stack(preds[i], dim=1)[r0:r1]
+                j.fi_draws[n0:r1] = 0.0
+            if j.fi_row is not None:
+                _fi_row_fold(j, r0, r1, preds[i])
+            for t in (j.out_mu, j.out_logvar, j.out_z, j.out_fi_pred):      # rows past the table: zeros, as from the pass
+                if t is not None:
+                    t[n0:r1] = 0.0
+            j.eps, j.eps_cap, j.seed = held
+            j.out_loc, j.out_sqerr, j.out_rowdev = bufs
+            j._version += 1
+
     def latent_stats(self):
         """Per job the column means and population variances of its exported joint mu over the table's rows (the training
         cohort's latent distribution, utils_vae.py:156-157) -- all jobs of the set in ONE launch of nm_latent_stats.
@@ -2065,6 +2250,51 @@ def _endtoend_row_fold(j: Job, r0: int, r1: int):
         bad = bad | ~torch.isfinite(d)
     j.e2e_row[r0:n1] = torch.stack([sd / sa, torch.argmax(lg, dim=1).float(), lg[:, 1:].max(dim=1).values - lg[:, 0], dh, dd, dh - dd,
                                     kl, bad.float()], dim=1)
+
+
+def _fi_row_fold(j: Job, r0: int, r1: int, preds: Sequence[torch.Tensor]):
+    """job.fi_row over table rows [r0, r1) from the S predictions of every row (preds[s]: [rows_alloc], s ascending) and the
+    job's exports of draw 0 (out_rowdev of every decoder, out_mu, out_logvar): nm_fi_pass' definition (include/nmhip.h) in
+    fp32 torch operations, operation by operation; rows past the table's end are zeros.  A job without latent exports gets
+    kl = 0 from this route (the statistics never left the forward kernel)."""
+    n1 = min(r1, j.tables[0].N)
+    j.fi_row[r0:r1] = 0.0
+    if n1 <= r0:
+        return
+    S, M, Z = len(preds), len(j.kmods), j.spec.latent
+    p = [q[r0:n1] for q in preds]
+    mean, m2, lo, hi = p[0].clone(), torch.zeros_like(p[0]), p[0].clone(), p[0].clone()
+    bad = ~torch.isfinite(p[0])
+    for s in range(1, S):
+        rs = float(np.float32(1.0) / np.float32(s + 1))
+        d = p[s] - mean
+        mean = mean + d * rs
+        m2 = m2 + d * (p[s] - mean)
+        lo, hi = torch.fmin(lo, p[s]), torch.fmax(hi, p[s])
+        bad = bad | ~torch.isfinite(p[s])
+    sd = torch.sqrt(m2 * float(np.float32(1.0) / np.float32(S - 1))) if S > 1 else torch.zeros_like(mean)
+    err = mean - j.fi_target[r0:n1] if j.fi_target is not None else torch.zeros_like(mean)
+    dev = None
+    for o in j.out_rowdev:
+        dev = o[r0:n1].clone() if dev is None else dev + o[r0:n1]
+        bad = bad | ~torch.isfinite(o[r0:n1])
+    dev = dev / torch.full_like(dev, M)                 # (a true division: by a Python scalar torch multiplies by 1 / M)
+    kl = torch.zeros_like(mean)
+    if j.out_mu is not None and j.out_logvar is not None:
+        mu, lv = j.out_mu[r0:n1], j.out_logvar[r0:n1]
+        t = ((1.0 + lv) - mu * mu) - torch.exp(lv)
+        # four interleaved partial sums, as in _endtoend_row_fold
+        cols = [[z for q in range(i, Z // 4, 4) for z in range(4 * q, 4 * q + 4)] if Z % 4 == 0 else list(range(i, Z, 4)) for i in range(4)]
+        parts = []
+        for cs in cols:
+            a = torch.zeros(n1 - r0, device=t.device)
+            for z in cs:
+                a = a + t[:, z]
+            parts.append(a)
+        kl = -0.5 * ((parts[0] + parts[1]) + (parts[2] + parts[3]))
+        bad = bad | ~(torch.isfinite(mu).all(dim=1) & torch.isfinite(lv).all(dim=1))
+    status = bad.float() + (0.0 if j.fi_target is not None else 2.0)
+    j.fi_row[r0:n1] = torch.stack([mean, sd, lo, hi, err, dev, kl, status], dim=1)
 
 
 def _latent_sets(arrays: Sequence[torch.Tensor]):

@@ -49,6 +49,12 @@ assert len(LOGLIK_ROW_COLUMNS) == _lib.NM_IW_ROW_COLUMNS
 # their difference (positive: the disease bank fits the subject better), the analytic KL, status 0 / 1 (a non-finite value)
 ENDTOEND_ROW_COLUMNS = ("p_disease", "pred", "margin", "dev_health", "dev_disease", "contrast", "kl", "status")
 assert len(ENDTOEND_ROW_COLUMNS) == _lib.NM_E2E_ROW_COLUMNS
+# the row export of the regression model's evaluation pass (nm_fi_pass, JobSet.forward_fi): NM_FI_ROW_COLUMNS values per
+# subject -- mean, standard deviation, minimum and maximum of the S FI predictions (one per latent draw), the mean's error
+# against the target, the mean deviation over the decoders (draw 0), the analytic KL, status (1: a non-finite value,
+# 2: no target, 3: both).  fi_sd is the spread the latent draw alone causes, not a predictive interval
+FI_ROW_COLUMNS = ("fi_pred", "fi_sd", "fi_min", "fi_max", "err", "dev", "kl", "status")
+assert len(FI_ROW_COLUMNS) == _lib.NM_FI_ROW_COLUMNS
 # a row of the normative chart (engine.JobSet.chart, nm_chart_pass): per (cell, ROI) the mean and the unbiased variance of
 # x_hat over the request's latent rows, the row count, and status 0 / -2 (fewer than two rows, or a non-finite value)
 CHART_COLUMNS = ("mean", "var_latent", "n_rows", "status")

@@ -281,8 +281,16 @@ def evaluate_regression(y_true: np.ndarray, y_pred: np.ndarray) -> Dict[str, flo
 def run_regression_folds(cohort: prep.SyntheticCohort, folds_to_run: Sequence[int], n_folds: int, epochs: int, device,
                          out_dir=None, modalities: Sequence[str] = prep.HCP_MODALITIES, combine: str = "gpoe",
                          lr: float = 1e-4, lambda_reg: float = 1.0, hidden: Sequence[int] = workload.HIDDEN,
-                         latent: int = workload.LATENT):
-    """The whole of multimodal_kfold_train_cvae_supervised_regression.py:52-192 for the given folds, all folds
+                         latent: int = workload.LATENT, scores: bool = False, score_latent: str = "draw", draws: int = 1,
+                         draw_seed: int = 0):
+    """scores: the held-out folds are evaluated as ONE JobSet in one launch (JobSet.forward_fi) in the place of one forward +
+    head_regression pair per fold: per subject metrics.FI_ROW_COLUMNS -- the mean of the FI prediction over `draws` latent draws
+    (draw s of every fold keyed engine.draw_seeds(draw_seed, draws)[s]; score_latent="mean": the joint mean, no draw), its
+    spread, minimum and maximum, the error, the mean deviation, the KL.  fold_{k}_pred.npy then holds fi_pred, RMSE / MAE / R2 /
+    MAPE come from it, per fold and -- in every result as pooled_RMSE ... -- over the folds of the call; with out_dir
+    regression_fold_{k}.csv per fold and regression_pooled.csv (IID, FI, then the row's columns).  fi_sd is the spread the
+    latent draw alone causes, not a predictive interval.  Without scores nothing changes:
+    The whole of multimodal_kfold_train_cvae_supervised_regression.py:52-192 for the given folds, all folds
     training concurrently: cVAE_multimodal_regression on RobustScaler-ed ROI tables with the two raw covariates
     (AGE, PTGENDER) and the FI target; FI prediction on the held-out fold (fold_{k}_pred.npy / _true.npy and
     RMSE / MAE / R2 / MAPE); ROI-wise deviation of every subject per modality
@@ -313,20 +321,47 @@ def run_regression_folds(cohort: prep.SyntheticCohort, folds_to_run: Sequence[in
     js.assert_finite()
     sps = n * len(jobs) / max(time.perf_counter() - t0, 1e-9)
     results = []
-    for k, j, sc in zip(folds_to_run, jobs, scalers):
-        te = folds[k][1]
-        # held-out FI prediction (:127-149): joint posterior, sampled z
-        xs = [prep.robust_scaler_transform(prep.source_table(cohort, m)[te], *sc[i]).astype(np.float32) for i, m in enumerate(modalities)]
-        tables = [Table(x, cov_all[te], device) for x in xs]
-        ev = Job(j.spec, tables, combine=combine, state=j.state_dict(), seed=j.seed + 17, n_tiles_ws=tables[0].n_tiles)
-        ev.enable_exports(loc=True, sqerr=False, rowdev=False, latent=False)
-        es = JobSet([ev])
-        es.forward()
-        es.head_regression(backward=False, tile0=0, n_tiles=tables[0].n_tiles)
+    evs, frames = [], []
+    if scores:
+        if score_latent not in ("mean", "draw"):
+            raise ValueError("score_latent: 'mean' or 'draw'")
+        for k, j, sc in zip(folds_to_run, jobs, scalers):
+            te = folds[k][1]
+            xs = [prep.robust_scaler_transform(prep.source_table(cohort, m)[te], *sc[i]).astype(np.float32) for i, m in enumerate(modalities)]
+            tables = [Table(x, cov_all[te], device) for x in xs]
+            ev = Job(j.spec, tables, combine=combine, state=j.state_dict(), seed=j.seed + 17, n_tiles_ws=tables[0].n_tiles)
+            ev.set_fi(cohort.fi[te].astype(np.float32))
+            ev.enable_fi_exports(rows=True, draws=False, loc=False, sqerr=False, rowdev=True, latent=True)
+            evs.append(ev)
+        nt = max(e.tables[0].n_tiles for e in evs)
+        if score_latent == "mean":
+            JobSet(evs).forward_fi(latent="mean", n_tiles=nt)
+        else:
+            from .engine import draw_seeds
+            JobSet(evs).forward_fi(latent="draw", n_draws=int(draws), seeds=draw_seeds(int(draw_seed), int(draws)), n_tiles=nt)
         torch.cuda.synchronize(device)
-        pred = ev.out_fi_pred[: len(te)].cpu().numpy().reshape(-1, 1)
+        for k, ev in zip(folds_to_run, evs):
+            frames.append(fi_scores_frame(ev, cohort.iid[folds[k][1]], cohort.fi[folds[k][1]]))
+    for fi_idx, (k, j, sc) in enumerate(zip(folds_to_run, jobs, scalers)):
+        te = folds[k][1]
         true = cohort.fi[te].astype(np.float32).reshape(-1, 1)
-        scores = evaluate_regression(true, pred)
+        if scores:
+            pred = frames[fi_idx]["fi_pred"].to_numpy(dtype=np.float32).reshape(-1, 1)
+        else:
+            # held-out FI prediction (:127-149): joint posterior, sampled z
+            xs = [prep.robust_scaler_transform(prep.source_table(cohort, m)[te], *sc[i]).astype(np.float32) for i, m in enumerate(modalities)]
+            tables = [Table(x, cov_all[te], device) for x in xs]
+            ev = Job(j.spec, tables, combine=combine, state=j.state_dict(), seed=j.seed + 17, n_tiles_ws=tables[0].n_tiles)
+            ev.enable_exports(loc=True, sqerr=False, rowdev=False, latent=False)
+            es = JobSet([ev])
+            es.forward()
+            es.head_regression(backward=False, tile0=0, n_tiles=tables[0].n_tiles)
+            torch.cuda.synchronize(device)
+            pred = ev.out_fi_pred[: len(te)].cpu().numpy().reshape(-1, 1)
+        scores_k = evaluate_regression(true, pred)
+        if scores and out_dir is not None:
+            Path(out_dir).mkdir(parents=True, exist_ok=True)
+            frames[fi_idx].to_csv(Path(out_dir) / f"regression_fold_{k}.csv", index=False)
         if out_dir is not None:
             out = Path(out_dir)
             out.mkdir(parents=True, exist_ok=True)
@@ -339,8 +374,27 @@ def run_regression_folds(cohort: prep.SyntheticCohort, folds_to_run: Sequence[in
                 io.write_roiwise_csv(out_dir, k, m, iids, dev)
         last = (j.step - 1) % j.loss_cap
         results.append({"fold": k, "steps_per_s": sps, "final_total": float(j.loss_log[last, 0]),
-                        "final_mse": float(j.loss_log[last, 12]), **scores})
+                        "final_mse": float(j.loss_log[last, 12]), **scores_k})
+    if scores and frames:
+        import pandas as pd
+        pooled = pd.concat(frames, ignore_index=True)
+        if out_dir is not None:
+            pooled.to_csv(Path(out_dir) / "regression_pooled.csv", index=False)
+        ps = evaluate_regression(pooled["FI"].to_numpy(dtype=np.float32), pooled["fi_pred"].to_numpy(dtype=np.float32))
+        for r in results:
+            r.update({f"pooled_{name}": v for name, v in ps.items()})
     return results
+
+
+def fi_scores_frame(job: Job, iids, fi):
+    """The per-subject table of an FI evaluation (JobSet.forward_fi) as a DataFrame: IID, FI (the target), then the eight
+    columns of metrics.FI_ROW_COLUMNS."""
+    import pandas as pd
+    n = len(iids)
+    row = job.fi_row[:n].cpu().numpy()
+    cols = {"IID": np.asarray(iids), "FI": np.asarray(fi, dtype=np.float32)}
+    cols.update({name: row[:, i] for i, name in enumerate(metrics.FI_ROW_COLUMNS)})
+    return pd.DataFrame(cols)
 
 
 def run_endtoend_folds(cohort: prep.SyntheticCohort, folds_to_run: Sequence[int], n_folds: int, epochs: int, device,
@@ -1534,8 +1588,24 @@ def main_regression(argv=None, _runner=None):
     ap.add_argument("--batch_size", type=int, default=128,
                     help="accepted for compatibility: a step takes 256 rows (the tile the kernel is built around)")
     ap.add_argument("-BaseLR", "--base_learning_rate", dest="base_learning_rate", type=float, default=1e-4)
+    ap.add_argument("--scores", action="store_true",
+                    help="evaluate the held-out folds in one launch and keep the per-subject table: the FI prediction as the mean over "
+                         "--draws latent draws, its spread (the latent draw's alone, not a predictive interval), minimum, maximum, "
+                         "error, deviation, KL (with --out-dir regression_fold_<k>.csv and regression_pooled.csv; the metrics come "
+                         "from the mean prediction)")
+    ap.add_argument("--score-latent", dest="score_latent", choices=("mean", "draw"), default=None,
+                    help="with --scores: predict from draws of the joint posterior (default) or from its mean")
+    ap.add_argument("--draws", type=int, default=None, help="with --scores: latent draws per subject, 1 to 64 (default 1)")
+    ap.add_argument("--draw-seed", dest="draw_seed", type=int, default=None, help="with --scores: the key of draw 0 (default 0)")
     _driver_common(ap)
     args = ap.parse_args(argv)
+    for flag, val in (("--score-latent", args.score_latent), ("--draws", args.draws), ("--draw-seed", args.draw_seed)):
+        if val is not None and not args.scores:
+            ap.error(f"{flag} needs --scores")
+    if args.draws is not None and not 1 <= args.draws <= 64:
+        ap.error("--draws takes 1 to 64")
+    if args.score_latent == "mean" and args.draws not in (None, 1):
+        ap.error("--score-latent mean is one deterministic pass: it does not go with --draws above 1")
     if len(args.hz_para_list) < 2:
         raise ValueError("-H takes the hidden widths followed by the latent size (the script's hz_para_list)")
     cohort = _cohort_from_args(args)
@@ -1543,9 +1613,13 @@ def main_regression(argv=None, _runner=None):
     device = _local_device()
     out_dir = None if args.out_dir is None else Path(args.out_dir) / args.dataset_resourse / "regression_outputs"
     runner = _runner or run_regression_folds
+    extra = {}
+    if args.scores:                                   # (without --scores the runner is called with the arguments it always had)
+        extra = dict(scores=True, score_latent=args.score_latent or "draw", draws=1 if args.draws is None else args.draws,
+                     draw_seed=0 if args.draw_seed is None else args.draw_seed)
     res = runner(cohort, _my_folds(args), args.n_splits, args.epochs, device, out_dir=out_dir, modalities=mods,
                  combine=args.combine.lower(), lr=args.base_learning_rate, hidden=list(args.hz_para_list[:-1]),
-                 latent=int(args.hz_para_list[-1]))
+                 latent=int(args.hz_para_list[-1]), **extra)
     for r in res:
         print("[regression] " + "  ".join(f"{k} {v:.5g}" if isinstance(v, float) else f"{k} {v}" for k, v in r.items()), flush=True)
     return res

@@ -93,6 +93,11 @@ LIMITS = {
     #  build shows 108 VGPRs and 73 SGPR spills -- the request's row pointer and mask stay alive across the decoders; the
     #  ceiling is that count)
     "nm_e2e_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 73, "vgpr_count": 128},
+    # (the draws kernel's shape with every decoder's residual chunk fed to the regressor's first layer, whose accumulators stay
+    #  in registers across the decoders of a draw, one workgroup per CU: the build shows 154 VGPRs and 163 SGPR spills -- the
+    #  request's pointers, the head's offsets and a decoder's export pointers stay alive across its chunks; the ceiling is
+    #  that count, the VGPR ceiling the next allocation granule)
+    "nm_fi_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 163, "vgpr_count": 160},
     "nm_rs_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 540},
     "nm_wide_step_kernel": {"vgpr_spill_count": 0, "private_segment_fixed_size": 0, "sgpr_spill_count": 400},
     # (both instantiations: one workgroup per model / one per decoder, nm_train_steps_head_split)
